@@ -8,10 +8,14 @@ projection of the ~300 k-point map + ds-grid target cloud, 10-iteration LM point
 (exact 1-NN association, 6x6 Gauss-Newton reduce/solve, SE(3) exp, accept/reject on device), pose
 composition -- i.e. ICPSLAM._localize of the reference (slam/icpslam.py:238-247), nothing skipped.
 
-    python bench.py --gpus N --steps K --warmup W          (N>1: launched by torch.distributed.run)
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]   (N>1: launched by torch.distributed.run)
 
-Prints ONE JSON line on rank 0.  `value` is the MEDIAN of GS_BENCH_REPEATS (default 5) timed regions of exactly
---steps steps each (one region of 20 steps is a 4.6 ms sample); `repeats_ms_per_step` lists them all.
+Prints ONE JSON line on rank 0.  A plain run sets the workload up, runs W warm-up steps, times ONE region of exactly K
+steps and reports it: `value` (frames/s) and `ms_per_step` come from that region.  --dump-outputs DIR then writes what
+the last timed step handed back (the pose and the live frame's local vertex / normal maps) as DIR/<name>.npy, float32;
+the inputs are seeded, so two runs with the same arguments see the same frames.
+--full adds what takes runs of its own: `value` becomes the MEDIAN of GS_BENCH_REPEATS (default 5) timed regions of
+exactly K steps each (one region of 20 steps is a 4.6 ms sample); `repeats_ms_per_step` lists them all.
 `roofline` is the HBM roofline of the ICP associate+reduce kernel (J) at a size that streams from HBM (2^24 points,
 40 algorithmic bytes per point), timed live in a second timed region -- the only size at which an HBM fraction is
 physically meaningful; its `traffic` is NOT measured in this run: it comes from the committed
@@ -20,7 +24,8 @@ fused step + association + linearise kernel, L2-resident at this size): launch t
 launch stream inside the C library (gs_profile_*), executed work (VALU instructions, issue utilisation) from the
 committed counter passes.  `aux` carries the other sizes SURVEY 8(d) asks for (ds = 1, 1296x968), the fusion update's
 HBM view at ~1 M map points and BASELINE configs[2] at full length (200 frames, forward and forward + backward).
-`cpu_baseline` times the CPU oracle on bounded samples of the same workloads on the host cores (rank 0, N=1 only).
+`cpu_baseline` times the CPU oracle on bounded samples of the same workloads on the host cores (rank 0, N=1 only;
+--no-cpu-baseline leaves it out).
 """
 import argparse
 import ctypes
@@ -60,9 +65,21 @@ def build_workload(gs, dev, seed):
     return slam, world_map, f0, lives, K, (c, d, K, P)
 
 
-def one_step(gs, slam, world_map, prev, live_cd, K):
+def one_step(gs, slam, world_map, prev, live_cd, K, keep=None):
     live = gs.RGBDImages(live_cd[0], live_cd[1], K)  # fresh object: maps are recomputed every step
+    if keep is not None:
+        keep.append(live)  # the step leaves the live frame's local maps on it: outputs too (--dump-outputs)
     return slam._localize(world_map, live, prev)
+
+
+def dump_outputs(out_dir, pose, live):
+    """--dump-outputs: what the last timed step handed back -- the pose (B,1,4,4) and the local vertex / normal maps
+    (B,1,H,W,3) the fused step left on the live frame -- as float32 .npy files (7.4 MB in all at 640x480)."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in (("pose", pose), ("vertex_map", live.vertex_map), ("normal_map", live.normal_map)):
+        np.save(os.path.join(out_dir, name + ".npy"), t.detach().to(torch.float32).cpu().numpy())
 
 
 def prof_read(nv, tag):
@@ -427,13 +444,72 @@ def cpu_baseline(raw, n_frames=24):
     return out
 
 
+def full_report(line, args, gs, dev, raw, world, prof):
+    """--full: what the headline does not need -- the timed region's dominant kernel (`prof` = steps, launches and ms of
+    the HIP-event pass; committed counter passes), the HBM rooflines of J, the auxiliary workloads and the CPU baseline
+    -- added to `line` (rank 0)."""
+    n_prof, n_knn, ms_knn = prof
+    ns = nt = (H // DS) * (W // DS)
+    avg_knn_ms = ms_knn / max(n_knn, 1)
+    valu = None
+    for name in ("r03_pmc_knn1_loop_valu.json", "r02_pmc_knn1_loop_valu.json"):  # executed work of the same kernel on the same
+        try:                                                                      # workload: committed counter passes, newest first
+            with open(os.path.join(ROOT, "profiles", name)) as f:
+                valu = json.load(f)
+            valu["profile_file"] = name  # (each profile carries the commit it was taken at)
+            break
+        except Exception:
+            pass
+    line["roofline_timed_region"] = {
+        "kernel": "knn1_loop_k<true> (X+K+J fused: the previous iteration's O(1) step -- reduce, LM decision, 6x6 solve, exp -- "
+                  "on wave 0 while one wave plans the tile's windows, one prepares the lanes' rows and seeds and thirteen stage the targets; then rigid transform, exact 1-NN association by grid "
+                  "search with a geometric proof per point (exact chunk-box search for the points it fails for), "
+                  "Jacobian rows and 29-term reduce of its 64-point tile)",
+        "launches": n_knn, "avg_launch_ms": round(avg_knn_ms, 5),
+        "timing_source": "HIP events on the launch stream, second eager pass of {} steps".format(n_prof),
+        "hbm_view": {"algorithmic_bytes_per_launch": 40.0 * ns, "achieved_GBps": round(40.0 * ns / (avg_knn_ms * 1e-3) / 1e9, 2)
+                     if n_knn else 0.0, "frac_of_8TBps": round(40.0 * ns / (avg_knn_ms * 1e-3) / 8e12, 5) if n_knn else 0.0,
+                     "note": "0.77 MB per launch lives in L2: not an HBM measurement (fetched / written bytes per launch from "
+                             "counter passes: profiles/r05_pmc_knn1_loop_traffic.json -- 1.8 MiB / 0.45 MiB raw)"},
+        "valu_view": valu if valu is not None else {"note": "no committed counter pass found under profiles/"}}
+    try:
+        line["roofline"] = hbm_roofline_linearize(gs, dev)
+    except Exception as e:  # pragma: no cover
+        line["roofline"] = {"error": str(e)}
+    if world == 1 and not os.environ.get("GS_BENCH_SHORT"):
+        try:
+            line["roofline_real_associations"] = hbm_linearize_real_associations(gs, dev)
+        except Exception as e:  # pragma: no cover
+            line["roofline_real_associations"] = {"error": str(e)}
+    if world == 1:
+        try:
+            line["aux"] = aux_pointfusion(gs, dev, raw)
+        except Exception as e:  # pragma: no cover
+            line["aux"] = {"error": str(e)}
+        for key, fn in (("association_other_sizes", aux_association_sizes), ("fusion_update_hbm_view", aux_fusion_update_roofline),
+                        ("pointfusion_c3_200_frames", aux_c3_full_length)):
+            if os.environ.get("GS_BENCH_SHORT"):
+                break
+            try:
+                line["aux"][key] = fn(gs, dev)
+            except Exception as e:  # pragma: no cover
+                line["aux"][key] = {"error": str(e)}
+    if world == 1 and not args.no_cpu_baseline:
+        line["cpu_baseline"] = cpu_baseline(raw)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=5)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also: median of GS_BENCH_REPEATS timed regions, per-kernel timing, rooflines, aux workloads, CPU baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave the CPU baseline out")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the last timed step's outputs as DIR/<name>.npy (float32)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     import gradslam_amd as gs
     from gradslam_amd import _native as nv
@@ -455,7 +531,7 @@ def main():
             torch.distributed.barrier()
         torch.cuda.synchronize()
 
-    poses = []
+    poses, prof = [], None
     with torch.no_grad():
         p0 = None
         for i in range(args.warmup):
@@ -469,17 +545,18 @@ def main():
         # of every run.  What long-running services do: collect now, then freeze the survivors out of future passes.
         gc.collect()
         gc.freeze()
-        # EXACTLY --steps steps per timed region, bracketed by barrier + synchronize on both sides; the region is
-        # repeated and the MEDIAN reported (one 20-step region is a 4.6 ms sample: too noisy for a headline)
-        repeats = max(1, int(os.environ.get("GS_BENCH_REPEATS", "5")))
+        # EXACTLY --steps steps per timed region, bracketed by barrier + synchronize on both sides; --full repeats the
+        # region and reports the MEDIAN (one 20-step region is a 4.6 ms sample: too noisy for a headline)
+        repeats = max(1, int(os.environ.get("GS_BENCH_REPEATS", "5"))) if args.full else 1
         dts = []
+        i_last = args.steps - 1
         for rep in range(repeats):
-            poses = []
+            poses, last = [], []
             barrier()
             t0 = time.perf_counter()
             marks = []
             for i in range(args.steps):
-                poses.append(one_step(gs, slam, world_map, prev, lives[i % N_LIVE], K))
+                poses.append(one_step(gs, slam, world_map, prev, lives[i % N_LIVE], K, keep=last if i == i_last else None))
                 if os.environ.get("GS_BENCH_TRACE"):
                     marks.append(time.perf_counter() - t0)
             t_enq = time.perf_counter() - t0
@@ -496,16 +573,19 @@ def main():
                   "per launch, %d graphs captured, %d replays" % (1e3 * t_enq, 1e3 * t_gat, 1e3 * dt, st[0], st[1], st[2], st[3]),
                   file=sys.stderr)
             print("[trace] per-step host ms:", " ".join("%.2f" % (1e3 * (b - a)) for a, b in zip([0.0] + marks[:-1], marks)), file=sys.stderr)
-        # per-kernel durations: a second, short pass of the same steps with HIP events recorded around the
-        # hot kernel on its launch stream (events force eager launches; the timed region above runs in the
-        # library's automatic mode: eager launches on a fast host, hipGraph replay of the loop on a slow one)
-        n_prof = min(args.steps, 20)
-        nv.lib().gs_profile_enable(1)
-        for i in range(n_prof):
-            one_step(gs, slam, world_map, prev, lives[i % N_LIVE], K)
-        torch.cuda.synchronize()
-    n_knn, ms_knn = prof_read(nv, 0)
-    nv.lib().gs_profile_enable(0)
+        if args.dump_outputs and rank == 0:
+            dump_outputs(args.dump_outputs, poses[-1], last[0])
+        if args.full:
+            # per-kernel durations: a second, short pass of the same steps with HIP events recorded around the
+            # hot kernel on its launch stream (events force eager launches; the timed region above runs in the
+            # library's automatic mode: eager launches on a fast host, hipGraph replay of the loop on a slow one)
+            n_prof = min(args.steps, 20)
+            nv.lib().gs_profile_enable(1)
+            for i in range(n_prof):
+                one_step(gs, slam, world_map, prev, lives[i % N_LIVE], K)
+            torch.cuda.synchronize()
+            prof = (n_prof,) + prof_read(nv, 0)
+            nv.lib().gs_profile_enable(0)
 
     # how many ranks really took part, counted THROUGH the collective the poses travel on (N > 1: RCCL = backend "nccl")
     backend_name = torch.distributed.get_backend() if world > 1 else "none (single process)"
@@ -528,17 +608,6 @@ def main():
         # (10 point-to-plane iterations on a nearly fronto-parallel wall slide a little along it: 2-3 cm over the 1-4 cm
         # of motion; a wrong association or a broken solve is off by decimetres.  Exact parity: tests/, -m gpu.)
         assert pose_err < 0.06, "recovered poses are off the synthetic trajectory by {} m".format(pose_err)
-        ns = nt = (H // DS) * (W // DS)
-        avg_knn_ms = ms_knn / max(n_knn, 1)
-        valu = None
-        for name in ("r03_pmc_knn1_loop_valu.json", "r02_pmc_knn1_loop_valu.json"):  # executed work of the same kernel on the same
-            try:                                                                      # workload: committed counter passes, newest first
-                with open(os.path.join(ROOT, "profiles", name)) as f:
-                    valu = json.load(f)
-                valu["profile_file"] = name  # (each profile carries the commit it was taken at)
-                break
-            except Exception:
-                pass
         line = {
             "metric": "RGB-D frames/sec (640x480, 10 ICP iters)",
             "value": round(world * args.steps / dt, 3),
@@ -557,44 +626,11 @@ def main():
             "config": {"workload": "c2: ICP odometry localisation step, 640x480 TUM-shape synthetic RGB-D, batch 1 per GPU, "
                                    "dsratio 4 (~19k x ~19k points), 10 LM iterations, map {} points".format(n_map),
                        "parallelism": "one sequence per GPU, final RCCL all_gather of poses", "pose_max_abs_err": pose_err,
-                       "timing": "median of {} timed regions of {} steps each".format(len(dts), args.steps)},
-            "roofline_timed_region": {
-                "kernel": "knn1_loop_k<true> (X+K+J fused: the previous iteration's O(1) step -- reduce, LM decision, 6x6 solve, exp -- "
-                          "on wave 0 while one wave plans the tile's windows, one prepares the lanes' rows and seeds and thirteen stage the targets; then rigid transform, exact 1-NN association by grid "
-                          "search with a geometric proof per point (exact chunk-box search for the points it fails for), "
-                          "Jacobian rows and 29-term reduce of its 64-point tile)",
-                "launches": n_knn, "avg_launch_ms": round(avg_knn_ms, 5),
-                "timing_source": "HIP events on the launch stream, second eager pass of {} steps".format(n_prof),
-                "hbm_view": {"algorithmic_bytes_per_launch": 40.0 * ns, "achieved_GBps": round(40.0 * ns / (avg_knn_ms * 1e-3) / 1e9, 2)
-                             if n_knn else 0.0, "frac_of_8TBps": round(40.0 * ns / (avg_knn_ms * 1e-3) / 8e12, 5) if n_knn else 0.0,
-                             "note": "0.77 MB per launch lives in L2: not an HBM measurement (fetched / written bytes per launch from "
-                                     "counter passes: profiles/r05_pmc_knn1_loop_traffic.json -- 1.8 MiB / 0.45 MiB raw)"},
-                "valu_view": valu if valu is not None else {"note": "no committed counter pass found under profiles/"}},
+                       "timing": "median of {} timed regions of {} steps each".format(len(dts), args.steps) if len(dts) > 1
+                                 else "one timed region of {} steps".format(args.steps)},
         }
-        try:
-            line["roofline"] = hbm_roofline_linearize(gs, dev)
-        except Exception as e:  # pragma: no cover
-            line["roofline"] = {"error": str(e)}
-        if world == 1 and not os.environ.get("GS_BENCH_SHORT"):
-            try:
-                line["roofline_real_associations"] = hbm_linearize_real_associations(gs, dev)
-            except Exception as e:  # pragma: no cover
-                line["roofline_real_associations"] = {"error": str(e)}
-        if world == 1:
-            try:
-                line["aux"] = aux_pointfusion(gs, dev, raw)
-            except Exception as e:  # pragma: no cover
-                line["aux"] = {"error": str(e)}
-            for key, fn in (("association_other_sizes", aux_association_sizes), ("fusion_update_hbm_view", aux_fusion_update_roofline),
-                            ("pointfusion_c3_200_frames", aux_c3_full_length)):
-                if os.environ.get("GS_BENCH_SHORT"):
-                    break
-                try:
-                    line["aux"][key] = fn(gs, dev)
-                except Exception as e:  # pragma: no cover
-                    line["aux"][key] = {"error": str(e)}
-        if world == 1 and not args.no_cpu_baseline:
-            line["cpu_baseline"] = cpu_baseline(raw)
+        if args.full:
+            full_report(line, args, gs, dev, raw, world, prof)
         print(json.dumps(line), flush=True)
     if world > 1:
         torch.distributed.barrier()

@@ -388,7 +388,7 @@ def test_rgbdimages_plotly_export():
 
 
 def test_recorded_bench_line_follows_the_contract():
-    """The bench line committed under profiles/ (what `python bench.py` printed on the MI355X) carries every key of
+    """The bench line committed under profiles/ (what `python bench.py --full` printed on the MI355X) carries every key of
     the driver's contract, BASELINE.json's metric, and a consistent roofline / cpu_baseline."""
     import glob
     import json
@@ -410,6 +410,24 @@ def test_recorded_bench_line_follows_the_contract():
     assert abs(r["achieved"] - r["algorithmic_bytes_per_launch"] / (r["avg_launch_ms"] * 1e-3) / 1e9) / r["achieved"] < 1e-2
     c = d["cpu_baseline"]
     assert c["kind"] in ("port", "reference") and c["cores"] >= 1 and c["value"] > 0 and c["unit"] == d["unit"] and c["sample"]
+
+
+def test_bench_dump_outputs_writes_float32_npy(tmp_path):
+    """bench.py --dump-outputs: the last timed step's pose and the live frame's local maps, one float32 .npy per array,
+    values unchanged (no GPU: the frame is a stand-in with the two attributes the dump reads)."""
+    import types
+
+    import numpy as np
+
+    import bench
+
+    pose = torch.eye(4).reshape(1, 1, 4, 4)
+    live = types.SimpleNamespace(vertex_map=torch.rand(1, 1, 6, 8, 3), normal_map=torch.rand(1, 1, 6, 8, 3, dtype=torch.float64))
+    bench.dump_outputs(str(tmp_path / "out"), pose, live)
+    assert sorted(os.listdir(tmp_path / "out")) == ["normal_map.npy", "pose.npy", "vertex_map.npy"]
+    for name, want in (("pose", pose), ("vertex_map", live.vertex_map), ("normal_map", live.normal_map.float())):
+        got = np.load(tmp_path / "out" / (name + ".npy"))
+        assert got.dtype == np.float32 and np.array_equal(got, want.numpy())
 
 
 def test_require_hip_rejects_tensors_of_another_device(monkeypatch):

@@ -8,7 +8,7 @@ echo "== all gpu tests"; date
 timeout -k 10 800 python -m pytest tests -q -m gpu > $O/gpu_tests.log 2>&1; echo "gpu tests rc=$?"
 tail -4 $O/gpu_tests.log
 echo "== full bench"; date
-timeout -k 10 900 python bench.py > $O/bench.json 2> $O/bench.err; echo "rc=$?"; tail -2 $O/bench.err
+timeout -k 10 900 python bench.py --full > $O/bench.json 2> $O/bench.err; echo "rc=$?"; tail -2 $O/bench.err
 python - <<P
 import json
 j=json.loads(open("$O/bench.json").read().strip().splitlines()[-1])

@@ -14,6 +14,6 @@ echo "== all gpu tests"; date
 timeout -k 10 600 python -m pytest tests -q -m gpu > $O/gpu_tests.log 2>&1; echo "gpu tests rc=$?"
 tail -8 $O/gpu_tests.log
 echo "== bench (short)"; date
-GS_BENCH_SHORT=1 timeout -k 10 300 python bench.py --no-cpu-baseline > $O/bench_short.json 2> $O/bench_short.err; echo "bench rc=$?"; cut -c1-400 $O/bench_short.json
+GS_BENCH_SHORT=1 timeout -k 10 300 python bench.py --full --no-cpu-baseline > $O/bench_short.json 2> $O/bench_short.err; echo "bench rc=$?"; cut -c1-400 $O/bench_short.json
 find $O -name "*kernel_trace.csv" -size +30M -delete
 date

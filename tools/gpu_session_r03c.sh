@@ -9,7 +9,7 @@ timeout -k 10 500 python -m pytest tests/test_gpu_parity.py -q -s -m gpu -k "den
 grep -E "passed|failed|pose rel err|merged rows|Error" $O/tests_dense.log | tail -20
 for mode in 1 2; do
   echo "== bench short, GS_GRID_MODE=$mode"; date
-  GS_GRID_MODE=$mode GS_BENCH_SHORT=1 timeout -k 10 300 python bench.py --no-cpu-baseline > $O/bench_short_m$mode.json 2> $O/bench_short_m$mode.err; echo "rc=$?"; cut -c1-330 $O/bench_short_m$mode.json
+  GS_GRID_MODE=$mode GS_BENCH_SHORT=1 timeout -k 10 300 python bench.py --full --no-cpu-baseline > $O/bench_short_m$mode.json 2> $O/bench_short_m$mode.err; echo "rc=$?"; cut -c1-330 $O/bench_short_m$mode.json
   GS_GRID_MODE=$mode timeout -k 10 200 python tools/profile_pointfusion.py 200 icp > $O/pf200_m$mode.txt 2>&1; tail -1 $O/pf200_m$mode.txt
   GS_GRID_MODE=$mode timeout -k 10 200 python tools/profile_pointfusion.py 200 gradicp > $O/pf200g_m$mode.txt 2>&1; tail -1 $O/pf200g_m$mode.txt
 done

@@ -8,7 +8,7 @@ timeout -k 10 500 python -m pytest tests/test_gpu_parity.py -q -s -m gpu -k "gri
 grep -E "passed|failed|pose rel err|map size differs|overflow|Error" $O/tests_a.log | tail -24
 run() {  # label, env...
   local label=$1; shift
-  env "$@" GS_BENCH_SHORT=1 timeout -k 10 300 python bench.py --no-cpu-baseline > $O/bench_$label.json 2> $O/bench_$label.err
+  env "$@" GS_BENCH_SHORT=1 timeout -k 10 300 python bench.py --full --no-cpu-baseline > $O/bench_$label.json 2> $O/bench_$label.err
   python - <<P
 import json
 j=json.loads(open("$O/bench_$label.json").read().strip().splitlines()[-1])

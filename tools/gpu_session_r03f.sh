@@ -11,7 +11,7 @@ for n in 150 6; do
 done
 run() {  # label, env...
   local label=$1; shift
-  env "$@" GS_BENCH_SHORT=1 timeout -k 10 300 python bench.py --no-cpu-baseline > $O/bench_$label.json 2> $O/bench_$label.err
+  env "$@" GS_BENCH_SHORT=1 timeout -k 10 300 python bench.py --full --no-cpu-baseline > $O/bench_$label.json 2> $O/bench_$label.err
   python - <<P
 import json
 j=json.loads(open("$O/bench_$label.json").read().strip().splitlines()[-1])

@@ -10,7 +10,7 @@ GS_GRID_MODE=2 timeout -k 10 200 python tools/knn_diag_long.py 150 > $O/diag_m2_
 GS_GRID_MODE=2 timeout -k 10 200 python tools/knn_diag_long.py 6 > $O/diag_m2_6.txt 2>&1; sed -n 3,12p $O/diag_m2_6.txt
 run() {  # label, env...
   local label=$1; shift
-  env "$@" GS_BENCH_SHORT=1 timeout -k 10 300 python bench.py --no-cpu-baseline > $O/bench_$label.json 2> $O/bench_$label.err
+  env "$@" GS_BENCH_SHORT=1 timeout -k 10 300 python bench.py --full --no-cpu-baseline > $O/bench_$label.json 2> $O/bench_$label.err
   python - <<P
 import json
 j=json.loads(open("$O/bench_$label.json").read().strip().splitlines()[-1])

@@ -14,5 +14,5 @@ GS_GRAPH=1 timeout -k 10 200 python tools/profile_pointfusion.py 60 icp 2>&1 | t
 timeout -k 10 200 python tools/profile_pointfusion.py 60 icp 2>&1 | tail -1
 timeout -k 10 200 python tools/profile_pointfusion.py 200 icp 2>&1 | tail -2
 timeout -k 10 200 python tools/profile_pointfusion.py 200 gradicp 2>&1 | tail -1
-GS_BENCH_SHORT=1 timeout -k 10 300 python bench.py --no-cpu-baseline > $O/bench_short.json 2> $O/bench_short.err; cut -c1-300 $O/bench_short.json
+GS_BENCH_SHORT=1 timeout -k 10 300 python bench.py --full --no-cpu-baseline > $O/bench_short.json 2> $O/bench_short.err; cut -c1-300 $O/bench_short.json
 date

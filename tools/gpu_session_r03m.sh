@@ -10,7 +10,7 @@ echo "== all gpu tests"; date
 timeout -k 10 700 python -m pytest tests -q -m gpu > $O/gpu_tests.log 2>&1; echo "gpu tests rc=$?"
 tail -5 $O/gpu_tests.log
 echo "== full bench"; date
-timeout -k 10 600 python bench.py --no-cpu-baseline > $O/bench.json 2> $O/bench.err; echo "rc=$?"; tail -3 $O/bench.err
+timeout -k 10 600 python bench.py --full --no-cpu-baseline > $O/bench.json 2> $O/bench.err; echo "rc=$?"; tail -3 $O/bench.err
 python - <<P
 import json
 j=json.loads(open("$O/bench.json").read().strip().splitlines()[-1])

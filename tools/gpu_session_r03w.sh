@@ -5,7 +5,7 @@ O=gpurun_out/r03w; mkdir -p $O
 export TMPDIR=/tmp
 timeout -k 10 800 python -m pytest tests -q -m gpu > $O/gpu_tests.log 2>&1; echo "gpu tests rc=$?"; tail -4 $O/gpu_tests.log
 timeout -k 10 200 python tools/knn_diag_long.py 150 > $O/diag_150.txt 2>&1; sed -n 3,12p $O/diag_150.txt
-GS_BENCH_SHORT=1 timeout -k 10 300 python bench.py --no-cpu-baseline 2>/dev/null | cut -c1-330
+GS_BENCH_SHORT=1 timeout -k 10 300 python bench.py --full --no-cpu-baseline 2>/dev/null | cut -c1-330
 timeout -k 10 200 python tools/profile_pointfusion.py 200 icp 2>&1 | tail -1
 timeout -k 10 200 python tools/profile_pointfusion.py 200 gradicp 2>&1 | tail -1
 timeout -k 10 300 python tools/fwd_bwd_c3.py 200 gradicp 2>&1 | tail -1

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Memory-side traffic of the association kernel from two rocprofv3 counter passes (FETCH_SIZE, WRITE_SIZE; each with
---kernel-trace only) over `python3 bench.py --no-cpu-baseline --steps 20 --warmup 3`.
+--kernel-trace only) over `python3 bench.py --full --no-cpu-baseline --steps 20 --warmup 3`.
 
     python3 tools/pmc_knn_traffic.py <fetch counter_collection.csv> <write counter_collection.csv> <out.json> [grid] [first_n]
 
@@ -34,7 +34,7 @@ nw, w_mean, _, _ = per_launch(wsrc, "WRITE_SIZE", grid, first_n)
 ns = 19200  # source points of the c2 step's capacity (160 x 120)
 out = {"commit": os.environ.get("GS_COMMIT", "unknown"),
        "source": "rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE (separate passes, with --kernel-trace only) over `python3 bench.py "
-                 "--no-cpu-baseline --steps 20 --warmup 3`, MI355X; tools/pmc_knn_traffic.py",
+                 "--full --no-cpu-baseline --steps 20 --warmup 3`, MI355X; tools/pmc_knn_traffic.py",
        "kernel": "knn1_loop_k, c2 grid (%d work-items), first %d launches in dispatch order" % (grid, nf),
        "FETCH_SIZE_KiB_mean": round(f_mean, 1), "FETCH_SIZE_KiB_min": round(f_min, 1), "FETCH_SIZE_KiB_max": round(f_max, 1),
        "WRITE_SIZE_KiB_mean": round(w_mean, 1),

@@ -4,7 +4,7 @@
     cd /tmp && export TMPDIR=/tmp
     GS_BENCH_SHORT=1 GS_BENCH_REPEATS=1 rocprofv3 --pmc SQ_INSTS_VALU SQ_WAVES SQ_BUSY_CYCLES SQ_ACTIVE_INST_VALU \
         SQ_WAVE_CYCLES SQ_WAIT_ANY GRBM_GUI_ACTIVE --kernel-trace --output-format csv -d <dir> -- \
-        python3 bench.py --no-cpu-baseline --steps 20 --warmup 3
+        python3 bench.py --full --no-cpu-baseline --steps 20 --warmup 3
     python3 tools/pmc_knn_valu.py <dir>/**/*counter_collection.csv profiles/r02_pmc_knn1_loop_valu.json [grid] [first_n]
 
 Takes the FIRST first_n (default 561 = (8 priming + 3 warm-up + 20 timed + 20 event-timed) steps x 11) launches of
@@ -39,7 +39,7 @@ assert n, "no knn1_loop_k launch with grid %d in %s" % (grid, src)
 mean = lambda k: sum(d.get(k, 0.0) for d in per.values()) / n
 import os
 out = {"commit": os.environ.get("GS_COMMIT", "unknown"),
-       "source": "rocprofv3 --pmc (one pass, with --kernel-trace only) over `python3 bench.py --no-cpu-baseline --steps 20 --warmup 3`, "
+       "source": "rocprofv3 --pmc (one pass, with --kernel-trace only) over `python3 bench.py --full --no-cpu-baseline --steps 20 --warmup 3`, "
                  "MI355X; tools/pmc_knn_valu.py; read from this committed profile by bench.py, NOT measured in the bench run",
        "kernel": sorted(set(x.split("(")[0] for x in names.values())), "launches": n, "grid_work_items": grid}
 for k in ("SQ_INSTS_VALU", "SQ_WAVES", "SQ_BUSY_CYCLES", "SQ_ACTIVE_INST_VALU", "SQ_WAVE_CYCLES", "SQ_WAIT_ANY", "GRBM_GUI_ACTIVE"):

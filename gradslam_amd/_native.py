@@ -93,6 +93,7 @@ SIGNATURES = {
     "gs_slam_localize": (c_i, [c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_p, c_p, c_p, c_i, c_i, c_i, c_f, c_f, c_f, c_f, c_f,
                                c_f, c_p, c_p, c_p, c_p, c_p, c_p, c_sz, c_p]),
     "gs_set_grid_search": (None, [c_i]),
+    "gs_set_fused_setup": (None, [c_i]),
     "gs_set_tile_points": (None, [c_i]),
     "gs_icp_launch_geometry": (c_i, [c_i, c_i, ctypes.POINTER(c_i), ctypes.POINTER(c_i), ctypes.POINTER(c_i)]),
     "gs_loop_counts": (c_i, [ctypes.POINTER(ctypes.c_uint), c_i]),

@@ -5,6 +5,7 @@
 // read of the points is served by L2 / Infinity Cache and costs less than a 4 B/pt flag round trip.
 #include "gs_common.hpp"
 #include "gs_compact.hpp"
+#include "gs_maps.hpp"
 #include "gs_project.hpp"
 
 namespace gs {
@@ -143,6 +144,33 @@ struct ActiveWriterH {
         r.x = 0; r.y = i; r.z = h; r.w = w;
         *reinterpret_cast<longlong4 *>(rows + 4 * pos) = r;
         atomicAdd(cnt + (h / ds) * Wd + (w / ds), 1);
+    }
+    __device__ void operator()(int64_t i, int64_t pos) const { put(ActivePredH::Item{ld3(points, i)}, i, pos); }
+};
+
+// The write pass of the fused front end (setup_front1): the active row at reference-order position `pos` goes straight to the
+// ICP target (what tgt_scatter_gather1_k gathers from the 32-byte row record), and only its ds-grid pixel is kept for the
+// bucketing (icp.hip's prepare launch); the per-pixel histogram as ActiveWriterH builds it.
+struct ActiveWriterT {
+    const float *points, *normals;
+    int H, W, ds, Wd;
+    float umax, vmax;
+    int *cnt;
+    int cap;
+    float *tgt, *tnrm;
+    int32_t *tgt_index;  // or NULL
+    int32_t *row_pix;
+    __device__ void put(const ActivePredH::Item &it, int64_t i, int64_t pos) const {
+        int h, w;
+        project_point(cam_cache()[0], it.p, H, W, umax, vmax, h, w);
+        const int pix = (h / ds) * Wd + (w / ds);
+        atomicAdd(cnt + pix, 1);
+        row_pix[pos] = pix;
+        if (pos < cap) {
+            st3(tgt, pos, it.p);
+            st3(tnrm, pos, ld3(normals, i));
+            if (tgt_index) tgt_index[pos] = (int32_t)i;
+        }
     }
     __device__ void operator()(int64_t i, int64_t pos) const { put(ActivePredH::Item{ld3(points, i)}, i, pos); }
 };
@@ -396,6 +424,135 @@ int project_target1(const float *points, const int32_t *counts, int Nmax, const 
     hipLaunchKernelGGL(pix_scan_k, dim3(1), dim3(1024), 0, st, cnt, npix, pix_start);
     hipLaunchKernelGGL(tgt_scatter_gather1_k, dim3(min(cdiv(Nmax, 256), 1024)), dim3(256), 0, st, rows, nrows, points, map_normals, cap,
                        tgt, tnrm, nt, tgt_index, Wd, ds, pix_start, fill, scan_points, scan_orig, tgt_pix);
+    GS_LAUNCH_CHECK(name);
+    return GS_OK;
+}
+
+// ---------------------------------------------------------------- fused front end of gs_slam_localize (one sequence)
+// The maps kernel, the projection of the map, the frame's ds-grid cloud and the target's bucketing by pixel in three launches
+// instead of six (vertex_normal_k, compact_count2_k, compact_write2_k, pix_scan_k, tgt_scatter_gather1_k):
+//   L1 setup_count_k: the map's and the frame's count passes (blocks [0, nbA) and [nbA, nbA + nbB), ahead in the grid so that
+//      they run beside the maps' tiles, not behind them) + vertex_normal_k's tiles; the count pass also zeroes the per-pixel
+//      counters.  Neither count pass reads the maps: only the frame's WRITE pass does (gvertex).
+//   L2 compact_write2_k<ActivePredH, ActiveWriterT, .., DsPred, DsWriter>: the target in reference order + the histogram, and
+//      the frame's source cloud.
+template <class PA, class PB>
+__global__ __launch_bounds__(kCT) void setup_count_k(int64_t nA, PA pa, int *__restrict__ countsA, unsigned char *__restrict__ flagsA, int nbA,
+                                                     int64_t nB, PB pb, int *__restrict__ countsB, int nbB, const float *__restrict__ depth,
+                                                     const float *__restrict__ Ks, const float *__restrict__ poses, int H, int W, int gx,
+                                                     float *__restrict__ vertex, float *__restrict__ normal, float *__restrict__ gvertex,
+                                                     float *__restrict__ gnormal, VnExtra ex) {
+    static_assert(kCT == TW * TH, "one block size for all three jobs");
+    const int bid = (int)blockIdx.x;
+    if (bid < nbA) {
+        compact_count_body(nA, pa, countsA, flagsA, bid, nbA);
+    } else if (bid < nbA + nbB) {
+        compact_count_body(nB, pb, countsB, (unsigned char *)nullptr, bid - nbA, nbB);
+    } else {
+        const int t = bid - nbA - nbB;
+        vertex_normal_body(depth, Ks, poses, 1, H, W, vertex, normal, gvertex, gnormal, ex, t % gx, t / gx, 0);
+    }
+}
+
+// L3 bucket_scatter_k: pix_scan_k + tgt_scatter_gather1_k's scatter in one launch:
+//  * every block scans the final per-pixel counts into LDS (the 77 KB of a 160x120 grid: one coalesced read, one block scan);
+//    block 0 also stores them as hints.pix_start for the association kernel;
+//  * every row of the reference-order target goes to slot start[pix] + atomicAdd(fill[pix]) -- the slot rule of
+//    tgt_scatter_gather1_k: within a pixel, arrival order.
+// (The loop's chunk boxes stay icp_prepare_k's.  Built here by atomic min / max on the float bits -- exact, and it would save
+// that launch too -- this launch took 43 us instead of ~5: ~115 k scattered atomics execute at the memory side, one 64-B
+// request per lane.)
+constexpr int kBucketPixMax = 24 * 1024;  // ds-grid pixels whose starts fit in LDS
+constexpr int kBucketBlocks = 128;
+__global__ __launch_bounds__(1024) void bucket_scatter_k(const float *__restrict__ tgt, const int32_t *__restrict__ d_nt, int cap,
+                                                         const int32_t *__restrict__ row_pix, const int *__restrict__ cnt,
+                                                         int *__restrict__ fill, int npix, int32_t *__restrict__ pix_start,
+                                                         float *__restrict__ scan_pts, int32_t *__restrict__ scan_orig) {
+    __shared__ int starts[kBucketPixMax];
+    __shared__ int sm[1024 / 64 + 1];
+    const int nt = *d_nt;
+    for (int i = threadIdx.x; i < npix; i += 1024) starts[i] = cnt[i];
+    // the thread's first row is requested before the scan: its loads overlap it
+    const int stride = gridDim.x * 1024;
+    int r = blockIdx.x * 1024 + threadIdx.x, pix = 0;
+    f3 p{0.0f, 0.0f, 0.0f};
+    if (r < nt) { pix = row_pix[r]; p = ld3(tgt, r); }
+    __syncthreads();
+    // exclusive scan of the counts in place (pix_scan_k's arithmetic on one tile)
+    const int per = (npix + 1023) / 1024;
+    const int i0 = min(npix, (int)threadIdx.x * per), i1 = min(npix, i0 + per);
+    int sum = 0;
+    for (int i = i0; i < i1; ++i) sum += starts[i];
+    int total;
+    int run = block_excl_scan<1024>(sum, sm, &total);
+    for (int i = i0; i < i1; ++i) { const int c = starts[i]; starts[i] = run; run += c; }
+    __syncthreads();
+    if (blockIdx.x == 0) {
+        for (int i = threadIdx.x; i < npix; i += 1024) pix_start[i] = starts[i];
+        if (threadIdx.x == 0) pix_start[npix] = total;
+    }
+    for (; r < nt; r += stride) {
+        const int slot = starts[pix] + atomicAdd(fill + pix, 1);
+        const int rn = r + stride;  // (the next row's loads go out while the atomic is in flight)
+        int pn = 0;
+        f3 pp{0.0f, 0.0f, 0.0f};
+        if (rn < nt) { pn = row_pix[rn]; pp = ld3(tgt, rn); }
+        if (slot < cap) {
+            st3(scan_pts, slot, p);
+            scan_orig[slot] = r;
+        }
+        pix = pn; p = pp;
+    }
+}
+
+int project_front1(const float *depth, const float *points, const int32_t *counts, int Nmax, const float *poses, const float *intrinsics,
+                   int H, int W, int ds, const float *map_normals, int cap, float *vertex, float *normal, float *gvertex, float *gnormal,
+                   float *cam_out, int32_t *row_pix, float *tgt, float *tnrm, int32_t *nt, int32_t *tgt_index, float *scan_points,
+                   int32_t *scan_orig, int32_t *pix_start, const DsJob &frame, void *ws, size_t ws_bytes, hipStream_t st) {
+    const char *name = "gs_slam_localize/front";
+    if (!ws || ws_bytes < project_target1_ws_bytes(H, W, ds, Nmax)) {  // (the same pieces in another order)
+        set_error("%s: workspace too small", name);
+        return GS_ERR_WORKSPACE_TOO_SMALL;
+    }
+    const int Wd = cdiv(W, ds), Hd = cdiv(H, ds), npix = Hd * Wd;
+    if (npix > kBucketPixMax) {
+        set_error("%s: ds-grid too large for the fused form", name);
+        return GS_ERR_INVALID_ARG;
+    }
+    int *cnt = (int *)ws, *fill = (int *)((char *)ws + align_up((size_t)npix * 4, 256));
+    char *p = (char *)ws + 2 * align_up((size_t)npix * 4, 256);
+    int *countsA = (int *)p; p += compact_ws_bytes(Nmax);
+    unsigned char *flags = (unsigned char *)p; p += compact_flags_bytes(Nmax);
+    int *countsB = (int *)p;
+    const float umax = (float)((double)W - 0.999), vmax = (float)((double)H - 0.999);
+    ActivePredH pa{points, counts, poses, intrinsics, Nmax, H, W, ds, umax, vmax, cnt, fill, npix};
+    ActiveWriterT wa{points, map_normals, H, W, ds, Wd, umax, vmax, cnt, cap, tgt, tnrm, tgt_index, row_pix};
+    DsPred pb{frame.depth, W, Wd, ds};
+    DsWriter wb{frame.gvertex, nullptr, nullptr, frame.out_points, nullptr, nullptr, frame.out_pix, W, Wd, ds};
+    const int64_t nA = Nmax, nB = (int64_t)npix;
+    const int nbA = compact_blocks(nA), nbB = compact_blocks(nB), gx = cdiv(W, TW), nbV = depth ? gx * cdiv(H, TH) : 0;  // (depth NULL: no maps)
+    if (nbB > kSelfScanBlocks) {
+        set_error("%s: ds-grid too large for the fused form", name);
+        return GS_ERR_INVALID_ARG;
+    }
+    const VnExtra ex{nullptr, 1.0f, 0.0f, nullptr, nullptr, nullptr, 0, cam_out};
+    hipLaunchKernelGGL((setup_count_k<ActivePredH, DsPred>), dim3(nbA + nbB + nbV), dim3(kCT), 0, st, nA, pa, countsA, flags, nbA, nB, pb,
+                       countsB, nbB, depth, intrinsics, poses, H, W, gx, vertex, normal, gvertex, gnormal, ex);
+    GS_LAUNCH_CHECK(name);
+    if (nbA <= kSelfScanBlocks) {
+        hipLaunchKernelGGL((compact_write2_k<ActivePredH, ActiveWriterT, true, DsPred, DsWriter>), dim3(nbA + nbB), dim3(kCT), 0, st, nA, pa, wa,
+                           (const int *)countsA, nt, (const unsigned char *)flags, nbA, nB, pb, wb, (const int *)countsB, frame.count, nbB);
+    } else {  // a map of more than a million points: its write pass needs the scan launch
+        int *offsetsA = countsA + nbA;
+        hipLaunchKernelGGL(compact_scan_k, dim3(1), dim3(1024), 0, st, countsA, nbA, offsetsA, nt);
+        GS_LAUNCH_CHECK(name);
+        hipLaunchKernelGGL((compact_write2_k<ActivePredH, ActiveWriterT, false, DsPred, DsWriter>), dim3(nbA + nbB), dim3(kCT), 0, st, nA, pa, wa,
+                           (const int *)offsetsA, (int *)nullptr, (const unsigned char *)flags, nbA, nB, pb, wb, (const int *)countsB,
+                           frame.count, nbB);
+    }
+    GS_LAUNCH_CHECK(name);
+    hipLaunchKernelGGL(bucket_scatter_k, dim3(std::min(cdiv(cap, 1024), kBucketBlocks)), dim3(1024), 0, st, (const float *)tgt,
+                       (const int32_t *)nt, cap, (const int32_t *)row_pix, (const int *)cnt, fill, npix, pix_start, scan_points, scan_orig);
     GS_LAUNCH_CHECK(name);
     return GS_OK;
 }

@@ -91,6 +91,12 @@ int project_target1(const float *points, const int32_t *counts, int Nmax, const 
                     int W, int ds, const float *map_normals, int cap, int64_t *rows, int32_t *nrows, float *tgt, float *tnrm,
                     int32_t *nt, float *scan_points, int32_t *scan_orig, int32_t *pix_start, int32_t *tgt_index, int32_t *tgt_pix,
                     void *ws, size_t ws_bytes, hipStream_t st, const DsJob *frame);
+// project.hip: the fused front end of one sequence, three launches (maps + counts, write, bucketing)
+int project_front1(const float *depth, const float *points, const int32_t *counts, int Nmax, const float *poses, const float *intrinsics,
+                   int H, int W, int ds, const float *map_normals, int cap, float *vertex, float *normal, float *gvertex, float *gnormal,
+                   float *cam_out, int32_t *row_pix, float *tgt, float *tnrm, int32_t *nt, int32_t *tgt_index, float *scan_points,
+                   int32_t *scan_orig, int32_t *pix_start, const DsJob &frame, void *ws, size_t ws_bytes, hipStream_t st);
+constexpr int kFusedPixMax = 24 * 1024;  // project.hip kBucketPixMax: the ds-grid's bin starts live in LDS
 
 struct LocWs {
     float *src;        // (B, capS, 3)
@@ -148,6 +154,13 @@ static size_t loc_layout(int B, int H, int W, int ds, int Nmax, void *ws, LocWs 
         out->sub = p + o_sub; out->sub_bytes = sub;
     }
     return off;
+}
+
+// gs_set_fused_setup: the fused front end (project.hip: project_front1) for one sequence; the environment's GS_FUSED_SETUP
+// (measurements) sets the default
+static int g_fused_setup = getenv("GS_FUSED_SETUP") ? atoi(getenv("GS_FUSED_SETUP")) : 1;
+static inline bool fused_front(int B, int H, int W, int ds) {
+    return g_fused_setup != 0 && B == 1 && (int64_t)cdiv(H, ds) * cdiv(W, ds) <= kFusedPixMax;
 }
 
 // fusion.hip: the fused correspondence chain of the PointFusion update (no tables: 4 bytes per map point), the merge that
@@ -313,6 +326,8 @@ extern "C" {
 
 void gs_set_graph_mode(int mode) { g_graph_mode = mode; }
 
+void gs_set_fused_setup(int on) { g_fused_setup = on; }
+
 int gs_graph_stats(double *out4) {
     GS_REQUIRE(out4, "gs_graph_stats: NULL argument");
     std::lock_guard<std::mutex> lock(g_graph_mu);
@@ -352,16 +367,23 @@ int gs_slam_localize(const float *depth, const float *intrinsics, const float *p
     // live frame posed with the previous pose: maps, then the ds-grid source cloud
     // (the maps kernel also leaves the bucketing camera -- previous pose and intrinsics -- in the workspace: the loops read it
     // from there, an address a captured graph may keep, never from the caller's tensors)
-    if ((rc = vertex_normal_maps_cam(depth, intrinsics, prev_poses, B, H, W, vertex, normal, gvertex, gnormal, w.cam, st))) return rc;
     // map points that land on the ds-grid of the previous frame: the ICP target
     // reference-order target (points, normals, counts) + the same points in pixel order and the first scan
-    // slot of every ds-grid pixel (search hints only); one sequence takes the 4-launch fused form, and the frame's ds-grid
-    // source cloud rides on its first two launches (two launches of ~5 us less on the step's chain)
-    if (B == 1) {
+    // slot of every ds-grid pixel (search hints only).  One sequence takes the fused front end (gs_set_fused_setup; maps +
+    // counts, write, bucketing: three launches) or, switched off, the 4-launch fused form behind the maps kernel, on whose
+    // first two launches the frame's ds-grid source cloud rides (two launches of ~5 us less on the step's chain)
+    if (fused_front(B, H, W, ds)) {
+        const DsJob frame{depth, gvertex, w.src, w.src_pix, w.ns};
+        if ((rc = project_front1(depth, map_points, map_counts, Nmax, prev_poses, intrinsics, H, W, ds, map_normals, capT, vertex, normal,
+                                 gvertex, gnormal, w.cam, (int32_t *)w.rows, w.tgt, w.tnrm, w.nt, nullptr, w.scan, w.scan_orig, w.pix_start,
+                                 frame, w.sub, w.sub_bytes, st))) return rc;
+    } else if (B == 1) {
+        if ((rc = vertex_normal_maps_cam(depth, intrinsics, prev_poses, B, H, W, vertex, normal, gvertex, gnormal, w.cam, st))) return rc;
         const DsJob frame{depth, gvertex, w.src, w.src_pix, w.ns};
         if ((rc = project_target1(map_points, map_counts, Nmax, prev_poses, intrinsics, H, W, ds, map_normals, capT, w.rows, w.nrows,
                                   w.tgt, w.tnrm, w.nt, w.scan, w.scan_orig, w.pix_start, nullptr, nullptr, w.sub, w.sub_bytes, st, &frame))) return rc;
     } else {
+        if ((rc = vertex_normal_maps_cam(depth, intrinsics, prev_poses, B, H, W, vertex, normal, gvertex, gnormal, w.cam, st))) return rc;
         if ((rc = gs_downsample_frame(depth, gvertex, nullptr, nullptr, B, H, W, ds, capS, w.src, nullptr, nullptr, w.src_pix, w.ns,
                                       w.sub, w.sub_bytes, stream))) return rc;
         if ((rc = gs_project_active(map_points, map_counts, B, Nmax, prev_poses, intrinsics, H, W, ds, w.rows, w.nrows, w.sub,
@@ -640,7 +662,12 @@ int gs_slam_localize_taped(const float *depth, const float *gvertex, const float
     loc_tape_layout(B, H, W, ds, Nmax, numiters, use_grad_lm, tape, &tp);
     const int capS = cdiv(H, ds) * cdiv(W, ds), capT = target_cap(Nmax);
     int rc;
-    if (B == 1) {
+    if (fused_front(B, H, W, ds)) {  // (the maps are the caller's: gvertex is an input here -- the count launch carries no maps' tiles)
+        const DsJob frame{depth, gvertex, tp.src, tp.src_pix, tp.ns};
+        if ((rc = project_front1(nullptr, map_points, map_counts, Nmax, prev_poses, intrinsics, H, W, ds, map_normals, capT, nullptr, nullptr,
+                                 nullptr, nullptr, nullptr, (int32_t *)w.rows, w.tgt, w.tnrm, tp.nt, tp.tgt_index, w.scan, w.scan_orig,
+                                 w.pix_start, frame, w.sub, w.sub_bytes, (hipStream_t)stream))) return rc;
+    } else if (B == 1) {
         const DsJob frame{depth, gvertex, tp.src, tp.src_pix, tp.ns};
         if ((rc = project_target1(map_points, map_counts, Nmax, prev_poses, intrinsics, H, W, ds, map_normals, capT, w.rows, w.nrows,
                                   w.tgt, w.tnrm, tp.nt, w.scan, w.scan_orig, w.pix_start, tp.tgt_index, nullptr, w.sub, w.sub_bytes,

@@ -402,6 +402,16 @@ int gs_profile_read(int tag, long *launches, double *total_ms);
  * reference (chamferdist.knn_points has no such switch); for measurements and tests. */
 void gs_set_grid_search(int on);
 
+/* How gs_slam_localize and gs_slam_localize_taped build the loop's input for ONE sequence (B == 1, a ds-grid of at most
+ * 24576 pixels).  1 (default) = the fused front end: three launches -- the maps' tiles with the count passes of the map's
+ * projection and of the frame's ds-grid, the write pass (reference-order target, per-pixel histogram, source cloud), and the
+ * target's bucketing by pixel (scan of the histogram + scatter); 0 = the separate chain (maps, count, write, pixel scan,
+ * target gather / scatter).  Same results bit for bit;
+ * the lines it stands for are gs_slam_localize's (slam/icpslam.py:238-247: live-frame maps, rgbdimages.py:643-762; ds-grid
+ * source cloud, icputils.py:651-669; active map points on the ds-grid, fusionutils.py:247-282 + icputils.py:596-619; the
+ * loop, odometry/icputils.py:310-367).  Replaces nothing in the reference; for measurements and tests. */
+void gs_set_fused_setup(int on);
+
 /* Source points per 1024-thread block of the loops' association kernel: 0 (default) = 64; 32 .. 64 = that many (tests:
  * the tile size fixes the summation order of the 6x6 system, so results of different settings agree to rounding, not bit
  * for bit; nearest neighbours are the brute-force scan's under every setting).  Replaces nothing in the reference. */

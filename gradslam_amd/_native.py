@@ -25,6 +25,9 @@ SIGNATURES = {
     "gs_vertex_normal_maps_backward_ws_bytes": (c_sz, [c_i, c_i, c_i, c_i]),
     "gs_vertex_normal_maps_backward": (c_i, [c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_p,
                                              c_p, c_sz, c_p]),
+    "gs_vertex_normal_maps_backward_det_ws_bytes": (c_sz, [c_i, c_i, c_i, c_i]),
+    "gs_vertex_normal_maps_backward_det": (c_i, [c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_p,
+                                                 c_p, c_sz, c_p]),
     "gs_get_alpha": (c_i, [c_p, c_i64, c_f, c_f, c_p, c_p]),
     "gs_get_alpha_backward": (c_i, [c_p, c_i64, c_f, c_f, c_p, c_p, c_p]),
     "gs_frames_from_raw": (c_i, [c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_f, c_i, c_p, c_p, c_p]),
@@ -62,6 +65,8 @@ SIGNATURES = {
     "gs_icp_linearize": (c_i, [c_p, c_p, c_i, c_p, c_p, c_p, c_f, c_p, c_p, c_sz, c_p]),
     "gs_icp_rows": (c_i, [c_p, c_p, c_i, c_p, c_p, c_p, c_f, c_p, c_p, c_p, c_p]),
     "gs_icp_linearize_backward": (c_i, [c_p, c_p, c_i, c_p, c_p, c_p, c_f, c_p, c_p, c_p, c_p, c_p]),
+    "gs_icp_linearize_backward_det_ws_bytes": (c_sz, [c_i, c_i]),
+    "gs_icp_linearize_backward_det": (c_i, [c_p, c_p, c_i, c_p, c_p, c_p, c_i, c_p, c_f, c_p, c_p, c_p, c_p, c_p, c_sz, c_p]),
     "gs_transform_points": (c_i, [c_p, c_p, c_i, c_p, c_p, c_p]),
     "gs_icp_ws_bytes": (c_sz, [c_i, c_i]),
     "gs_icp_point_to_plane": (c_i, [c_p, c_p, c_i, c_p, c_p, c_p, c_i, c_p, c_i, c_f, c_f, c_p, c_p, c_p, c_p, c_p, c_sz,
@@ -74,12 +79,18 @@ SIGNATURES = {
     "gs_icp_backward_ws_bytes": (c_sz, [c_i]),
     "gs_icp_point_to_plane_backward": (c_i, [c_p, c_p, c_i, c_p, c_p, c_p, c_i, c_p, c_i, c_f, c_i, c_f, c_f, c_f, c_f, c_p, c_sz,
                                              c_p, c_p, c_p, c_p, c_p, c_p, c_sz, c_p]),
+    "gs_icp_backward_det_ws_bytes": (c_sz, [c_i, c_i, c_i, c_i]),
+    "gs_icp_point_to_plane_backward_det": (c_i, [c_p, c_p, c_i, c_p, c_p, c_p, c_i, c_p, c_i, c_f, c_i, c_f, c_f, c_f, c_f, c_p,
+                                                 c_sz, c_p, c_p, c_p, c_p, c_p, c_p, c_sz, c_p]),
     "gs_slam_localize_tape_bytes": (c_sz, [c_i, c_i, c_i, c_i, c_i, c_i, c_i]),
     "gs_slam_localize_taped": (c_i, [c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_p, c_p, c_p, c_i, c_i, c_i, c_f, c_f, c_f, c_f,
                                      c_f, c_f, c_p, c_p, c_sz, c_p, c_sz, c_p]),
     "gs_slam_localize_backward_ws_bytes": (c_sz, [c_i, c_i, c_i, c_i, c_i]),
     "gs_slam_localize_backward": (c_i, [c_p, c_i, c_i, c_i, c_i, c_p, c_p, c_i, c_i, c_i, c_f, c_f, c_f, c_f, c_f, c_p, c_sz,
                                         c_p, c_p, c_p, c_p, c_p, c_i, c_p, c_sz, c_p]),
+    "gs_slam_localize_backward_det_ws_bytes": (c_sz, [c_i, c_i, c_i, c_i, c_i, c_i, c_i]),
+    "gs_slam_localize_backward_det": (c_i, [c_p, c_i, c_i, c_i, c_i, c_p, c_p, c_i, c_i, c_i, c_f, c_f, c_f, c_f, c_f, c_p, c_sz,
+                                            c_p, c_p, c_p, c_p, c_p, c_i, c_p, c_sz, c_p]),
     "gs_pointfusion_update_tape_bytes": (c_sz, [c_i, c_i, c_i]),
     "gs_pointfusion_update_taped": (c_i, [c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_i, c_f, c_f, c_f, c_p, c_p,
                                           c_sz, c_p, c_sz, c_p]),

@@ -41,6 +41,7 @@
 #include "gs_common.hpp"
 #include <type_traits>
 #include "gs_project.hpp"
+#include "gs_detfold.hpp"
 
 namespace gs {
 
@@ -895,7 +896,8 @@ __global__ void icp_rows_k(const float *__restrict__ src, const int32_t *__restr
     }
 }
 
-// adjoint of linearize
+// adjoint of linearize.  DET: g_tgt = contribution rows (gs_detfold.hpp), g_nrm unused
+template <bool DET>
 __global__ void linearize_bwd_k(const float *__restrict__ src, const int32_t *__restrict__ d_ns,
                                 const float *__restrict__ tgt, const float *__restrict__ nrm,
                                 const unsigned long long *__restrict__ best, float thresh,
@@ -909,6 +911,7 @@ __global__ void linearize_bwd_k(const float *__restrict__ src, const int32_t *__
         const Row r = make_row(src, tgt, nrm, best, i, ns, thresh);
         if (!r.valid) {
             if (g_src) st3(g_src, i, f3{0, 0, 0});
+            if (DET && g_tgt) det_store_none(g_tgt, i);
             continue;
         }
         const uint32_t j = (uint32_t)(best[i] & 0xffffffffu);
@@ -933,6 +936,10 @@ __global__ void linearize_bwd_k(const float *__restrict__ src, const int32_t *__
         sb.x -= bb * n.x; sb.y -= bb * n.y; sb.z -= bb * n.z;
         nb.x += bb * (d.x - s.x); nb.y += bb * (d.y - s.y); nb.z += bb * (d.z - s.z);
         if (g_src) st3(g_src, i, sb);
+        if constexpr (DET) {
+            if (g_tgt) det_store_row(g_tgt, i, f3{bb * n.x, bb * n.y, bb * n.z}, nb, (int)j);
+            continue;
+        }
         if (g_tgt) {
             atomicAdd(g_tgt + 3 * (int64_t)j, bb * n.x);
             atomicAdd(g_tgt + 3 * (int64_t)j + 1, bb * n.y);
@@ -2227,9 +2234,11 @@ struct BwdState {
 
 __device__ __forceinline__ const IcpState *rec_state(const float *rec) { return reinterpret_cast<const IcpState *>(rec + REC_STATE); }
 
-// adjoint of one linearised point: returns s_bar, scatters d_bar / n_bar
+// adjoint of one linearised point: returns s_bar, scatters d_bar / n_bar -- or, DET, stores them in row i of this launch's
+// contribution rows (g_tgt = those rows, gs_detfold.hpp; NULL: no target adjoint wanted)
+template <bool DET = false>
 __device__ __forceinline__ f3 lin_point_bwd(const float *G, const Row &r, const f3 s, const uint32_t j, const float *tgt,
-                                            const float *nrm, float *g_tgt, float *g_nrm) {
+                                            const float *nrm, float *g_tgt, float *g_nrm, int i = 0) {
     const f3 d = ld3(tgt, j), n = ld3(nrm, j);
     float ab[6];
 #pragma unroll
@@ -2247,6 +2256,10 @@ __device__ __forceinline__ f3 lin_point_bwd(const float *G, const Row &r, const 
     f3 nb{an.x + (ac.y * s.z - ac.z * s.y), an.y + (ac.z * s.x - ac.x * s.z), an.z + (ac.x * s.y - ac.y * s.x)};
     sb.x -= bb * n.x; sb.y -= bb * n.y; sb.z -= bb * n.z;
     nb.x += bb * (d.x - s.x); nb.y += bb * (d.y - s.y); nb.z += bb * (d.z - s.z);
+    if constexpr (DET) {
+        if (g_tgt) det_store_row(g_tgt, i, f3{bb * n.x, bb * n.y, bb * n.z}, nb, (int)j);
+        return sb;
+    }
     if (g_tgt) {
         atomicAdd(g_tgt + 3 * (int64_t)j, bb * n.x);
         atomicAdd(g_tgt + 3 * (int64_t)j + 1, bb * n.y);
@@ -2512,6 +2525,8 @@ __device__ __forceinline__ void bwd_fold(BwdState &sb, const BwdState *__restric
 }
 
 // B (gradLM), with S1 folded in: adjoint of new_err = e(look, NN(look)); gP_i <- R2^T gP_i + R1^T glook_i ; sums glook (x) s
+// (DET: g_tgt = this launch's contribution rows, g_nrm unused -- gs_detfold.hpp)
+template <bool DET>
 __global__ __launch_bounds__(BWD_T) void bwd_look_k(const BwdState *__restrict__ Sb_in, BwdState *__restrict__ Sb_out,
                                                     const float *__restrict__ rec, const float *__restrict__ partials_in, int nblocks,
                                                     GradParams gp, int prev_slot, LoopBufs B, const int32_t *__restrict__ d_ns,
@@ -2533,7 +2548,8 @@ __global__ __launch_bounds__(BWD_T) void bwd_look_k(const BwdState *__restrict__
     for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < ns; i += gridDim.x * blockDim.x) {
         const Row r = make_row(look, tgt, nrm, nn, i, ns, thresh);
         f3 gl{0.0f, 0.0f, 0.0f};
-        if (r.valid) gl = lin_point_bwd(G, r, ld3(look, i), (uint32_t)(nn[i] & 0xffffffffu), tgt, nrm, g_tgt, g_nrm);
+        if (r.valid) gl = lin_point_bwd<DET>(G, r, ld3(look, i), (uint32_t)(nn[i] & 0xffffffffu), tgt, nrm, g_tgt, g_nrm, i);
+        else if (DET && g_tgt) det_store_none(g_tgt, i);
         acc_outer(acc, gl, ld3(src, i));
         const f3 a = rot_t(R, ld3(gP, i)), b = rot_t(R1, gl);
         st3(gP, i, f3{a.x + b.x, a.y + b.y, a.z + b.z});
@@ -2543,6 +2559,8 @@ __global__ __launch_bounds__(BWD_T) void bwd_look_k(const BwdState *__restrict__
 
 // C, with S2 (gradLM) or S (LM) folded in: gP_i <- (rotate ? R2^T gP_i : gP_i) + adjoint of (H, g, e) at the iteration's
 // source cloud; sums of gP (x) predecessor cloud for the small step of the iteration that made this cloud
+// (DET: g_tgt = this launch's contribution rows, g_nrm unused -- gs_detfold.hpp)
+template <bool DET>
 __global__ __launch_bounds__(BWD_T) void bwd_lin_k(const BwdState *__restrict__ Sb_in, BwdState *__restrict__ Sb_out, int fold,
                                                    const float *__restrict__ rec, const float *__restrict__ partials_in, int nblocks,
                                                    int iter, int rotate, LoopBufs B, const float *__restrict__ user_src,
@@ -2554,6 +2572,8 @@ __global__ __launch_bounds__(BWD_T) void bwd_lin_k(const BwdState *__restrict__ 
     bwd_fold(sb, Sb_in, Sb_out, fold, rec, partials_in, nblocks, GradParams{}, iter);
     if (!sb.active) {  // rejected LM iteration: gP stays as it is, the pending sums are handed on unchanged
         if (threadIdx.x < 12) partials[blockIdx.x * 12 + threadIdx.x] = partials_in[blockIdx.x * 12 + threadIdx.x];
+        if (DET && g_tgt)  // no contributions from this launch
+            for (int i = blockIdx.x * blockDim.x + threadIdx.x, ns = *d_ns; i < ns; i += gridDim.x * blockDim.x) det_store_none(g_tgt, i);
         return;
     }
     const float *G = sb.G, *R = sb.R2;
@@ -2569,8 +2589,10 @@ __global__ __launch_bounds__(BWD_T) void bwd_lin_k(const BwdState *__restrict__ 
         f3 g = ld3(gP, i);
         if (rotate) g = rot_t(R, g);
         if (r.valid) {
-            const f3 sb_ = lin_point_bwd(G, r, ld3(src, i), (uint32_t)(nn[i] & 0xffffffffu), tgt, nrm, g_tgt, g_nrm);
+            const f3 sb_ = lin_point_bwd<DET>(G, r, ld3(src, i), (uint32_t)(nn[i] & 0xffffffffu), tgt, nrm, g_tgt, g_nrm, i);
             g.x += sb_.x; g.y += sb_.y; g.z += sb_.z;
+        } else if (DET && g_tgt) {
+            det_store_none(g_tgt, i);
         }
         st3(gP, i, g);
         acc_outer(acc, g, ld3(prev, i));
@@ -2637,14 +2659,23 @@ __global__ __launch_bounds__(BWD_T) void bwd_finish_k(const float *__restrict__ 
     }
 }
 
+// det: the target / normal adjoints by the deterministic fold (gs_detfold.hpp) -- reverse launch q (q = numiters - 1 - k for LM;
+// 2 (numiters - 1 - k) and + 1 for gradLM's look / lin pair) stores its contributions in its own rows, the fold adds them up
+static inline int bwd_launches(bool grad, int numiters) { return grad ? 2 * numiters : numiters; }
+static inline size_t bwd_det_ws_bytes(bool grad, int max_ns, int max_nt, int numiters) {
+    return align_up(bwd_ws_layout(max_ns, nullptr, nullptr), 256) +
+           det_ws_layout(bwd_launches(grad, numiters > 0 ? numiters : 1), max_ns, max_nt, nullptr, nullptr);
+}
+
 static int icp_backward_run(bool grad, const float *src, const int32_t *d_ns, int max_ns, const float *tgt, const float *nrm,
                             const int32_t *d_nt, int max_nt, const float *init_T, int numiters, float thresh, GradParams gp, const void *tape,
                             size_t tape_bytes, const float *grad_T, float *g_src, float *g_tgt, float *g_nrm, float *g_init_T,
-                            void *ws, size_t ws_bytes, hipStream_t st) {
-    const char *name = "gs_icp_backward";
+                            void *ws, size_t ws_bytes, hipStream_t st, bool det = false) {
+    const char *name = det ? "gs_icp_backward_det" : "gs_icp_backward";
     GS_REQUIRE(src && d_ns && tgt && nrm && d_nt && init_T && tape && grad_T && g_src && g_init_T, "%s: NULL argument", name);
     GS_REQUIRE(max_ns > 0 && max_nt > 0 && numiters >= 0, "%s: bad sizes", name);
-    if (!ws || ws_bytes < bwd_ws_layout(max_ns, nullptr, nullptr)) {
+    GS_REQUIRE(!det || bwd_launches(grad, numiters) <= 65535, "%s: too many iterations for the deterministic fold", name);
+    if (!ws || ws_bytes < (det ? bwd_det_ws_bytes(grad, max_ns, max_nt, numiters) : bwd_ws_layout(max_ns, nullptr, nullptr))) {
         set_error("%s: workspace too small", name);
         return GS_ERR_WORKSPACE_TOO_SMALL;
     }
@@ -2653,33 +2684,43 @@ static int icp_backward_run(bool grad, const float *src, const int32_t *d_ns, in
     tape_layout(grad, max_ns, numiters, (void *)tape, &tp);
     BwdWs w;
     bwd_ws_layout(max_ns, ws, &w);
+    DetWs dw{};
+    const bool fold = det && (g_tgt || g_nrm);
+    if (fold) det_ws_layout(bwd_launches(grad, numiters), max_ns, max_nt, (char *)ws + align_up(bwd_ws_layout(max_ns, nullptr, nullptr), 256), &dw);
+    // what the walk's kernels scatter into: the outputs (float atomics) or, DET, launch q's contribution rows
+    auto rows_of = [&](int q) { return fold ? dw.rows + (size_t)q * max_ns * DET_ROW : nullptr; };
+    float *walk_nrm = det ? nullptr : g_nrm;
     const int nb = min(cdiv(max_ns, BWD_T), BWD_MAXB);
     int cur = 0;  // buffer the next launch READS its state / the previous sums from
     hipLaunchKernelGGL(bwd_begin_k, dim3(min(cdiv(3 * max(max_nt, max_ns), 256), 1024)), dim3(256), 0, st, w.S[0], grad_T, w.gP, 3 * max_ns,
-                       w.partials[0], nb * 12, g_tgt, g_nrm, d_nt, max_nt);
-    for (int k = numiters - 1; k >= 0; --k) {
+                       w.partials[0], nb * 12, det ? nullptr : g_tgt, walk_nrm, d_nt, max_nt);
+    for (int k = numiters - 1, q = 0; k >= 0; --k) {
         if (!grad) {
             const float *rec = tp.rec + (size_t)(1 + k) * REC_WORDS;
-            hipLaunchKernelGGL(bwd_lin_k, dim3(nb), dim3(BWD_T), 0, st, (const BwdState *)w.S[cur], w.S[1 - cur], (int)FOLD_LM, rec,
-                               (const float *)w.partials[cur], nb, k, 1, tp.B, src, d_ns, tgt, nrm, thresh, w.gP, g_tgt, g_nrm,
-                               w.partials[1 - cur]);
+            float *gt = det ? rows_of(q++) : g_tgt;
+            hipLaunchKernelGGL(det ? bwd_lin_k<true> : bwd_lin_k<false>, dim3(nb), dim3(BWD_T), 0, st, (const BwdState *)w.S[cur],
+                               w.S[1 - cur], (int)FOLD_LM, rec, (const float *)w.partials[cur], nb, k, 1, tp.B, src, d_ns, tgt, nrm, thresh,
+                               w.gP, gt, walk_nrm, w.partials[1 - cur]);
             cur = 1 - cur;
         } else {
             const float *rec = tp.rec + (size_t)(1 + 2 * k) * REC_WORDS;
             // slots of the gradLM loop are fixed: cloud k lives in slot 0 (k = 0) or 2k
-            hipLaunchKernelGGL(bwd_look_k, dim3(nb), dim3(BWD_T), 0, st, (const BwdState *)w.S[cur], w.S[1 - cur], rec,
-                               (const float *)w.partials[cur], nb, gp, k == 0 ? -1 : (k == 1 ? 0 : 2 * (k - 1)), tp.B, d_ns, tgt, nrm, thresh,
-                               w.gP, g_tgt, g_nrm, w.partials[1 - cur]);
+            float *gt = det ? rows_of(q++) : g_tgt;
+            hipLaunchKernelGGL(det ? bwd_look_k<true> : bwd_look_k<false>, dim3(nb), dim3(BWD_T), 0, st, (const BwdState *)w.S[cur],
+                               w.S[1 - cur], rec, (const float *)w.partials[cur], nb, gp, k == 0 ? -1 : (k == 1 ? 0 : 2 * (k - 1)), tp.B, d_ns,
+                               tgt, nrm, thresh, w.gP, gt, walk_nrm, w.partials[1 - cur]);
             cur = 1 - cur;
-            hipLaunchKernelGGL(bwd_lin_k, dim3(nb), dim3(BWD_T), 0, st, (const BwdState *)w.S[cur], w.S[1 - cur], (int)FOLD_G2, rec,
-                               (const float *)w.partials[cur], nb, 0, 0, tp.B, src, d_ns, tgt, nrm, thresh, w.gP, g_tgt, g_nrm,
-                               w.partials[1 - cur]);
+            gt = det ? rows_of(q++) : g_tgt;
+            hipLaunchKernelGGL(det ? bwd_lin_k<true> : bwd_lin_k<false>, dim3(nb), dim3(BWD_T), 0, st, (const BwdState *)w.S[cur],
+                               w.S[1 - cur], (int)FOLD_G2, rec, (const float *)w.partials[cur], nb, 0, 0, tp.B, src, d_ns, tgt, nrm, thresh,
+                               w.gP, gt, walk_nrm, w.partials[1 - cur]);
             cur = 1 - cur;
         }
     }
     hipLaunchKernelGGL(bwd_finish_k, dim3(nb), dim3(BWD_T), 0, st, init_T, d_ns, (const float *)w.gP, g_src, (const BwdState *)w.S[cur],
                        (const float *)w.partials[cur], nb, g_init_T);
     GS_LAUNCH_CHECK(name);
+    if (fold) return det_fold_run(dw, bwd_launches(grad, numiters), max_ns, d_ns, d_nt, max_nt, g_tgt, g_nrm, st, name);
     return GS_OK;
 }
 
@@ -2838,9 +2879,35 @@ int gs_icp_linearize_backward(const float *src, const int32_t *d_ns, int max_ns,
                               float *g_src, float *g_tgt, float *g_normals, gs_stream_t stream) {
     GS_REQUIRE(src && d_ns && tgt && tgt_normals && best && g_out43, "gs_icp_linearize_backward: NULL argument");
     if (max_ns <= 0) return GS_OK;
-    hipLaunchKernelGGL(linearize_bwd_k, dim3(min(cdiv(max_ns, 256), 2048)), dim3(256), 0, (hipStream_t)stream, src, d_ns,
+    hipLaunchKernelGGL(linearize_bwd_k<false>, dim3(min(cdiv(max_ns, 256), 2048)), dim3(256), 0, (hipStream_t)stream, src, d_ns,
                        tgt, tgt_normals, (const unsigned long long *)best, dist_thresh, g_out43, g_src, g_tgt, g_normals);
     GS_LAUNCH_CHECK("gs_icp_linearize_backward");
+    return GS_OK;
+}
+
+size_t gs_icp_linearize_backward_det_ws_bytes(int max_ns, int max_nt) {
+    return det_ws_layout(1, max_ns > 0 ? max_ns : 1, max_nt > 0 ? max_nt : 1, nullptr, nullptr);
+}
+
+int gs_icp_linearize_backward_det(const float *src, const int32_t *d_ns, int max_ns, const float *tgt, const float *tgt_normals,
+                                  const int32_t *d_nt, int max_nt, const uint64_t *best, float dist_thresh, const float *g_out43,
+                                  float *g_src, float *g_tgt, float *g_normals, void *ws, size_t ws_bytes, gs_stream_t stream) {
+    const char *name = "gs_icp_linearize_backward_det";
+    GS_REQUIRE(src && d_ns && tgt && tgt_normals && d_nt && best && g_out43, "%s: NULL argument", name);
+    if (max_ns <= 0) return GS_OK;
+    GS_REQUIRE(max_nt > 0, "%s: bad sizes", name);
+    if (!ws || ws_bytes < gs_icp_linearize_backward_det_ws_bytes(max_ns, max_nt)) {
+        set_error("%s: workspace too small", name);
+        return GS_ERR_WORKSPACE_TOO_SMALL;
+    }
+    hipStream_t st = (hipStream_t)stream;
+    DetWs dw;
+    det_ws_layout(1, max_ns, max_nt, ws, &dw);
+    const bool fold = g_tgt || g_normals;
+    hipLaunchKernelGGL(linearize_bwd_k<true>, dim3(min(cdiv(max_ns, 256), 2048)), dim3(256), 0, st, src, d_ns, tgt, tgt_normals,
+                       (const unsigned long long *)best, dist_thresh, g_out43, g_src, fold ? dw.rows : nullptr, nullptr);
+    GS_LAUNCH_CHECK(name);
+    if (fold) return det_fold_run(dw, 1, max_ns, d_ns, d_nt, max_nt, g_tgt, g_normals, st, name);
     return GS_OK;
 }
 
@@ -2899,12 +2966,16 @@ int gs_icp_point_to_plane_taped(const float *src, const int32_t *d_ns, int max_n
 
 size_t gs_icp_backward_ws_bytes(int max_ns) { return bwd_ws_layout(max_ns > 0 ? max_ns : 1, nullptr, nullptr); }
 
-int gs_icp_point_to_plane_backward(const float *src, const int32_t *d_ns, int max_ns, const float *tgt, const float *tgt_normals,
-                                   const int32_t *d_nt, int max_nt, const float *init_T, int numiters, float dist_thresh, int grad_lm,
-                                   float lambda_max, float B, float B2, float nu, const void *tape, size_t tape_bytes,
-                                   const float *grad_T, float *grad_src, float *grad_tgt, float *grad_normals,
-                                   float *grad_init_T, void *ws, size_t ws_bytes, gs_stream_t stream) {
-    if (numiters == 0) {  // T = init_T, nothing else depends on the inputs
+size_t gs_icp_backward_det_ws_bytes(int max_ns, int max_nt, int numiters, int grad_lm) {
+    return bwd_det_ws_bytes(grad_lm != 0, max_ns > 0 ? max_ns : 1, max_nt > 0 ? max_nt : 1, numiters);
+}
+
+static int icp_backward_entry(bool det, const float *src, const int32_t *d_ns, int max_ns, const float *tgt, const float *tgt_normals,
+                              const int32_t *d_nt, int max_nt, const float *init_T, int numiters, float dist_thresh, int grad_lm,
+                              float lambda_max, float B, float B2, float nu, const void *tape, size_t tape_bytes,
+                              const float *grad_T, float *grad_src, float *grad_tgt, float *grad_normals,
+                              float *grad_init_T, void *ws, size_t ws_bytes, gs_stream_t stream) {
+    if (numiters == 0) {  // T = init_T, nothing else depends on the inputs (no scatter: the same in both modes)
         GS_REQUIRE(grad_T && grad_src && grad_init_T && d_nt && max_ns > 0 && max_nt > 0, "gs_icp_point_to_plane_backward: bad arguments");
         hipStream_t st = (hipStream_t)stream;
         GS_HIP(hipMemsetAsync(grad_src, 0, (size_t)max_ns * 12, st), "gs_icp_point_to_plane_backward");
@@ -2915,7 +2986,25 @@ int gs_icp_point_to_plane_backward(const float *src, const int32_t *d_ns, int ma
     }
     return icp_backward_run(grad_lm != 0, src, d_ns, max_ns, tgt, tgt_normals, d_nt, max_nt, init_T, numiters, dist_thresh,
                             grad_lm ? make_grad_params(lambda_max, B, B2, nu) : GradParams{0.5f, 1.5f, 1.0f, 1.0f, 0.005f}, tape,
-                            tape_bytes, grad_T, grad_src, grad_tgt, grad_normals, grad_init_T, ws, ws_bytes, (hipStream_t)stream);
+                            tape_bytes, grad_T, grad_src, grad_tgt, grad_normals, grad_init_T, ws, ws_bytes, (hipStream_t)stream, det);
+}
+
+int gs_icp_point_to_plane_backward(const float *src, const int32_t *d_ns, int max_ns, const float *tgt, const float *tgt_normals,
+                                   const int32_t *d_nt, int max_nt, const float *init_T, int numiters, float dist_thresh, int grad_lm,
+                                   float lambda_max, float B, float B2, float nu, const void *tape, size_t tape_bytes,
+                                   const float *grad_T, float *grad_src, float *grad_tgt, float *grad_normals,
+                                   float *grad_init_T, void *ws, size_t ws_bytes, gs_stream_t stream) {
+    return icp_backward_entry(false, src, d_ns, max_ns, tgt, tgt_normals, d_nt, max_nt, init_T, numiters, dist_thresh, grad_lm, lambda_max,
+                              B, B2, nu, tape, tape_bytes, grad_T, grad_src, grad_tgt, grad_normals, grad_init_T, ws, ws_bytes, stream);
+}
+
+int gs_icp_point_to_plane_backward_det(const float *src, const int32_t *d_ns, int max_ns, const float *tgt, const float *tgt_normals,
+                                       const int32_t *d_nt, int max_nt, const float *init_T, int numiters, float dist_thresh, int grad_lm,
+                                       float lambda_max, float B, float B2, float nu, const void *tape, size_t tape_bytes,
+                                       const float *grad_T, float *grad_src, float *grad_tgt, float *grad_normals,
+                                       float *grad_init_T, void *ws, size_t ws_bytes, gs_stream_t stream) {
+    return icp_backward_entry(true, src, d_ns, max_ns, tgt, tgt_normals, d_nt, max_nt, init_T, numiters, dist_thresh, grad_lm, lambda_max,
+                              B, B2, nu, tape, tape_bytes, grad_T, grad_src, grad_tgt, grad_normals, grad_init_T, ws, ws_bytes, stream);
 }
 
 }  // extern "C"

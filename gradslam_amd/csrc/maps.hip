@@ -193,7 +193,9 @@ __global__ __launch_bounds__(256) void vn_bwd_pass2_k(const float *__restrict__ 
             sm[0][threadIdx.x] + sm[1][threadIdx.x] + sm[2][threadIdx.x] + sm[3][threadIdx.x];
 }
 
-// one block per (b,l): adds the per-block partials up and applies them to the pose / intrinsics adjoints
+// one block per (b,l): adds the per-block partials up and applies them to the pose / intrinsics adjoints.
+// DET: the four K terms of (b,l) go to g_K + 4 bl (a workspace) instead; vn_bwd_k_sum_k adds them in increasing l
+template <bool DET>
 __global__ __launch_bounds__(1024) void vn_bwd_final_k(const float *__restrict__ part, int nblocks, int have_pass1,
                                                       const float *__restrict__ Ks, const float *__restrict__ poses, int L,
                                                       float *__restrict__ g_K, float *__restrict__ g_poses) {
@@ -224,12 +226,31 @@ __global__ __launch_bounds__(1024) void vn_bwd_final_k(const float *__restrict__
         // a = 1/(fx+eps), c = -cx/(fx+eps), e = 1/(fy+eps), f = -cy/(fy+eps)
         const float *K = Ks + 16 * b;
         const float fx = K[0] + 1e-6f, fy = K[5] + 1e-6f;
+        if constexpr (DET) {
+            float *tk = g_K + 4 * bl;
+            tk[0] = -tot[12] / (fx * fx) + tot[13] * K[2] / (fx * fx);
+            tk[1] = -tot[13] / fx;
+            tk[2] = -tot[14] / (fy * fy) + tot[15] * K[6] / (fy * fy);
+            tk[3] = -tot[15] / fy;
+            return;
+        }
         float *gk = g_K + 16 * b;  // L frames share one K: atomics (L per address)
         atomicAdd(gk + 0, -tot[12] / (fx * fx) + tot[13] * K[2] / (fx * fx));
         atomicAdd(gk + 2, -tot[13] / fx);
         atomicAdd(gk + 5, -tot[14] / (fy * fy) + tot[15] * K[6] / (fy * fy));
         atomicAdd(gk + 6, -tot[15] / fy);
     }
+}
+
+// g_K[b] += the K terms of (b, 0), (b, 1), ... (b, L - 1), in that order (one thread per (b, entry))
+__global__ void vn_bwd_k_sum_k(const float *__restrict__ terms, int B, int L, float *__restrict__ g_K) {
+    const int t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= 4 * B) return;
+    const int b = t >> 2, e = t & 3;
+    const int slot = e == 0 ? 0 : (e == 1 ? 2 : (e == 2 ? 5 : 6));
+    float v = g_K[16 * b + slot];
+    for (int l = 0; l < L; ++l) v += terms[4 * ((int64_t)b * L + l) + e];
+    g_K[16 * b + slot] = v;
 }
 
 // ------------------------------------------------------------------ get_alpha
@@ -401,12 +422,20 @@ size_t gs_vertex_normal_maps_backward_ws_bytes(int B, int L, int H, int W) {
            align_up((size_t)B * L * cdiv((int64_t)H * W, 256) * VN_PART * sizeof(float), 256);
 }
 
-int gs_vertex_normal_maps_backward(const float *depth, const float *intrinsics, const float *poses, int B, int L, int H,
-                                   int W, const float *g_vertex, const float *g_normal, const float *g_gvertex,
-                                   const float *g_gnormal, float *g_depth, float *g_intrinsics, float *g_poses,
-                                   void *ws, size_t ws_bytes, gs_stream_t stream) {
+size_t gs_vertex_normal_maps_backward_det_ws_bytes(int B, int L, int H, int W) {
+    return gs_vertex_normal_maps_backward_ws_bytes(B, L, H, W) + align_up((size_t)B * L * 4 * sizeof(float), 256);
+}
+
+static int maps_backward(bool det, const float *depth, const float *intrinsics, const float *poses, int B, int L, int H,
+                         int W, const float *g_vertex, const float *g_normal, const float *g_gvertex,
+                         const float *g_gnormal, float *g_depth, float *g_intrinsics, float *g_poses,
+                         void *ws, size_t ws_bytes, gs_stream_t stream) {
     GS_REQUIRE(depth && intrinsics, "gs_vertex_normal_maps_backward: depth/intrinsics must not be NULL");
     GS_REQUIRE(B > 0 && L > 0 && H >= 2 && W >= 2 && (int64_t)B * L <= 65535, "gs_vertex_normal_maps_backward: bad shape");
+    if (det && (ws_bytes < gs_vertex_normal_maps_backward_det_ws_bytes(B, L, H, W) || !ws)) {
+        set_error("gs_vertex_normal_maps_backward_det: workspace too small");
+        return GS_ERR_WORKSPACE_TOO_SMALL;
+    }
     const bool need_n = g_normal || g_gnormal;
     float *dhb = nullptr, *dvb = nullptr;
     hipStream_t st = (hipStream_t)stream;
@@ -427,11 +456,34 @@ int gs_vertex_normal_maps_backward(const float *depth, const float *intrinsics, 
     }
     hipLaunchKernelGGL(vn_bwd_pass2_k, grid, dim3(256), 0, st, depth, intrinsics, poses, L, H, W, g_vertex, g_gvertex,
                        dhb, dvb, g_depth, part);
-    if (g_intrinsics || (g_poses && poses))
-        hipLaunchKernelGGL(vn_bwd_final_k, dim3(B * L), dim3(1024), 0, st, part, (int)grid.x, need_n ? 1 : 0, intrinsics, poses, L,
+    if (det) {  // the K terms of every (b,l) to the workspace's tail, then added in increasing l
+        float *terms = (float *)((char *)ws + gs_vertex_normal_maps_backward_ws_bytes(B, L, H, W));
+        if (g_intrinsics || (g_poses && poses))
+            hipLaunchKernelGGL(vn_bwd_final_k<true>, dim3(B * L), dim3(1024), 0, st, part, (int)grid.x, need_n ? 1 : 0, intrinsics, poses, L,
+                               g_intrinsics ? terms : nullptr, g_poses);
+        if (g_intrinsics) hipLaunchKernelGGL(vn_bwd_k_sum_k, dim3(cdiv(4 * B, 256)), dim3(256), 0, st, (const float *)terms, B, L, g_intrinsics);
+    } else if (g_intrinsics || (g_poses && poses)) {
+        hipLaunchKernelGGL(vn_bwd_final_k<false>, dim3(B * L), dim3(1024), 0, st, part, (int)grid.x, need_n ? 1 : 0, intrinsics, poses, L,
                            g_intrinsics, g_poses);
+    }
     GS_LAUNCH_CHECK("gs_vertex_normal_maps_backward/2");
     return GS_OK;
+}
+
+int gs_vertex_normal_maps_backward(const float *depth, const float *intrinsics, const float *poses, int B, int L, int H,
+                                   int W, const float *g_vertex, const float *g_normal, const float *g_gvertex,
+                                   const float *g_gnormal, float *g_depth, float *g_intrinsics, float *g_poses,
+                                   void *ws, size_t ws_bytes, gs_stream_t stream) {
+    return maps_backward(false, depth, intrinsics, poses, B, L, H, W, g_vertex, g_normal, g_gvertex, g_gnormal, g_depth, g_intrinsics,
+                         g_poses, ws, ws_bytes, stream);
+}
+
+int gs_vertex_normal_maps_backward_det(const float *depth, const float *intrinsics, const float *poses, int B, int L, int H,
+                                       int W, const float *g_vertex, const float *g_normal, const float *g_gvertex,
+                                       const float *g_gnormal, float *g_depth, float *g_intrinsics, float *g_poses,
+                                       void *ws, size_t ws_bytes, gs_stream_t stream) {
+    return maps_backward(true, depth, intrinsics, poses, B, L, H, W, g_vertex, g_normal, g_gvertex, g_gnormal, g_depth, g_intrinsics,
+                         g_poses, ws, ws_bytes, stream);
 }
 
 int gs_get_alpha(const float *points, int64_t n, float sigma, float eps, float *alpha, gs_stream_t stream) {

@@ -702,16 +702,25 @@ size_t gs_slam_localize_backward_ws_bytes(int B, int H, int W, int ds, int Nmax)
            align_up(gs_icp_backward_ws_bytes(capS), 256);
 }
 
-int gs_slam_localize_backward(const float *prev_poses, int B, int H, int W, int ds, const float *map_points,
-                              const float *map_normals, int Nmax, int use_grad_lm, int numiters, float dist_thresh,
-                              float lambda_max, float Bp, float B2, float nu, const void *tape, size_t tape_bytes,
-                              const float *grad_out_poses, float *grad_gvertex, float *grad_map_points, float *grad_map_normals,
-                              float *grad_prev_poses, int accumulate_map_grads, void *ws, size_t ws_bytes, gs_stream_t stream) {
-    const char *name = "gs_slam_localize_backward";
+size_t gs_slam_localize_backward_det_ws_bytes(int B, int H, int W, int ds, int Nmax, int numiters, int grad_lm) {
+    if (B <= 0 || H <= 0 || W <= 0 || ds <= 0 || Nmax <= 0) return 0;
+    const int capS = cdiv(H, ds) * cdiv(W, ds), capT = target_cap(Nmax);
+    // the same layout, with the deterministic ICP reverse pass's workspace at the end
+    return 4 * align_up((size_t)capT * 12, 256) + align_up((size_t)capS * 12, 256) + 3 * align_up((size_t)B * 64, 256) +
+           align_up(gs_icp_backward_det_ws_bytes(capS, capT, numiters, grad_lm), 256);
+}
+
+static int localize_backward(bool det, const float *prev_poses, int B, int H, int W, int ds, const float *map_points,
+                             const float *map_normals, int Nmax, int use_grad_lm, int numiters, float dist_thresh,
+                             float lambda_max, float Bp, float B2, float nu, const void *tape, size_t tape_bytes,
+                             const float *grad_out_poses, float *grad_gvertex, float *grad_map_points, float *grad_map_normals,
+                             float *grad_prev_poses, int accumulate_map_grads, void *ws, size_t ws_bytes, gs_stream_t stream) {
+    const char *name = det ? "gs_slam_localize_backward_det" : "gs_slam_localize_backward";
     GS_REQUIRE(prev_poses && map_points && map_normals && tape && grad_out_poses && grad_gvertex && grad_prev_poses,
                "%s: NULL argument", name);
     GS_REQUIRE(B > 0 && H >= 2 && W >= 2 && ds > 0 && Nmax > 0 && numiters >= 0, "%s: bad shape", name);
-    if (!ws || ws_bytes < gs_slam_localize_backward_ws_bytes(B, H, W, ds, Nmax)) {
+    if (!ws || ws_bytes < (det ? gs_slam_localize_backward_det_ws_bytes(B, H, W, ds, Nmax, numiters, use_grad_lm)
+                               : gs_slam_localize_backward_ws_bytes(B, H, W, ds, Nmax))) {
         set_error("%s: workspace too small", name);
         return GS_ERR_WORKSPACE_TOO_SMALL;
     }
@@ -727,7 +736,8 @@ int gs_slam_localize_backward(const float *prev_poses, int B, int H, int W, int 
     float *g_src = (float *)take((size_t)capS * 12);
     float *g_T = (float *)take((size_t)B * 64), *g_init = (float *)take((size_t)B * 64), *eye = (float *)take((size_t)B * 64);
     void *sub = p;
-    const size_t sub_bytes = gs_icp_backward_ws_bytes(capS);
+    const size_t sub_bytes = det ? gs_icp_backward_det_ws_bytes(capS, capT, numiters, use_grad_lm) : gs_icp_backward_ws_bytes(capS);
+    auto icp_backward = det ? gs_icp_point_to_plane_backward_det : gs_icp_point_to_plane_backward;
 
     GS_HIP(hipMemsetAsync(grad_gvertex, 0, (size_t)B * H * W * 12, st), name);
     if (grad_map_points && !accumulate_map_grads) GS_HIP(hipMemsetAsync(grad_map_points, 0, (size_t)B * Nmax * 12, st), name);
@@ -742,7 +752,7 @@ int gs_slam_localize_backward(const float *prev_poses, int B, int H, int W, int 
                            map_points + (size_t)b * Nmax * 3, map_normals + (size_t)b * Nmax * 3, Nmax, tgt, tnrm);
         GS_LAUNCH_CHECK(name);
         int rc;
-        if ((rc = gs_icp_point_to_plane_backward(tp.src + (size_t)b * capS * 3, tp.ns + b, capS, tgt, tnrm, tp.nt + b, capT, eye + 16 * b, numiters,
+        if ((rc = icp_backward(tp.src + (size_t)b * capS * 3, tp.ns + b, capS, tgt, tnrm, tp.nt + b, capT, eye + 16 * b, numiters,
                                                  dist_thresh, use_grad_lm, lambda_max, Bp, B2, nu, tp.icp + (size_t)b * tp.icp_bytes,
                                                  tp.icp_bytes, g_T + 16 * b, g_src, grad_map_points ? g_tgt : nullptr,
                                                  grad_map_normals ? g_nrm : nullptr, g_init + 16 * b, sub, sub_bytes, stream)))
@@ -754,6 +764,26 @@ int gs_slam_localize_backward(const float *prev_poses, int B, int H, int W, int 
         GS_LAUNCH_CHECK(name);
     }
     return GS_OK;
+}
+
+int gs_slam_localize_backward(const float *prev_poses, int B, int H, int W, int ds, const float *map_points,
+                              const float *map_normals, int Nmax, int use_grad_lm, int numiters, float dist_thresh,
+                              float lambda_max, float Bp, float B2, float nu, const void *tape, size_t tape_bytes,
+                              const float *grad_out_poses, float *grad_gvertex, float *grad_map_points, float *grad_map_normals,
+                              float *grad_prev_poses, int accumulate_map_grads, void *ws, size_t ws_bytes, gs_stream_t stream) {
+    return localize_backward(false, prev_poses, B, H, W, ds, map_points, map_normals, Nmax, use_grad_lm, numiters, dist_thresh, lambda_max,
+                             Bp, B2, nu, tape, tape_bytes, grad_out_poses, grad_gvertex, grad_map_points, grad_map_normals, grad_prev_poses,
+                             accumulate_map_grads, ws, ws_bytes, stream);
+}
+
+int gs_slam_localize_backward_det(const float *prev_poses, int B, int H, int W, int ds, const float *map_points,
+                                  const float *map_normals, int Nmax, int use_grad_lm, int numiters, float dist_thresh,
+                                  float lambda_max, float Bp, float B2, float nu, const void *tape, size_t tape_bytes,
+                                  const float *grad_out_poses, float *grad_gvertex, float *grad_map_points, float *grad_map_normals,
+                                  float *grad_prev_poses, int accumulate_map_grads, void *ws, size_t ws_bytes, gs_stream_t stream) {
+    return localize_backward(true, prev_poses, B, H, W, ds, map_points, map_normals, Nmax, use_grad_lm, numiters, dist_thresh, lambda_max,
+                             Bp, B2, nu, tape, tape_bytes, grad_out_poses, grad_gvertex, grad_map_points, grad_map_normals, grad_prev_poses,
+                             accumulate_map_grads, ws, ws_bytes, stream);
 }
 
 }  // extern "C"

@@ -21,6 +21,12 @@ def _f32c(t: Optional[torch.Tensor]) -> Optional[torch.Tensor]:
     return t.contiguous()
 
 
+def deterministic() -> bool:
+    """torch's switch for reproducible training: under torch.use_deterministic_algorithms(True) every backward below calls the
+    `_det` entry of its kernel (no float atomics: the same gradient bits from run to run), otherwise the default one."""
+    return torch.are_deterministic_algorithms_enabled()
+
+
 def dev_int(value: int, device) -> torch.Tensor:
     """A device-resident int32 scalar (filled by a kernel: no host->device copy, no sync)."""
     return torch.full((1,), int(value), dtype=torch.int32, device=device)
@@ -72,10 +78,15 @@ def vertex_normal_maps_backward_raw(depth, K, poses, gV_l=None, gN_l=None, gV_g=
     g_depth = torch.zeros_like(depth_c)
     g_K = torch.zeros_like(K_c)
     g_P = torch.zeros_like(poses_c) if poses_c is not None else None
-    ws = workspace(ws_bytes("gs_vertex_normal_maps_backward_ws_bytes", B, L, H, W), depth_c.device, "maps_bwd")
-    call("gs_vertex_normal_maps_backward", ptr(depth_c), ptr(K_c), ptr(poses_c), B, L, H, W, ptr(gV_l), ptr(gN_l),
-         ptr(gV_g), ptr(gN_g), ptr(g_depth), ptr(g_K), ptr(g_P), ptr(ws), ws.numel(), stream())
+    _maps_backward(depth_c, K_c, poses_c, B, L, H, W, gV_l, gN_l, gV_g, gN_g, g_depth, g_K, g_P)
     return g_depth, g_K, g_P
+
+
+def _maps_backward(depth_c, K_c, poses_c, B, L, H, W, gV_l, gN_l, gV_g, gN_g, g_depth, g_K, g_P):
+    det = "_det" if deterministic() else ""
+    ws = workspace(ws_bytes("gs_vertex_normal_maps_backward{}_ws_bytes".format(det), B, L, H, W), depth_c.device, "maps_bwd" + det)
+    call("gs_vertex_normal_maps_backward" + det, ptr(depth_c), ptr(K_c), ptr(poses_c), B, L, H, W, ptr(gV_l), ptr(gN_l),
+         ptr(gV_g), ptr(gN_g), ptr(g_depth), ptr(g_K), ptr(g_P), ptr(ws), ws.numel(), stream())
 
 
 def vertex_normal_maps_backward_into(depth, K, poses, gV_l, gN_l, gV_g, gN_g, g_depth, g_K, g_poses):
@@ -88,9 +99,7 @@ def vertex_normal_maps_backward_into(depth, K, poses, gV_l, gN_l, gV_g, gN_g, g_
         if x is not None and not (x.is_contiguous() and x.dtype == torch.float32):
             raise ValueError("vertex_normal_maps_backward_into: the adjoint buffers must be contiguous float32")
     gV_l, gN_l, gV_g, gN_g = _f32c(gV_l), _f32c(gN_l), _f32c(gV_g), _f32c(gN_g)
-    ws = workspace(ws_bytes("gs_vertex_normal_maps_backward_ws_bytes", B, L, H, W), depth_c.device, "maps_bwd")
-    call("gs_vertex_normal_maps_backward", ptr(depth_c), ptr(K_c), ptr(poses_c), B, L, H, W, ptr(gV_l), ptr(gN_l),
-         ptr(gV_g), ptr(gN_g), ptr(g_depth), ptr(g_K), ptr(g_poses), ptr(ws), ws.numel(), stream())
+    _maps_backward(depth_c, K_c, poses_c, B, L, H, W, gV_l, gN_l, gV_g, gN_g, g_depth, g_K, g_poses)
 
 
 def vertex_normal_maps(depth, K, poses, want_local=True, want_global=True):
@@ -380,8 +389,14 @@ class _LinearizeFn(torch.autograd.Function):
         g_src = torch.zeros_like(src_c)
         g_tgt = torch.zeros_like(tgt_c)
         g_nrm = torch.zeros_like(nrm_c)
-        call("gs_icp_linearize_backward", ptr(src_c), ptr(dev_int(src_c.shape[0], dev)), src_c.shape[0], ptr(tgt_c),
-             ptr(nrm_c), ptr(best), _thresh(ctx.dist_thresh), ptr(gout), ptr(g_src), ptr(g_tgt), ptr(g_nrm), stream())
+        ns, nt = src_c.shape[0], tgt_c.shape[0]
+        if deterministic():
+            ws = workspace(ws_bytes("gs_icp_linearize_backward_det_ws_bytes", ns, nt), dev, "linearize_bwd_det")
+            d_ns, d_nt = dev_int(ns, dev), dev_int(nt, dev)  # (held: two temporaries could share one freed block)
+            call("gs_icp_linearize_backward_det", ptr(src_c), ptr(d_ns), ns, ptr(tgt_c), ptr(nrm_c), ptr(d_nt), nt, ptr(best), _thresh(ctx.dist_thresh), ptr(gout), ptr(g_src), ptr(g_tgt), ptr(g_nrm), ptr(ws), ws.numel(), stream())
+        else:
+            call("gs_icp_linearize_backward", ptr(src_c), ptr(dev_int(ns, dev)), ns, ptr(tgt_c), ptr(nrm_c), ptr(best),
+                 _thresh(ctx.dist_thresh), ptr(gout), ptr(g_src), ptr(g_tgt), ptr(g_nrm), stream())
         return g_src, g_tgt, g_nrm, None, None
 
 
@@ -499,8 +514,13 @@ class _IcpLoopFn(torch.autograd.Function):
         g_tgt = torch.empty_like(tgt) if need_tgt else None
         g_nrm = torch.empty_like(nrm) if need_nrm else None
         g_init = torch.empty((4, 4), dtype=torch.float32, device=dev)
-        ws = workspace(ws_bytes("gs_icp_backward_ws_bytes", ns), dev, "icp_bwd")
-        call("gs_icp_point_to_plane_backward", ptr(src), ptr(d_ns), ns, ptr(tgt), ptr(nrm), ptr(d_nt), nt, ptr(init_T), numiters, thresh,
+        if deterministic():
+            entry = "gs_icp_point_to_plane_backward_det"
+            ws = workspace(ws_bytes("gs_icp_backward_det_ws_bytes", ns, nt, numiters, grad_lm), dev, "icp_bwd_det")
+        else:
+            entry = "gs_icp_point_to_plane_backward"
+            ws = workspace(ws_bytes("gs_icp_backward_ws_bytes", ns), dev, "icp_bwd")
+        call(entry, ptr(src), ptr(d_ns), ns, ptr(tgt), ptr(nrm), ptr(d_nt), nt, ptr(init_T), numiters, thresh,
              grad_lm, lmax, Bp, B2, nu, ptr(tape), tape.numel(), ptr(gT), ptr(g_src), ptr(g_tgt), ptr(g_nrm), ptr(g_init),
              ptr(ws), ws.numel(), stream())
         return g_src, g_tgt, g_nrm, g_init, None, None, None, None
@@ -574,10 +594,18 @@ class _LocalizeFn(torch.autograd.Function):
         g_mp = torch.empty_like(mp) if ctx.needs_input_grad[4] else None
         g_mn = torch.empty_like(mn) if ctx.needs_input_grad[5] else None
         g_prev = torch.empty((B, 1, 4, 4), dtype=torch.float32, device=dev)
-        ws = workspace(ws_bytes("gs_slam_localize_backward_ws_bytes", B, H, W, ds, Nmax), dev, "localize_bwd")
-        call("gs_slam_localize_backward", ptr(prev), B, H, W, ds, ptr(mp), ptr(mn), Nmax, grad_lm, numiters, thresh, lmax, Bp, B2,
+        entry, ws = _localize_backward_ws(B, H, W, ds, Nmax, numiters, grad_lm, dev)
+        call(entry, ptr(prev), B, H, W, ds, ptr(mp), ptr(mn), Nmax, grad_lm, numiters, thresh, lmax, Bp, B2,
              nu, ptr(tape), tape.numel(), ptr(g_out), ptr(g_gV), ptr(g_mp), ptr(g_mn), ptr(g_prev), 0, ptr(ws), ws.numel(), stream())
         return g_gV, None, None, g_prev, g_mp, g_mn, None, None, None, None, None, None
+
+
+def _localize_backward_ws(B, H, W, ds, Nmax, numiters, grad_lm, dev):
+    """(entry, workspace) of the localisation reverse pass: the `_det` one under torch.use_deterministic_algorithms."""
+    if deterministic():
+        return "gs_slam_localize_backward_det", workspace(
+            ws_bytes("gs_slam_localize_backward_det_ws_bytes", B, H, W, ds, Nmax, numiters, grad_lm), dev, "localize_bwd_det")
+    return "gs_slam_localize_backward", workspace(ws_bytes("gs_slam_localize_backward_ws_bytes", B, H, W, ds, Nmax), dev, "localize_bwd")
 
 
 def slam_localize_autograd(gV, depth, K, prev_poses, map_points, map_normals, map_counts_i32, ds, numiters, damp, dist_thresh,
@@ -759,8 +787,8 @@ class _PointFusionSeqFn(torch.autograd.Function):
                 tape, nmax = frames[s]["loc"]
                 restride(nmax)
                 prev = recovered[:, s - 1:s].contiguous()
-                ws = workspace(ws_bytes("gs_slam_localize_backward_ws_bytes", B, H, W, ds, nmax), dev, "localize_bwd")
-                call("gs_slam_localize_backward", ptr(prev), B, H, W, ds, ptr(mp), ptr(mn), nmax, grad_lm, numiters, thresh, lmax, Bp, B2,
+                entry, ws = _localize_backward_ws(B, H, W, ds, nmax, numiters, grad_lm, dev)
+                call(entry, ptr(prev), B, H, W, ds, ptr(mp), ptr(mn), nmax, grad_lm, numiters, thresh, lmax, Bp, B2,
                      nu, ptr(tape), tape.numel(), ptr(gpose[:, s:s + 1].contiguous()), ptr(g_live), ptr(Gp), ptr(Gn), ptr(g_prev), 1,
                      ptr(ws), ws.numel(), stream())
                 gprev_s = gpose[:, s - 1] if one else t_pose2.zero_()

@@ -59,6 +59,16 @@ int gs_vertex_normal_maps_backward(const float *depth, const float *intrinsics, 
                                    const float *g_normal, const float *g_gvertex,
                                    const float *g_gnormal, float *g_depth, float *g_intrinsics,
                                    float *g_poses, void *ws, size_t ws_bytes, gs_stream_t stream);
+/* Deterministic form (what backward calls under torch.use_deterministic_algorithms): the same arguments and
+ * results, but the intrinsics adjoint -- shared by the L frames of a batch element (inverse_intrinsics,
+ * geometry/projutils.py:437-450, used by structures/rgbdimages.py:643-762) -- is added in increasing l from a
+ * workspace instead of by float atomics: the same bits from run to run.  The workspace is larger. */
+size_t gs_vertex_normal_maps_backward_det_ws_bytes(int B, int L, int H, int W);
+int gs_vertex_normal_maps_backward_det(const float *depth, const float *intrinsics, const float *poses,
+                                       int B, int L, int H, int W, const float *g_vertex,
+                                       const float *g_normal, const float *g_gvertex,
+                                       const float *g_gnormal, float *g_depth, float *g_intrinsics,
+                                       float *g_poses, void *ws, size_t ws_bytes, gs_stream_t stream);
 
 /* get_alpha (slam/fusionutils.py:69-73) on an (n,3) block: clamp(exp(-|p|^2/(2 sigma^2)), eps, 1.01) */
 int gs_get_alpha(const float *points, int64_t n, float sigma, float eps, float *alpha,
@@ -208,6 +218,15 @@ int gs_icp_linearize_backward(const float *src, const int32_t *d_ns, int max_ns,
                               const float *tgt_normals, const uint64_t *best, float dist_thresh,
                               const float *g_out43, float *g_src, float *g_tgt, float *g_normals,
                               gs_stream_t stream);
+/* Deterministic form: d/dtgt, d/dnormals (rows < *d_nt, each optional) are WRITTEN, as a pure function of the
+ * inputs -- the scatter of index_select's adjoint (odometry/icputils.py:215-216; the reference's CPU
+ * index_select backward is deterministic) is added up in exact fixed point and rounded once (DESIGN.md, X bar),
+ * with no float atomics; d/dsrc as above. */
+size_t gs_icp_linearize_backward_det_ws_bytes(int max_ns, int max_nt);
+int gs_icp_linearize_backward_det(const float *src, const int32_t *d_ns, int max_ns, const float *tgt,
+                                  const float *tgt_normals, const int32_t *d_nt, int max_nt, const uint64_t *best,
+                                  float dist_thresh, const float *g_out43, float *g_src, float *g_tgt,
+                                  float *g_normals, void *ws, size_t ws_bytes, gs_stream_t stream);
 
 /* transform_pointcloud (geometry/geometryutils.py:780-792): out = R p + t, T is a DEVICE 4x4. */
 int gs_transform_points(const float *pts, const int32_t *d_n, int max_n, const float *T,
@@ -285,6 +304,18 @@ int gs_icp_point_to_plane_backward(const float *src, const int32_t *d_ns, int ma
                                    const float *grad_T, float *grad_src, float *grad_tgt,
                                    float *grad_normals, float *grad_init_T, void *ws, size_t ws_bytes,
                                    gs_stream_t stream);
+/* Deterministic reverse pass (torch.use_deterministic_algorithms): the same arguments and outputs; every output is a
+ * pure function of the inputs, bit for bit.  The target / normal adjoints -- the scatter of index_select's adjoint,
+ * odometry/icputils.py:215-216, at every iteration of :310-367 / :479-545 -- are stored per reverse launch and added
+ * up afterwards in exact fixed point, rounded once (no float atomics).  The workspace grows with numiters and grad_lm. */
+size_t gs_icp_backward_det_ws_bytes(int max_ns, int max_nt, int numiters, int grad_lm);
+int gs_icp_point_to_plane_backward_det(const float *src, const int32_t *d_ns, int max_ns, const float *tgt,
+                                       const float *tgt_normals, const int32_t *d_nt, int max_nt, const float *init_T,
+                                       int numiters, float dist_thresh, int grad_lm, float lambda_max,
+                                       float B, float B2, float nu, const void *tape, size_t tape_bytes,
+                                       const float *grad_T, float *grad_src, float *grad_tgt,
+                                       float *grad_normals, float *grad_init_T, void *ws, size_t ws_bytes,
+                                       gs_stream_t stream);
 
 /* ---------------------------------------------------------------- whole PointFusion map update
  * update_map_fusion(pointclouds, live_frame, dist_th, dot_th, sigma, inplace=True)
@@ -362,6 +393,17 @@ int gs_slam_localize_backward(const float *prev_poses, int B, int H, int W, int 
                               float *grad_prev_poses, int accumulate_map_grads /* 1: add into grad_map_* (a running
                               adjoint of the whole map) instead of overwriting them */,
                               void *ws, size_t ws_bytes, gs_stream_t stream);
+/* Deterministic form (torch.use_deterministic_algorithms): the same arguments and outputs, bit for bit the same
+ * from run to run -- each batch element's ICP reverse pass is gs_icp_point_to_plane_backward_det (the map
+ * adjoints of icpslam.py:238-247 through icputils.py:215-216).  The workspace grows with numiters and use_grad_lm. */
+size_t gs_slam_localize_backward_det_ws_bytes(int B, int H, int W, int ds, int Nmax, int numiters, int use_grad_lm);
+int gs_slam_localize_backward_det(const float *prev_poses, int B, int H, int W, int ds, const float *map_points,
+                                  const float *map_normals, int Nmax, int use_grad_lm, int numiters,
+                                  float dist_thresh, float lambda_max, float Bp, float B2, float nu,
+                                  const void *tape, size_t tape_bytes, const float *grad_out_poses,
+                                  float *grad_gvertex, float *grad_map_points, float *grad_map_normals,
+                                  float *grad_prev_poses, int accumulate_map_grads, void *ws, size_t ws_bytes,
+                                  gs_stream_t stream);
 
 /* gs_slam_localize can replay its ICP loops as a cached hipGraph once a configuration repeats (all loop
  * arguments live in the caller's workspace).  mode: 1 on, 0 off (eager launches), -1 automatic: the library

@@ -12,6 +12,8 @@ K=1 nearest-neighbour search, of the algorithm in the reference's
 * ``gradslam/slam/fusionutils.py:16-789``         (PointFusion map update)       -> fusion.py
 * ``gradslam/slam/icpslam.py:99-264``, ``slam/pointfusion.py:107-112`` (frame loop) -> slam.py
 * ``gradslam/geometry/{se3utils,projutils,geometryutils}.py`` pieces the path calls -> geometry.py
+* one step of ``odometry/icputils.py:310-367, :479-545`` from a device trace row, and the loops in float64 with
+  autograd, for the step and reverse-pass tests                                     -> icp_step.py
 
 Each function cites the reference file:line it follows.  It uses the same torch ops in the same
 order wherever rounding or an integer decision depends on it, so that on CPU it reproduces the

@@ -65,6 +65,8 @@ def point_to_plane_ICP(src, tgt, nrm, T0: Optional[torch.Tensor] = None, numiter
             T = torch.mm(dT, T)
         else:
             damp = damp * 2
+        if trace is not None:
+            trace[-1]["T"] = T.clone()  # the transform after the step
     return T, idx
 
 
@@ -100,6 +102,8 @@ def point_to_plane_gradICP(src, tgt, nrm, T0=None, numiters: int = 20, damp: flo
         dT = se3_exp(sig * xi)
         src = transform_pointcloud(src[0], dT).unsqueeze(0)
         T = torch.mm(dT, T)
+        if trace is not None:
+            trace[-1]["T"] = T.detach().clone()
     return T, idx
 
 

@@ -106,6 +106,7 @@ SIGNATURES = {
     "gs_set_grid_search": (None, [c_i]),
     "gs_set_fused_setup": (None, [c_i]),
     "gs_set_tile_points": (None, [c_i]),
+    "gs_set_loop_waves": (c_i, [c_i]),
     "gs_icp_launch_geometry": (c_i, [c_i, c_i, ctypes.POINTER(c_i), ctypes.POINTER(c_i), ctypes.POINTER(c_i)]),
     "gs_loop_counts": (c_i, [ctypes.POINTER(ctypes.c_uint), c_i]),
     "gs_profile_enable": (None, [c_i]),

@@ -46,7 +46,8 @@
 namespace gs {
 
 constexpr int KNN_T = 256;      // brute force: threads per block
-constexpr int KNN_NW = 16;      // pruned search: waves per block, ALL serving the same 64 source points
+constexpr int KNN_NW = 16;      // pruned search: waves per block, ALL serving the same 64 source points (knn1_box_k; the loops'
+                                // association kernel takes its wave count as a template parameter NW: 16 or 8, see loop_waves)
 constexpr int KNN_BT = KNN_NW * 64;
 constexpr int KNN_COARSE = 512; // target points sampled by the seed pass when no seed is given
 constexpr int CHUNK = 16;       // target points per AABB chunk
@@ -175,7 +176,7 @@ __global__ __launch_bounds__(64) void tgt_boxes_k(const float *__restrict__ tgt,
     }
 }
 
-// Cooperative exact search of one 64-point source tile by the KNN_NW waves of a block.  Every wave
+// Cooperative exact search of one 64-point source tile by the NW waves of a block.  Every wave
 // holds the same 64 source points (lane = point); the waves share the work over TARGET chunks:
 //   seed   : one real candidate per lane (given index, or the best of a strided sample of the target)
 //   coarse : lanes = chunk boxes.  A chunk survives iff the gap between ITS box and the TILE's box is not
@@ -226,7 +227,8 @@ struct KnnShared {
 __device__ unsigned int g_loop_counts[4];
 
 #ifdef GS_DIAG_STAMPS
-// Diagnostic build only (libgradslam_hip_diag.so, never loaded by the product): per-wave phase stamps.
+// Diagnostic build only (libgradslam_hip_diag.so, never loaded by the product): per-wave phase stamps.  A block owns
+// KNN_NW = 16 wave slots whatever its wave count (an eight-wave block leaves slots 8 .. 15 at zero).
 __device__ unsigned long long *g_diag = nullptr;
 #define GS_STAMP(slot)                                                                                   \
     do {                                                                                                 \
@@ -305,6 +307,7 @@ __device__ __forceinline__ void key_unpack(unsigned long long k, float &bd, int 
 // pixels around its own pixel (scan order = pixel order, pix_start = first slot per pixel), the window
 // pixels shared over the waves.  A projective guess used as a SEED only: it hands the exact search a bound
 // that is already the true nearest distance for almost every lane.
+template <int NW>
 __device__ __forceinline__ void knn_window_seed(KnnShared &sh, const f3 s, const bool ok, const int i,
                                                 const gs_icp_hints &h, const int nt) {
     constexpr int R = 2, WIN = (2 * R + 1) * (2 * R + 1), CAP = 4;  // at most CAP targets per window pixel
@@ -316,7 +319,7 @@ __device__ __forceinline__ void knn_window_seed(KnnShared &sh, const f3 s, const
     const int npix = h.grid_w * h.grid_h;
     const int p = ok ? min(max(h.src_pix[i], 0), npix - 1) : 0;
     const int pr = p / h.grid_w, pc = p - pr * h.grid_w;
-    for (int wdx = wave; wdx < WIN; wdx += KNN_NW) {
+    for (int wdx = wave; wdx < WIN; wdx += NW) {
         const int rr = pr + wdx / (2 * R + 1) - R, cc = pc + wdx % (2 * R + 1) - R;
         if (!ok || rr < 0 || rr >= h.grid_h || cc < 0 || cc >= h.grid_w) continue;
         const int q0 = rr * h.grid_w + cc;
@@ -342,7 +345,7 @@ __device__ __forceinline__ void knn_window_seed(KnnShared &sh, const f3 s, const
 
 // The source tile's box over the lanes selected by `act`: one wave per component, published through LDS
 // (the caller synchronises before reading sh.tbox).
-__device__ __forceinline__ void tile_box(KnnShared &sh, const f3 s, const bool act) {
+__device__ __forceinline__ void tile_box(KnnShared &sh, const f3 s, const bool act) {  // (waves 1 .. 6: any block of >= 7 waves)
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     if (wave >= 1 && wave <= 6) {
         const int a = wave - 1;
@@ -386,7 +389,7 @@ __device__ __forceinline__ int sel4(int k, int a0, int a1, int a2, int a3) { ret
 // visible): coarse pass with the tile's box and loosest bound, fine pass with per-lane bounds (see knn_tile).
 // GRID: chunks inside a lane's own window `win` were examined already and are skipped for that lane.
 // Ends with a barrier.
-template <bool GRID>
+template <bool GRID, int NW>
 __device__ __forceinline__ void knn_prune_search(KnnShared &sh, const f3 s, const bool ok, const bool act,
                                                  const float *__restrict__ scan, const int32_t *__restrict__ scan_orig,
                                                  const float *__restrict__ boxes, const float *__restrict__ sboxes /* or NULL */,
@@ -411,7 +414,7 @@ __device__ __forceinline__ void knn_prune_search(KnnShared &sh, const f3 s, cons
         GS_TICK(tc0);
         const int r1 = min(nchunks, r0 + KNN_LIST);
         // coarse: lanes = chunk boxes; box-to-box gap with the distance's accumulation order
-        for (int c0 = r0 + wave * 64; c0 < r1; c0 += KNN_NW * 64) {
+        for (int c0 = r0 + wave * 64; c0 < r1; c0 += NW * 64) {
             if (sboxes) {
                 // the 64 chunks of this round are one super-box (c0 is a multiple of SUPER): its box contains theirs, so
                 // its gap to the tile's box is, axis by axis, at most theirs and -- same operation order, monotone
@@ -451,12 +454,12 @@ __device__ __forceinline__ void knn_prune_search(KnnShared &sh, const f3 s, cons
         // brings the boxes and the 4 x CHUNK candidate points of a group into registers (lane l holds
         // point l%CHUNK of the group's survivor l/CHUNK), then tests and scans run without memory ops
         const int nlist = sh.cnt;
-        const int ni = (nlist > wave) ? (nlist - wave + KNN_NW - 1) / KNN_NW : 0;
+        const int ni = (nlist > wave) ? (nlist - wave + NW - 1) / NW : 0;
         constexpr int SEG = 64 / CHUNK;
         for (int g = 0; g < ni; g += SEG) {
             const int seg = lane / CHUNK, idx = g + seg;
             const bool have = idx < ni;
-            const int c = have ? sh.u.a.list[wave + KNN_NW * idx] : 0;
+            const int c = have ? sh.u.a.list[wave + NW * idx] : 0;
             const int j = c * CHUNK + (lane % CHUNK);
             const bool pv = have && j < nt;
             const f3 q = pv ? ld3(scan, j) : f3{0.0f, 0.0f, 0.0f};
@@ -528,6 +531,7 @@ __device__ __forceinline__ void knn_prune_search(KnnShared &sh, const f3 s, cons
 // every proof holds.  sh.cnt must be zero on entry (all waves past their last use of the
 // list's storage); ends with a barrier.  Returns false (block-uniform) when the pair list overflowed: nothing found is
 // final then and the caller must search again with knn_prune_search<true>.
+template <int NW>
 __device__ __forceinline__ bool knn_point_search(KnnShared &sh, const f3 s, const unsigned long long need_mask,
                                                  const float *__restrict__ scan, const int32_t *__restrict__ scan_orig,
                                                  const float *__restrict__ boxes, const float *__restrict__ sboxes, const int nt) {
@@ -539,7 +543,7 @@ __device__ __forceinline__ bool knn_point_search(KnnShared &sh, const f3 s, cons
         float bd;
         int bi;
         key_unpack(sh.key[L], bd, bi);  // wave-uniform
-        for (int b0 = wave * 64; b0 < nsb; b0 += KNN_NW * 64) {
+        for (int b0 = wave * 64; b0 < nsb; b0 += NW * 64) {
             const int sb = b0 + lane;
             bool hit = false;
             if (sb < nsb) {
@@ -571,7 +575,7 @@ __device__ __forceinline__ bool knn_point_search(KnnShared &sh, const f3 s, cons
         return false;
     }
     const int npairs = sh.cnt;
-    for (int pi = wave; pi < npairs; pi += KNN_NW) {  // phase B
+    for (int pi = wave; pi < npairs; pi += NW) {  // phase B
         const int pr = sh.u.a.list[pi];
         const int L = pr >> 24, sb = pr & 0xffffff;
         const f3 p{rlane(s.x, L), rlane(s.y, L), rlane(s.z, L)};
@@ -627,6 +631,7 @@ __device__ __forceinline__ bool knn_point_search(KnnShared &sh, const f3 s, cons
 // scan     : the same points in the order they are scanned (== tgt when scan_orig is NULL); boxes are
 //            built over this order
 // scan_orig: reference index of every scan slot, or NULL
+template <int NW>
 __device__ __forceinline__ unsigned long long knn_tile(KnnShared &sh, const f3 s, const bool ok, const int seed_j,
                                                        const float *__restrict__ tgt, const float *__restrict__ scan,
                                                        const int32_t *__restrict__ scan_orig,
@@ -650,7 +655,7 @@ __device__ __forceinline__ unsigned long long knn_tile(KnnShared &sh, const f3 s
         const float stride = (float)nt / (float)M;
         float bd = INFINITY;
         int bi = 0x7fffffff;
-        for (int k0 = wave * 16; k0 < M; k0 += KNN_NW * 16) {
+        for (int k0 = wave * 16; k0 < M; k0 += NW * 16) {
             const int k = k0 + lane;
             const int n = min(16, M - k0);
             const int j = min((int)((float)k * stride), nt - 1);
@@ -666,8 +671,8 @@ __device__ __forceinline__ unsigned long long knn_tile(KnnShared &sh, const f3 s
         constexpr int R = 64;
         key_unpack(sh.key[lane], bd, bi);
         const int jstar = bi;
-        for (int t = 0; t < 2 * R / KNN_NW; ++t) {
-            const int j = min(max(jstar - R + wave * (2 * R / KNN_NW) + t, 0), nt - 1);
+        for (int t = 0; t < 2 * R / NW; ++t) {
+            const int j = min(max(jstar - R + wave * (2 * R / NW) + t, 0), nt - 1);
             const f3 q = ok ? ld3(tgt, j) : f3{0.0f, 0.0f, 0.0f};
             const float d = dist2(s, q.x, q.y, q.z);
             const bool better = (d < bd) | ((d == bd) & (j < bi));
@@ -679,7 +684,7 @@ __device__ __forceinline__ unsigned long long knn_tile(KnnShared &sh, const f3 s
         }
     }
     GS_STAMP(1);
-    knn_prune_search<false>(sh, s, ok, ok, scan, scan_orig, boxes, sboxes, nt);
+    knn_prune_search<false, NW>(sh, s, ok, ok, scan, scan_orig, boxes, sboxes, nt);
     GS_STAMP(2);
     GS_STAMP(3);
     return ok ? sh.key[lane] : KEY_NONE;
@@ -726,7 +731,7 @@ __global__ __launch_bounds__(KNN_BT) void knn1_box_k(const float *__restrict__ s
         if (ok && wave == 0) best[i] = KEY_NONE;
         return;
     }
-    const unsigned long long key = knn_tile(sh, s, ok, -1, tgt, tgt, nullptr, boxes, nullptr, nt);
+    const unsigned long long key = knn_tile<KNN_NW>(sh, s, ok, -1, tgt, tgt, nullptr, boxes, nullptr, nt);
     if (ok && wave == 0) best[i] = key;
 }
 
@@ -831,20 +836,38 @@ __device__ __forceinline__ void rp_finish(float v, float *acc_sm) {
     }
     __syncthreads();
 }
+// rp_finish for a 512-thread block: thread (g, k) brings the sums of row groups g and g + 16
+__device__ __forceinline__ void rp_finish2(float v, float v2, float *acc_sm) {
+    __shared__ float stage[32][33];
+    const int k = threadIdx.x & 31, g = threadIdx.x >> 5;  // blockDim.x == 512 -> g in [0, 16)
+    stage[k][g] = v;
+    stage[k][g + 16] = v2;
+    __syncthreads();
+    if (threadIdx.x < NACC) {
+        float t = 0.0f;
+#pragma unroll
+        for (int q = 0; q < 32; ++q) t += stage[threadIdx.x][q];
+        acc_sm[threadIdx.x] = t;
+    }
+    __syncthreads();
+}
 // rp_finish for a block in which only wave 0 needs the sums (knn1_loop_k<true>: the other fifteen waves stage the search's
 // windows meanwhile, and the two block barriers above kept them from starting for 1.2 us -- phase stamps, r04a).  Every
 // wave leaves its 128 sums in LDS, waits for its OWN LDS writes (the caller's state words among them) and counts itself in;
 // wave 0 waits for the count, then adds the 32 group sums in the same order as rp_finish.  `cnt` must be zero and visible
-// to all waves before the first of them gets here (the caller's raw barrier at kernel start).
-__device__ __forceinline__ void rp_finish_wave0(float v, int g, float v2, int g2, float *acc_sm, unsigned int *cnt) {
+// to all waves before the first of them gets here (the caller's raw barrier at kernel start).  NW: the block's waves; an
+// eight-wave block brings up to three groups per thread (g3).
+template <int NW>
+__device__ __forceinline__ void rp_finish_wave0(float v, int g, float v2, int g2, float v3, int g3, float *acc_sm, unsigned int *cnt) {
     __shared__ float stage[32][33];
     const int k = threadIdx.x & 31;
     if (g >= 0) stage[k][g] = v;     // (g, g2: the row groups this thread summed, -1 = none -- knn1_loop_k hands the planning
     if (g2 >= 0) stage[k][g2] = v2;  // waves' groups to two of the waves that only wait)
+    if (NW != 16 && g3 >= 0) stage[k][g3] = v3;
     if (threadIdx.x >= 64) {
         if ((threadIdx.x & 63) == 0) __hip_atomic_fetch_add(cnt, 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
     } else {
-        while (__hip_atomic_load(cnt, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP) < (unsigned int)(KNN_NW - 1)) __builtin_amdgcn_s_sleep(1);
+        while (__hip_atomic_load(cnt, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP) < (unsigned int)(NW - 1)) __builtin_amdgcn_s_sleep(1);
         if (threadIdx.x < NACC) {
             float t = 0.0f;
 #pragma unroll
@@ -1357,16 +1380,19 @@ __device__ __forceinline__ float cam_bound2(const CamK &k, const f3 s, const int
     return L > 0.0f ? L * L : 0.0f;  // (NaN compares false: no proof)
 }
 
-template <bool GRID, int NL>
+template <bool GRID, int NL, int NW>
+// (NW: waves per block, 16 or 8 -- chosen by the host, loop_waves; every result is the same bit for bit: the neighbour is a
+// minimum over packed keys whoever finds it, and the row sums keep their groups and their order)
 // (argument order: what the first batch of requests needs comes first -- the leading sixteen dwords of the kernel arguments
 // can be preloaded into SGPRs with the dispatch, -amdgpu-kernarg-preload-count in the Makefile)
-__global__ __launch_bounds__(KNN_BT, 8) void knn1_loop_k(const LoopConst *__restrict__ C, const IcpState *__restrict__ S_in,
+__global__ __launch_bounds__(NW * 64, 2 * NW / 4) void knn1_loop_k(const LoopConst *__restrict__ C, const IcpState *__restrict__ S_in,
                                                          const float *__restrict__ partials_in, const int32_t *__restrict__ pix_ws,
                                                          const int32_t *__restrict__ cells_in, int cap, int tile_points,
                                                          int phase /* first | launch parity << 1 */, int step_mode, int look_slot,
                                                          int nblocks_in, IcpState *__restrict__ S_out, float *__restrict__ rec, int out_slot,
                                                          LoopBufs B, float *__restrict__ partials /* gridDim.x x NACC */,
                                                          const float *__restrict__ user_src) {
+    static_assert(NW == 16 || NW == 8, "row groups, tile_box and the J epilogue are laid out for sixteen or eight waves");
     const int first = phase & 1, par = phase >> 1;
     __shared__ KnnShared sh;
     __shared__ IcpState st_sm;
@@ -1412,13 +1438,30 @@ __global__ __launch_bounds__(KNN_BT, 8) void knn1_loop_k(const LoopConst *__rest
     // GRID: waves 1 and 2 (the planner and the lanes' wave: the critical path of the prologue) sum no rows; their four row
     // groups are the second duty of waves 14 and 15, which otherwise only wait for the plan.  (Same groups, same order
     // inside each: the sums do not change.)
-    const int rp_g = (GRID && (wave == 1 || wave == 2)) ? -1 : (int)(threadIdx.x >> 5);
-    const int rp_g2 = (GRID && wave >= 14) ? (int)(threadIdx.x >> 5) - 26 : -1;
-    float rp_b[RP_LOADS];
+    // NW = 8: sixteen thread groups for the 32 row groups.  GRID: the twelve outside waves 1 and 2 take groups w, w + 12 and
+    // (w < 8) w + 24, w = the thread group's rank among the twelve; chunk boxes: every thread group takes g and g + 16.
+    int rp_g, rp_g2, rp_g3 = -1;
+    if constexpr (NW == 16) {
+        rp_g = (GRID && (wave == 1 || wave == 2)) ? -1 : (int)(threadIdx.x >> 5);
+        rp_g2 = (GRID && wave >= 14) ? (int)(threadIdx.x >> 5) - 26 : -1;
+    } else if constexpr (GRID) {
+        const int tg = threadIdx.x >> 5, w = tg < 2 ? tg : tg - 4;
+        const bool sums = wave != 1 && wave != 2;
+        rp_g = sums ? w : -1;
+        rp_g2 = sums ? w + 12 : -1;
+        rp_g3 = (sums && w < 8) ? w + 24 : -1;  // (waves 0, 3, 4, 5: wave-uniform)
+    } else {
+        rp_g = threadIdx.x >> 5;
+        rp_g2 = rp_g + 16;
+    }
+    float rp_b[RP_LOADS], rp_c[RP_LOADS];
 #pragma unroll
-    for (int u = 0; u < RP_LOADS; ++u) { rp_a[u] = 0.0f; rp_b[u] = 0.0f; }
+    for (int u = 0; u < RP_LOADS; ++u) { rp_a[u] = 0.0f; rp_b[u] = 0.0f; rp_c[u] = 0.0f; }
     if (rp_g >= 0) rp_issue_padded<NL>(partials_in, rp_g, rp_a);  // (wave-uniform branches around loads only: nothing is waited for inside)
     if (rp_g2 >= 0) rp_issue_padded<NL>(partials_in, rp_g2, rp_b);
+    if constexpr (NW != 16 && GRID) {
+        if (rp_g3 >= 0) rp_issue_padded<NL>(partials_in, rp_g3, rp_c);
+    }
     static_assert(offsetof(LoopConst, nt) == offsetof(LoopConst, ns) + 4, "ns | nt are read as a pair");
     const int nn = reinterpret_cast<const int *>(&C->ns)[lane & 1];
     int e_h = 0, e_c = -1, e_cam = 0;
@@ -1434,7 +1477,10 @@ __global__ __launch_bounds__(KNN_BT, 8) void knn1_loop_k(const LoopConst *__rest
         asm volatile("" ::"v"(e_h), "v"(e_c), "v"(e_cam), "v"((unsigned)e_k0), "v"((unsigned)(e_k0 >> 32)),
                      "v"((unsigned)e_k1), "v"((unsigned)(e_k1 >> 32)));
     }
-    if constexpr (GRID)
+    if constexpr (NW != 16 && GRID)
+        asm volatile("" ::"v"(rp_c[0]), "v"(rp_c[1]), "v"(rp_c[2]), "v"(rp_c[3]), "v"(rp_c[4]), "v"(rp_c[5]), "v"(rp_c[6]), "v"(rp_c[7]), "v"(rp_c[8]),
+                     "v"(rp_c[9]), "v"(rp_c[10]), "v"(rp_c[11]), "v"(rp_c[12]), "v"(rp_c[13]), "v"(rp_c[14]), "v"(rp_c[15]));
+    if constexpr (GRID || NW != 16)
         asm volatile("" ::"v"(rp_b[0]), "v"(rp_b[1]), "v"(rp_b[2]), "v"(rp_b[3]), "v"(rp_b[4]), "v"(rp_b[5]), "v"(rp_b[6]), "v"(rp_b[7]), "v"(rp_b[8]),
                      "v"(rp_b[9]), "v"(rp_b[10]), "v"(rp_b[11]), "v"(rp_b[12]), "v"(rp_b[13]), "v"(rp_b[14]), "v"(rp_b[15]));
     asm volatile("" ::"v"(st_w), "v"(nn), "v"(rp_a[0]), "v"(rp_a[1]), "v"(rp_a[2]), "v"(rp_a[3]), "v"(rp_a[4]), "v"(rp_a[5]), "v"(rp_a[6]),
@@ -1467,12 +1513,17 @@ __global__ __launch_bounds__(KNN_BT, 8) void knn1_loop_k(const LoopConst *__rest
     if (threadIdx.x < kWords) reinterpret_cast<int *>(&st_sm)[threadIdx.x] = st_w;
     if (step_mode >= 0) {
         if constexpr (GRID) {
-            float v = 0.0f, v2 = 0.0f;
+            float v = 0.0f, v2 = 0.0f, v3 = 0.0f;
             if (rp_g >= 0) v = rp_sum_padded<NL>(rp_a);
             if (rp_g2 >= 0) v2 = rp_sum_padded<NL>(rp_b);
-            rp_finish_wave0(v, rp_g, v2, rp_g2, acc_sm, &rp_cnt);  // wave 0 leaves it with acc_sm and every wave's st_sm words visible TO IT
-        } else {
+            if constexpr (NW != 16) {
+                if (rp_g3 >= 0) v3 = rp_sum_padded<NL>(rp_c);
+            }
+            rp_finish_wave0<NW>(v, rp_g, v2, rp_g2, v3, rp_g3, acc_sm, &rp_cnt);  // wave 0 leaves it with acc_sm and every wave's st_sm words visible TO IT
+        } else if constexpr (NW == 16) {
             rp_finish(rp_sum_padded<NL>(rp_a), acc_sm);  // ends with a barrier: st_sm and acc_sm are visible
+        } else {
+            rp_finish2(rp_sum_padded<NL>(rp_a), rp_sum_padded<NL>(rp_b), acc_sm);
         }
         GS_STAMP(9);  // (diagnostic build: the rows are summed)
         // (the record takes the state BEFORE the step from the global copy: wave 0 is about to change the LDS one)
@@ -1635,7 +1686,7 @@ __global__ __launch_bounds__(KNN_BT, 8) void knn1_loop_k(const LoopConst *__rest
         }
         GS_STAMP(14);
         // staging loads first (they are the long ones), the per-lane rows behind them
-        constexpr int ST = KNN_BT - 64, NR = (POOL + ST - 1) / ST;
+        constexpr int ST = NW * 64 - 64, NR = (POOL + ST - 1) / ST;
         float4 sreg[NR];
 #pragma unroll
         for (int r = 0; r < NR; ++r) {
@@ -1729,7 +1780,7 @@ __global__ __launch_bounds__(KNN_BT, 8) void knn1_loop_k(const LoopConst *__rest
             }
             atomicMin(&sh.key[lane], k0);
         }
-        {   // window: every wave takes every 16th slot of the lane's row ranges
+        {   // window: every wave takes every NW-th slot of the lane's row ranges
             float bd = INFINITY;
             int bi = 0x7fffffff;
 #pragma unroll
@@ -1738,7 +1789,7 @@ __global__ __launch_bounds__(KNN_BT, 8) void knn1_loop_k(const LoopConst *__rest
                 const int kk = (rel & 3) + r, wn = LaneWin::len(wr, nt);
                 const int po = sh.band[WBANDS + min(kk, WBANDS - 1)];
                 const float *row = sh.u.stage + 4 * (max(po, 0) + LaneWin::lo(wr) - sh.band[min(kk, WBANDS - 1)]);
-                for (int p = wave; p < wn; p += KNN_NW) {
+                for (int p = wave; p < wn; p += NW) {
                     float4 q;
                     if (po >= 0) {
                         q = *reinterpret_cast<const float4 *>(row + 4 * p);
@@ -1770,12 +1821,12 @@ __global__ __launch_bounds__(KNN_BT, 8) void knn1_loop_k(const LoopConst *__rest
         GS_COUNT(12, (unsigned long long)__popcll(need_mask));
         bool tile_search = __popcll(need_mask) > 6;
         if (!tile_search && need_mask) {
-            tile_search = !knn_point_search(sh, s, need_mask, C->hints.scan_points, C->hints.scan_orig, C->boxes, C->sboxes, nt);  // ends with a barrier
+            tile_search = !knn_point_search<NW>(sh, s, need_mask, C->hints.scan_points, C->hints.scan_orig, C->boxes, C->sboxes, nt);  // ends with a barrier
         }
         if (tile_search) {
             tile_box(sh, s, need);
             __syncthreads();
-            knn_prune_search<true>(sh, s, ok, need, C->hints.scan_points, C->hints.scan_orig, C->boxes, C->sboxes, nt);  // ends with a barrier
+            knn_prune_search<true, NW>(sh, s, ok, need, C->hints.scan_points, C->hints.scan_orig, C->boxes, C->sboxes, nt);  // ends with a barrier
         }
         GS_STAMP(2);
         key = ok ? sh.key[lane] : KEY_NONE;
@@ -1800,8 +1851,8 @@ __global__ __launch_bounds__(KNN_BT, 8) void knn1_loop_k(const LoopConst *__rest
         if (window_seed) sj = -2;  // seeded by knn_window_seed below (block-uniform decision)
         const float *scan = C->hints.scan_points ? C->hints.scan_points : C->tgt;
         const int32_t *scan_orig = C->hints.scan_points ? C->hints.scan_orig : nullptr;
-        if (window_seed) knn_window_seed(sh, s, ok, i, C->hints, nt);
-        key = knn_tile(sh, s, ok, sj, C->tgt, scan, scan_orig, C->boxes, C->sboxes, nt);
+        if (window_seed) knn_window_seed<NW>(sh, s, ok, i, C->hints, nt);
+        key = knn_tile<NW>(sh, s, ok, sj, C->tgt, scan, scan_orig, C->boxes, C->sboxes, nt);
     }
     // linearise this tile straight away (J fused into K's epilogue): 29 sums over the tile's 64 points,
     // reduced through LDS by the whole block in a fixed order (two short stages instead of 29 butterflies)
@@ -1817,6 +1868,7 @@ __global__ __launch_bounds__(KNN_BT, 8) void knn1_loop_k(const LoopConst *__rest
         for (int k = 0; k < NACC; ++k) sh.u.a.rows[k][lane] = acc[k];
     }
     __syncthreads();
+    static_assert(NACC * 16 <= NW * 64, "the J epilogue's first stage is one pass");
     if (threadIdx.x < NACC * 16) {
         const int k = threadIdx.x >> 4, p4 = (threadIdx.x & 15) * 4;
         sh.u.a.part[k][threadIdx.x & 15] = ((sh.u.a.rows[k][p4] + sh.u.a.rows[k][p4 + 1]) + sh.u.a.rows[k][p4 + 2]) + sh.u.a.rows[k][p4 + 3];
@@ -1996,6 +2048,7 @@ bool profiling_enabled() { return g_prof.on; }
 
 static int g_grid_mode = getenv("GS_GRID_MODE") ? atoi(getenv("GS_GRID_MODE")) : 1;  // gs_set_grid_search (environment: measurements)
 static int g_tile_points = 0;  // gs_set_tile_points (0 = automatic)
+static int g_loop_waves = 0;   // gs_set_loop_waves (0 = automatic)
 
 // Source points per block of the loops' association kernel (knn1_loop_k): 64 -- lane = point.  Round 2 cut a dense
 // target's cloud into 38-point tiles (every CU two equal tiles: the chunk-box search there was VALU-issue bound and a
@@ -2010,7 +2063,20 @@ static inline int loop_tile_points() {
     const int forced = g_tile_points ? g_tile_points : env;
     return (forced >= TILE_MIN && forced <= 64) ? forced : 64;
 }
-int icp_config_stamp() { return g_grid_mode | (g_tile_points << 4); }  // part of slam.hip's graph-cache key
+// Waves per block of the loops' association kernel.  Results do not depend on it (see knn1_loop_k), so the host chooses
+// freely: eight where the grid search runs -- two such blocks on a CU are the sixteen waves one block used to be, and the
+// launch lasts as long as the CUs that host two ("eight-wave blocks") -- sixteen for the chunk-box
+// search, which is VALU-bound, and for a target whose CAPACITY exceeds LOOP_WAVES_DENSE slots per grid pixel: a long
+// sequence's arena, where the 200-frame forward measured 2 % slower with eight (capacity 218 per pixel; the c2 step,
+// capacity 27, is where eight gain).  gs_set_loop_waves / GS_LOOP_WAVES (8 or 16) force one for A/B runs and tests.
+constexpr int LOOP_WAVES_DENSE = 64;
+static inline int loop_waves(bool grid_search, int max_nt, int cells) {
+    static const int env = getenv("GS_LOOP_WAVES") ? atoi(getenv("GS_LOOP_WAVES")) : 0;
+    const int forced = g_loop_waves ? g_loop_waves : env;
+    if (forced == 8 || forced == 16) return forced;
+    return (grid_search && (int64_t)max_nt <= (int64_t)LOOP_WAVES_DENSE * cells) ? 8 : 16;
+}
+int icp_config_stamp() { return g_grid_mode | (g_tile_points << 4) | (g_loop_waves << 12); }  // part of slam.hip's graph-cache key
 static inline int loop_blocks_max(int max_ns) { return cdiv(max_ns, TILE_MIN); }  // workspace: whatever the tile size
 // rows of a partial-sum buffer: the association kernel's prologue reads rows 0 .. 32 RP_LOADS - 1 without testing them against
 // the launch's row count (icp_prepare_k zeroes the rows the loop's launches do not write), four bytes at a time up to twelve
@@ -2150,15 +2216,19 @@ static int icp_run(bool grad, const float *src, const int32_t *d_ns, int max_ns,
         const int nxt = pending >= 0 ? 1 - cur : cur;  // a folded step publishes the new state to the other buffer
         prof_mark(0, 0, st);
         float *rec_p = (tape && pending >= 0) ? tp.rec + (size_t)n_step * REC_WORDS : nullptr;
-        auto launch = [&](auto kernel) {
-            hipLaunchKernelGGL(kernel, kgrid, dim3(KNN_BT), 0, st, (const LoopConst *)w.lc, (const IcpState *)w.S[cur], (const float *)w.partials[cur],
+        const int nw = loop_waves(grid_search, max_nt, hints.grid_w * hints.grid_h);
+        auto launch_nw = [&](auto kernel, int waves) {
+            hipLaunchKernelGGL(kernel, kgrid, dim3(waves * 64), 0, st, (const LoopConst *)w.lc, (const IcpState *)w.S[cur], (const float *)w.partials[cur],
                                (const int32_t *)(w.cells + 2 * (size_t)max_ns), (const int32_t *)(w.cells + (size_t)(1 - (n_assoc & 1)) * max_ns),
                                max_ns, tile_points, first | ((n_assoc & 1) << 1), pending, pending_slot, lb, w.S[nxt], rec_p,
                                tape ? n_assoc : -1, w.B, w.partials[nxt], src);
         };
-        if (grid_search && lb <= 32 * RP_FEW) launch(knn1_loop_k<true, RP_FEW>);
-        else if (grid_search) launch(knn1_loop_k<true, RP_LOADS>);
-        else launch(knn1_loop_k<false, RP_LOADS>);
+        auto launch = [&](auto k16, auto k8) {
+            if (nw == 16) launch_nw(k16, 16); else launch_nw(k8, 8);
+        };
+        if (grid_search && lb <= 32 * RP_FEW) launch(knn1_loop_k<true, RP_FEW, 16>, knn1_loop_k<true, RP_FEW, 8>);
+        else if (grid_search) launch(knn1_loop_k<true, RP_LOADS, 16>, knn1_loop_k<true, RP_LOADS, 8>);
+        else launch(knn1_loop_k<false, RP_LOADS, 16>, knn1_loop_k<false, RP_LOADS, 8>);
         prof_mark(0, 1, st);
         if (pending >= 0) ++n_step;
         cur = nxt;
@@ -2749,6 +2819,10 @@ int gs_diag_set_buffer(void *p) {
 
 void gs_set_grid_search(int on) { g_grid_mode = on; }
 void gs_set_tile_points(int n) { g_tile_points = n; }
+int gs_set_loop_waves(int n) {
+    if (n == 0 || n == 8 || n == 16) g_loop_waves = n;
+    return g_loop_waves;
+}
 int gs_icp_launch_geometry(int max_ns, int have_hints, int *blocks, int *tile_points_dense, int *partial_rows) {
     GS_REQUIRE(max_ns > 0, "gs_icp_launch_geometry: max_ns must be positive");
     (void)have_hints;

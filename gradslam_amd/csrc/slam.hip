@@ -23,7 +23,7 @@ struct GraphKey {
     void *ws;
     int B, capS, capT, numiters, use_grad;
     float damp, thresh, lmax, Bp, B2, nu;
-    int icp_cfg;             // what else decides WHICH kernels a loop launches: gs_set_grid_search / gs_set_tile_points
+    int icp_cfg;             // what else decides WHICH kernels a loop launches: gs_set_grid_search / gs_set_tile_points / gs_set_loop_waves
     int H, W, ds;            // the loop's constants hold the ds-grid's dimensions
     bool operator==(const GraphKey &o) const {
         return H == o.H && W == o.W && ds == o.ds && ws == o.ws && B == o.B && capS == o.capS && capT == o.capT && numiters == o.numiters && use_grad == o.use_grad &&

@@ -458,6 +458,12 @@ void gs_set_fused_setup(int on);
  * the tile size fixes the summation order of the 6x6 system, so results of different settings agree to rounding, not bit
  * for bit; nearest neighbours are the brute-force scan's under every setting).  Replaces nothing in the reference. */
 void gs_set_tile_points(int n);
+/* Waves per block of the loops' association kernel: 0 (default) = automatic (eight where the grid search runs on a target of
+ * at most 64 slots of capacity per grid pixel, sixteen otherwise); 8 or 16 = that many, for A/B measurements and tests.  Any other value is ignored.  Returns
+ * the setting in force after the call.  Every result of the loops is the same bit for bit under either count.  The
+ * environment variable GS_LOOP_WAVES (read once) does the same where the setter is at 0.  Replaces nothing in the
+ * reference. */
+int gs_set_loop_waves(int n);
 /* Launch geometry of one association launch of the loops above for a source capacity (host-side query, no device
  * work): blocks launched, source points per block, and the number of partial rows the workspace (gs_icp_ws_bytes)
  * holds per buffer (>= blocks for every tile-size setting).  The rows are padded to at least 513: the association

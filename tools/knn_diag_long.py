@@ -43,7 +43,10 @@ with torch.no_grad():
         short._localize(pcs, live, prevf)
 torch.cuda.synchronize()
 print("frames", n, "map", int(pcs.num_points_per_pointcloud.item()))
-raw = dbg.cpu().numpy().reshape(nblk, 16, 16)
+raw = dbg.cpu().numpy().reshape(nblk, 16, 16)  # 16 wave slots per block, whatever the launch's wave count (GS_LOOP_WAVES / the host's rule)
+nw = int((raw[..., 6] != 0).any(0).sum())       # waves that stamped their kernel entry: 16 or 8
+raw = raw[:, :nw]
+print("waves per block", nw)
 a = raw.astype(np.float64)
 live = a[..., 3].max(1) > 0
 a = a[live]

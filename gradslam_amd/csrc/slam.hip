@@ -7,11 +7,10 @@
 #include <vector>
 
 #include "gs_common.hpp"
+#include "gs_icp.hpp"
 #include "gs_project.hpp"
 
 namespace gs {
-
-bool profiling_enabled();  // icp.hip
 
 // ------------------------------------------------------------------ hipGraph cache for the ICP loops
 // Every argument of the (grad)ICP loop launched by gs_slam_localize lives in the caller's workspace, so
@@ -70,13 +69,6 @@ __global__ void compose_k(const float *__restrict__ T, const float *__restrict__
     compose44(T + 16 * b, P + 16 * b, out + 16 * b);
 }
 
-// icp.hip: gs_icp_point_to_plane[_grad|_taped] with the pose composition folded into the loop's last launch
-// (compose_out = out_T . compose_right; both optional)
-int icp_localize_run(int grad_lm, const float *src, const int32_t *d_ns, int max_ns, const float *tgt, const float *nrm,
-                     const int32_t *d_nt, int max_nt, int numiters, float damp, float thresh, float lambda_max, float Bp,
-                     float B2, float nu, const gs_icp_hints *hints, float *out_T, void *ws, size_t ws_bytes, hipStream_t st,
-                     void *tape, size_t tape_bytes, const float *compose_right, float *compose_out);
-int icp_config_stamp();  // icp.hip: the process-wide search / tiling switches, as one number
 // maps.hip: the maps of one frame per batch element + (pose | intrinsics) copied to cam_out (B, 32)
 int vertex_normal_maps_cam(const float *depth, const float *intrinsics, const float *poses, int B, int H, int W, float *vertex,
                            float *normal, float *gvertex, float *gnormal, float *cam_out, hipStream_t st);

@@ -2,7 +2,7 @@
 """Diagnostic only: phase stamps of the LAST association launch of a long streamed PointFusion run, i.e. with
 the ICP target grown to the downsampled active map (needs make -C gradslam_amd/csrc diag).
 
-Stamp slots per wave (16 x 8 bytes per wave, GS_STAMP / GS_COUNT in icp.hip; times are s_memrealtime ticks of 10 ns):
+Stamp slots per wave (16 x 8 bytes per wave, GS_STAMP / GS_COUNT in csrc/gs_icp_assoc.hpp; times are s_memrealtime ticks of 10 ns):
   6 kernel entry | 8 first batch of requests arrived | 9 row sums handed over (wave 0: sums ready) | 7 prologue barrier passed
   wave 0 (the folded step): 13 decision taken + state updated | 14 6x6 system solved | 10 step done
   wave 1 (planner): 13 window centres + majority displacement known | 14 plan published | 15 its share staged

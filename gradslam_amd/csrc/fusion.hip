@@ -9,6 +9,7 @@
 // points (corr_pass1_k / corr_pass2_k / merge_corr_k below).
 #include "gs_common.hpp"
 #include "gs_compact.hpp"
+#include "gs_drivers.hpp"
 #include "gs_project.hpp"
 
 namespace gs {
@@ -676,29 +677,26 @@ __global__ __launch_bounds__(1024) void fuse_finish_k(const int32_t *__restrict_
 }
 
 // ---- the fused chain's host side (slam.hip drives it).  state = [pix_key (npix x 8) | pix_n (npix x 4) | pt_pix
-// (B*Nmax x 4) | part_active, part_u (blocks x 4 each)]; pix_key / pix_n are initialised by the maps kernel (VnExtra).
+// (B*Nmax x 4) | part_active, part_similar, part_u (blocks x 4 each)]; pix_key / pix_n are initialised by the maps kernel (VnExtra).
 static inline int corr_blocks(int Nmax) { return cdiv(Nmax > 0 ? Nmax : 1, CORR_B); }
-size_t fusion_corr_state_bytes(int B, int H, int W, int Nmax) {
-    const size_t npix = (size_t)B * H * W;
-    return align_up(npix * 8, 256) + align_up(npix * 4, 256) + align_up((size_t)B * Nmax * 4, 256) +
-           3 * align_up((size_t)B * corr_blocks(Nmax) * 4, 256);
-}
 struct CorrState {
     unsigned long long *pix_key;
     unsigned int *pix_n;
     int *pt_pix;
     int32_t *part_active, *part_similar, *part_u;
 };
+static size_t corr_state_layout(int B, int H, int W, int Nmax, void *state, CorrState *out) {
+    const size_t npix = (size_t)B * H * W, part = (size_t)B * corr_blocks(Nmax) * 4;
+    Carve c{(char *)state};
+    CorrState scratch, &s = out ? *out : scratch;
+    s.pix_key = c.take<unsigned long long>(npix * 8); s.pix_n = c.take<unsigned int>(npix * 4); s.pt_pix = c.take<int>((size_t)B * Nmax * 4);
+    s.part_active = c.take<int32_t>(part); s.part_similar = c.take<int32_t>(part); s.part_u = c.take<int32_t>(part);
+    return c.off;
+}
+size_t fusion_corr_state_bytes(int B, int H, int W, int Nmax) { return corr_state_layout(B, H, W, Nmax, nullptr, nullptr); }
 static inline CorrState corr_state_ptrs(void *state, int B, int H, int W, int Nmax) {
-    const size_t npix = (size_t)B * H * W;
-    char *p = (char *)state;
     CorrState c;
-    c.pix_key = (unsigned long long *)p; p += align_up(npix * 8, 256);
-    c.pix_n = (unsigned int *)p; p += align_up(npix * 4, 256);
-    c.pt_pix = (int *)p; p += align_up((size_t)B * Nmax * 4, 256);
-    c.part_active = (int32_t *)p; p += align_up((size_t)B * corr_blocks(Nmax) * 4, 256);
-    c.part_similar = (int32_t *)p; p += align_up((size_t)B * corr_blocks(Nmax) * 4, 256);
-    c.part_u = (int32_t *)p;
+    corr_state_layout(B, H, W, Nmax, state, &c);
     return c;
 }
 void fusion_corr_init_ptrs(void *state, int B, int H, int W, int Nmax, unsigned long long **pix_key, unsigned int **pix_n) {
@@ -755,23 +753,23 @@ int fusion_finish(void *state, int B, int H, int W, int Nmax, int32_t *ctr, int3
 const unsigned int *fusion_corr_pix_n(const void *state, int B, int H, int W, int Nmax) {
     return corr_state_ptrs((void *)state, B, H, W, Nmax).pix_n;
 }
-size_t fusion_tape_bytes(int B, int H, int W) {
-    const size_t npix = (size_t)B * H * W;
-    return 2 * align_up((size_t)B * 4, 256) + align_up(npix * 4, 256) + align_up(npix * 40, 256);
-}
 struct FusionTape {
-    int32_t *n_before, *appended;
-    unsigned int *pix_n;
-    float *old;
+    int32_t *n_before, *appended;  // (B) each
+    unsigned int *pix_n;           // (B*H*W) every pixel's winner
+    float *old;                    // (B*H*W, 10) the matched rows' values before the merge
 };
-static inline FusionTape fusion_tape_ptrs(void *tape, int B, int H, int W) {
+static size_t fusion_tape_layout(int B, int H, int W, void *tape, FusionTape *out) {
     const size_t npix = (size_t)B * H * W;
-    char *p = (char *)tape;
+    Carve c{(char *)tape};
+    FusionTape scratch, &t = out ? *out : scratch;
+    t.n_before = c.take<int32_t>((size_t)B * 4); t.appended = c.take<int32_t>((size_t)B * 4);
+    t.pix_n = c.take<unsigned int>(npix * 4); t.old = c.take<float>(npix * 40);
+    return c.off;
+}
+size_t fusion_tape_bytes(int B, int H, int W) { return fusion_tape_layout(B, H, W, nullptr, nullptr); }
+static inline FusionTape fusion_tape_ptrs(void *tape, int B, int H, int W) {
     FusionTape t;
-    t.n_before = (int32_t *)p; p += align_up((size_t)B * 4, 256);
-    t.appended = (int32_t *)p; p += align_up((size_t)B * 4, 256);
-    t.pix_n = (unsigned int *)p; p += align_up(npix * 4, 256);
-    t.old = (float *)p;
+    fusion_tape_layout(B, H, W, tape, &t);
     return t;
 }
 // after fusion_correspond, before the merge: winners, pre-merge values and the row counts before the append

@@ -47,6 +47,15 @@ void set_error(const char *fmt, ...);
 static inline int cdiv(int64_t a, int64_t b) { return (int)((a + b - 1) / b); }
 static inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 
+// Carves a workspace into 256-byte aligned pieces, in order; with a NULL base it only adds up the size.  A *_layout function
+// runs it once for both questions, so a workspace's size and its pointers cannot drift apart.
+struct Carve {
+    char *base;
+    size_t off = 0;
+    template <class T = void>
+    T *take(size_t bytes) { const size_t o = off; off += align_up(bytes, 256); return (T *)(base ? base + o : nullptr); }
+};
+
 // ------------------------------------------------------------------ device helpers
 struct f3 {
     float x, y, z;

@@ -8,6 +8,7 @@
 
 #include "gs_common.hpp"
 #include "gs_compact.hpp"
+#include "gs_drivers.hpp"
 #include "gs_maps.hpp"
 #include "gs_project.hpp"
 

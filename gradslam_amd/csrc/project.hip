@@ -5,6 +5,7 @@
 // read of the points is served by L2 / Infinity Cache and costs less than a 4 B/pt flag round trip.
 #include "gs_common.hpp"
 #include "gs_compact.hpp"
+#include "gs_drivers.hpp"
 #include "gs_maps.hpp"
 #include "gs_project.hpp"
 
@@ -462,7 +463,6 @@ __global__ __launch_bounds__(kCT) void setup_count_k(int64_t nA, PA pa, int *__r
 // (The loop's chunk boxes stay icp_prepare_k's.  Built here by atomic min / max on the float bits -- exact, and it would save
 // that launch too -- this launch took 43 us instead of ~5: ~115 k scattered atomics execute at the memory side, one 64-B
 // request per lane.)
-constexpr int kBucketPixMax = 24 * 1024;  // ds-grid pixels whose starts fit in LDS
 constexpr int kBucketBlocks = 128;
 __global__ __launch_bounds__(1024) void bucket_scatter_k(const float *__restrict__ tgt, const int32_t *__restrict__ d_nt, int cap,
                                                          const int32_t *__restrict__ row_pix, const int *__restrict__ cnt,

@@ -1,14 +1,15 @@
 // slam.hip -- whole-step drivers: chains of the kernels of this library with every data-dependent size
 // kept on the device, so one C call enqueues a complete ICPSLAM._localize (reference
 // slam/icpslam.py:238-247) without a single host round trip.
+#include <algorithm>
 #include <chrono>
 #include <mutex>
 #include <stdlib.h>
 #include <vector>
 
 #include "gs_common.hpp"
+#include "gs_drivers.hpp"
 #include "gs_icp.hpp"
-#include "gs_project.hpp"
 
 namespace gs {
 
@@ -62,6 +63,78 @@ static bool graphs_allowed() {
     return g_auto_samples >= 4 && g_auto_min_us > kSlowLaunchUs;
 }
 
+// The cache's one call.  Replays the graph of `key` on `st`; a key seen for the second time is captured first:
+// enqueue(capture stream) on a private non-blocking stream.  *launched stays false where there is no graph to replay (first
+// sighting, or a capture that failed: its error is cleared) -- the caller then launches eagerly.
+template <class Enqueue>
+static int graph_replay(const GraphKey &key, hipStream_t st, Enqueue &&enqueue, bool *launched) {
+    std::lock_guard<std::mutex> lock(g_graph_mu);
+    int device = 0;
+    (void)hipGetDevice(&device);
+    GraphEntry *hit = nullptr;
+    for (auto &e : g_graphs)
+        if (e.device == device && e.key == key) hit = &e;
+    bool seen = false;
+    if (!hit) {
+        for (auto &k : g_seen_once) seen = seen || (k == key);
+        if (!seen) {
+            if (g_seen_once.size() >= 16) g_seen_once.erase(g_seen_once.begin());
+            g_seen_once.push_back(key);
+        }
+    }
+    if (!hit && seen) {
+        hipStream_t cs = nullptr;
+        hipGraph_t graph = nullptr;
+        hipGraphExec_t exec = nullptr;
+        bool ok = hipStreamCreateWithFlags(&cs, hipStreamNonBlocking) == hipSuccess;
+        ok = ok && hipStreamBeginCapture(cs, hipStreamCaptureModeThreadLocal) == hipSuccess;
+        if (ok) {
+            const int r = enqueue(cs);
+            const hipError_t e = hipStreamEndCapture(cs, &graph);
+            ok = (r == GS_OK) && e == hipSuccess && graph != nullptr;
+        }
+        ok = ok && hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0) == hipSuccess;
+        if (graph) (void)hipGraphDestroy(graph);
+        if (cs) (void)hipStreamDestroy(cs);
+        if (ok) {
+            if (g_graphs.size() >= 8) {  // evict the least recently used
+                size_t v = 0;
+                for (size_t i = 1; i < g_graphs.size(); ++i)
+                    if (g_graphs[i].last_use < g_graphs[v].last_use) v = i;
+                (void)hipGraphExecDestroy(g_graphs[v].exec);
+                g_graphs.erase(g_graphs.begin() + v);
+            }
+            g_graphs.push_back(GraphEntry{key, device, exec, 0});
+            hit = &g_graphs.back();
+            ++g_captures;
+        } else {
+            (void)hipGetLastError();
+        }
+    }
+    if (hit) {
+        hit->last_use = ++g_graph_clock;
+        ++g_replays;
+        GS_HIP(hipGraphLaunch(hit->exec, st), "gs_slam_localize/graph");
+        *launched = true;
+    }
+    return GS_OK;
+}
+
+// Automatic mode's sample: enqueue() eagerly, and what one of its `launches` launches cost the host.
+template <class Enqueue>
+static int eager_timed(int launches, Enqueue &&enqueue) {
+    const auto t0 = std::chrono::steady_clock::now();
+    const int rc = enqueue();
+    if (rc) return rc;
+    const double us = std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count();
+    std::lock_guard<std::mutex> lock(g_graph_mu);
+    if (g_auto_samples < 64) {
+        ++g_auto_samples;
+        g_auto_min_us = std::min(g_auto_min_us, us / launches);
+    }
+    return GS_OK;
+}
+
 // out[b] = T[b] . P[b]   (compose44, gs_common.hpp)
 __global__ void compose_k(const float *__restrict__ T, const float *__restrict__ P, int B, float *__restrict__ out) {
     const int b = blockIdx.x * blockDim.x + threadIdx.x;
@@ -69,26 +142,10 @@ __global__ void compose_k(const float *__restrict__ T, const float *__restrict__
     compose44(T + 16 * b, P + 16 * b, out + 16 * b);
 }
 
-// maps.hip: the maps of one frame per batch element + (pose | intrinsics) copied to cam_out (B, 32)
-int vertex_normal_maps_cam(const float *depth, const float *intrinsics, const float *poses, int B, int H, int W, float *vertex,
-                           float *normal, float *gvertex, float *gnormal, float *cam_out, hipStream_t st);
 __global__ void eye4_k(float *__restrict__ T, int B) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i < 16 * B) T[i] = ((i % 16) % 5 == 0) ? 1.0f : 0.0f;
 }
-
-// project.hip: active-point projection on the ds grid + ICP target build for one sequence, 4 launches
-size_t project_target1_ws_bytes(int H, int W, int ds, int Nmax);
-int project_target1(const float *points, const int32_t *counts, int Nmax, const float *poses, const float *intrinsics, int H,
-                    int W, int ds, const float *map_normals, int cap, int64_t *rows, int32_t *nrows, float *tgt, float *tnrm,
-                    int32_t *nt, float *scan_points, int32_t *scan_orig, int32_t *pix_start, int32_t *tgt_index, int32_t *tgt_pix,
-                    void *ws, size_t ws_bytes, hipStream_t st, const DsJob *frame);
-// project.hip: the fused front end of one sequence, three launches (maps + counts, write, bucketing)
-int project_front1(const float *depth, const float *points, const int32_t *counts, int Nmax, const float *poses, const float *intrinsics,
-                   int H, int W, int ds, const float *map_normals, int cap, float *vertex, float *normal, float *gvertex, float *gnormal,
-                   float *cam_out, int32_t *row_pix, float *tgt, float *tnrm, int32_t *nt, int32_t *tgt_index, float *scan_points,
-                   int32_t *scan_orig, int32_t *pix_start, const DsJob &frame, void *ws, size_t ws_bytes, hipStream_t st);
-constexpr int kFusedPixMax = 24 * 1024;  // project.hip kBucketPixMax: the ds-grid's bin starts live in LDS
 
 struct LocWs {
     float *src;        // (B, capS, 3)
@@ -118,74 +175,69 @@ static inline int target_cap(int Nmax) {
 
 static size_t loc_layout(int B, int H, int W, int ds, int Nmax, void *ws, LocWs *out) {
     const int capS = cdiv(H, ds) * cdiv(W, ds), capT = target_cap(Nmax);
-    size_t off = 0;
-    auto take = [&](size_t bytes) { size_t o = off; off += align_up(bytes, 256); return o; };
-    const size_t o_src = take((size_t)B * capS * 12), o_ns = take((size_t)B * 4);
-    const size_t o_spix = take((size_t)B * capS * 4), o_scan = take((size_t)B * capT * 12);
-    const size_t o_sorig = take((size_t)B * capT * 4), o_pseed = take((size_t)B * (capS + 1) * 4);
+    Carve c{(char *)ws};
+    LocWs scratch, &w = out ? *out : scratch;
+    w.src = c.take<float>((size_t)B * capS * 12); w.ns = c.take<int32_t>((size_t)B * 4);
+    w.src_pix = c.take<int32_t>((size_t)B * capS * 4); w.scan = c.take<float>((size_t)B * capT * 12);
+    w.scan_orig = c.take<int32_t>((size_t)B * capT * 4); w.pix_start = c.take<int32_t>((size_t)B * (capS + 1) * 4);
     // NB every size below depends on (B, H, W, ds, capT) only -- never on Nmax itself -- so that pointers baked
     // into a captured graph stay valid while the map grows inside one capacity bucket
-    const size_t o_rows = take((size_t)B * capT * 32), o_nrows = take(4);
-    const size_t o_tgt = take((size_t)B * capT * 12), o_tnrm = take((size_t)B * capT * 12), o_nt = take((size_t)B * 4);
-    const size_t o_T = take((size_t)B * 64), o_eye = take((size_t)B * 64), o_cam = take((size_t)B * 128);
-    size_t sub = gs_downsample_frame_ws_bytes(H, W, ds);
-    sub = std::max(sub, gs_project_active_ws_bytes(B, Nmax));
-    sub = std::max(sub, gs_gather_table_rows_ws_bytes(B));
-    sub = std::max(sub, gs_bucket_by_pixel_ws_bytes(B, H, W, ds));
-    sub = std::max(sub, gs_icp_ws_bytes(capS, capT));
-    sub = std::max(sub, project_target1_ws_bytes(H, W, ds, Nmax));
-    const size_t o_sub = take(sub);
-    if (ws && out) {
-        char *p = (char *)ws;
-        out->src = (float *)(p + o_src); out->ns = (int32_t *)(p + o_ns);
-        out->src_pix = (int32_t *)(p + o_spix); out->scan = (float *)(p + o_scan);
-        out->scan_orig = (int32_t *)(p + o_sorig); out->pix_start = (int32_t *)(p + o_pseed);
-        out->rows = (int64_t *)(p + o_rows); out->nrows = (int32_t *)(p + o_nrows);
-        out->tgt = (float *)(p + o_tgt); out->tnrm = (float *)(p + o_tnrm); out->nt = (int32_t *)(p + o_nt);
-        out->T = (float *)(p + o_T); out->eye = (float *)(p + o_eye); out->cam = (float *)(p + o_cam);
-        out->sub = p + o_sub; out->sub_bytes = sub;
-    }
-    return off;
+    w.rows = c.take<int64_t>((size_t)B * capT * 32); w.nrows = c.take<int32_t>(4);
+    w.tgt = c.take<float>((size_t)B * capT * 12); w.tnrm = c.take<float>((size_t)B * capT * 12); w.nt = c.take<int32_t>((size_t)B * 4);
+    w.T = c.take<float>((size_t)B * 64); w.eye = c.take<float>((size_t)B * 64); w.cam = c.take<float>((size_t)B * 128);
+    w.sub_bytes = std::max({gs_downsample_frame_ws_bytes(H, W, ds), gs_project_active_ws_bytes(B, Nmax), gs_gather_table_rows_ws_bytes(B),
+                            gs_bucket_by_pixel_ws_bytes(B, H, W, ds), gs_icp_ws_bytes(capS, capT), project_target1_ws_bytes(H, W, ds, Nmax)});
+    w.sub = c.take(w.sub_bytes);
+    return c.off;
 }
 
 // gs_set_fused_setup: the fused front end (project.hip: project_front1) for one sequence; the environment's GS_FUSED_SETUP
 // (measurements) sets the default
 static int g_fused_setup = getenv("GS_FUSED_SETUP") ? atoi(getenv("GS_FUSED_SETUP")) : 1;
 static inline bool fused_front(int B, int H, int W, int ds) {
-    return g_fused_setup != 0 && B == 1 && (int64_t)cdiv(H, ds) * cdiv(W, ds) <= kFusedPixMax;
+    return g_fused_setup != 0 && B == 1 && (int64_t)cdiv(H, ds) * cdiv(W, ds) <= kBucketPixMax;  // project_front1's limit
 }
 
-// fusion.hip: the fused correspondence chain of the PointFusion update (no tables: 4 bytes per map point), the merge that
-// reads it, the append of the unmatched pixels and the update's last launch; maps.hip: the maps kernel with its riders
-size_t fusion_corr_state_bytes(int B, int H, int W, int Nmax);
-void fusion_corr_init_ptrs(void *state, int B, int H, int W, int Nmax, unsigned long long **pix_key, unsigned int **pix_n);
-int fusion_correspond(void *state, const float *map_points, const float *map_normals, const float *map_ccounts, const int32_t *counts,
-                      int B, int Nmax, const float *poses, const float *intrinsics, int H, int W, const float *gvertex,
-                      const float *gnormal, float dist_th, float dot_th, int32_t *ctr, hipStream_t st);
-int fusion_merge_corr(void *state, const int32_t *ctr, const float *gvertex, const float *gnormal, const float *rgb, const float *alpha,
-                      int B, int H, int W, int Nmax, const int32_t *counts, float *points, float *normals, float *colors,
-                      float *ccounts, hipStream_t st);
-int fusion_append_corr(void *state, int B, int H, int W, int Nmax, int b, const float *depth, const float *const *h_src,
-                       const int *h_row_floats, float *const *h_dst, const int32_t *d_count, int cap, int *d_total, void *cws,
-                       hipStream_t st);
-int fusion_finish(void *state, int B, int H, int W, int Nmax, int32_t *ctr, int32_t *counts, const int *totals, int cap,
-                  int32_t *appended, int32_t *stats, hipStream_t st);
-int vertex_normal_maps_fusion(const float *depth, const float *intrinsics, const float *poses, int B, int H, int W, float *gvertex,
-                              float *gnormal, float *alpha, float sigma, float eps, unsigned long long *pix_key, unsigned int *pix_n,
-                              int32_t *zero, int n_zero, hipStream_t st);
+// The front end of both localisation entry points: the live frame's ds-grid source cloud (src, src_pix, ns) and, from the map
+// points that land on the ds-grid of the previous frame, the ICP target -- reference-order points, normals and count (nt), the
+// map index of every slot (tgt_index, optional), and the same points in pixel order with the first scan slot of every ds-grid
+// pixel (search hints only).  The destinations are the workspace's (gs_slam_localize) or the tape's (gs_slam_localize_taped).
+// compute_maps: the frame's maps under the previous pose are computed too (gvertex is then gvertex_out), and the bucketing
+// camera -- previous pose | intrinsics -- lands at cam_out.  Otherwise gvertex is the caller's and the map outputs are NULL.
+// One sequence takes the fused form (gs_set_fused_setup; maps + counts, write, bucketing: three launches) or, switched off,
+// the 4-launch form behind the maps kernel, on whose first two launches the frame's ds-grid source cloud rides (two launches
+// of ~5 us less on the step's chain); a batch takes the separate entry points.
+static int enqueue_front(const float *depth, const float *gvertex, const float *intrinsics, const float *prev_poses, int B, int H, int W,
+                         int ds, const float *map_points, const float *map_normals, const int32_t *map_counts, int Nmax, const LocWs &w,
+                         float *src, int32_t *src_pix, int32_t *ns, int32_t *nt, int32_t *tgt_index, bool compute_maps, float *vertex,
+                         float *normal, float *gvertex_out, float *gnormal, float *cam_out, hipStream_t st) {
+    const int capS = cdiv(H, ds) * cdiv(W, ds), capT = target_cap(Nmax);
+    const DsJob frame{depth, gvertex, src, src_pix, ns};
+    int rc;
+    if (fused_front(B, H, W, ds))
+        return project_front1(compute_maps ? depth : nullptr, map_points, map_counts, Nmax, prev_poses, intrinsics, H, W, ds, map_normals,
+                              capT, vertex, normal, gvertex_out, gnormal, cam_out, (int32_t *)w.rows, w.tgt, w.tnrm, nt, tgt_index, w.scan,
+                              w.scan_orig, w.pix_start, frame, w.sub, w.sub_bytes, st);
+    if (compute_maps &&
+        (rc = vertex_normal_maps_cam(depth, intrinsics, prev_poses, B, H, W, vertex, normal, gvertex_out, gnormal, cam_out, st))) return rc;
+    if (B == 1)
+        return project_target1(map_points, map_counts, Nmax, prev_poses, intrinsics, H, W, ds, map_normals, capT, w.rows, w.nrows, w.tgt,
+                               w.tnrm, nt, w.scan, w.scan_orig, w.pix_start, tgt_index, nullptr, w.sub, w.sub_bytes, st, &frame);
+    if ((rc = gs_downsample_frame(depth, gvertex, nullptr, nullptr, B, H, W, ds, capS, src, nullptr, nullptr, src_pix, ns, w.sub,
+                                  w.sub_bytes, (gs_stream_t)st))) return rc;
+    if ((rc = gs_project_active(map_points, map_counts, B, Nmax, prev_poses, intrinsics, H, W, ds, w.rows, w.nrows, w.sub, w.sub_bytes,
+                                (gs_stream_t)st))) return rc;
+    return gs_build_icp_target(w.rows, w.nrows, (int64_t)B * Nmax, B, H, W, ds, map_points, map_normals, Nmax, capT, w.tgt, w.tnrm, nt,
+                               w.scan, w.scan_orig, w.pix_start, tgt_index, nullptr, w.sub, w.sub_bytes, (gs_stream_t)st);
+}
 
-size_t fusion_tape_bytes(int B, int H, int W);
-int fusion_tape_record(const void *state, void *tape, int B, int H, int W, int Nmax, const int32_t *counts, const float *points,
-                       const float *normals, const float *colors, const float *ccounts, hipStream_t st);
-int fusion_tape_appended(void *tape, int B, int H, int W, const int32_t *appended, hipStream_t st);
-int fusion_update_reverse(const void *tape, int B, int H, int W, int Nmax, const float *depth, const float *gvertex,
-                          const float *gnormal, const float *rgb, const float *alpha, float *points, float *normals, float *colors,
-                          float *ccounts, int32_t *counts, float *Gp, float *Gn, float *Gc, float *Gcc, float *g_gvertex,
-                          float *g_gnormal, float *g_rgb, float *g_alpha, void *cws, hipStream_t st);
-
-int append_valid_pixels(int n_arrays, const float *depth_b, int64_t HW, const float *const *h_src, const int *h_row_floats,
-                        float *const *h_dst, int32_t *d_count, int cap, int32_t *d_appended, int32_t *d_overflow, void *cws,
-                        hipStream_t st);
+// the search hints of batch element b's loop: the pixel-ordered target of the workspace, the source cloud's ds-grid pixels
+// and the bucketing camera (pose, intrinsics: 16 floats each)
+static inline gs_icp_hints loc_hints(const LocWs &w, const int32_t *src_pix, int b, int H, int W, int ds, int capS, int capT,
+                                     const float *pose, const float *intrinsics) {
+    return gs_icp_hints{w.scan + (size_t)b * capT * 3, w.scan_orig + (size_t)b * capT, src_pix + (size_t)b * capS,
+                        w.pix_start + (size_t)b * (capS + 1), nullptr, cdiv(W, ds), cdiv(H, ds), pose, intrinsics, ds};
+}
 
 // ------------------------------------------------------------------ PointFusion map update on an arena
 struct FuseWs {
@@ -197,25 +249,59 @@ struct FuseWs {
     void *sub;
     size_t sub_bytes;
 };
+// the compaction's scratch for one H x W frame and, behind it, the room for its total: fusion.hip's append passes keep the
+// total at cws + compact_ws_bytes(HW)
+constexpr size_t kCompactTotalBytes = 256;
+static inline size_t compact_total_ws_bytes(int H, int W) { return gs_compact_ws_bytes((int64_t)H * W) + kCompactTotalBytes; }
+
 constexpr int kCtrWords = 64;  // counter block (zeroed by the maps kernel): ctr[0..], appended at +64, totals at +128
 static size_t fuse_layout(int B, int H, int W, int Nmax, void *ws, FuseWs *out) {
     const size_t npix = (size_t)B * H * W;
-    size_t off = 0;
-    auto take = [&](size_t bytes) { size_t o = off; off += align_up(bytes, 256); return o; };
-    const size_t ogV = take(npix * 12), ogN = take(npix * 12), oA = take(npix * 4);
-    const size_t oM = take(fusion_corr_state_bytes(B, H, W, Nmax));
-    const size_t oC = take((size_t)(kCtrWords + 2 * 64) * 4);
-    const size_t sub = gs_compact_ws_bytes((int64_t)H * W) + 256;
-    const size_t oS = take(sub);
-    if (ws && out) {
-        char *p = (char *)ws;
-        out->gV = (float *)(p + ogV); out->gN = (float *)(p + ogN);
-        out->alpha = (float *)(p + oA); out->state = p + oM;
-        int32_t *c = (int32_t *)(p + oC);
-        out->ctr = c; out->appended = c + kCtrWords; out->totals = (int *)(c + kCtrWords + 64);
-        out->sub = p + oS; out->sub_bytes = sub;
-    }
-    return off;
+    Carve c{(char *)ws};
+    FuseWs scratch, &w = out ? *out : scratch;
+    w.gV = c.take<float>(npix * 12); w.gN = c.take<float>(npix * 12); w.alpha = c.take<float>(npix * 4);
+    w.state = c.take(fusion_corr_state_bytes(B, H, W, Nmax));
+    w.ctr = c.take<int32_t>((size_t)(kCtrWords + 2 * 64) * 4);
+    w.appended = w.ctr + kCtrWords; w.totals = (int *)(w.ctr + kCtrWords + 64);
+    w.sub_bytes = compact_total_ws_bytes(H, W);
+    w.sub = c.take(w.sub_bytes);
+    return c.off;
+}
+
+// gs_pointfusion_update_backward: the frame's maps again (B,H,W,3), alpha and its adjoint (B,H,W), the compaction's scratch
+struct FuseBwdWs {
+    float *V, *N, *gV, *gN, *alpha, *g_alpha;
+    void *cws;
+};
+static size_t fuse_bwd_layout(int B, int H, int W, void *ws, FuseBwdWs *out) {
+    const size_t npix = (size_t)B * H * W;
+    Carve c{(char *)ws};
+    FuseBwdWs scratch, &w = out ? *out : scratch;
+    w.V = c.take<float>(npix * 12); w.N = c.take<float>(npix * 12); w.gV = c.take<float>(npix * 12); w.gN = c.take<float>(npix * 12);
+    w.alpha = c.take<float>(npix * 4); w.g_alpha = c.take<float>(npix * 4);
+    w.cws = c.take(compact_total_ws_bytes(H, W));
+    c.take(256);  // spare: nothing lives here, the size has always carried it
+    return c.off;
+}
+
+// gs_aggregate_update: the frame's global maps (B,H,W,3), the counters its memset clears -- overflow flag (1), rows appended
+// per sequence (B), counter_bytes in all -- and the compaction's scratch
+struct AggWs {
+    float *gV, *gN;
+    int32_t *overflow, *appended;
+    size_t counter_bytes;
+    void *cws;
+};
+static size_t agg_layout(int B, int H, int W, void *ws, AggWs *out) {
+    const size_t npix = (size_t)B * H * W;
+    Carve c{(char *)ws};
+    AggWs scratch, &w = out ? *out : scratch;
+    w.gV = c.take<float>(npix * 12); w.gN = c.take<float>(npix * 12);
+    const size_t counters = c.off;
+    w.overflow = c.take<int32_t>(4); w.appended = c.take<int32_t>((size_t)B * 4);
+    w.counter_bytes = c.off - counters;
+    w.cws = c.take(compact_total_ws_bytes(H, W));
+    return c.off;
 }
 
 __global__ void fuse_stats_k(const int32_t *__restrict__ nrows, const int32_t *__restrict__ ucnt, const int32_t *__restrict__ overflow,
@@ -240,20 +326,35 @@ struct LocTape {
 };
 static size_t loc_tape_layout(int B, int H, int W, int ds, int Nmax, int numiters, int grad_lm, void *tape, LocTape *out) {
     const int capS = cdiv(H, ds) * cdiv(W, ds), capT = target_cap(Nmax);
-    size_t off = 0;
-    auto take = [&](size_t bytes) { size_t o = off; off += align_up(bytes, 256); return o; };
-    const size_t o_src = take((size_t)B * capS * 12), o_pix = take((size_t)B * capS * 4), o_ns = take((size_t)B * 4);
-    const size_t o_nt = take((size_t)B * 4), o_idx = take((size_t)B * capT * 4), o_T = take((size_t)B * 64);
-    const size_t icp_b = align_up(gs_icp_tape_bytes(capS, numiters, grad_lm), 256);
-    const size_t o_icp = take((size_t)B * icp_b);
-    if (tape && out) {
-        char *p = (char *)tape;
-        out->src = (float *)(p + o_src); out->src_pix = (int32_t *)(p + o_pix);
-        out->ns = (int32_t *)(p + o_ns); out->nt = (int32_t *)(p + o_nt);
-        out->tgt_index = (int32_t *)(p + o_idx); out->T = (float *)(p + o_T);
-        out->icp = p + o_icp; out->icp_bytes = icp_b;
-    }
-    return off;
+    Carve c{(char *)tape};
+    LocTape scratch, &t = out ? *out : scratch;
+    t.src = c.take<float>((size_t)B * capS * 12); t.src_pix = c.take<int32_t>((size_t)B * capS * 4);
+    t.ns = c.take<int32_t>((size_t)B * 4); t.nt = c.take<int32_t>((size_t)B * 4);
+    t.tgt_index = c.take<int32_t>((size_t)B * capT * 4); t.T = c.take<float>((size_t)B * 64);
+    t.icp_bytes = align_up(gs_icp_tape_bytes(capS, numiters, grad_lm), 256);
+    t.icp = c.take<char>((size_t)B * t.icp_bytes);
+    return c.off;
+}
+
+// Workspace of the localisation reverse pass; its two modes differ in the last piece only, the ICP reverse pass's own.
+struct LocBwdWs {
+    float *tgt, *tnrm, *g_tgt, *g_nrm;  // (capT, 3): one batch element at a time
+    float *g_src;                       // (capS, 3)
+    float *g_T, *g_init, *eye;          // (B, 16)
+    void *sub;
+    size_t sub_bytes;
+};
+static size_t loc_bwd_layout(bool det, int B, int H, int W, int ds, int Nmax, int numiters, int grad_lm, void *ws, LocBwdWs *out) {
+    const int capS = cdiv(H, ds) * cdiv(W, ds), capT = target_cap(Nmax);
+    Carve c{(char *)ws};
+    LocBwdWs scratch, &w = out ? *out : scratch;
+    w.tgt = c.take<float>((size_t)capT * 12); w.tnrm = c.take<float>((size_t)capT * 12);
+    w.g_tgt = c.take<float>((size_t)capT * 12); w.g_nrm = c.take<float>((size_t)capT * 12);
+    w.g_src = c.take<float>((size_t)capS * 12);
+    w.g_T = c.take<float>((size_t)B * 64); w.g_init = c.take<float>((size_t)B * 64); w.eye = c.take<float>((size_t)B * 64);
+    w.sub_bytes = det ? gs_icp_backward_det_ws_bytes(capS, capT, numiters, grad_lm) : gs_icp_backward_ws_bytes(capS);
+    w.sub = c.take(w.sub_bytes);
+    return c.off;
 }
 
 // adjoint of compose_k: out = T . P
@@ -356,118 +457,32 @@ int gs_slam_localize(const float *depth, const float *intrinsics, const float *p
     loc_layout(B, H, W, ds, Nmax, ws, &w);
     const int capS = cdiv(H, ds) * cdiv(W, ds), capT = target_cap(Nmax);
     int rc;
-    // live frame posed with the previous pose: maps, then the ds-grid source cloud
-    // (the maps kernel also leaves the bucketing camera -- previous pose and intrinsics -- in the workspace: the loops read it
-    // from there, an address a captured graph may keep, never from the caller's tensors)
-    // map points that land on the ds-grid of the previous frame: the ICP target
-    // reference-order target (points, normals, counts) + the same points in pixel order and the first scan
-    // slot of every ds-grid pixel (search hints only).  One sequence takes the fused front end (gs_set_fused_setup; maps +
-    // counts, write, bucketing: three launches) or, switched off, the 4-launch fused form behind the maps kernel, on whose
-    // first two launches the frame's ds-grid source cloud rides (two launches of ~5 us less on the step's chain)
-    if (fused_front(B, H, W, ds)) {
-        const DsJob frame{depth, gvertex, w.src, w.src_pix, w.ns};
-        if ((rc = project_front1(depth, map_points, map_counts, Nmax, prev_poses, intrinsics, H, W, ds, map_normals, capT, vertex, normal,
-                                 gvertex, gnormal, w.cam, (int32_t *)w.rows, w.tgt, w.tnrm, w.nt, nullptr, w.scan, w.scan_orig, w.pix_start,
-                                 frame, w.sub, w.sub_bytes, st))) return rc;
-    } else if (B == 1) {
-        if ((rc = vertex_normal_maps_cam(depth, intrinsics, prev_poses, B, H, W, vertex, normal, gvertex, gnormal, w.cam, st))) return rc;
-        const DsJob frame{depth, gvertex, w.src, w.src_pix, w.ns};
-        if ((rc = project_target1(map_points, map_counts, Nmax, prev_poses, intrinsics, H, W, ds, map_normals, capT, w.rows, w.nrows,
-                                  w.tgt, w.tnrm, w.nt, w.scan, w.scan_orig, w.pix_start, nullptr, nullptr, w.sub, w.sub_bytes, st, &frame))) return rc;
-    } else {
-        if ((rc = vertex_normal_maps_cam(depth, intrinsics, prev_poses, B, H, W, vertex, normal, gvertex, gnormal, w.cam, st))) return rc;
-        if ((rc = gs_downsample_frame(depth, gvertex, nullptr, nullptr, B, H, W, ds, capS, w.src, nullptr, nullptr, w.src_pix, w.ns,
-                                      w.sub, w.sub_bytes, stream))) return rc;
-        if ((rc = gs_project_active(map_points, map_counts, B, Nmax, prev_poses, intrinsics, H, W, ds, w.rows, w.nrows, w.sub,
-                                    w.sub_bytes, stream))) return rc;
-        if ((rc = gs_build_icp_target(w.rows, w.nrows, (int64_t)B * Nmax, B, H, W, ds, map_points, map_normals, Nmax, capT, w.tgt,
-                                      w.tnrm, w.nt, w.scan, w.scan_orig, w.pix_start, nullptr, nullptr, w.sub, w.sub_bytes, stream))) return rc;
-    }
+    if ((rc = enqueue_front(depth, gvertex, intrinsics, prev_poses, B, H, W, ds, map_points, map_normals, map_counts, Nmax, w, w.src,
+                            w.src_pix, w.ns, w.nt, nullptr, true, vertex, normal, gvertex, gnormal, w.cam, st))) return rc;
     // fold_compose: the loop's last launch also writes out_poses = T . prev_poses.  Only for eager launches: a
-    // captured graph must not bake the caller's prev_poses / out_poses addresses in (they change every call).
-    auto enqueue_loops = [&](gs_stream_t s, bool fold_compose) -> int {
+    // captured graph must not bake the caller's prev_poses / out_poses addresses in (they change every call); for the same
+    // reason the loops read the camera from the workspace, never from the caller's tensors.
+    auto enqueue_loops = [&](hipStream_t s, bool fold_compose) -> int {
         for (int b = 0; b < B; ++b) {  // sequences are independent; one device-resident loop each
-            const float *src = w.src + (size_t)b * capS * 3;
-            const float *tgt = w.tgt + (size_t)b * capT * 3, *nrm = w.tnrm + (size_t)b * capT * 3;
-            const gs_icp_hints hints{w.scan + (size_t)b * capT * 3, w.scan_orig + (size_t)b * capT, w.src_pix + (size_t)b * capS,
-                                     w.pix_start + (size_t)b * (capS + 1), nullptr, cdiv(W, ds), cdiv(H, ds),
-                                     w.cam + 32 * b, w.cam + 32 * b + 16, ds};
-            // the loop's last launch also writes out_poses[b] = T . prev_poses[b]
-            const int r = icp_localize_run(use_grad_lm, src, w.ns + b, capS, tgt, nrm, w.nt + b, capT, numiters, damp, dist_thresh,
-                                           lambda_max, Bp, B2, nu, &hints, w.T + 16 * b, w.sub, w.sub_bytes, (hipStream_t)s, nullptr,
-                                           0, fold_compose ? prev_poses + 16 * b : nullptr,
-                                           fold_compose ? out_poses + 16 * b : nullptr);
+            const gs_icp_hints hints = loc_hints(w, w.src_pix, b, H, W, ds, capS, capT, w.cam + 32 * b, w.cam + 32 * b + 16);
+            const int r = icp_localize_run(use_grad_lm, w.src + (size_t)b * capS * 3, w.ns + b, capS, w.tgt + (size_t)b * capT * 3,
+                                           w.tnrm + (size_t)b * capT * 3, w.nt + b, capT, numiters, damp, dist_thresh, lambda_max, Bp,
+                                           B2, nu, &hints, w.T + 16 * b, w.sub, w.sub_bytes, s, nullptr, 0,
+                                           fold_compose ? prev_poses + 16 * b : nullptr, fold_compose ? out_poses + 16 * b : nullptr);
             if (r) return r;
         }
         return GS_OK;
     };
     bool launched = false;
     if (graphs_allowed() && numiters > 0) {
-        std::lock_guard<std::mutex> lock(g_graph_mu);
-        int device = 0;
-        (void)hipGetDevice(&device);
         const GraphKey key{ws, B, capS, capT, numiters, use_grad_lm, damp, dist_thresh, lambda_max, Bp, B2, nu,
                            icp_config_stamp(), H, W, ds};
-        GraphEntry *hit = nullptr;
-        for (auto &e : g_graphs)
-            if (e.device == device && e.key == key) hit = &e;
-        bool seen = false;
-        if (!hit) {
-            for (auto &k : g_seen_once) seen = seen || (k == key);
-            if (!seen) {
-                if (g_seen_once.size() >= 16) g_seen_once.erase(g_seen_once.begin());
-                g_seen_once.push_back(key);
-            }
-        }
-        if (!hit && seen) {
-            hipStream_t cs = nullptr;
-            hipGraph_t graph = nullptr;
-            hipGraphExec_t exec = nullptr;
-            bool ok = hipStreamCreateWithFlags(&cs, hipStreamNonBlocking) == hipSuccess;
-            ok = ok && hipStreamBeginCapture(cs, hipStreamCaptureModeThreadLocal) == hipSuccess;
-            if (ok) {
-                const int r = enqueue_loops((gs_stream_t)cs, false);
-                const hipError_t e = hipStreamEndCapture(cs, &graph);
-                ok = (r == GS_OK) && e == hipSuccess && graph != nullptr;
-            }
-            ok = ok && hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0) == hipSuccess;
-            if (graph) (void)hipGraphDestroy(graph);
-            if (cs) (void)hipStreamDestroy(cs);
-            if (ok) {
-                if (g_graphs.size() >= 8) {  // evict the least recently used
-                    size_t v = 0;
-                    for (size_t i = 1; i < g_graphs.size(); ++i)
-                        if (g_graphs[i].last_use < g_graphs[v].last_use) v = i;
-                    (void)hipGraphExecDestroy(g_graphs[v].exec);
-                    g_graphs.erase(g_graphs.begin() + v);
-                }
-                g_graphs.push_back(GraphEntry{key, device, exec, 0});
-                hit = &g_graphs.back();
-                ++g_captures;
-            } else {
-                (void)hipGetLastError();  // fall back to eager launches below
-            }
-        }
-        if (hit) {
-            hit->last_use = ++g_graph_clock;
-            ++g_replays;
-            GS_HIP(hipGraphLaunch(hit->exec, st), "gs_slam_localize/graph");
-            launched = true;
-        }
+        if ((rc = graph_replay(key, st, [&](hipStream_t cs) { return enqueue_loops(cs, false); }, &launched))) return rc;
     }
     if (!launched) {
-        const auto t0 = std::chrono::steady_clock::now();
-        if ((rc = enqueue_loops(stream, numiters > 0))) return rc;
-        if (numiters > 0) {
-            const double us = std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count();
-            const int launches = B * ((use_grad_lm ? 2 * numiters : numiters + 1) + 2);
-            std::lock_guard<std::mutex> lock(g_graph_mu);
-            if (g_auto_samples < 64) {
-                ++g_auto_samples;
-                g_auto_min_us = std::min(g_auto_min_us, us / launches);
-            }
-            return GS_OK;  // composed by the loop's last launch
-        }
+        if (numiters > 0)  // composed by the loop's last launch
+            return eager_timed(B * ((use_grad_lm ? 2 * numiters : numiters + 1) + 2), [&] { return enqueue_loops(st, true); });
+        if ((rc = enqueue_loops(st, false))) return rc;
     }
     return gs_compose_poses(w.T, prev_poses, B, out_poses, stream);
 }
@@ -546,9 +561,7 @@ int gs_pointfusion_update_taped(const float *depth, const float *rgb, const floa
 
 size_t gs_pointfusion_update_backward_ws_bytes(int B, int H, int W) {
     if (B <= 0 || H <= 0 || W <= 0) return 0;
-    const size_t npix = (size_t)B * H * W;
-    // V, N, gV, gN (recomputed), alpha, g_alpha + the compaction's scratch
-    return 4 * align_up(npix * 12, 256) + 2 * align_up(npix * 4, 256) + gs_compact_ws_bytes((int64_t)H * W) + 512;
+    return fuse_bwd_layout(B, H, W, nullptr, nullptr);
 }
 
 int gs_pointfusion_update_backward(const float *depth, const float *rgb, const float *intrinsics, const float *poses, int B, int H,
@@ -567,30 +580,24 @@ int gs_pointfusion_update_backward(const float *depth, const float *rgb, const f
     }
     hipStream_t st = (hipStream_t)stream;
     const size_t npix = (size_t)B * H * W;
-    char *p = (char *)ws;
-    auto take = [&](size_t bytes) { char *o = p; p += align_up(bytes, 256); return o; };
-    float *V = (float *)take(npix * 12), *N = (float *)take(npix * 12), *gV = (float *)take(npix * 12), *gN = (float *)take(npix * 12);
-    float *alpha = (float *)take(npix * 4), *g_alpha = (float *)take(npix * 4);
-    void *cws = p;
+    FuseBwdWs w;
+    fuse_bwd_layout(B, H, W, ws, &w);
     int rc;
     // the frame's maps and sample confidences again (cheaper to recompute than to keep per frame)
-    if ((rc = gs_vertex_normal_maps(depth, intrinsics, poses, B, 1, H, W, V, N, gV, gN, stream))) return rc;
-    if ((rc = gs_get_alpha(V, (int64_t)npix, sigma, 1e-7f, alpha, stream))) return rc;
-    if ((rc = fusion_update_reverse(tape, B, H, W, Nmax, depth, gV, gN, rgb, alpha, map_points, map_normals, map_colors, map_ccounts,
-                                    map_counts, G_points, G_normals, G_colors, G_ccounts, g_gvertex, g_gnormal, g_rgb, g_alpha, cws, st)))
-        return rc;
+    if ((rc = gs_vertex_normal_maps(depth, intrinsics, poses, B, 1, H, W, w.V, w.N, w.gV, w.gN, stream))) return rc;
+    if ((rc = gs_get_alpha(w.V, (int64_t)npix, sigma, 1e-7f, w.alpha, stream))) return rc;
+    if ((rc = fusion_update_reverse(tape, B, H, W, Nmax, depth, w.gV, w.gN, rgb, w.alpha, map_points, map_normals, map_colors, map_ccounts,
+                                    map_counts, G_points, G_normals, G_colors, G_ccounts, g_gvertex, g_gnormal, g_rgb, w.g_alpha, w.cws,
+                                    st))) return rc;
     // alpha = f(local vertex map): its adjoint is the only one the local vertex map receives from the update
     // (gs_get_alpha_backward adds into its output)
     GS_HIP(hipMemsetAsync(g_vertex, 0, npix * 12, st), name);
-    return gs_get_alpha_backward(V, (int64_t)npix, sigma, 1e-7f, g_alpha, g_vertex, stream);
+    return gs_get_alpha_backward(w.V, (int64_t)npix, sigma, 1e-7f, w.g_alpha, g_vertex, stream);
 }
-
-
 
 size_t gs_aggregate_update_ws_bytes(int B, int H, int W) {
     if (B <= 0 || H <= 0 || W <= 0) return 0;
-    const size_t npix = (size_t)B * H * W;
-    return 2 * align_up(npix * 12, 256) + 256 + align_up((size_t)B * 4, 256) + gs_compact_ws_bytes((int64_t)H * W) + 256;
+    return agg_layout(B, H, W, nullptr, nullptr);
 }
 
 int gs_aggregate_update(const float *depth, const float *rgb, const float *intrinsics, const float *poses, int B, int H, int W,
@@ -604,26 +611,22 @@ int gs_aggregate_update(const float *depth, const float *rgb, const float *intri
         return GS_ERR_WORKSPACE_TOO_SMALL;
     }
     hipStream_t st = (hipStream_t)stream;
-    const size_t npix = (size_t)B * H * W;
-    char *p = (char *)ws;
-    float *gV = (float *)p; p += align_up(npix * 12, 256);
-    float *gN = (float *)p; p += align_up(npix * 12, 256);
-    int32_t *overflow = (int32_t *)p; p += 256;
-    int32_t *appended = (int32_t *)p; p += align_up((size_t)B * 4, 256);
-    void *cws = p;
-    GS_HIP(hipMemsetAsync(overflow, 0, 256 + align_up((size_t)B * 4, 256), st), name);
+    AggWs w;
+    agg_layout(B, H, W, ws, &w);
+    GS_HIP(hipMemsetAsync(w.overflow, 0, w.counter_bytes, st), name);
     int rc;
-    if ((rc = gs_vertex_normal_maps(depth, intrinsics, poses, B, 1, H, W, nullptr, nullptr, gV, gN, stream))) return rc;
+    if ((rc = gs_vertex_normal_maps(depth, intrinsics, poses, B, 1, H, W, nullptr, nullptr, w.gV, w.gN, stream))) return rc;
     const int64_t HW = (int64_t)H * W;
     for (int b = 0; b < B; ++b) {
-        const float *src[3] = {gV + b * HW * 3, gN + b * HW * 3, rgb + b * HW * 3};
+        const float *src[3] = {w.gV + b * HW * 3, w.gN + b * HW * 3, rgb + b * HW * 3};
         float *dst[3] = {map_points + (size_t)b * Nmax * 3, map_normals + (size_t)b * Nmax * 3, map_colors + (size_t)b * Nmax * 3};
         const int widths[3] = {3, 3, 3};
-        if ((rc = append_valid_pixels(3, depth + b * HW, HW, src, widths, dst, map_counts + b, Nmax, appended + b, overflow, cws, st)))
-            return rc;
+        if ((rc = append_valid_pixels(3, depth + b * HW, HW, src, widths, dst, map_counts + b, Nmax, w.appended + b, w.overflow, w.cws,
+                                      st))) return rc;
     }
     if (stats) {
-        hipLaunchKernelGGL(fuse_stats_k, dim3(1), dim3(64), 0, st, overflow, overflow, overflow, (const float *)overflow, appended, B, stats);
+        hipLaunchKernelGGL(fuse_stats_k, dim3(1), dim3(64), 0, st, w.overflow, w.overflow, w.overflow, (const float *)w.overflow, w.appended, B,
+                           stats);
         GS_LAUNCH_CHECK(name);
     }
     return GS_OK;
@@ -648,38 +651,22 @@ int gs_slam_localize_taped(const float *depth, const float *gvertex, const float
     }
     GS_REQUIRE(tape_bytes >= gs_slam_localize_tape_bytes(B, H, W, ds, Nmax, numiters, use_grad_lm),
                "gs_slam_localize_taped: tape too small");
+    hipStream_t st = (hipStream_t)stream;
     LocWs w;
     loc_layout(B, H, W, ds, Nmax, ws, &w);
     LocTape tp;
     loc_tape_layout(B, H, W, ds, Nmax, numiters, use_grad_lm, tape, &tp);
     const int capS = cdiv(H, ds) * cdiv(W, ds), capT = target_cap(Nmax);
     int rc;
-    if (fused_front(B, H, W, ds)) {  // (the maps are the caller's: gvertex is an input here -- the count launch carries no maps' tiles)
-        const DsJob frame{depth, gvertex, tp.src, tp.src_pix, tp.ns};
-        if ((rc = project_front1(nullptr, map_points, map_counts, Nmax, prev_poses, intrinsics, H, W, ds, map_normals, capT, nullptr, nullptr,
-                                 nullptr, nullptr, nullptr, (int32_t *)w.rows, w.tgt, w.tnrm, tp.nt, tp.tgt_index, w.scan, w.scan_orig,
-                                 w.pix_start, frame, w.sub, w.sub_bytes, (hipStream_t)stream))) return rc;
-    } else if (B == 1) {
-        const DsJob frame{depth, gvertex, tp.src, tp.src_pix, tp.ns};
-        if ((rc = project_target1(map_points, map_counts, Nmax, prev_poses, intrinsics, H, W, ds, map_normals, capT, w.rows, w.nrows,
-                                  w.tgt, w.tnrm, tp.nt, w.scan, w.scan_orig, w.pix_start, tp.tgt_index, nullptr, w.sub, w.sub_bytes,
-                                  (hipStream_t)stream, &frame))) return rc;
-    } else {
-        if ((rc = gs_downsample_frame(depth, gvertex, nullptr, nullptr, B, H, W, ds, capS, tp.src, nullptr, nullptr, tp.src_pix, tp.ns,
-                                      w.sub, w.sub_bytes, stream))) return rc;
-        if ((rc = gs_project_active(map_points, map_counts, B, Nmax, prev_poses, intrinsics, H, W, ds, w.rows, w.nrows, w.sub,
-                                    w.sub_bytes, stream))) return rc;
-        if ((rc = gs_build_icp_target(w.rows, w.nrows, (int64_t)B * Nmax, B, H, W, ds, map_points, map_normals, Nmax, capT, w.tgt,
-                                      w.tnrm, tp.nt, w.scan, w.scan_orig, w.pix_start, tp.tgt_index, nullptr, w.sub, w.sub_bytes, stream))) return rc;
-    }
+    // (the maps are the caller's: gvertex is an input here -- the fused form's count launch carries no maps' tiles)
+    if ((rc = enqueue_front(depth, gvertex, intrinsics, prev_poses, B, H, W, ds, map_points, map_normals, map_counts, Nmax, w, tp.src,
+                            tp.src_pix, tp.ns, tp.nt, tp.tgt_index, false, nullptr, nullptr, nullptr, nullptr, nullptr, st))) return rc;
     for (int b = 0; b < B; ++b) {
-        const gs_icp_hints hints{w.scan + (size_t)b * capT * 3, w.scan_orig + (size_t)b * capT, tp.src_pix + (size_t)b * capS,
-                                 w.pix_start + (size_t)b * (capS + 1), nullptr, cdiv(W, ds), cdiv(H, ds),
-                                 prev_poses + 16 * b, intrinsics + 16 * b, ds};
+        const gs_icp_hints hints = loc_hints(w, tp.src_pix, b, H, W, ds, capS, capT, prev_poses + 16 * b, intrinsics + 16 * b);
         if ((rc = icp_localize_run(use_grad_lm, tp.src + (size_t)b * capS * 3, tp.ns + b, capS, w.tgt + (size_t)b * capT * 3,
                                    w.tnrm + (size_t)b * capT * 3, tp.nt + b, capT, numiters, damp, dist_thresh, lambda_max, Bp, B2, nu,
-                                   &hints, tp.T + 16 * b, w.sub, w.sub_bytes, (hipStream_t)stream, tp.icp + (size_t)b * tp.icp_bytes,
-                                   tp.icp_bytes, prev_poses + 16 * b, out_poses + 16 * b)))
+                                   &hints, tp.T + 16 * b, w.sub, w.sub_bytes, st, tp.icp + (size_t)b * tp.icp_bytes, tp.icp_bytes,
+                                   prev_poses + 16 * b, out_poses + 16 * b)))
             return rc;
     }
     if (numiters == 0) return gs_compose_poses(tp.T, prev_poses, B, out_poses, stream);
@@ -688,18 +675,12 @@ int gs_slam_localize_taped(const float *depth, const float *gvertex, const float
 
 size_t gs_slam_localize_backward_ws_bytes(int B, int H, int W, int ds, int Nmax) {
     if (B <= 0 || H <= 0 || W <= 0 || ds <= 0 || Nmax <= 0) return 0;
-    const int capS = cdiv(H, ds) * cdiv(W, ds), capT = target_cap(Nmax);
-    // tgt, tnrm, g_tgt, g_nrm (one batch element at a time) + g_src + g_T, g_init, eye + the ICP reverse pass's own
-    return 4 * align_up((size_t)capT * 12, 256) + align_up((size_t)capS * 12, 256) + 3 * align_up((size_t)B * 64, 256) +
-           align_up(gs_icp_backward_ws_bytes(capS), 256);
+    return loc_bwd_layout(false, B, H, W, ds, Nmax, 0, 0, nullptr, nullptr);
 }
 
 size_t gs_slam_localize_backward_det_ws_bytes(int B, int H, int W, int ds, int Nmax, int numiters, int grad_lm) {
     if (B <= 0 || H <= 0 || W <= 0 || ds <= 0 || Nmax <= 0) return 0;
-    const int capS = cdiv(H, ds) * cdiv(W, ds), capT = target_cap(Nmax);
-    // the same layout, with the deterministic ICP reverse pass's workspace at the end
-    return 4 * align_up((size_t)capT * 12, 256) + align_up((size_t)capS * 12, 256) + 3 * align_up((size_t)B * 64, 256) +
-           align_up(gs_icp_backward_det_ws_bytes(capS, capT, numiters, grad_lm), 256);
+    return loc_bwd_layout(true, B, H, W, ds, Nmax, numiters, grad_lm, nullptr, nullptr);
 }
 
 static int localize_backward(bool det, const float *prev_poses, int B, int H, int W, int ds, const float *map_points,
@@ -711,8 +692,7 @@ static int localize_backward(bool det, const float *prev_poses, int B, int H, in
     GS_REQUIRE(prev_poses && map_points && map_normals && tape && grad_out_poses && grad_gvertex && grad_prev_poses,
                "%s: NULL argument", name);
     GS_REQUIRE(B > 0 && H >= 2 && W >= 2 && ds > 0 && Nmax > 0 && numiters >= 0, "%s: bad shape", name);
-    if (!ws || ws_bytes < (det ? gs_slam_localize_backward_det_ws_bytes(B, H, W, ds, Nmax, numiters, use_grad_lm)
-                               : gs_slam_localize_backward_ws_bytes(B, H, W, ds, Nmax))) {
+    if (!ws || ws_bytes < loc_bwd_layout(det, B, H, W, ds, Nmax, numiters, use_grad_lm, nullptr, nullptr)) {
         set_error("%s: workspace too small", name);
         return GS_ERR_WORKSPACE_TOO_SMALL;
     }
@@ -721,36 +701,30 @@ static int localize_backward(bool det, const float *prev_poses, int B, int H, in
     LocTape tp;
     loc_tape_layout(B, H, W, ds, Nmax, numiters, use_grad_lm, (void *)tape, &tp);
     const int capS = cdiv(H, ds) * cdiv(W, ds), capT = target_cap(Nmax);
-    char *p = (char *)ws;
-    auto take = [&](size_t bytes) { char *o = p; p += align_up(bytes, 256); return o; };
-    float *tgt = (float *)take((size_t)capT * 12), *tnrm = (float *)take((size_t)capT * 12);
-    float *g_tgt = (float *)take((size_t)capT * 12), *g_nrm = (float *)take((size_t)capT * 12);
-    float *g_src = (float *)take((size_t)capS * 12);
-    float *g_T = (float *)take((size_t)B * 64), *g_init = (float *)take((size_t)B * 64), *eye = (float *)take((size_t)B * 64);
-    void *sub = p;
-    const size_t sub_bytes = det ? gs_icp_backward_det_ws_bytes(capS, capT, numiters, use_grad_lm) : gs_icp_backward_ws_bytes(capS);
+    LocBwdWs w;
+    loc_bwd_layout(det, B, H, W, ds, Nmax, numiters, use_grad_lm, ws, &w);
     auto icp_backward = det ? gs_icp_point_to_plane_backward_det : gs_icp_point_to_plane_backward;
 
     GS_HIP(hipMemsetAsync(grad_gvertex, 0, (size_t)B * H * W * 12, st), name);
     if (grad_map_points && !accumulate_map_grads) GS_HIP(hipMemsetAsync(grad_map_points, 0, (size_t)B * Nmax * 12, st), name);
     if (grad_map_normals && !accumulate_map_grads) GS_HIP(hipMemsetAsync(grad_map_normals, 0, (size_t)B * Nmax * 12, st), name);
-    hipLaunchKernelGGL(eye4_k, dim3(cdiv(16 * B, 64)), dim3(64), 0, st, eye, B);
-    hipLaunchKernelGGL(compose_bwd_k, dim3(cdiv(B, 64)), dim3(64), 0, st, tp.T, prev_poses, grad_out_poses, B, g_T, grad_prev_poses);
+    hipLaunchKernelGGL(eye4_k, dim3(cdiv(16 * B, 64)), dim3(64), 0, st, w.eye, B);
+    hipLaunchKernelGGL(compose_bwd_k, dim3(cdiv(B, 64)), dim3(64), 0, st, tp.T, prev_poses, grad_out_poses, B, w.g_T, grad_prev_poses);
     GS_LAUNCH_CHECK(name);
     const int gb = min(cdiv(capS, 256), 512);
     for (int b = 0; b < B; ++b) {
         // NB the gathered arrays hold one batch element at a time: index them with b = 0
         hipLaunchKernelGGL(regather_k, dim3(gb, 1), dim3(256), 0, st, tp.tgt_index + (size_t)b * capT, tp.nt + b, capT,
-                           map_points + (size_t)b * Nmax * 3, map_normals + (size_t)b * Nmax * 3, Nmax, tgt, tnrm);
+                           map_points + (size_t)b * Nmax * 3, map_normals + (size_t)b * Nmax * 3, Nmax, w.tgt, w.tnrm);
         GS_LAUNCH_CHECK(name);
         int rc;
-        if ((rc = icp_backward(tp.src + (size_t)b * capS * 3, tp.ns + b, capS, tgt, tnrm, tp.nt + b, capT, eye + 16 * b, numiters,
-                                                 dist_thresh, use_grad_lm, lambda_max, Bp, B2, nu, tp.icp + (size_t)b * tp.icp_bytes,
-                                                 tp.icp_bytes, g_T + 16 * b, g_src, grad_map_points ? g_tgt : nullptr,
-                                                 grad_map_normals ? g_nrm : nullptr, g_init + 16 * b, sub, sub_bytes, stream)))
+        if ((rc = icp_backward(tp.src + (size_t)b * capS * 3, tp.ns + b, capS, w.tgt, w.tnrm, tp.nt + b, capT, w.eye + 16 * b, numiters,
+                               dist_thresh, use_grad_lm, lambda_max, Bp, B2, nu, tp.icp + (size_t)b * tp.icp_bytes, tp.icp_bytes,
+                               w.g_T + 16 * b, w.g_src, grad_map_points ? w.g_tgt : nullptr, grad_map_normals ? w.g_nrm : nullptr,
+                               w.g_init + 16 * b, w.sub, w.sub_bytes, stream)))
             return rc;
-        hipLaunchKernelGGL(scatter_grads_k, dim3(gb), dim3(256), 0, st, g_src, tp.src_pix + (size_t)b * capS, tp.ns + b, capS,
-                           cdiv(W, ds), ds, H, W, grad_gvertex + (size_t)b * H * W * 3, g_tgt, g_nrm, tp.tgt_index + (size_t)b * capT,
+        hipLaunchKernelGGL(scatter_grads_k, dim3(gb), dim3(256), 0, st, w.g_src, tp.src_pix + (size_t)b * capS, tp.ns + b, capS,
+                           cdiv(W, ds), ds, H, W, grad_gvertex + (size_t)b * H * W * 3, w.g_tgt, w.g_nrm, tp.tgt_index + (size_t)b * capT,
                            tp.nt + b, capT, grad_map_points ? grad_map_points + (size_t)b * Nmax * 3 : nullptr,
                            grad_map_normals ? grad_map_normals + (size_t)b * Nmax * 3 : nullptr, accumulate_map_grads);
         GS_LAUNCH_CHECK(name);

@@ -173,3 +173,39 @@ def test_fused_setup_taped_gradients(gs):
             lib.gs_set_fused_setup(1)
     for x, y in zip(res[True], res[False]):
         assert torch.equal(x, y)
+
+
+def _taped_vs_untaped(gs, depth, K, prev, mp, mn, cnt, numiters, grad_params):
+    B, _, H, W = depth.shape[:4]
+    gV = torch.zeros((B, 1, H, W, 3), dtype=torch.float32, device=depth.device)
+    gs._native.lib().gs_vertex_normal_maps(depth.data_ptr(), K.data_ptr(), prev.data_ptr(), B, 1, H, W, None, None, gV.data_ptr(), None,
+                                           torch.cuda.current_stream().cuda_stream)
+    with torch.no_grad():
+        raw, _, _ = gs.ops.slam_localize_raw(depth, K, prev, mp, mn, cnt, 4, numiters, 1e-8, 0.1, grad_params)
+        taped = gs.ops.slam_localize_autograd(gV, depth, K, prev, mp, mn, cnt, 4, numiters, 1e-8, 0.1, grad_params)
+    torch.cuda.synchronize()
+    assert torch.isfinite(raw).all()
+    assert torch.equal(raw.cpu(), taped.cpu())
+
+
+@pytest.fixture(scope="module")
+def scene6(gs):
+    return scene(gs, 120, 160, seed=6)
+
+
+@pytest.mark.parametrize("grad_params", [None, (2.0, 1.0, 1.0, 200.0)], ids=["lm", "gradlm"])
+@pytest.mark.parametrize("front", ["fused", "separate", "batch2"])
+def test_taped_and_untaped_localize_return_the_same_pose(gs, scene6, front, grad_params):
+    """gs_slam_localize and gs_slam_localize_taped share one front end and one loop: the same pose, bit for bit, through the fused
+    front end, the 4-launch one (fused setup off) and the batched chain (B = 2: the same scene twice)."""
+    args = [x.repeat(2, *([1] * (x.dim() - 1))).contiguous() for x in scene6] if front == "batch2" else list(scene6)
+    lib = gs._native.lib()
+    lib.gs_set_fused_setup(0 if front == "separate" else 1)
+    try:
+        _taped_vs_untaped(gs, *args, 10, grad_params)
+    finally:
+        lib.gs_set_fused_setup(1)
+
+
+def test_taped_and_untaped_localize_return_the_same_pose_without_iterations(gs, scene6):
+    _taped_vs_untaped(gs, *scene6, 0, None)

@@ -62,6 +62,23 @@ def test_icp_launch_geometry_fits_the_workspace():
     assert lib.gs_icp_launch_geometry(0, 1, None, None, None) != 0  # error contract: positive capacity
 
 
+@pytest.mark.parametrize("B,H,W,ds,Nmax,numiters,grad_lm", [(1, 120, 160, 4, 19200, 10, 0), (2, 48, 64, 2, 3072, 3, 1),
+                                                             (1, 480, 640, 4, 307200, 10, 1)])
+def test_localize_backward_modes_share_one_layout(B, H, W, ds, Nmax, numiters, grad_lm):
+    """The two modes of the localisation reverse pass carve one workspace layout and differ in its last piece alone, the ICP
+    reverse pass's own workspace: so do their sizes (every piece is rounded up to 256 bytes)."""
+    lib = _native.lib()
+    align256 = lambda n: -(-n // 256) * 256
+    capS, capT = -(-H // ds) * -(-W // ds), 1024
+    while capT < Nmax and capT < (1 << 30):
+        capT <<= 1
+    det = lib.gs_slam_localize_backward_det_ws_bytes(B, H, W, ds, Nmax, numiters, grad_lm)
+    plain = lib.gs_slam_localize_backward_ws_bytes(B, H, W, ds, Nmax)
+    assert plain > 0 and det > 0
+    assert det - plain == (align256(lib.gs_icp_backward_det_ws_bytes(capS, capT, numiters, grad_lm))
+                           - align256(lib.gs_icp_backward_ws_bytes(capS)))
+
+
 def test_integration_notes_cover_every_entry_point():
     """INTEGRATION.md (the reference-side binding notes) names every symbol the header declares."""
     notes = open(os.path.join(REPO, "INTEGRATION.md")).read()

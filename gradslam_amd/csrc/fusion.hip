@@ -10,6 +10,7 @@
 #include "gs_common.hpp"
 #include "gs_compact.hpp"
 #include "gs_drivers.hpp"
+#include "gs_fusion_row.hpp"
 #include "gs_project.hpp"
 
 namespace gs {
@@ -22,15 +23,12 @@ __global__ void similar_k(const int64_t *__restrict__ rows, const int32_t *__res
     const int n = *d_n;
     float md = 0.0f;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-        const longlong4 r = *reinterpret_cast<const longlong4 *>(rows + 4 * i);
-        const int64_t pix = ((int64_t)r.x * H + r.z) * W + r.w;
-        const int64_t pt = (int64_t)r.x * Nmax + r.y;
+        const longlong4 r = ld_table_row(rows, i);
+        const int64_t pix = row_pix(r, H, W), pt = row_pt(r, Nmax);
         const f3 fv = ld3(gv, pix), fn = ld3(gn, pix), p = ld3(mp, pt), q = ld3(mn, pt);
-        const float dx = fv.x - p.x, dy = fv.y - p.y, dz = fv.z - p.z;
-        // (a-b).norm(dim=-1): sqrt(fma(z,z,fma(y,y,x*x)));  (a*b).sum(-1): unfused
-        const float dist = sqrtf(__fmaf_rn(dz, dz, __fmaf_rn(dy, dy, dx * dx)));
-        const float dot = (fn.x * q.x + fn.y * q.y) + fn.z * q.z;
-        keep[i] = (dist < dist_th && dot > dot_th) ? 1 : 0;
+        float dot;
+        const bool sim = similar_pair(fv, fn, p, q, dist_th, dot_th, dot);
+        keep[i] = sim ? 1 : 0;
         md = fmaxf(md, dot);
     }
     if (max_dot) {
@@ -44,14 +42,11 @@ __global__ void similar_k(const int64_t *__restrict__ rows, const int32_t *__res
 }
 
 // ------------------------------------------------------------------ U
-// key = (1/(c + 1e-20), squared ray distance) as order-preserving bits (both are >= +0)
 __device__ __forceinline__ unsigned long long unique_key(const float *__restrict__ gv, const float *__restrict__ mp,
                                                          const float *__restrict__ cc, int64_t pix, int64_t pt) {
-    const float inv_c = 1.0f / (cc[pt] + 1e-20f);
+    const float c = cc[pt];
     const f3 fv = ld3(gv, pix), p = ld3(mp, pt);
-    const float dx = p.x - fv.x, dy = p.y - fv.y, dz = p.z - fv.z;
-    const float ray = (dx * dx + dy * dy) + dz * dz;  // ((a-b)**2).sum(-1): unfused
-    return ((unsigned long long)fbits(inv_c) << 32) | fbits(ray);
+    return unique_key(c, p, fv);
 }
 
 __global__ void unique_pass1_k(const int64_t *__restrict__ rows, const uint8_t *__restrict__ keep,
@@ -61,9 +56,9 @@ __global__ void unique_pass1_k(const int64_t *__restrict__ rows, const uint8_t *
     const int n = *d_n;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
         if (keep && !keep[i]) continue;
-        const longlong4 r = *reinterpret_cast<const longlong4 *>(rows + 4 * i);
-        const int64_t pix = ((int64_t)r.x * H + r.z) * W + r.w;
-        atomicMin(pix_key + pix, unique_key(gv, mp, cc, pix, (int64_t)r.x * Nmax + r.y));
+        const longlong4 r = ld_table_row(rows, i);
+        const int64_t pix = row_pix(r, H, W);
+        atomicMin(pix_key + pix, unique_key(gv, mp, cc, pix, row_pt(r, Nmax)));
     }
 }
 __global__ void unique_pass2_k(const int64_t *__restrict__ rows, const uint8_t *__restrict__ keep,
@@ -73,9 +68,9 @@ __global__ void unique_pass2_k(const int64_t *__restrict__ rows, const uint8_t *
     const int n = *d_n;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
         if (keep && !keep[i]) continue;
-        const longlong4 r = *reinterpret_cast<const longlong4 *>(rows + 4 * i);
-        const int64_t pix = ((int64_t)r.x * H + r.z) * W + r.w;
-        if (unique_key(gv, mp, cc, pix, (int64_t)r.x * Nmax + r.y) == pix_key[pix]) atomicMin(pix_n + pix, (unsigned int)r.y);
+        const longlong4 r = ld_table_row(rows, i);
+        const int64_t pix = row_pix(r, H, W);
+        if (unique_key(gv, mp, cc, pix, row_pt(r, Nmax)) == pix_key[pix]) atomicMin(pix_n + pix, (unsigned int)r.y);
     }
 }
 struct PixPred {
@@ -90,9 +85,7 @@ struct PixWriter {
         const int64_t hw = (int64_t)H * W;
         const int b = (int)(i / hw);
         const int rem = (int)(i - (int64_t)b * hw);
-        longlong4 r;
-        r.x = b; r.y = pix_n[i]; r.z = rem / W; r.w = rem % W;
-        *reinterpret_cast<longlong4 *>(rows + 4 * pos) = r;
+        st_table_row(rows, pos, b, pix_n[i], rem / W, rem % W);
     }
 };
 
@@ -117,13 +110,11 @@ __global__ void scatter_match_k(const int64_t *__restrict__ rows, const int32_t 
                                 int *__restrict__ match_pix) {
     const int n = *d_n;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-        const longlong4 r = *reinterpret_cast<const longlong4 *>(rows + 4 * i);
-        match_pix[(int64_t)r.x * Nmax + r.y] = (int)(r.z * W + r.w);
+        const longlong4 r = ld_table_row(rows, i);
+        match_pix[row_pt(r, Nmax)] = (int)(r.z * W + r.w);
     }
 }
-// Every map point goes through the reference's formula, matched or not: an unmatched point becomes
-// (c*x + 0*0) * (1/c), which is NOT bit-identical to x -- part of the reference's observable result
-// (slam/fusionutils.py:678-699 operate on the whole padded tensors).
+// Every map point goes through the merge, matched or not (gs_fusion_row.hpp says why).
 __global__ void merge_k(const int *__restrict__ match_pix, const int32_t *__restrict__ counts, int Nmax, int HW,
                         const float *__restrict__ gv, const float *__restrict__ gn, const float *__restrict__ rgb,
                         const float *__restrict__ alpha, const float *__restrict__ ip, const float *__restrict__ inn,
@@ -138,26 +129,13 @@ __global__ void merge_k(const int *__restrict__ match_pix, const int32_t *__rest
             continue;
         }
         const int m = match_pix[pt];
-        float a = 0.0f;
-        f3 fp{0, 0, 0}, fn{0, 0, 0}, fc{0, 0, 0};
-        if (m >= 0) {
-            const int64_t pix = (int64_t)b * HW + m;
-            a = alpha[pix]; fp = ld3(gv, pix); fn = ld3(gn, pix); fc = ld3(rgb, pix);
-        }
-        const float c = icc[pt];
-        const float c2 = c + a;
-        const float inv = 1.0f / (c2 == 0.0f ? 1.0f : c2);
+        const FrameRow f = gather_frame(m >= 0, (int64_t)b * HW + m, gv, gn, rgb, alpha);
+        const MergeW w(icc[pt], f.a);
         const f3 x = ld3(ip, pt), y = ld3(inn, pt), z = ld3(ic, pt);
-        st3(op, pt, f3{((c * x.x) + (a * fp.x)) * inv, ((c * x.y) + (a * fp.y)) * inv, ((c * x.z) + (a * fp.z)) * inv});
-        st3(on, pt, f3{((c * y.x) + (a * fn.x)) * inv, ((c * y.y) + (a * fn.y)) * inv, ((c * y.z) + (a * fn.z)) * inv});
-        st3(oc, pt, f3{((c * z.x) + (a * fc.x)) * inv, ((c * z.y) + (a * fc.y)) * inv, ((c * z.z) + (a * fc.z)) * inv});
-        occ[pt] = c2;
+        st3(op, pt, w.avg(x, f.p)); st3(on, pt, w.avg(y, f.n)); st3(oc, pt, w.avg(z, f.c)); occ[pt] = w.c2;
     }
 }
 
-// adjoint of merge_k.  x' = (c x + a xf) / c2 (c2 != 0):
-//   x_bar = (c/c2) x'_bar ; xf_bar = (a/c2) x'_bar ; c_bar = c2_bar + sum (x - x').x'_bar / c2 ;
-//   a_bar = c2_bar + sum (xf - x').x'_bar / c2      (sums over points, normals, colours)
 // In-place form for an arena-backed map: same arithmetic on the rows that exist, padding untouched, and
 // nothing at all when there is no correspondence (fuse_with_map skips the merge then, fusionutils.py:654).
 __global__ void merge_inplace_k(const int *__restrict__ match_pix, const int32_t *__restrict__ counts,
@@ -170,20 +148,10 @@ __global__ void merge_inplace_k(const int *__restrict__ match_pix, const int32_t
     for (int n = blockIdx.x * blockDim.x + threadIdx.x; n < cnt; n += gridDim.x * blockDim.x) {
         const int64_t pt = (int64_t)b * Nmax + n;
         const int m = match_pix[pt];
-        float a = 0.0f;
-        f3 fp{0, 0, 0}, fn{0, 0, 0}, fc{0, 0, 0};
-        if (m >= 0) {
-            const int64_t pix = (int64_t)b * HW + m;
-            a = alpha[pix]; fp = ld3(gv, pix); fn = ld3(gn, pix); fc = ld3(rgb, pix);
-        }
-        const float c = cc[pt];
-        const float c2 = c + a;
-        const float inv = 1.0f / (c2 == 0.0f ? 1.0f : c2);
+        const FrameRow f = gather_frame(m >= 0, (int64_t)b * HW + m, gv, gn, rgb, alpha);
+        const MergeW w(cc[pt], f.a);
         const f3 x = ld3(p, pt), y = ld3(nn, pt), z = ld3(cl, pt);
-        st3(p, pt, f3{((c * x.x) + (a * fp.x)) * inv, ((c * x.y) + (a * fp.y)) * inv, ((c * x.z) + (a * fp.z)) * inv});
-        st3(nn, pt, f3{((c * y.x) + (a * fn.x)) * inv, ((c * y.y) + (a * fn.y)) * inv, ((c * y.z) + (a * fn.z)) * inv});
-        st3(cl, pt, f3{((c * z.x) + (a * fc.x)) * inv, ((c * z.y) + (a * fc.y)) * inv, ((c * z.z) + (a * fc.z)) * inv});
-        cc[pt] = c2;
+        st3(p, pt, w.avg(x, f.p)); st3(nn, pt, w.avg(y, f.n)); st3(cl, pt, w.avg(z, f.c)); cc[pt] = w.c2;
     }
 }
 
@@ -208,35 +176,21 @@ __global__ void merge_bwd_k(const int *__restrict__ match_pix, const int32_t *__
         }
         const int m = match_pix[pt];
         const int64_t pix = (int64_t)b * HW + (m >= 0 ? m : 0);
-        float a = 0.0f;
-        f3 fp{0, 0, 0}, fn{0, 0, 0}, fc{0, 0, 0};
-        if (m >= 0) { a = alpha[pix]; fp = ld3(gv, pix); fn = ld3(gn, pix); fc = ld3(rgb, pix); }
-        const float c = icc[pt], c2 = c + a;
-        const float inv = 1.0f / (c2 == 0.0f ? 1.0f : c2);
-        const f3 x = ld3(ip, pt), y = ld3(inn, pt), z = ld3(ic, pt);
-        const f3 gx = gop ? ld3(gop, pt) : f3{0, 0, 0}, gy = gon ? ld3(gon, pt) : f3{0, 0, 0},
-                 gz = goc ? ld3(goc, pt) : f3{0, 0, 0};
-        const float gc2 = gocc ? gocc[pt] : 0.0f;
-        if (gip) st3(gip, pt, f3{c * inv * gx.x, c * inv * gx.y, c * inv * gx.z});
-        if (ginn) st3(ginn, pt, f3{c * inv * gy.x, c * inv * gy.y, c * inv * gy.z});
-        if (gic) st3(gic, pt, f3{c * inv * gz.x, c * inv * gz.y, c * inv * gz.z});
-        // d x'/d c2 = -(c x + a xf) inv^2 = -x' inv (zero when c2 == 0, where the where() picks the constant 1)
-        const f3 xo{((c * x.x) + (a * fp.x)) * inv, ((c * x.y) + (a * fp.y)) * inv, ((c * x.z) + (a * fp.z)) * inv};
-        const f3 yo{((c * y.x) + (a * fn.x)) * inv, ((c * y.y) + (a * fn.y)) * inv, ((c * y.z) + (a * fn.z)) * inv};
-        const f3 zo{((c * z.x) + (a * fc.x)) * inv, ((c * z.y) + (a * fc.y)) * inv, ((c * z.z) + (a * fc.z)) * inv};
-        const float dinv = (c2 == 0.0f) ? 0.0f : 1.0f;
-        const float s_out = (xo.x * gx.x + xo.y * gx.y + xo.z * gx.z) + (yo.x * gy.x + yo.y * gy.y + yo.z * gy.z) +
-                            (zo.x * gz.x + zo.y * gz.y + zo.z * gz.z);
-        const float s_in = (x.x * gx.x + x.y * gx.y + x.z * gx.z) + (y.x * gy.x + y.y * gy.y + y.z * gy.z) +
-                           (z.x * gz.x + z.y * gz.y + z.z * gz.z);
-        const float s_f = (fp.x * gx.x + fp.y * gx.y + fp.z * gx.z) + (fn.x * gy.x + fn.y * gy.y + fn.z * gy.z) +
-                          (fc.x * gz.x + fc.y * gz.y + fc.z * gz.z);
-        if (gicc) gicc[pt] = gc2 + (s_in - dinv * s_out) * inv;
+        const FrameRow f = gather_frame(m >= 0, pix, gv, gn, rgb, alpha);
+        const MergeW w(icc[pt], f.a);
+        const MapRow in{ld3(ip, pt), ld3(inn, pt), ld3(ic, pt), w.c};
+        const MapRow g{gop ? ld3(gop, pt) : f3{0, 0, 0}, gon ? ld3(gon, pt) : f3{0, 0, 0}, goc ? ld3(goc, pt) : f3{0, 0, 0},
+                       gocc ? gocc[pt] : 0.0f};
+        if (gip) st3(gip, pt, w.map_bar(g.x));
+        if (ginn) st3(ginn, pt, w.map_bar(g.y));
+        if (gic) st3(gic, pt, w.map_bar(g.z));
+        const MergeSums s = merge_sums(w, in, f, g);
+        if (gicc) gicc[pt] = w.weight_bar(g.c, s.in, s.out);
         if (m >= 0) {  // unique rows: one map point per pixel -> plain stores
-            if (ggv) st3(ggv, pix, f3{a * inv * gx.x, a * inv * gx.y, a * inv * gx.z});
-            if (ggn) st3(ggn, pix, f3{a * inv * gy.x, a * inv * gy.y, a * inv * gy.z});
-            if (grgb) st3(grgb, pix, f3{a * inv * gz.x, a * inv * gz.y, a * inv * gz.z});
-            if (galpha) galpha[pix] = gc2 + (s_f - dinv * s_out) * inv;
+            if (ggv) st3(ggv, pix, w.frame_bar(g.x));
+            if (ggn) st3(ggn, pix, w.frame_bar(g.y));
+            if (grgb) st3(grgb, pix, w.frame_bar(g.z));
+            if (galpha) galpha[pix] = w.weight_bar(g.c, s.f, s.out);
         }
     }
 }
@@ -253,12 +207,10 @@ __global__ void tape_old_k(const unsigned int *__restrict__ pix_n, int64_t npix,
         t_pix_n[i] = n;
         if (n == 0xffffffffu) continue;
         const int64_t pt = (i / HW) * (int64_t)Nmax + n;
-        const f3 x = ld3(p, pt), y = ld3(nn, pt), z = ld3(cl, pt);
-        float *o = t_old + 10 * i;
-        o[0] = x.x; o[1] = x.y; o[2] = x.z; o[3] = y.x; o[4] = y.y; o[5] = y.z; o[6] = z.x; o[7] = z.y; o[8] = z.z; o[9] = cc[pt];
+        st_row10(t_old, i, MapRow{ld3(p, pt), ld3(nn, pt), ld3(cl, pt), cc[pt]});
     }
 }
-// Reverse of the merge for the matched pixels (the formulas of merge_bwd_k; an UNMATCHED map point passes its
+// Reverse of the merge for the matched pixels (the adjoint of merge_bwd_k; an UNMATCHED map point passes its
 // adjoint through unchanged -- x' = (c x + 0) / c -- so nothing is done for it: the pass costs O(pixels), not O(map)):
 // the map point's adjoint G is pulled back in place, the frame's adjoints are written (one map point per pixel: plain
 // stores), and the arena row gets its pre-merge values back, so that the arena is the map of the previous frame again
@@ -277,32 +229,16 @@ __global__ void fuse_bwd_matched_k(const unsigned int *__restrict__ t_pix_n, con
             continue;
         }
         const int64_t pt = (pix / HW) * (int64_t)Nmax + n;
-        const float *o = t_old + 10 * pix;
-        const f3 x{o[0], o[1], o[2]}, y{o[3], o[4], o[5]}, z{o[6], o[7], o[8]};
-        const float c = o[9], a = alpha[pix];
-        const f3 fp = ld3(gv, pix), fn = ld3(gn, pix), fc = ld3(rgb, pix);
-        const float c2 = c + a;
-        const float inv = 1.0f / (c2 == 0.0f ? 1.0f : c2), dinv = (c2 == 0.0f) ? 0.0f : 1.0f;
-        const f3 gx = ld3(Gp, pt), gy = ld3(Gn, pt), gz = ld3(Gc, pt);
-        const float gc2 = Gcc[pt];
-        const f3 xo{((c * x.x) + (a * fp.x)) * inv, ((c * x.y) + (a * fp.y)) * inv, ((c * x.z) + (a * fp.z)) * inv};
-        const f3 yo{((c * y.x) + (a * fn.x)) * inv, ((c * y.y) + (a * fn.y)) * inv, ((c * y.z) + (a * fn.z)) * inv};
-        const f3 zo{((c * z.x) + (a * fc.x)) * inv, ((c * z.y) + (a * fc.y)) * inv, ((c * z.z) + (a * fc.z)) * inv};
-        const float s_out = (xo.x * gx.x + xo.y * gx.y + xo.z * gx.z) + (yo.x * gy.x + yo.y * gy.y + yo.z * gy.z) +
-                            (zo.x * gz.x + zo.y * gz.y + zo.z * gz.z);
-        const float s_in = (x.x * gx.x + x.y * gx.y + x.z * gx.z) + (y.x * gy.x + y.y * gy.y + y.z * gy.z) +
-                           (z.x * gz.x + z.y * gz.y + z.z * gz.z);
-        const float s_f = (fp.x * gx.x + fp.y * gx.y + fp.z * gx.z) + (fn.x * gy.x + fn.y * gy.y + fn.z * gy.z) +
-                          (fc.x * gz.x + fc.y * gz.y + fc.z * gz.z);
-        st3(Gp, pt, f3{c * inv * gx.x, c * inv * gx.y, c * inv * gx.z});
-        st3(Gn, pt, f3{c * inv * gy.x, c * inv * gy.y, c * inv * gy.z});
-        st3(Gc, pt, f3{c * inv * gz.x, c * inv * gz.y, c * inv * gz.z});
-        Gcc[pt] = gc2 + (s_in - dinv * s_out) * inv;
-        st3(ggv, pix, f3{a * inv * gx.x, a * inv * gx.y, a * inv * gx.z});
-        st3(ggn, pix, f3{a * inv * gy.x, a * inv * gy.y, a * inv * gy.z});
-        st3(grgb, pix, f3{a * inv * gz.x, a * inv * gz.y, a * inv * gz.z});
-        galpha[pix] = gc2 + (s_f - dinv * s_out) * inv;
-        st3(p, pt, x); st3(nn, pt, y); st3(cl, pt, z); cc[pt] = c;  // the arena row as it was before this frame
+        const MapRow old = ld_row10(t_old, pix);
+        const float a = alpha[pix];
+        const FrameRow f{ld3(gv, pix), ld3(gn, pix), ld3(rgb, pix), a};
+        const MergeW w(old.c, a);
+        const MapRow g{ld3(Gp, pt), ld3(Gn, pt), ld3(Gc, pt), Gcc[pt]};
+        const MergeSums s = merge_sums(w, old, f, g);
+        st3(Gp, pt, w.map_bar(g.x)); st3(Gn, pt, w.map_bar(g.y)); st3(Gc, pt, w.map_bar(g.z)); Gcc[pt] = w.weight_bar(g.c, s.in, s.out);
+        st3(ggv, pix, w.frame_bar(g.x)); st3(ggn, pix, w.frame_bar(g.y)); st3(grgb, pix, w.frame_bar(g.z));
+        galpha[pix] = w.weight_bar(g.c, s.f, s.out);
+        st3(p, pt, old.x); st3(nn, pt, old.y); st3(cl, pt, old.z); cc[pt] = old.c;  // the arena row as it was before this frame
     }
 }
 // appended rows: row base + k of the arena is the k-th unmatched valid pixel in row-major order -- the adjoint of the
@@ -329,8 +265,7 @@ __global__ void clear_matched_k(const int64_t *__restrict__ rows, const int32_t 
                                 uint8_t *__restrict__ mask) {
     const int n = *d_n;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-        const longlong4 r = *reinterpret_cast<const longlong4 *>(rows + 4 * i);
-        mask[((int64_t)r.x * H + r.z) * W + r.w] = 0;
+        mask[row_pix(ld_table_row(rows, i), H, W)] = 0;
     }
 }
 
@@ -494,7 +429,7 @@ __global__ __launch_bounds__(CORR_T) void corr_pass1_k(const float *__restrict__
         const int64_t pt = base + ((live[k] && act[k]) ? n0 + k * CORR_T : 0), pix = b * HW + px[k];
         fv[k] = ld3(gv, pix); fn[k] = ld3(gn, pix); q[k] = ld3(mn, pt); c[k] = cc[pt];
     }
-    // phase 3: tests (similar_k's arithmetic), keys (unique_key's), atomics
+    // phase 3: tests (similar_pair), keys (unique_key), atomics
     int n_act = 0, n_sim = 0;
     float md = 0.0f;
 #pragma unroll
@@ -503,19 +438,13 @@ __global__ __launch_bounds__(CORR_T) void corr_pass1_k(const float *__restrict__
         int out = -1;
         if (act[k]) {
             ++n_act;
-            const float dx = fv[k].x - p[k].x, dy = fv[k].y - p[k].y, dz = fv[k].z - p[k].z;
-            // (a-b).norm(dim=-1): sqrt(fma(z,z,fma(y,y,x*x)));  (a*b).sum(-1): unfused      (similar_k)
-            const float dist = sqrtf(__fmaf_rn(dz, dz, __fmaf_rn(dy, dy, dx * dx)));
-            const float dot = (fn[k].x * q[k].x + fn[k].y * q[k].y) + fn[k].z * q[k].z;
+            float dot;
+            const bool sim = similar_pair(fv[k], fn[k], p[k], q[k], dist_th, dot_th, dot);
             md = fmaxf(md, dot);
-            if (dist < dist_th && dot > dot_th) {
+            if (sim) {
                 out = px[k];
                 ++n_sim;
-                // unique_key: 1 / (c + 1e-20) and ((p - fv)**2).sum(-1), unfused
-                const float inv_c = 1.0f / (c[k] + 1e-20f);
-                const float ex = p[k].x - fv[k].x, ey = p[k].y - fv[k].y, ez = p[k].z - fv[k].z;
-                const float ray = (ex * ex + ey * ey) + ez * ez;
-                atomicMin(pix_key + b * HW + px[k], ((unsigned long long)fbits(inv_c) << 32) | fbits(ray));
+                atomicMin(pix_key + b * HW + px[k], unique_key(c[k], p[k], fv[k]));
             }
         }
         pt_pix[base + n0 + k * CORR_T] = out;
@@ -572,10 +501,7 @@ __global__ __launch_bounds__(CORR_T) void corr_pass2_k(const int *__restrict__ p
 #pragma unroll
     for (int k = 0; k < CORR_I; ++k) {
         if (px[k] < 0) continue;
-        const float inv_c = 1.0f / (c[k] + 1e-20f);
-        const float ex = p[k].x - fv[k].x, ey = p[k].y - fv[k].y, ez = p[k].z - fv[k].z;
-        const float ray = (ex * ex + ey * ey) + ez * ez;
-        if ((((unsigned long long)fbits(inv_c) << 32) | fbits(ray)) == kmin[k]) atomicMin(pix_n + b * HW + px[k], (unsigned int)(n0 + k * CORR_T));
+        if (unique_key(c[k], p[k], fv[k]) == kmin[k]) atomicMin(pix_n + b * HW + px[k], (unsigned int)(n0 + k * CORR_T));
     }
 }
 
@@ -627,15 +553,10 @@ __global__ __launch_bounds__(CORR_T) void merge_corr_k(const int *__restrict__ p
             if (!live[k]) continue;
             const bool m = px[k] >= 0;
             n_u += m ? 1 : 0;
-            const float ak = m ? a[k] : 0.0f;
-            const f3 vp = m ? fp[k] : f3{0, 0, 0}, vn = m ? fn[k] : f3{0, 0, 0}, vc = m ? fc[k] : f3{0, 0, 0};
-            const float c2 = c[k] + ak;
-            const float inv = 1.0f / (c2 == 0.0f ? 1.0f : c2);
+            const FrameRow none, f = m ? FrameRow{fp[k], fn[k], fc[k], a[k]} : none;  // none: zeros, "unmatched"
+            const MergeW w(c[k], f.a);
             const int64_t pt = base + n0 + k * CORR_T;
-            st3(p, pt, f3{((c[k] * x[k].x) + (ak * vp.x)) * inv, ((c[k] * x[k].y) + (ak * vp.y)) * inv, ((c[k] * x[k].z) + (ak * vp.z)) * inv});
-            st3(nn, pt, f3{((c[k] * y[k].x) + (ak * vn.x)) * inv, ((c[k] * y[k].y) + (ak * vn.y)) * inv, ((c[k] * y[k].z) + (ak * vn.z)) * inv});
-            st3(cl, pt, f3{((c[k] * z[k].x) + (ak * vc.x)) * inv, ((c[k] * z[k].y) + (ak * vc.y)) * inv, ((c[k] * z[k].z) + (ak * vc.z)) * inv});
-            cc[pt] = c2;
+            st3(p, pt, w.avg(x[k], f.p)); st3(nn, pt, w.avg(y[k], f.n)); st3(cl, pt, w.avg(z[k], f.c)); cc[pt] = w.c2;
         }
     }
     n_u = wave_sum_i(n_u);
@@ -727,6 +648,18 @@ int fusion_merge_corr(void *state, const int32_t *ctr, const float *gvertex, con
     GS_LAUNCH_CHECK("gs_pointfusion_update/merge");
     return GS_OK;
 }
+// rows of the first n_arrays host-listed arrays go behind the *base rows their destinations hold, up to cap
+static AppendWriter append_writer(int n_arrays, const float *const *h_src, const int *h_row_floats, float *const *h_dst,
+                                  const int32_t *base, int cap) {
+    AppendWriter wr;
+    wr.n_arrays = n_arrays; wr.base = base; wr.cap = cap;
+    for (int a = 0; a < 4; ++a) {
+        wr.src[a] = a < n_arrays ? (const uint32_t *)h_src[a] : nullptr;
+        wr.out[a] = a < n_arrays ? (uint32_t *)h_dst[a] : nullptr;
+        wr.words[a] = a < n_arrays ? h_row_floats[a] : 0;
+    }
+    return wr;
+}
 // unmatched valid pixels of batch element b appended behind the rows its arena holds; the row count itself advances
 // in fusion_finish (AppendWriter reads the count as the append offset, so it must not move before every b is written)
 int fusion_append_corr(void *state, int B, int H, int W, int Nmax, int b, const float *depth, const float *const *h_src,
@@ -734,11 +667,7 @@ int fusion_append_corr(void *state, int B, int H, int W, int Nmax, int b, const 
                        hipStream_t st) {
     const CorrState c = corr_state_ptrs(state, B, H, W, Nmax);
     const int64_t HW = (int64_t)H * W;
-    AppendWriter wr;
-    wr.n_arrays = 4; wr.base = d_count; wr.cap = cap;
-    for (int a = 0; a < 4; ++a) {
-        wr.src[a] = (const uint32_t *)h_src[a]; wr.out[a] = (uint32_t *)h_dst[a]; wr.words[a] = h_row_floats[a];
-    }
+    const AppendWriter wr = append_writer(4, h_src, h_row_floats, h_dst, d_count, cap);
     AppendPredPix pred{depth + b * HW, c.pix_n + b * HW};
     return compact_launch(HW, pred, wr, d_total, cws, st, "gs_pointfusion_update/append");
 }
@@ -822,13 +751,7 @@ int fusion_update_reverse(const void *tape, int B, int H, int W, int Nmax, const
 int append_valid_pixels(int n_arrays, const float *depth_b, int64_t HW, const float *const *h_src, const int *h_row_floats,
                         float *const *h_dst, int32_t *d_count, int cap, int32_t *d_appended, int32_t *d_overflow, void *cws,
                         hipStream_t st) {
-    AppendWriter wr;
-    wr.n_arrays = n_arrays; wr.base = d_count; wr.cap = cap;
-    for (int a = 0; a < 4; ++a) {
-        wr.src[a] = a < n_arrays ? (const uint32_t *)h_src[a] : nullptr;
-        wr.out[a] = a < n_arrays ? (uint32_t *)h_dst[a] : nullptr;
-        wr.words[a] = a < n_arrays ? h_row_floats[a] : 0;
-    }
+    const AppendWriter wr = append_writer(n_arrays, h_src, h_row_floats, h_dst, d_count, cap);
     int *total = (int *)((char *)cws + compact_ws_bytes(HW));
     ValidDepthPred pred{depth_b};
     const int rc = compact_launch(HW, pred, wr, total, cws, st, "gs_aggregate_update/append");

@@ -72,6 +72,17 @@ __device__ __forceinline__ void st3(float *__restrict__ p, int64_t i, f3 v) {
     q[2] = v.z;
 }
 
+// one row [b, n, h, w] of a correspondence / active-point table: four int64 moved as ONE 32-byte access
+__device__ __forceinline__ longlong4 ld_table_row(const int64_t *rows, int64_t i) { return *reinterpret_cast<const longlong4 *>(rows + 4 * i); }
+__device__ __forceinline__ void st_table_row(int64_t *rows, int64_t pos, const longlong4 &r) { *reinterpret_cast<longlong4 *>(rows + 4 * pos) = r; }
+__device__ __forceinline__ void st_table_row(int64_t *rows, int64_t pos, int64_t b, int64_t n, int64_t h, int64_t w) {
+    longlong4 r;
+    r.x = b; r.y = n; r.z = h; r.w = w;
+    st_table_row(rows, pos, r);
+}
+__device__ __forceinline__ int64_t row_pix(const longlong4 &r, int H, int W) { return ((int64_t)r.x * H + r.z) * W + r.w; }  // into (B,H,W)
+__device__ __forceinline__ int64_t row_pt(const longlong4 &r, int Nmax) { return (int64_t)r.x * Nmax + r.y; }              // into (B,Nmax)
+
 // K=3 contraction in the order the reference's CPU GEMM was measured to use:
 //   fma(a2, b2, fma(a1, b1, a0 * b0))
 __device__ __forceinline__ float dot3_fma(float a0, float a1, float a2, float b0, float b1, float b2);

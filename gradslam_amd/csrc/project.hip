@@ -63,9 +63,7 @@ struct ActiveWriter {
         const int b = (int)(i / Nmax), n = (int)(i - (int64_t)b * Nmax);
         int h, w;
         project_point(cams[b], ld3(points, i), H, W, umax, vmax, h, w);
-        longlong4 r;  // one 32-byte store per row
-        r.x = b; r.y = n; r.z = h; r.w = w;
-        *reinterpret_cast<longlong4 *>(rows + 4 * pos) = r;
+        st_table_row(rows, pos, b, n, h, w);
     }
 };
 
@@ -99,9 +97,9 @@ struct ActiveWriterL {
         const int b = (int)(i / Nmax), n = (int)(i - (int64_t)b * Nmax);
         int h, w;
         project_point(cam_cache()[b], it.p, H, W, umax, vmax, h, w);
-        longlong4 r;  // one 32-byte store per row
+        longlong4 r;  // (built here, in this order: through the six-argument form this kernel's instruction schedule moves)
         r.x = b; r.y = n; r.z = h; r.w = w;
-        *reinterpret_cast<longlong4 *>(rows + 4 * pos) = r;
+        st_table_row(rows, pos, r);
     }
     __device__ void operator()(int64_t i, int64_t pos) const { put(ActivePredL::Item{ld3(points, i)}, i, pos); }
 };
@@ -141,9 +139,7 @@ struct ActiveWriterH {
     __device__ void put(const ActivePredH::Item &it, int64_t i, int64_t pos) const {
         int h, w;
         project_point(cam_cache()[0], it.p, H, W, umax, vmax, h, w);
-        longlong4 r;
-        r.x = 0; r.y = i; r.z = h; r.w = w;
-        *reinterpret_cast<longlong4 *>(rows + 4 * pos) = r;
+        st_table_row(rows, pos, 0, i, h, w);
         atomicAdd(cnt + (h / ds) * Wd + (w / ds), 1);
     }
     __device__ void operator()(int64_t i, int64_t pos) const { put(ActivePredH::Item{ld3(points, i)}, i, pos); }
@@ -220,7 +216,7 @@ __global__ void pix_count_k(const int64_t *__restrict__ rows, const int32_t *__r
                             const int32_t *__restrict__ starts, int Wd, int npix, int ds, int *__restrict__ cnt) {
     const int n = *d_n;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-        const longlong4 r = *reinterpret_cast<const longlong4 *>(rows + 4 * i);
+        const longlong4 r = ld_table_row(rows, i);
         const int b = (int)r.x;
         const int pix = (int)(r.z / ds) * Wd + (int)(r.w / ds);
         atomicAdd(cnt + (int64_t)b * npix + pix, 1);
@@ -263,7 +259,7 @@ __global__ void pix_scatter_k(const int64_t *__restrict__ rows, const int32_t *_
                               int32_t *__restrict__ tgt_pix /* or NULL */) {
     const int n = *d_n;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-        const longlong4 r = *reinterpret_cast<const longlong4 *>(rows + 4 * i);
+        const longlong4 r = ld_table_row(rows, i);
         const int b = (int)r.x;
         const int pix = (int)(r.z / ds) * Wd + (int)(r.w / ds);
         const int k = (int)(i - starts[b]);
@@ -301,7 +297,7 @@ __global__ void tgt_gather_count_k(const int64_t *__restrict__ rows, const int32
     const int n = *d_n;
     if (blockIdx.x == 0 && threadIdx.x < B) counts[threadIdx.x] = starts[threadIdx.x + 1] - starts[threadIdx.x];
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-        const longlong4 r = *reinterpret_cast<const longlong4 *>(rows + 4 * i);
+        const longlong4 r = ld_table_row(rows, i);
         const int b = (int)r.x;
         const int k = (int)(i - starts[b]);
         const int pix = (int)(r.z / ds) * Wd + (int)(r.w / ds);
@@ -324,7 +320,7 @@ __global__ void tgt_scatter_gather1_k(const int64_t *__restrict__ rows, const in
     const int n = *d_n;
     if (blockIdx.x == 0 && threadIdx.x == 0) counts[0] = n;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-        const longlong4 r = *reinterpret_cast<const longlong4 *>(rows + 4 * i);
+        const longlong4 r = ld_table_row(rows, i);
         const f3 p = ld3(map_points, r.y);
         if (i < cap) {
             st3(tgt, i, p);
@@ -338,10 +334,6 @@ __global__ void tgt_scatter_gather1_k(const int64_t *__restrict__ rows, const in
         st3(scan_pts, slot, p);
         scan_orig[slot] = (int32_t)i;
     }
-}
-
-__global__ void fill_i32b_k(int *__restrict__ p, int64_t n, int v) {
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) p[i] = v;
 }
 
 }  // namespace gs

@@ -926,6 +926,125 @@ def test_arena_entry_points_against_torch(gs):
                 assert torch.equal(x, y)
 
 
+# rel_err of gs_fusion_merge_backward's eight outputs against float64 autograd in test_merge_row_edges.  Measured worst on an
+# MI355X: 1.09e-7 (g_alpha); g_ccounts 9.1e-8, the three map adjoints 4.9e-8 .. 7.5e-8, the frame's vertex / normal / colour
+# adjoints 1.2e-8 .. 3.8e-8.  The bound is under 3x the worst.
+MERGE_BWD_TOL = 3e-7
+
+
+def test_merge_row_edges(gs):
+    """The merge of one map row (slam/fusionutils.py:678-699) and its adjoint at the rows where the formula branches,
+    through the C ABI: ordinary matched rows, matched rows with c == 0 and a == 0 (c2 == 0: the where() picks the
+    constant 1, so inv == 1 and d inv / d c2 == 0), matched rows with c == 0 and a > 0, unmatched live rows (one of
+    them with c == 0) and zero padding.  Forward: out-of-place == in-place == the float32 restatement, bit for bit.
+    Backward: float64 autograd through the same restatement; the c2 == 0 rows hold multiples of 1/8, so every sum
+    there is exact in float32 and their adjoints are asserted exactly."""
+    from gradslam_amd import _native as nv
+    from gradslam_amd import ops
+
+    B, H, W, N = 2, 4, 6, 40
+    cnts = (33, 7)
+    gen = torch.Generator().manual_seed(11)
+    rn = lambda *s: torch.randn(*s, generator=gen)
+    eighths = lambda *s: torch.round(rn(*s) * 8) / 8
+    gV, gN, rgb = rn(B, 1, H, W, 3), rn(B, 1, H, W, 3), rn(B, 1, H, W, 3)
+    alpha = torch.rand(B, 1, H, W, 1, generator=gen) + 0.1
+    mp, mn, mc = rn(B, N, 3), rn(B, N, 3), rn(B, N, 3)
+    cc = torch.rand(B, N, 1, generator=gen) + 0.5
+    g_out = [rn(B, N, 3), rn(B, N, 3), rn(B, N, 3), rn(B, N, 1)]
+    # (b, n, h, w) of every kind of matched row; one map point per pixel and one pixel per map point
+    ordinary = [(0, 0, 0, 0), (0, 1, 3, 5), (0, 2, 1, 2), (0, 5, 2, 4), (0, 13, 0, 3), (0, 32, 3, 0), (1, 0, 1, 1), (1, 6, 3, 5)]
+    zero_zero = [(0, 3, 2, 2), (1, 1, 0, 0)]  # c == 0 and a == 0
+    zero_c = [(0, 4, 1, 5), (1, 3, 2, 3)]     # c == 0, a > 0
+    zero_unmatched = [(0, 6)]                 # unmatched live row with c == 0: c2 == 0 without a pixel
+    for b, n, h, w in zero_zero + zero_c:
+        cc[b, n] = 0
+    for b, n, h, w in zero_zero:
+        alpha[b, 0, h, w] = 0
+        for t_ in (gV, gN, rgb):
+            t_[b, 0, h, w] = eighths(3)
+    for b, n in [r[:2] for r in zero_zero] + zero_unmatched:
+        cc[b, n] = 0
+        for t_ in (mp, mn, mc) + tuple(g_out[:3]):
+            t_[b, n] = eighths(3)
+        g_out[3][b, n] = eighths(1)
+    for b in range(B):
+        for t_ in (mp, mn, mc, cc):
+            t_[b, cnts[b]:] = 0
+    gV, gN, rgb, alpha, mp, mn, mc, cc = (x.to(DEV) for x in (gV, gN, rgb, alpha, mp, mn, mc, cc))
+    g_out = [x.to(DEV) for x in g_out]
+    rows = torch.tensor(sorted(ordinary + zero_zero + zero_c), dtype=torch.int64, device=DEV)
+    n_rows = rows.shape[0]
+    rb, rpt, rh, rw = rows.unbind(1)
+    counts = torch.tensor(cnts, dtype=torch.int32, device=DEV)
+    live = (torch.arange(N, device=DEV)[None] < counts[:, None])  # (B, N)
+    d_n = ops.dev_int(n_rows, DEV)
+    ws = nv.workspace(nv.ws_bytes("gs_fusion_merge_ws_bytes", B, N), mp.device, "merge_test")
+    frame = (nv.ptr(rows), nv.ptr(d_n), n_rows, nv.ptr(gV), nv.ptr(gN), nv.ptr(rgb), nv.ptr(alpha), B, H, W, N, nv.ptr(counts))
+
+    def restate(gV, gN, rgb, alpha, mp, mn, mc, cc):  # fusionutils.py:660-699, op by op
+        fp, fn, fc, fa = (torch.zeros_like(x) for x in (mp, mn, mc, cc))
+        fp[rb, rpt], fn[rb, rpt], fc[rb, rpt], fa[rb, rpt] = gV[rb, 0, rh, rw], gN[rb, 0, rh, rw], rgb[rb, 0, rh, rw], alpha[rb, 0, rh, rw]
+        c2 = cc + fa
+        inv = 1 / torch.where(c2 == 0, torch.ones_like(c2), c2)
+        return ((cc * mp) + (fa * fp)) * inv, ((cc * mn) + (fa * fn)) * inv, ((cc * mc) + (fa * fc)) * inv, c2
+
+    # ---- forward
+    out = [torch.full_like(x, float("nan")) for x in (mp, mn, mc, cc)]
+    nv.call("gs_fusion_merge", *frame, nv.ptr(mp), nv.ptr(mn), nv.ptr(mc), nv.ptr(cc), *(nv.ptr(x) for x in out), nv.ptr(ws), ws.numel(),
+            nv.stream())
+    inpl = [x.clone() for x in (mp, mn, mc, cc)]
+    for x in inpl:
+        x[~live] = 7.0
+    nv.call("gs_fusion_merge_inplace", *frame, *(nv.ptr(x) for x in inpl), nv.ptr(ws), ws.numel(), nv.stream())
+    want = restate(gV, gN, rgb, alpha, mp, mn, mc, cc)
+    for name, o, i, r in zip(("points", "normals", "colors", "ccounts"), out, inpl, want):
+        print("merge_row_edges forward", name, "max |out - restatement|", float((o - r).abs().max()))
+        assert torch.equal(o[live], i[live]), name
+        assert (o[~live] == 0).all() and (i[~live] == 7.0).all(), name
+        assert torch.equal(o, r), name
+    for b, n in [r[:2] for r in zero_zero] + zero_unmatched:  # (0 x + 0 f) * 1
+        assert all((o[b, n] == 0).all() for o in out)
+
+    # ---- backward
+    g_in = [torch.full_like(x, float("nan")) for x in (mp, mn, mc, cc)]
+    g_fr = [torch.zeros_like(x) for x in (gV, gN, rgb, alpha)]
+    nv.call("gs_fusion_merge_backward", *frame, nv.ptr(mp), nv.ptr(mn), nv.ptr(mc), nv.ptr(cc), *(nv.ptr(x) for x in g_out),
+            *(nv.ptr(x) for x in g_in), *(nv.ptr(x) for x in g_fr), nv.ptr(ws), ws.numel(), nv.stream())
+    leaves = [x.double().requires_grad_(True) for x in (gV, gN, rgb, alpha, mp, mn, mc, cc)]
+    ref = torch.autograd.grad(restate(*leaves), leaves, [x.double() for x in g_out])
+    ref_fr, ref_in = ref[:4], ref[4:]
+    matched = torch.zeros(B, 1, H, W, dtype=torch.bool, device=DEV)
+    matched[rb, 0, rh, rw] = True
+    worst = 0.0
+    for name, got, r in zip(("g_points", "g_normals", "g_colors", "g_ccounts"), g_in, ref_in):
+        assert (got[~live] == 0).all(), name  # the kernel's padding carries no adjoint
+        e = rel_err(got[live], r[live])
+        print("merge_row_edges backward", name, "rel_err", e)
+        worst = max(worst, e)
+    for name, got, r in zip(("g_gvertex", "g_gnormal", "g_rgb", "g_alpha"), g_fr, ref_fr):
+        assert (got[~matched] == 0).all(), name  # unmatched pixels keep the caller's zeros
+        e = rel_err(got[matched], r[matched])
+        print("merge_row_edges backward", name, "rel_err", e)
+        worst = max(worst, e)
+    print("merge_row_edges backward worst rel_err", worst)
+    # c2 == 0: inv == 1 and dinv == 0, so x_bar = c g = 0, c_bar = c2_bar + sum x.g, and at a matched pixel
+    # f_bar = a g = 0, a_bar = c2_bar + sum f.g -- exact in float32 on multiples of 1/8
+    for b, n in [r[:2] for r in zero_zero] + zero_unmatched:
+        for got, r in zip(g_in, ref_in):
+            assert torch.equal(got[b, n].double(), r[b, n])
+        assert all((got[b, n] == 0).all() for got in g_in[:3])
+        s_in = sum((x[b, n] * g[b, n]).sum() for x, g in zip((mp, mn, mc), g_out))
+        assert float(g_in[3][b, n]) == float(g_out[3][b, n, 0] + s_in)
+    for b, n, h, w in zero_zero:
+        for got, r in zip(g_fr, ref_fr):
+            assert torch.equal(got[b, 0, h, w].double(), r[b, 0, h, w])
+        assert all((got[b, 0, h, w] == 0).all() for got in g_fr[:3])
+        s_f = sum((f[b, 0, h, w] * g[b, n]).sum() for f, g in zip((gV, gN, rgb), g_out))
+        assert float(g_fr[3][b, 0, h, w]) == float(g_out[3][b, n, 0] + s_f)
+    assert worst <= MERGE_BWD_TOL
+
+
 @pytest.mark.parametrize("H,W,ds,B", [(50, 70, 3, 1), (33, 65, 2, 2), (17, 19, 1, 1), (121, 67, 5, 2)])
 def test_odd_image_shapes_vs_oracle(gs, H, W, ds, B):
     """Image sizes that are no multiple of any tile (64x4 map tiles, 64-point ICP tiles, 256-row compaction blocks)

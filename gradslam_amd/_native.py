@@ -121,6 +121,11 @@ SIGNATURES = {
                                        c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_sz,
                                        c_p]),
     "gs_fusion_new_mask": (c_i, [c_p, c_p, c_p, c_i64, c_i, c_i, c_i, c_p, c_p]),
+    "gs_render_map_ws_bytes": (c_sz, [c_i, c_i, c_i]),
+    "gs_render_map": (c_i, [c_p, c_p, c_p, c_p, c_i, c_i, c_p, c_p, c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_sz, c_p]),
+    "gs_render_map_backward_ws_bytes": (c_sz, [c_i, c_i, c_i]),
+    "gs_render_map_backward": (c_i, [c_p, c_p, c_i, c_i, c_p, c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_sz,
+                                     c_p]),
 }
 
 _lib = None

@@ -31,11 +31,14 @@ __device__ __forceinline__ Cam make_cam(const float *__restrict__ T, const float
 // Projects map point p of batch element with camera c.  Returns true iff the point is active and
 // fills (h, w).  reference slam/fusionutils.py:250-274, structures/pointclouds.py:501-517,423-425,
 // geometry/projutils.py:221-236.
-__device__ __forceinline__ bool project_point(const Cam &c, f3 p, int H, int W, float umax, float vmax, int &h, int &w) {
+// project_point_z also hands out z, the camera-frame depth the in-front test reads (fp32, before K): the renderer's
+// (render.hip) z-buffer key.  project_point is the same function without it -- ONE body, so the pixel a map point
+// is rendered into is the pixel the active-point search and the fused correspondence pass find it on.
+__device__ __forceinline__ bool project_point_z(const Cam &c, f3 p, int H, int W, float umax, float vmax, int &h, int &w, float &z) {
     // p' = p . Rinv^T + tinv, Rinv^T == R: p'_k = sum_j p_j R[j][k]   (GEMM contraction)
     const float x = dot3_fma(p.x, p.y, p.z, c.R[0], c.R[3], c.R[6]) + c.tinv[0];
     const float y = dot3_fma(p.x, p.y, p.z, c.R[1], c.R[4], c.R[7]) + c.tinv[1];
-    const float z = dot3_fma(p.x, p.y, p.z, c.R[2], c.R[5], c.R[8]) + c.tinv[2];
+    z = dot3_fma(p.x, p.y, p.z, c.R[2], c.R[5], c.R[8]) + c.tinv[2];
     const bool front = z > 0.0f;
     // K4x4 . [p',1]: broadcast batched 4x4 @ 4x1 -> plain (unfused) accumulation
     const float *K = c.K;
@@ -52,6 +55,10 @@ __device__ __forceinline__ bool project_point(const Cam &c, f3 p, int H, int W, 
     w = (int)fminf(fmaxf(ru, 0.0f), (float)(W - 1));
     h = (int)fminf(fmaxf(rv, 0.0f), (float)(H - 1));
     return in;
+}
+__device__ __forceinline__ bool project_point(const Cam &c, f3 p, int H, int W, float umax, float vmax, int &h, int &w) {
+    float z;
+    return project_point_z(c, p, H, W, umax, vmax, h, w, z);
 }
 
 

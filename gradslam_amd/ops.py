@@ -886,3 +886,90 @@ def fusion_new_mask_raw(depth, rows, n_rows_dev, max_rows):
     mask = torch.empty((B, H, W), dtype=torch.uint8, device=depth.device)
     call("gs_fusion_new_mask", ptr(depth), ptr(rows), ptr(n_rows_dev), max_rows, B, H, W, ptr(mask), stream())
     return mask
+
+
+# ---------------------------------------------------------------------------------------------- R
+def _render_args(points_padded, normals_padded, colors_padded, counts_i32, poses_b44, K_b44, H, W, op):
+    require_hip(points_padded, normals_padded, colors_padded, counts_i32, poses_b44, K_b44, op=op)
+    pts, nrm, col = _f32c(points_padded), _f32c(normals_padded), _f32c(colors_padded)
+    poses, K = _f32c(poses_b44), _f32c(K_b44)
+    if pts.ndim != 3 or pts.shape[-1] != 3:
+        raise ValueError("{}: points_padded should have shape (B, N, 3). Got {}.".format(op, tuple(pts.shape)))
+    B = pts.shape[0]
+    for name, x in (("normals_padded", nrm), ("colors_padded", col)):
+        if x is not None and x.shape != pts.shape:
+            raise ValueError("{}: {} should have the shape of points_padded {}. Got {}.".format(op, name, tuple(pts.shape), tuple(x.shape)))
+    for name, x in (("poses", poses), ("intrinsics", K)):
+        if x.numel() != 16 * B or x.shape[-2:] != (4, 4):
+            raise ValueError("{}: {} should hold one 4x4 matrix per batch element (B = {}). Got {}.".format(op, name, B, tuple(x.shape)))
+    if counts_i32.dtype != torch.int32 or counts_i32.numel() != B:
+        raise ValueError("{}: counts should be {} int32 values. Got {} of {}.".format(op, B, counts_i32.numel(), counts_i32.dtype))
+    if int(H) <= 0 or int(W) <= 0 or pts.shape[1] == 0:
+        raise ValueError("{}: needs a non-empty map array and a positive image size. Got N = {}, H = {}, W = {}.".format(
+            op, pts.shape[1], H, W))
+    return pts, nrm, col, counts_i32.contiguous(), poses, K
+
+
+def render_map_raw(points_padded, normals_padded, colors_padded, counts_i32, poses_b44, K_b44, H: int, W: int):
+    """The map seen from one camera per batch element: z-buffered (index (B,H,W) int32, depth (B,H,W), points, normals,
+    colors (B,H,W,3)).  A pixel shows the map row with the smallest camera-frame z among the rows find_active_map_points
+    puts on it (ties: the smallest row), or index -1 / zeros; normals / colors are None when the map has none.  Three
+    launches, no [b,n,h,w] table (the chain it replaces: project_active_raw rows, a scatter-min key per pixel, gathers)."""
+    pts, nrm, col, counts, poses, K = _render_args(points_padded, normals_padded, colors_padded, counts_i32, poses_b44, K_b44, H, W,
+                                                   "render_map")
+    B, Nmax = pts.shape[:2]
+    H, W = int(H), int(W)
+    dev = pts.device
+    index = torch.empty((B, H, W), dtype=torch.int32, device=dev)
+    depth = torch.empty((B, H, W), dtype=torch.float32, device=dev)
+    img = lambda have: torch.empty((B, H, W, 3), dtype=torch.float32, device=dev) if have else None
+    op, on, oc = img(True), img(nrm is not None), img(col is not None)
+    ws = workspace(ws_bytes("gs_render_map_ws_bytes", B, H, W), dev, "render")
+    call("gs_render_map", ptr(pts), ptr(nrm), ptr(col), ptr(counts), B, Nmax, ptr(poses), ptr(K), H, W, ptr(index), ptr(depth),
+         ptr(op), ptr(on), ptr(oc), ptr(ws), ws.numel(), stream())
+    return index, depth, op, on, oc
+
+
+def render_map_backward_raw(points_padded, counts_i32, poses_b44, index, g_depth=None, g_points=None, g_normals=None,
+                            g_colors=None, want=(True, True, True, True)):
+    """Adjoint of render_map_raw for the winners in `index` (constants): -> (g_map_points, g_map_normals, g_map_colors
+    (B,N,3), g_poses (B,4,4)), each fully written, or None where `want` says it is not needed.  No atomics: bit-reproducible."""
+    require_hip(points_padded, counts_i32, poses_b44, index, g_depth, g_points, g_normals, g_colors, op="render_map_backward")
+    pts, poses = _f32c(points_padded), _f32c(poses_b44)
+    B, Nmax = pts.shape[:2]
+    H, W = index.shape[1:3]
+    dev = pts.device
+    index = index.contiguous()
+    gd, gp, gn, gc = (_f32c(g) for g in (g_depth, g_points, g_normals, g_colors))
+    row = lambda w: torch.empty((B, Nmax, 3), dtype=torch.float32, device=dev) if w else None
+    o_p, o_n, o_c = row(want[0]), row(want[1]), row(want[2])
+    o_T = torch.empty((B, 4, 4), dtype=torch.float32, device=dev) if want[3] else None
+    ws = workspace(ws_bytes("gs_render_map_backward_ws_bytes", B, H, W), dev, "render_bwd")
+    call("gs_render_map_backward", ptr(pts), ptr(counts_i32), B, Nmax, ptr(poses), H, W, ptr(index), ptr(gd), ptr(gp), ptr(gn),
+         ptr(gc), ptr(o_p), ptr(o_n), ptr(o_c), ptr(o_T), ptr(ws), ws.numel(), stream())
+    return o_p, o_n, o_c, o_T
+
+
+class _RenderFn(torch.autograd.Function):
+    """(map points, normals, colors, poses) -> (index, depth, points, normals, colors) with the hand-written adjoint.
+    `index` is not differentiable; neither is the pixel a row lands on (a constant of the graph), so the intrinsics get None."""
+
+    @staticmethod
+    def forward(ctx, points, normals, colors, counts_i32, poses, K, H, W):
+        index, depth, op, on, oc = render_map_raw(points, normals, colors, counts_i32, poses, K, H, W)
+        ctx.save_for_backward(points, counts_i32, poses, index)
+        ctx.mark_non_differentiable(index)
+        return index, depth, op, on, oc
+
+    @staticmethod
+    def backward(ctx, _g_index, g_depth, g_op, g_on, g_oc):
+        points, counts_i32, poses, index = ctx.saved_tensors
+        want = tuple(ctx.needs_input_grad[i] for i in (0, 1, 2, 4))
+        g_p, g_n, g_c, g_T = render_map_backward_raw(points, counts_i32, poses, index, g_depth, g_op, g_on, g_oc, want)
+        return (None if g_p is None else g_p.view_as(points), g_n, g_c, None, None if g_T is None else g_T.view_as(poses), None,
+                None, None)
+
+
+def render_map(points_padded, normals_padded, colors_padded, counts_i32, poses_b44, K_b44, H: int, W: int):
+    """Autograd-aware render_map_raw: gradients reach the map's points / normals / colors and the poses."""
+    return _RenderFn.apply(points_padded, normals_padded, colors_padded, counts_i32, poses_b44, K_b44, int(H), int(W))

@@ -543,6 +543,38 @@ int gs_fusion_merge_inplace(const int64_t *rows, const int32_t *d_n_rows, int64_
 int gs_fusion_new_mask(const float *depth, const int64_t *rows, const int32_t *d_n_rows,
                        int64_t max_rows, int B, int H, int W, uint8_t *mask, gs_stream_t stream);
 
+/* ---------------------------------------------------------------- R: the map rendered into a camera
+ * The inverse of pointclouds_from_rgbdimages (structures/utils.py:7-57): per pixel the nearest map point that
+ * find_active_map_points (slam/fusionutils.py:247-282) puts on it, as z-buffered index, depth, position, normal and colour
+ * images.  The reference has no such function; a user builds it from find_active_map_points (one [b,n,h,w] row per active
+ * point), a per-pixel scatter-min of the camera-frame depth over those rows, and index_select gathers of the map
+ * attributes.  Here: three launches, one pass over the map with a 64-bit atomicMin per candidate, no table.
+ * Candidates: rows n < min(counts[b], Nmax) that gs_project_active would keep (ds <= 0), on the pixel it reports; depth = the
+ * camera-frame z (fp32).  Winner of a pixel: smallest z, ties to the smallest n; independent of arrival order.
+ * Outputs (all fully written): out_index (B,H,W) int32 = winner's n or -1; out_depth (B,H,W) = its z or 0; out_points /
+ * out_normals / out_colors (B,H,W,3) = its map attributes or zeros; an attribute image is skipped when its output pointer or
+ * (normals, colors) its map array is NULL.  points (B,Nmax,3); poses / intrinsics: B x 16. */
+size_t gs_render_map_ws_bytes(int B, int H, int W);
+int gs_render_map(const float *points, const float *normals, const float *colors, const int32_t *counts,
+                  int B, int Nmax, const float *poses, const float *intrinsics, int H, int W,
+                  int32_t *out_index, float *out_depth, float *out_points, float *out_normals,
+                  float *out_colors, void *ws, size_t ws_bytes, gs_stream_t stream);
+
+/* Adjoint of gs_render_map (replaces torch autograd through the gathers and the depth's rigid transform of that chain): the
+ * output adjoints go to the map row each pixel shows and to the pose, with no atomics.  The pixel assignment and the winner (`index`, the forward's output) are constants.  Any of the four output adjoints may be NULL
+ * (= zero); any of the four results may be NULL (= not wanted).  g_points / g_normals / g_colors (B,Nmax,3) and g_poses
+ * (B x 16) are fully written: zeros for rows that won no pixel or lie beyond the count, and for the pose entries other than
+ * rotation column 2 and the translation.  With z = sum_j R[j][2] (p_j - t_j):
+ *   g_points[n] = g_out_points[pix] + g_depth[pix] R[:,2];  g_normals[n], g_colors[n] = their pixel's adjoint;
+ *   g_poses[b][j][2] = sum_pix g_depth (p_j - t_j);  g_poses[b][j][3] = -R[j][2] sum_pix g_depth.
+ * The intrinsics adjoint is zero almost everywhere and not produced.  No atomics: the same bits from run to run. */
+size_t gs_render_map_backward_ws_bytes(int B, int H, int W);
+int gs_render_map_backward(const float *points, const int32_t *counts, int B, int Nmax, const float *poses,
+                           int H, int W, const int32_t *index, const float *g_depth,
+                           const float *g_out_points, const float *g_out_normals,
+                           const float *g_out_colors, float *g_points, float *g_normals, float *g_colors,
+                           float *g_poses, void *ws, size_t ws_bytes, gs_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

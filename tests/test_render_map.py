@@ -1,0 +1,496 @@
+"""The renderer (gs_render_map, ops.render_map, rgbdimages_from_pointclouds): the map seen from a camera.
+
+CPU part: the four entry points exist, their workspaces have the documented size, bad arguments are refused before any device
+work, and the Python front refuses CPU tensors and malformed arguments.
+
+GPU part: the z-buffer against exact statements of its rules.  A frame's own cloud rendered into the frame's camera gives the
+frame back; copies of a cloud at half the distance win every pixel and equal depths go to the smaller row (both exact in
+fp32); a general view is compared bit for bit with a restatement of the key in fp32 (fused steps through oracle.icp_step.fma32);
+rows beyond the count, image borders and empty maps; and the reverse pass against a float64 restatement gathered by the
+kernel's own index image."""
+import ctypes
+
+import numpy as np
+import pytest
+import torch
+
+import gradslam_amd as gs
+from gradslam_amd import _native as nv
+from gradslam_amd import ops
+from gradslam_amd.structures.utils import pointclouds_from_rgbdimages, rgbdimages_from_pointclouds
+from gradslam_amd.synthetic import make_sequence
+
+DEV = "cuda:0"
+U = 2.0 ** -24  # unit roundoff of fp32
+
+
+def _align256(n):
+    return -(-n // 256) * 256
+
+
+# ------------------------------------------------------------------ CPU: ABI and error contracts
+def test_render_symbols_load():
+    lib = nv.lib()
+    for name in ("gs_render_map_ws_bytes", "gs_render_map", "gs_render_map_backward_ws_bytes", "gs_render_map_backward"):
+        assert hasattr(lib, name) and name in nv.SIGNATURES, name
+    assert len(nv.SIGNATURES["gs_render_map"][1]) == 18 and len(nv.SIGNATURES["gs_render_map_backward"][1]) == 19
+    assert lib.gs_abi_version() == 3
+
+
+@pytest.mark.parametrize("B,H,W", [(1, 6, 8), (1, 48, 64), (2, 30, 40), (3, 5, 7), (1, 480, 640)])
+def test_render_workspace_sizes_follow_the_layout(B, H, W):
+    """Forward: the B*H*W 64-bit keys and nothing else.  Reverse: four partial sums per block of 256 pixels and batch element."""
+    lib = nv.lib()
+    assert lib.gs_render_map_ws_bytes(B, H, W) == _align256(8 * B * H * W)
+    assert lib.gs_render_map_backward_ws_bytes(B, H, W) == _align256(B * -(-(H * W) // 256) * 4 * 4)
+
+
+def test_render_refuses_bad_arguments_before_any_device_work():
+    """NULL pointers, non-positive shapes and a missing workspace return a non-zero code (the pointers below are never read:
+    every check happens on the host before the first launch)."""
+    lib = nv.lib()
+    P = 4096  # a non-NULL stand-in
+    ok_fwd = [P, P, P, P, 1, 10, P, P, 6, 8, P, P, P, P, P, P, 1 << 20, None]
+    assert lib.gs_render_map(*[None if a == P else a for a in ok_fwd]) != 0
+    for pos in (0, 3, 6, 7, 10, 11):  # points, counts, poses, intrinsics, out_index, out_depth
+        args = list(ok_fwd)
+        args[pos] = None
+        assert lib.gs_render_map(*args) == -1, pos
+    for pos, bad in ((4, 0), (4, -1), (5, 0), (8, 0), (9, -3)):  # B, Nmax, H, W
+        args = list(ok_fwd)
+        args[pos] = bad
+        assert lib.gs_render_map(*args) == -1, pos
+    args = list(ok_fwd)
+    args[15], args[16] = None, 0  # no workspace
+    assert lib.gs_render_map(*args) == -2
+    args = list(ok_fwd)
+    args[16] = lib.gs_render_map_ws_bytes(1, 6, 8) - 1
+    assert lib.gs_render_map(*args) == -2
+    assert b"gs_render_map" in lib.gs_last_error()
+
+    ok_bwd = [P, P, 1, 10, P, 6, 8, P, P, P, P, P, P, P, P, P, P, 1 << 20, None]
+    for pos in (0, 1, 4, 7):  # points, counts, poses, index
+        args = list(ok_bwd)
+        args[pos] = None
+        assert lib.gs_render_map_backward(*args) == -1, pos
+    for pos, bad in ((2, 0), (3, -1), (5, 0), (6, 0)):
+        args = list(ok_bwd)
+        args[pos] = bad
+        assert lib.gs_render_map_backward(*args) == -1, pos
+    args = list(ok_bwd)
+    args[16], args[17] = None, 0
+    assert lib.gs_render_map_backward(*args) == -2
+    assert lib.gs_render_map_ws_bytes(0, 6, 8) == 0 and lib.gs_render_map_backward_ws_bytes(1, 0, 8) == 0
+
+
+def test_render_map_refuses_cpu_tensors():
+    pts = torch.rand(1, 10, 3)
+    counts = torch.full((1,), 10, dtype=torch.int32)
+    T = torch.eye(4).view(1, 4, 4)
+    with pytest.raises(RuntimeError, match="no CPU fallback"):
+        ops.render_map(pts, pts, pts, counts, T, T, 6, 8)
+    with pytest.raises(RuntimeError, match="no CPU fallback"):
+        ops.render_map_raw(pts, None, None, counts, T, T, 6, 8)
+    pc = gs.Pointclouds(pts, colors=pts)
+    with pytest.raises(RuntimeError, match="no CPU fallback"):
+        rgbdimages_from_pointclouds(pc, T.view(1, 1, 4, 4), T.view(1, 1, 4, 4), 6, 8)
+
+
+def test_rgbdimages_from_pointclouds_error_contracts():
+    assert gs.structures.rgbdimages_from_pointclouds is rgbdimages_from_pointclouds
+    pts = torch.rand(2, 10, 3)
+    T = torch.eye(4).view(1, 1, 4, 4).repeat(2, 1, 1, 1)
+    with pytest.raises(TypeError, match="Expected pointclouds to be of type gradslam.Pointclouds"):
+        rgbdimages_from_pointclouds(pts, T, T, 6, 8)
+    with pytest.raises(ValueError, match="Pointclouds must have colors"):
+        rgbdimages_from_pointclouds(gs.Pointclouds(pts, normals=pts), T, T, 6, 8)
+    pc = gs.Pointclouds(pts, colors=pts)
+    with pytest.raises(ValueError, match=r"Expected poses to have shape \(2, 1, 4, 4\)"):
+        rgbdimages_from_pointclouds(pc, T, T[:1], 6, 8)
+    with pytest.raises(ValueError, match=r"Expected intrinsics to have shape \(2, 1, 4, 4\)"):
+        rgbdimages_from_pointclouds(pc, T[:, 0], T, 6, 8)
+    with pytest.raises(ValueError, match=r"Expected poses to have shape \(2, 1, 4, 4\)"):
+        rgbdimages_from_pointclouds(pc, T, T.repeat(1, 2, 1, 1), 6, 8)
+
+
+# ------------------------------------------------------------------ GPU
+@pytest.fixture(scope="module")
+def dev():
+    if not torch.cuda.is_available():
+        pytest.skip("no HIP device")
+    nv.lib()
+    return DEV
+
+
+def _frame(seq, s, dev):
+    """frame s of a make_sequence result as a one-frame RGBDImages on the device"""
+    c, d, K, P = seq
+    return gs.RGBDImages(c[:, s:s + 1].to(dev), d[:, s:s + 1].to(dev), K.to(dev), P[:, s:s + 1].to(dev))
+
+
+def _render_into(pts, nrm, col, counts, poses, K, H, W):
+    """gs_render_map through the C ABI into buffers pre-filled with NaN / 0x7f bytes: what comes back was written by the call"""
+    B, N = pts.shape[:2]
+    dev = pts.device
+    index = torch.full((B, H, W), 0x7F7F7F7F, dtype=torch.int32, device=dev)
+    depth = torch.full((B, H, W), float("nan"), device=dev)
+    img = lambda have: torch.full((B, H, W, 3), float("nan"), device=dev) if have else None
+    op, on, oc = img(True), img(nrm is not None), img(col is not None)
+    ws = torch.full((nv.ws_bytes("gs_render_map_ws_bytes", B, H, W),), 0x7F, dtype=torch.uint8, device=dev)
+    nv.call("gs_render_map", nv.ptr(pts), nv.ptr(nrm), nv.ptr(col), nv.ptr(counts), B, N, nv.ptr(poses), nv.ptr(K), H, W, nv.ptr(index),
+            nv.ptr(depth), nv.ptr(op), nv.ptr(on), nv.ptr(oc), nv.ptr(ws), ws.numel(), nv.stream())
+    return index, depth, op, on, oc
+
+
+def _raster_rank(valid):
+    """(H,W) bool -> (H,W) int32: the running count of valid pixels in raster order at valid pixels, -1 elsewhere"""
+    flat = valid.reshape(-1)
+    rank = torch.cumsum(flat.to(torch.int64), 0) - 1
+    return torch.where(flat, rank, torch.full_like(rank, -1)).to(torch.int32).view(valid.shape)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("H,W", [(48, 64), (30, 40), (120, 160)])
+def test_round_trip_of_a_frames_own_cloud(dev, H, W):
+    """A frame's cloud rendered into its own camera: pixel k of the valid ones shows row k, its colour bit for bit, and its
+    depth -- bit for bit under the identity pose (frame 0), and for the posed frame (frame 2) within
+    16 * 2^-24 * (|p|_1 + |t|_1): two fp32 rigid transforms (camera -> world in the maps, world -> camera here) of three
+    fused multiply-adds and an add each, on magnitudes bounded by |p|_1 + |t|_1."""
+    seq = make_sequence(1, 3, H, W)
+    for s in (0, 2):
+        fr = _frame(seq, s, dev)
+        pc = pointclouds_from_rgbdimages(fr)
+        pose, K = fr.poses[:, 0], fr.intrinsics[:, 0]
+        index, depth, pts, nrm, col = ops.render_map_raw(pc.points_padded, pc.normals_padded, pc.colors_padded, pc._counts_i32(), pose, K,
+                                                         H, W)
+        valid = fr.valid_depth_mask[0, 0, :, :, 0]
+        assert int(valid.sum()) == pc.points_padded.shape[1] > 0
+        assert torch.equal(index[0], _raster_rank(valid))
+        zero3 = torch.zeros(3, device=dev)
+        for img, ref in ((col, fr.rgb_image), (pts, fr.global_vertex_map), (nrm, fr.global_normal_map)):
+            assert torch.equal(img[0][valid], ref[0, 0][valid]) and bool((img[0][~valid] == zero3).all())
+        d_in = fr.depth_image[0, 0, :, :, 0]
+        assert bool((depth[0][~valid] == 0).all())
+        if s == 0:
+            assert torch.equal(pose[0], torch.eye(4, device=dev))
+            assert torch.equal(depth[0], d_in)
+        else:
+            assert not torch.equal(pose[0], torch.eye(4, device=dev))
+            bound = 16 * U * (pts[0].double().abs().sum(-1) + pose[0, :3, 3].double().abs().sum())
+            err = (depth[0].double() - d_in.double()).abs()
+            print("round trip %dx%d: max depth error %.3e, smallest bound %.3e" % (H, W, float(err[valid].max()), float(bound[valid].min())))
+            assert bool((err[valid] <= bound[valid]).all())
+
+
+@pytest.mark.gpu
+def test_occlusion_and_ties_are_exact(dev):
+    """Identity pose.  far = the frame's cloud, near = the same cloud at half the distance (a scaling by 0.5 in camera
+    coordinates is exact in fp32 and keeps u = x / z, so near and far rows share their pixels), dup = the first 100 rows again.
+    [far | near | dup]: every pixel shows its near copy.  [far | dup]: equal depth, the lower row wins every tie."""
+    H, W = 48, 64
+    fr = _frame(make_sequence(1, 3, H, W), 0, dev)
+    pc = pointclouds_from_rgbdimages(fr)
+    far, col = pc.points_padded, pc.colors_padded
+    N = far.shape[1]
+    pose, K = fr.poses[:, 0], fr.intrinsics[:, 0]
+    valid = fr.valid_depth_mask[0, 0, :, :, 0]
+    rank = _raster_rank(valid)
+    d_in = fr.depth_image[0, 0, :, :, 0]
+
+    pts3 = torch.cat([far, far * 0.5, far[:, :100]], 1).contiguous()
+    col3 = torch.cat([col, col + 1000.0, col[:, :100] + 2000.0], 1).contiguous()
+    counts = torch.full((1,), pts3.shape[1], dtype=torch.int32, device=dev)
+    index, depth, pts, _, cimg = ops.render_map_raw(pts3, None, col3, counts, pose, K, H, W)
+    assert torch.equal(index[0], torch.where(valid, rank + N, rank))
+    assert torch.equal(depth[0], d_in * 0.5)
+    assert torch.equal(cimg[0][valid], fr.rgb_image[0, 0][valid] + 1000.0)
+    assert torch.equal(pts[0][valid], fr.global_vertex_map[0, 0][valid] * 0.5)
+
+    pts2 = torch.cat([far, far[:, :100]], 1).contiguous()
+    col2 = torch.cat([col, col[:, :100] + 2000.0], 1).contiguous()
+    counts = torch.full((1,), pts2.shape[1], dtype=torch.int32, device=dev)
+    index, depth, _, nimg, cimg = ops.render_map_raw(pts2, None, col2, counts, pose, K, H, W)
+    assert nimg is None
+    assert torch.equal(index[0], rank) and torch.equal(depth[0], d_in)
+    assert torch.equal(cimg[0][valid], fr.rgb_image[0, 0][valid])
+    # and with the duplicates in FRONT of their originals, they are the lower rows
+    pts2 = torch.cat([far[:, :100], far], 1).contiguous()
+    index, depth, _, _, _ = ops.render_map_raw(pts2, None, None, counts, pose, K, H, W)
+    want = torch.where(valid, torch.where(rank < 100, rank, rank + 100), rank)
+    assert torch.equal(index[0], want) and torch.equal(depth[0], d_in)
+
+
+# ---- the general view (scene 3): clouds of frames 0 and 2 seen from frame 1's camera
+H3, W3 = 48, 64
+
+
+def _z_restated(p, T):
+    """The key's depth exactly as project_point_z forms it, in fp32: dot3_fma(p, R[:,2]) + tinv[2] with
+    dot3_fma(a, b) = fma(a2, b2, fma(a1, b1, a0 * b0)) and tinv[2] = ((-R02) t0 + (-R12) t1) + (-R22) t2, every step that is
+    not an fma rounded by itself (the library is built with -ffp-contract=off)."""
+    from oracle.icp_step import fma32
+
+    p = np.asarray(p, dtype=np.float32)
+    T = np.asarray(T, dtype=np.float32)
+    r0, r1, r2 = T[0, 2], T[1, 2], T[2, 2]
+    tinv2 = np.float32(np.float32(np.float32(np.float32(-r0) * T[0, 3]) + np.float32(np.float32(-r1) * T[1, 3])) + np.float32(np.float32(-r2) * T[2, 3]))
+    first = (p[:, 0] * r0).astype(np.float32)
+    z = np.empty(len(p), dtype=np.float32)
+    for i in range(len(p)):
+        z[i] = np.float32(fma32(p[i, 2], r2, fma32(p[i, 1], r1, first[i])) + tinv2)
+    return z
+
+
+@pytest.fixture(scope="module")
+def scene3(dev):
+    seq = make_sequence(1, 3, H3, W3, seed=7, step_t=0.08, step_r=0.03)
+    a, b = pointclouds_from_rgbdimages(_frame(seq, 0, dev)), pointclouds_from_rgbdimages(_frame(seq, 2, dev))
+    cat = lambda x, y: torch.cat([x, y], 1).contiguous()
+    pts, nrm, col = cat(a.points_padded, b.points_padded), cat(a.normals_padded, b.normals_padded), cat(a.colors_padded, b.colors_padded)
+    counts = torch.full((1,), pts.shape[1], dtype=torch.int32, device=dev)
+    pose, K = seq[3][:, 1].to(dev).contiguous(), seq[2][:, 0].to(dev).contiguous()
+    out = ops.render_map_raw(pts, nrm, col, counts, pose, K, H3, W3)
+    return dict(pts=pts, nrm=nrm, col=col, counts=counts, pose=pose, K=K, out=out)
+
+
+@pytest.mark.gpu
+def test_general_pose_against_an_exact_restatement(dev, scene3):
+    s = scene3
+    index, depth, pimg, nimg, cimg = (x.cpu() for x in s["out"])
+    rows, cnt = ops.project_active_raw(s["pts"], s["counts"], s["pose"], s["K"], H3, W3)
+    rows = rows[: int(cnt.item())].cpu().numpy()
+    n_act = len(rows)
+    pix = rows[:, 2] * W3 + rows[:, 3]
+    per_pix = np.bincount(pix, minlength=H3 * W3)
+    print("scene 3: %d rows, %d active, %d pixels with 2 or more candidates" % (s["pts"].shape[1], n_act, int((per_pix >= 2).sum())))
+    assert n_act > 3000 and int((per_pix >= 2).sum()) > 500  # the scene does exercise the z-buffer
+    # pixels: the winner is one of the rows gs_project_active puts on that pixel, and a pixel is empty iff it has none
+    idx = index[0].reshape(-1).numpy()
+    assert np.array_equal(idx >= 0, per_pix > 0)
+    on_pix = np.full(s["pts"].shape[1], -1, dtype=np.int64)
+    on_pix[rows[:, 1]] = pix
+    hit = np.nonzero(idx >= 0)[0]
+    assert np.array_equal(on_pix[idx[hit]], hit)
+    # depths: the smallest restated z of the pixel's rows, ties to the smallest row; bit for bit, no pixel left out
+    z = _z_restated(s["pts"][0].cpu().numpy()[rows[:, 1]], s["pose"][0].cpu().numpy())
+    assert (z > 0).all()
+    key = (z.view(np.uint32).astype(np.uint64) << np.uint64(32)) | rows[:, 1].astype(np.uint64)
+    best = np.full(H3 * W3, np.iinfo(np.uint64).max, dtype=np.uint64)
+    np.minimum.at(best, pix, key)
+    want_idx = np.where(per_pix > 0, (best & np.uint64(0xFFFFFFFF)).astype(np.int64), -1).astype(np.int32)
+    want_z = np.where(per_pix > 0, (best >> np.uint64(32)).astype(np.uint32), 0).astype(np.uint32).view(np.float32)
+    assert np.array_equal(idx, want_idx)
+    assert np.array_equal(depth[0].reshape(-1).numpy().view(np.uint32), want_z.view(np.uint32))
+    # attributes: gathered from the winner's row, zeros where there is none
+    sel = torch.from_numpy(np.where(idx >= 0, idx, 0).astype(np.int64))
+    mask = torch.from_numpy(idx >= 0).unsqueeze(-1)
+    for img, attr in ((pimg, s["pts"]), (nimg, s["nrm"]), (cimg, s["col"])):
+        assert torch.equal(img[0].reshape(-1, 3), torch.where(mask, attr[0].cpu()[sel], torch.zeros(1, 3)))
+
+
+@pytest.mark.gpu
+def test_counts_padding_and_several_blocks(dev):
+    """B = 2, Nmax = 5000 (five blocks of the map pass), counts (4999, 1337): rows beyond a count are not candidates, though
+    each batch element holds one there that would be the nearest point of a pixel; every output is written everywhere."""
+    H, W, N = 48, 64, 5000
+    counts_l = (4999, 1337)
+    g = torch.Generator().manual_seed(11)
+    K = gs.synthetic.make_intrinsics(H, W)[0].repeat(2, 1, 1)
+    z = 1.0 + 2.0 * torch.rand(2, N, generator=g)
+    u = -4.0 + (W + 8.0) * torch.rand(2, N, generator=g)  # some outside the image
+    v = -4.0 + (H + 8.0) * torch.rand(2, N, generator=g)
+    pts = torch.stack([(u - K[0, 0, 2]) / K[0, 0, 0] * z, (v - K[0, 1, 2]) / K[0, 1, 1] * z, z], -1)
+    pose = torch.eye(4).repeat(2, 1, 1)
+    pose[1, 0, 3] = 0.05
+    planted = []
+    for b, c in enumerate(counts_l):  # the nearest point of the centre pixel, in the first row beyond the count
+        pts[b, c] = torch.tensor([pose[b, 0, 3], 0.0, 0.25])
+        planted.append(c)
+    nrm, col = torch.rand(2, N, 3, generator=g), torch.rand(2, N, 3, generator=g) * 255
+    pts, nrm, col, K, pose = (x.to(dev).contiguous() for x in (pts, nrm, col, K, pose))
+    counts = torch.tensor(counts_l, dtype=torch.int32, device=dev)
+    outs = _render_into(pts, nrm, col, counts, pose, K, H, W)
+    index = outs[0]
+    for x in outs:
+        assert x is not None and bool(torch.isfinite(x.float()).all())
+    assert int(index.min()) == -1 and int(index.max()) < N and int((index >= 0).sum()) > 1000
+    for b, c in enumerate(counts_l):
+        assert int(index[b].max()) < c and not bool((index[b] == planted[b]).any())
+        assert bool((outs[1][b][index[b] < 0] == 0).all()) and bool((outs[1][b][index[b] >= 0] >= 1.0).all())
+        # the same as rendering the map cut at the count, and the planted point does win once it is inside the count
+        alone = ops.render_map_raw(pts[b:b + 1, :c].contiguous(), nrm[b:b + 1, :c].contiguous(), col[b:b + 1, :c].contiguous(),
+                                   counts[b:b + 1], pose[b:b + 1], K[b:b + 1], H, W)
+        for x, y in zip(outs, alone):
+            assert torch.equal(x[b:b + 1], y)
+        more = ops.render_map_raw(pts[b:b + 1], None, None, counts[b:b + 1] + 1, pose[b:b + 1], K[b:b + 1], H, W)
+        assert int((more[0] == planted[b]).sum()) == 1 and float(more[1][more[0] == planted[b]]) == 0.25
+    # a count beyond Nmax reads no row beyond Nmax
+    big = ops.render_map_raw(pts[:1], None, None, torch.full((1,), N + 100, dtype=torch.int32, device=dev), pose[:1], K[:1], H, W)
+    full = ops.render_map_raw(pts[:1], None, None, torch.full((1,), N, dtype=torch.int32, device=dev), pose[:1], K[:1], H, W)
+    assert torch.equal(big[0], full[0]) and torch.equal(big[1], full[1])
+
+
+@pytest.mark.gpu
+def test_borders_and_empties_on_a_hand_made_image(dev):
+    """6 x 8 image, K = I, identity pose: a point (x, y, 1) has u = x, v = y exactly.  The in-frame test is open at both ends
+    (u > -1e-3, u < W - 0.999 as fp32), rounding is half-to-even, z <= 0 and NaN rows are no candidates."""
+    H, W = 6, 8
+    f = np.float32
+    umax, vmax, lo = f(W - 0.999), f(H - 0.999), f(-1e-3)
+    below = lambda x: np.nextafter(f(x), f(-np.inf))
+    above = lambda x: np.nextafter(f(x), f(np.inf))
+    rows = [
+        (umax, 1.0, 1.0, None),                 # 0: exactly on the right border: excluded
+        (below(umax), 1.0, 1.0, (1, 7)),        # 1: just inside it
+        (lo, 2.0, 1.0, None),                   # 2: exactly on the left border: excluded
+        (above(lo), 2.0, 1.0, (2, 0)),          # 3: just inside it
+        (3.0, vmax, 1.0, None),                 # 4: bottom border
+        (3.0, below(vmax), 1.0, (5, 3)),        # 5
+        (4.0, lo, 1.0, None),                   # 6: top border
+        (4.0, above(lo), 1.0, (0, 4)),          # 7
+        (2.5, 3.0, 1.0, (3, 2)),                # 8: half-to-even: 2.5 -> 2
+        (3.5, 3.0, 1.0, (3, 4)),                # 9: 3.5 -> 4
+        (5.0, 4.5, 1.0, (4, 5)),                # 10: 4.5 -> 4
+        (1.0, 1.0, 0.0, None),                  # 11: z == 0
+        (1.0, 1.0, -1.0, None),                 # 12: behind the camera (u = -1, v = -1 as well)
+        (-2.0, -2.0, -2.0, None),               # 13: behind the camera with u = v = 1 in frame
+        (float("nan"), 1.0, 1.0, None),         # 14
+        (1.0, 1.0, float("nan"), None),         # 15
+        (12.0, 8.0, 2.0, (4, 6)),               # 16: u = 6, v = 4 at depth 2
+        (6.0, 4.0, 1.0, (4, 6)),                # 17: the same pixel, nearer: wins
+    ]
+    pts = torch.tensor([[r[0], r[1], r[2]] for r in rows], dtype=torch.float32).view(1, -1, 3).to(dev)
+    col = torch.arange(len(rows), dtype=torch.float32).view(1, -1, 1).repeat(1, 1, 3).to(dev) + 1.0
+    I = torch.eye(4, device=dev).view(1, 4, 4)
+    counts = torch.full((1,), len(rows), dtype=torch.int32, device=dev)
+    index, depth, _, nimg, cimg = _render_into(pts, None, col, counts, I, I, H, W)
+    want = torch.full((H, W), -1, dtype=torch.int32)
+    for n, r in enumerate(rows):
+        if r[3] is not None and n != 16:
+            want[r[3]] = n
+    assert nimg is None
+    assert torch.equal(index[0].cpu(), want)
+    assert torch.equal(depth[0].cpu(), (want >= 0).float())
+    assert torch.equal(cimg[0, :, :, 0].cpu(), (want + 1).float())
+    # the active-point search agrees row by row
+    arows, cnt = ops.project_active_raw(pts, counts, I, I, H, W)
+    arows = arows[: int(cnt.item())].cpu()
+    assert arows[:, 1].tolist() == [n for n, r in enumerate(rows) if r[3] is not None]
+    assert [tuple(x) for x in arows[:, 2:].tolist()] == [r[3] for r in rows if r[3] is not None]
+    # an empty map: all -1 / zeros
+    index, depth, pimg, _, cimg = _render_into(pts, None, col, torch.zeros(1, dtype=torch.int32, device=dev), I, I, H, W)
+    assert bool((index == -1).all()) and bool((depth == 0).all()) and bool((pimg == 0).all()) and bool((cimg == 0).all())
+
+
+@pytest.mark.gpu
+def test_gradients_against_a_float64_restatement(dev, scene3):
+    """Reverse pass on scene 3 with random output adjoints, against float64 torch on the CPU gathering by the kernel's index
+    image and z = (p - t) . R[:,2].  Colour and normal adjoints are copies: bit-equal.  A point adjoint is one fma:
+    2 ulp of the larger term.  A pose entry is a sum of n products: n * 2^-24 * sum |terms| (each term carries two
+    roundings, the sum n - 1 more).  Rows that won nothing: exactly zero.  The same bits from run to run, with and without
+    torch.use_deterministic_algorithms."""
+    s = scene3
+    N = s["pts"].shape[1]
+    g = torch.Generator().manual_seed(5)
+    g_depth = torch.randn(1, H3, W3, generator=g)
+    g_p, g_n, g_c = (torch.randn(1, H3, W3, 3, generator=g) for _ in range(3))
+
+    def run():
+        leaves = [x.clone().requires_grad_(True) for x in (s["pts"], s["nrm"], s["col"], s["pose"])]
+        K = s["K"].clone().requires_grad_(True)
+        index, depth, pimg, nimg, cimg = ops.render_map(leaves[0], leaves[1], leaves[2], s["counts"], leaves[3], K, H3, W3)
+        assert not index.requires_grad and depth.requires_grad
+        for got, ref in zip((index, depth, pimg, nimg, cimg), s["out"]):
+            assert torch.equal(got, ref)
+        loss = (depth * g_depth.to(dev)).sum() + (pimg * g_p.to(dev)).sum() + (nimg * g_n.to(dev)).sum() + (cimg * g_c.to(dev)).sum()
+        loss.backward()
+        assert K.grad is None
+        return [x.grad for x in leaves]
+
+    first = run()
+    again = run()
+    torch.use_deterministic_algorithms(True)
+    try:
+        det = run()
+    finally:
+        torch.use_deterministic_algorithms(False)
+    for a, b, c in zip(first, again, det):
+        assert torch.equal(a, b) and torch.equal(a, c)
+    gp, gn, gc, gT = (x.cpu() for x in first)
+
+    idx = s["out"][0][0].reshape(-1).cpu().long()
+    hit = idx >= 0
+    n = idx[hit]
+    n_terms = int(hit.sum())
+    assert n_terms > 1500 and len(torch.unique(n)) == n_terms
+    T = s["pose"][0].cpu().double()
+    R2, t = T[:3, 2], T[:3, 3]
+    gd = g_depth.reshape(-1)[hit].double()
+    won = torch.zeros(N, dtype=torch.bool)
+    won[n] = True
+    # copies
+    for got, adj in ((gc, g_c), (gn, g_n)):
+        ref = torch.zeros(N, 3)
+        ref[n] = adj.reshape(-1, 3)[hit]
+        assert torch.equal(got[0], ref)
+    # points: g_out_points[pix] + g_depth[pix] R[:,2]
+    t1, t2 = g_p.reshape(-1, 3)[hit].double(), gd[:, None] * R2[None, :]
+    err = (gp[0][n].double() - (t1 + t2)).abs()
+    tol = 2 * 2.0 ** -23 * torch.maximum(t1.abs(), t2.abs())
+    print("g_points: max error / tolerance %.3f" % float((err / tol.clamp_min(1e-300)).max()))
+    assert bool((err <= tol).all())
+    assert bool((gp[0][~won] == 0).all()) and bool((gn[0][~won] == 0).all()) and bool((gc[0][~won] == 0).all())
+    # poses: rotation column 2 and the translation; nothing else
+    p = s["pts"][0].cpu().double()[n]
+    want = torch.zeros(4, 4, dtype=torch.float64)
+    bound = torch.zeros(4, 4, dtype=torch.float64)
+    for j in range(3):
+        terms = gd * (p[:, j] - t[j])
+        want[j, 2], bound[j, 2] = terms.sum(), n_terms * U * terms.abs().sum()
+        terms = -R2[j] * gd
+        want[j, 3], bound[j, 3] = terms.sum(), n_terms * U * terms.abs().sum()
+    err = (gT[0].double() - want).abs()
+    print("g_poses error:\n", err, "\nbound:\n", bound)
+    assert bool((err <= bound).all())
+    assert bool(torch.isfinite(gT).all())
+
+    # through the C ABI into NaN-filled buffers, with only some adjoints given: finite, and the same numbers
+    nan = lambda *shape: torch.full(shape, float("nan"), device=dev)
+    o_p, o_n, o_c, o_T = nan(1, N, 3), nan(1, N, 3), nan(1, N, 3), nan(1, 16)
+    ws = torch.full((nv.ws_bytes("gs_render_map_backward_ws_bytes", 1, H3, W3),), 0xFF, dtype=torch.uint8, device=dev)
+    gd_d, gp_d, gn_d, gc_d = (x.to(dev).contiguous() for x in (g_depth, g_p, g_n, g_c))
+    nv.call("gs_render_map_backward", nv.ptr(s["pts"]), nv.ptr(s["counts"]), 1, N, nv.ptr(s["pose"]), H3, W3, nv.ptr(s["out"][0]),
+            nv.ptr(gd_d), nv.ptr(gp_d), nv.ptr(gn_d), nv.ptr(gc_d), nv.ptr(o_p), nv.ptr(o_n), nv.ptr(o_c), nv.ptr(o_T), nv.ptr(ws), ws.numel(),
+            nv.stream())
+    for got, ref in ((o_p, gp), (o_n, gn), (o_c, gc), (o_T.view(1, 4, 4), gT)):
+        assert bool(torch.isfinite(got).all()) and torch.equal(got.cpu(), ref)
+    o_p, o_T = nan(1, N, 3), nan(1, 16)
+    nv.call("gs_render_map_backward", nv.ptr(s["pts"]), nv.ptr(s["counts"]), 1, N, nv.ptr(s["pose"]), H3, W3, nv.ptr(s["out"][0]),
+            nv.ptr(gd_d), None, None, None, nv.ptr(o_p), None, None, nv.ptr(o_T), nv.ptr(ws), ws.numel(), nv.stream())
+    assert torch.equal(o_T.view(1, 4, 4).cpu(), gT) and bool(torch.isfinite(o_p).all())
+    assert torch.equal(o_p[0].cpu()[n], (g_depth.reshape(-1)[hit][:, None] * T[:3, 2].float()[None, :]))
+
+
+@pytest.mark.gpu
+def test_rgbdimages_from_pointclouds_gives_the_frame_back(dev):
+    """B = 2: rgbdimages_from_pointclouds(pointclouds_from_rgbdimages(frame), K, pose, H, W) has the frame's rgb at its valid
+    pixels (zeros elsewhere) and its valid_depth_mask; the maps are the frame's global maps and the raster ranks."""
+    H, W = 48, 64
+    fr = _frame(make_sequence(2, 2, H, W), 1, dev)
+    pc = pointclouds_from_rgbdimages(fr)
+    assert len(set(pc.num_points_per_pointcloud.tolist())) == 2  # padded rows in one of the two
+    out, maps = rgbdimages_from_pointclouds(pc, fr.intrinsics, fr.poses, H, W, return_maps=True)
+    assert isinstance(out, gs.RGBDImages) and out.shape == (2, 1, H, W) and not out.channels_first
+    only = rgbdimages_from_pointclouds(pc, fr.intrinsics, fr.poses, H, W)
+    assert isinstance(only, gs.RGBDImages) and torch.equal(only.rgb_image, out.rgb_image)
+    valid = fr.valid_depth_mask
+    assert torch.equal(out.valid_depth_mask, valid)
+    assert torch.equal(out.rgb_image, fr.rgb_image * valid)
+    assert torch.equal(out.intrinsics, fr.intrinsics) and torch.equal(out.poses, fr.poses)
+    assert maps["index"].shape == (2, 1, H, W) and maps["index"].dtype == torch.int32
+    for b in range(2):
+        assert torch.equal(maps["index"][b, 0], _raster_rank(valid[b, 0, :, :, 0]))
+    assert torch.equal(maps["global_vertex_map"], fr.global_vertex_map * valid)
+    assert torch.equal(maps["global_normal_map"], fr.global_normal_map * valid)
+    err = (out.depth_image - fr.depth_image).abs()
+    assert float(err.max()) < 16 * U * 8.0  # (|p|_1 + |t|_1 < 8 in this scene: the round-trip bound above)

@@ -126,6 +126,12 @@ SIGNATURES = {
     "gs_render_map_backward_ws_bytes": (c_sz, [c_i, c_i, c_i]),
     "gs_render_map_backward": (c_i, [c_p, c_p, c_i, c_i, c_p, c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_sz,
                                      c_p]),
+    "gs_chamfer_ws_bytes": (c_sz, [c_i, c_i, c_i]),
+    "gs_chamfer": (c_i, [c_p, c_p, c_i, c_p, c_p, c_i, c_i, c_f, c_i, c_p, c_p, c_p, c_p, c_sz, c_p]),
+    "gs_chamfer_backward_ws_bytes": (c_sz, [c_i, c_i, c_i]),
+    "gs_chamfer_backward": (c_i, [c_p, c_p, c_i, c_p, c_p, c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_sz, c_p]),
+    "gs_chamfer_backward_det_ws_bytes": (c_sz, [c_i, c_i, c_i]),
+    "gs_chamfer_backward_det": (c_i, [c_p, c_p, c_i, c_p, c_p, c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_sz, c_p]),
 }
 
 _lib = None

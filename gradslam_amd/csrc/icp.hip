@@ -834,3 +834,7 @@ int gs_icp_point_to_plane_backward_det(const float *src, const int32_t *d_ns, in
 }
 
 }  // extern "C"
+
+// The map metrics' deterministic scatter shares gs_detfold.hpp's kernels with the reverse passes above; it comes last, so the
+// kernels above are emitted as before.
+#include "gs_metrics_det.hpp"

@@ -973,3 +973,87 @@ class _RenderFn(torch.autograd.Function):
 def render_map(points_padded, normals_padded, colors_padded, counts_i32, poses_b44, K_b44, H: int, W: int):
     """Autograd-aware render_map_raw: gradients reach the map's points / normals / colors and the poses."""
     return _RenderFn.apply(points_padded, normals_padded, colors_padded, counts_i32, poses_b44, K_b44, int(H), int(W))
+
+
+# ---------------------------------------------------------------------------------------------- M
+KEY_NONE = -1  # a packed key without a neighbour (all ones), as int64
+
+
+def _chamfer_args(a, b, a_counts, b_counts, op):
+    require_hip(a, b, a_counts, b_counts, op=op)
+    a, b = _f32c(a), _f32c(b)
+    for name, x in (("a", a), ("b", b)):
+        if x.ndim != 3 or x.shape[-1] != 3 or x.shape[1] == 0:
+            raise ValueError("{}: {} should have shape (B, N, 3) with N > 0. Got {}.".format(op, name, tuple(x.shape)))
+    B = a.shape[0]
+    if b.shape[0] != B or B == 0:
+        raise ValueError("{}: a and b should share a batch size B > 0. Got {} and {}.".format(op, a.shape[0], b.shape[0]))
+    for name, c in (("a_counts", a_counts), ("b_counts", b_counts)):
+        if c.dtype != torch.int32 or c.numel() != B:
+            raise ValueError("{}: {} should be {} int32 values. Got {} of {}.".format(op, name, B, c.numel(), c.dtype))
+    return a, b, a_counts.contiguous(), b_counts.contiguous()
+
+
+def chamfer_raw(a, b, a_counts, b_counts, tau2: float = float("inf"), reorder: bool = True, out=None):
+    """Two-sided exact nearest neighbours of padded clouds a (B,Na,3), b (B,Nb,3) with int32 device counts ->
+    (stats (B,2,4) float64, keys_ab (B,Na) int64, keys_ba (B,Nb) int64).  stats[b, d] = [sum d2, sum d, #(d2 < tau2), max d2]
+    of direction d (0: a -> b, 1: b -> a); keys are dist2_bits << 32 | index, KEY_NONE beyond the counts and where the other
+    cloud is empty.  reorder scans each target in cell-grid order (same bits, another cost).  `out`: (keys_ab, keys_ba)
+    buffers to write into (rows beyond the counts are left as they are)."""
+    a, b, ca, cb = _chamfer_args(a, b, a_counts, b_counts, "chamfer")
+    B, Na, Nb = a.shape[0], a.shape[1], b.shape[1]
+    dev = a.device
+    stats = torch.empty((B, 2, 4), dtype=torch.float64, device=dev)
+    if out is None:
+        keys_ab = torch.full((B, Na), KEY_NONE, dtype=torch.int64, device=dev)
+        keys_ba = torch.full((B, Nb), KEY_NONE, dtype=torch.int64, device=dev)
+    else:
+        keys_ab, keys_ba = out
+    ws = workspace(ws_bytes("gs_chamfer_ws_bytes", B, Na, Nb), dev, "chamfer")
+    call("gs_chamfer", ptr(a), ptr(ca), Na, ptr(b), ptr(cb), Nb, B, float(tau2), int(bool(reorder)), ptr(stats), ptr(keys_ab),
+         ptr(keys_ba), ptr(ws), ws.numel(), stream())
+    return stats, keys_ab, keys_ba
+
+
+def chamfer_backward_raw(a, b, a_counts, b_counts, keys_ab, keys_ba, g2, g1, out=None):
+    """Adjoint of chamfer_raw's sum d2 / sum d w.r.t. both clouds: g2, g1 (B,2) -> (g_a (B,Na,3), g_b (B,Nb,3)); the keys are
+    constants.  The deterministic fold under torch.use_deterministic_algorithms, float atomics otherwise.  `out`: (g_a, g_b)
+    buffers to write into (rows beyond the counts are left as they are; fresh buffers hold zeros there)."""
+    a, b, ca, cb = _chamfer_args(a, b, a_counts, b_counts, "chamfer_backward")
+    require_hip(keys_ab, keys_ba, g2, g1, op="chamfer_backward")
+    B, Na, Nb = a.shape[0], a.shape[1], b.shape[1]
+    dev = a.device
+    g2, g1 = _f32c(g2).reshape(B, 2), _f32c(g1).reshape(B, 2)
+    keys_ab, keys_ba = keys_ab.contiguous(), keys_ba.contiguous()
+    g_a, g_b = (torch.zeros_like(a), torch.zeros_like(b)) if out is None else out
+    det = "_det" if deterministic() else ""
+    nbytes = ws_bytes("gs_chamfer_backward{}_ws_bytes".format(det), B, Na, Nb)
+    ws = workspace(nbytes, dev, "chamfer_bwd") if nbytes else None
+    call("gs_chamfer_backward" + det, ptr(a), ptr(ca), Na, ptr(b), ptr(cb), Nb, B, ptr(keys_ab), ptr(keys_ba), ptr(g2), ptr(g1),
+         ptr(g_a), ptr(g_b), ptr(ws), 0 if ws is None else ws.numel(), stream())
+    return g_a, g_b
+
+
+class _ChamferFn(torch.autograd.Function):
+    """(a, b | counts) -> (sum d2 (B,2), sum d (B,2) in fp32; stats, keys_ab, keys_ba: constants).  The nearest neighbours are
+    constants of the graph, as in every chamfer loss: the gradient is that of the distances to them."""
+
+    @staticmethod
+    def forward(ctx, a, b, a_counts, b_counts, tau2, reorder):
+        stats, keys_ab, keys_ba = chamfer_raw(a, b, a_counts, b_counts, tau2, reorder)
+        ctx.save_for_backward(a, b, a_counts, b_counts, keys_ab, keys_ba)
+        ctx.mark_non_differentiable(stats, keys_ab, keys_ba)
+        return stats[..., 0].float(), stats[..., 1].float(), stats, keys_ab, keys_ba
+
+    @staticmethod
+    def backward(ctx, g2, g1, _gs, _gk0, _gk1):
+        a, b, a_counts, b_counts, keys_ab, keys_ba = ctx.saved_tensors
+        zero = lambda g: torch.zeros((a.shape[0], 2), dtype=torch.float32, device=a.device) if g is None else g
+        g_a, g_b = chamfer_backward_raw(a, b, a_counts, b_counts, keys_ab, keys_ba, zero(g2), zero(g1))
+        return (g_a.view_as(a).to(a.dtype) if ctx.needs_input_grad[0] else None,
+                g_b.view_as(b).to(b.dtype) if ctx.needs_input_grad[1] else None, None, None, None, None)
+
+
+def chamfer(a, b, a_counts, b_counts, tau2: float = float("inf"), reorder: bool = True):
+    """Autograd-aware chamfer_raw: gradients of sum d2 / sum d reach both clouds' points."""
+    return _ChamferFn.apply(a, b, a_counts, b_counts, float(tau2), bool(reorder))

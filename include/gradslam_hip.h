@@ -575,6 +575,47 @@ int gs_render_map_backward(const float *points, const int32_t *counts, int B, in
                            const float *g_out_colors, float *g_points, float *g_normals, float *g_colors,
                            float *g_poses, void *ws, size_t ws_bytes, gs_stream_t stream);
 
+/* ---------------------------------------------------------------- M: map metrics (two-sided nearest neighbours)
+ * Fills the reference's empty gradslam.metrics: chamfer distance, accuracy / completeness, precision / recall / F-score and
+ * Hausdorff distance all come from one call.  a (B,Na_max,3), b (B,Nb_max,3): padded fp32 clouds; a_counts / b_counts: (B,)
+ * int32 on the device; rows at or beyond a count are never read.  Direction 0 searches every row of a in b, direction 1 every
+ * row of b in a: the exact search of gs_knn1 (bit-identical to gs_knn1_bruteforce, the lowest index wins ties).
+ *   keys_ab (B,Na_max), keys_ba (B,Nb_max): dist2_bits << 32 | index per row below the count (the others are left untouched);
+ *       all ones (no neighbour) where the other cloud of the batch element is empty.
+ *   stats (B,2,4) float64, per (batch element, direction) over the rows that have a neighbour, each term widened to fp64:
+ *       sum d2 | sum d, d = sqrt(d2) correctly rounded in fp32 | number of rows with d2 < tau2 (strict) | max d2.
+ *       Zeros when either cloud is empty.  No float atomics: the same bits from run to run.
+ *   reorder != 0: each target is scanned in the order of a uniform cell grid over its bounding box (histogram, scan, scatter)
+ *       so that the search prunes whatever the row order; reorder == 0: the rows are scanned as they come, as gs_knn1 does,
+ *       which suits image-ordered clouds.  The results are the same bits either way.
+ * Workspace, every piece rounded up to 256 bytes, with cells(N) = g^3 for the smallest g <= 64 with 16 g^2 >= N:
+ *   per cloud N in (Na_max, Nb_max): 12 B N | 4 B N | 4 B N | 24 B ceil(N/16);  then 64 B | 4 B (cells(Na_max)+1) |
+ *   4 B (cells(Nb_max)+1) | 32 B ceil(Na_max/64) | 32 B ceil(Nb_max/64).
+ * The launch count depends neither on the counts nor on B.  Non-finite coordinates: the result is undefined (nothing is
+ * written out of bounds). */
+size_t gs_chamfer_ws_bytes(int B, int Na_max, int Nb_max);
+int gs_chamfer(const float *a, const int32_t *a_counts, int Na_max, const float *b, const int32_t *b_counts,
+               int Nb_max, int B, float tau2, int reorder, double *stats, uint64_t *keys_ab, uint64_t *keys_ba,
+               void *ws, size_t ws_bytes, gs_stream_t stream);
+
+/* Reverse pass: g2 / g1 (B,2) fp32 are the adjoints of sum d2 / sum d per direction.  For source row i with nearest row j
+ * (from the keys, constants of the graph): delta = s_i - t_j, d = sqrt(d2), c = 2 g2 + (d > 0 ? g1 / d : 0); c delta goes to
+ * the source's row and -c delta is scattered into the target's row j.  g_a (B,Na_max,3), g_b (B,Nb_max,3): each cloud's direct
+ * part from one direction plus its scattered part from the other, written for the rows below the counts (zeros where there
+ * is no neighbour); rows beyond are left untouched.  The scatter uses float atomics (arrival order) and needs no workspace
+ * (ws may be NULL); the _det entry folds it in exact fixed point (four launches per batch element and direction): the same
+ * bits from run to run.  Its workspace: 32 B Na_max | 32 B Nb_max | 4 | 4 max(Na_max, Nb_max) | 96 max(Na_max, Nb_max). */
+size_t gs_chamfer_backward_ws_bytes(int B, int Na_max, int Nb_max);
+int gs_chamfer_backward(const float *a, const int32_t *a_counts, int Na_max, const float *b,
+                        const int32_t *b_counts, int Nb_max, int B, const uint64_t *keys_ab,
+                        const uint64_t *keys_ba, const float *g2, const float *g1, float *g_a, float *g_b,
+                        void *ws, size_t ws_bytes, gs_stream_t stream);
+size_t gs_chamfer_backward_det_ws_bytes(int B, int Na_max, int Nb_max);
+int gs_chamfer_backward_det(const float *a, const int32_t *a_counts, int Na_max, const float *b,
+                            const int32_t *b_counts, int Nb_max, int B, const uint64_t *keys_ab,
+                            const uint64_t *keys_ba, const float *g2, const float *g1, float *g_a, float *g_b,
+                            void *ws, size_t ws_bytes, gs_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

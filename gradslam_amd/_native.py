@@ -132,6 +132,11 @@ SIGNATURES = {
     "gs_chamfer_backward": (c_i, [c_p, c_p, c_i, c_p, c_p, c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_sz, c_p]),
     "gs_chamfer_backward_det_ws_bytes": (c_sz, [c_i, c_i, c_i]),
     "gs_chamfer_backward_det": (c_i, [c_p, c_p, c_i, c_p, c_p, c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_sz, c_p]),
+    "gs_voxel_assign_ws_bytes": (c_sz, [c_i, c_i]),
+    "gs_voxel_assign": (c_i, [c_p, c_p, c_i, c_i, c_f, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_sz, c_p]),
+    "gs_voxel_reduce_ws_bytes": (c_sz, [c_i, c_i, c_i]),
+    "gs_voxel_reduce": (c_i, [c_p, c_p, c_i, c_i, c_i, c_p, c_p, c_p, c_i, c_i, c_p, c_p, c_sz, c_p]),
+    "gs_voxel_reduce_backward": (c_i, [c_p, c_p, c_i, c_i, c_i, c_p, c_p, c_i, c_i, c_p, c_p]),
 }
 
 _lib = None

@@ -105,8 +105,9 @@ __global__ __launch_bounds__(kCT) void compact_count_k(int64_t n, Pred pred, int
 }
 
 // single block; out_total[0] = sum, optionally added to *accum_base first (for segmented use)
-static __global__ __launch_bounds__(1024) void compact_scan_k(const int *__restrict__ block_counts, int nblocks,
-                                                       int *__restrict__ block_offsets, int *__restrict__ out_total) {
+// (the body as a device function: voxel.hip scans one row of block counts per batch element with it)
+__device__ __forceinline__ void compact_scan_body(const int *__restrict__ block_counts, int nblocks,
+                                                  int *__restrict__ block_offsets, int *__restrict__ out_total) {
     __shared__ int sm[1024 / 64 + 1];
     __shared__ int carry;
     if (threadIdx.x == 0) carry = 0;
@@ -122,6 +123,10 @@ static __global__ __launch_bounds__(1024) void compact_scan_k(const int *__restr
         __syncthreads();
     }
     if (threadIdx.x == 0 && out_total) out_total[0] = carry;
+}
+static __global__ __launch_bounds__(1024) void compact_scan_k(const int *__restrict__ block_counts, int nblocks,
+                                                       int *__restrict__ block_offsets, int *__restrict__ out_total) {
+    compact_scan_body(block_counts, nblocks, block_offsets, out_total);
 }
 
 constexpr int kSelfScanBlocks = 1024;

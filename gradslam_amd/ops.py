@@ -5,6 +5,7 @@ Nothing here computes on the CPU.  Tensors must live on a HIP device (`require_h
 Shapes follow the reference: images channels-last (B,L,H,W,C), clouds padded (B,N,C), tables
 (P,4) int64 rows [b,n,h,w].
 """
+import math
 from typing import Optional, Tuple
 
 import torch
@@ -1057,3 +1058,120 @@ class _ChamferFn(torch.autograd.Function):
 def chamfer(a, b, a_counts, b_counts, tau2: float = float("inf"), reorder: bool = True):
     """Autograd-aware chamfer_raw: gradients of sum d2 / sum d reach both clouds' points."""
     return _ChamferFn.apply(a, b, a_counts, b_counts, float(tau2), bool(reorder))
+
+
+# ---------------------------------------------------------------------------------------------- V
+def _voxel_size(voxel_size, op):
+    try:
+        v = float(voxel_size)
+    except (TypeError, ValueError):
+        v = float("nan")
+    v32 = float(torch.tensor(v, dtype=torch.float32)) if math.isfinite(v) else v  # what the kernels divide by
+    if not (math.isfinite(v32) and v32 > 0.0):
+        raise ValueError("{}: voxel_size should be a finite positive number. Got {!r}.".format(op, voxel_size))
+    return v
+
+
+def _voxel_origin(origin, op):
+    vals = [0.0, 0.0, 0.0] if origin is None else [float(t) for t in (origin.tolist() if torch.is_tensor(origin) else origin)]
+    if len(vals) != 3 or not all(math.isfinite(t) for t in vals):
+        raise ValueError("{}: origin should be three finite numbers. Got {!r}.".format(op, origin))
+    return (nv.c_f * 3)(*vals)
+
+
+def _voxel_rows(x, counts, op):
+    require_hip(x, counts, op=op)
+    x = _f32c(x)
+    if x.ndim != 3 or x.shape[0] == 0 or x.shape[1] == 0:
+        raise ValueError("{}: expected a padded (B, N, C) tensor with B > 0 and N > 0. Got {}.".format(op, tuple(x.shape)))
+    if counts.dtype != torch.int32 or counts.numel() != x.shape[0]:
+        raise ValueError("{}: counts should be {} int32 values. Got {} of {}.".format(op, x.shape[0], counts.numel(), counts.dtype))
+    return x, counts.contiguous()
+
+
+def voxel_assign(points_padded, counts_i32, voxel_size, origin=None):
+    """The voxel of every row of a padded batch (B,N,3) with int32 device counts, on the grid of edge `voxel_size` through
+    `origin` (default 0): k = floor((p - origin) / voxel_size) in fp32.  Returns (voxel_of (B,N), n_voxels (B,), n_dropped (B,),
+    voxel_count (B,N), voxel_first (B,N)), all int32: voxels are numbered in order of first appearance; voxel_of is -1 for
+    padding rows and for dropped ones (non-finite, or |k| >= 2^20: counted in n_dropped); voxel_count / voxel_first hold 0 / -1
+    beyond n_voxels.  No gradient: the assignment is a constant of the graph.  Nothing synchronises the host."""
+    v, o = _voxel_size(voxel_size, "voxel_assign"), _voxel_origin(origin, "voxel_assign")
+    with torch.no_grad():
+        pts, counts = _voxel_rows(points_padded.detach(), counts_i32, "voxel_assign")
+        if pts.shape[-1] != 3:
+            raise ValueError("voxel_assign: points should have shape (B, N, 3). Got {}.".format(tuple(pts.shape)))
+        B, N = pts.shape[0], pts.shape[1]
+        dev = pts.device
+        voxel_of, voxel_count, voxel_first = (torch.empty((B, N), dtype=torch.int32, device=dev) for _ in range(3))
+        n_voxels, n_dropped = (torch.empty((B,), dtype=torch.int32, device=dev) for _ in range(2))
+        ws = workspace(ws_bytes("gs_voxel_assign_ws_bytes", B, N), dev, "voxel_assign")
+        call("gs_voxel_assign", ptr(pts), ptr(counts), N, B, v, o, ptr(voxel_of), ptr(n_voxels), ptr(n_dropped), ptr(voxel_count),
+             ptr(voxel_first), ptr(ws), ws.numel(), stream())
+    return voxel_of, n_voxels, n_dropped, voxel_count, voxel_first
+
+
+VOXEL_SUM, VOXEL_MEAN = 0, 1  # gs_voxel_reduce's modes
+VOXEL_NO_PREAGG = 2  # measurement switch of tools/voxel_timing.py (same bits, no pre-aggregation); not part of the stable interface
+
+
+def _voxel_index_args(x, voxel_of, voxel_count, M_max, op):
+    B, N = x.shape[0], x.shape[1]
+    require_hip(voxel_of, voxel_count, op=op)
+    for name, t in (("voxel_of", voxel_of), ("voxel_count", voxel_count)):
+        if t.dtype != torch.int32 or tuple(t.shape) != (B, N):
+            raise ValueError("{}: {} should be int32 of shape {}. Got {} of shape {}.".format(op, name, (B, N), t.dtype, tuple(t.shape)))
+    if not 1 <= int(M_max) <= N:
+        raise ValueError("{}: M_max should lie in 1 .. N = {}. Got {}.".format(op, N, M_max))
+    if not 1 <= x.shape[2] <= 64:
+        raise ValueError("{}: between 1 and 64 components per row are supported. Got {}.".format(op, x.shape[2]))
+    return voxel_of.contiguous(), voxel_count.contiguous()
+
+
+def voxel_reduce_raw(x, counts_i32, voxel_of, n_voxels, voxel_count, M_max, mode=VOXEL_MEAN):
+    """x (B,N,C) -> (B,M_max,C): per voxel the exact sum of its members rounded once to fp32 (mode 0) or that value divided by
+    the member count (mode 1); rows beyond n_voxels are zero.  Same bits whatever the order of the rows."""
+    x, counts = _voxel_rows(x, counts_i32, "voxel_reduce")
+    voxel_of, voxel_count = _voxel_index_args(x, voxel_of, voxel_count, M_max, "voxel_reduce")
+    require_hip(n_voxels, op="voxel_reduce")
+    B, N, C = x.shape
+    if n_voxels.dtype != torch.int32 or n_voxels.numel() != B:
+        raise ValueError("voxel_reduce: n_voxels should be {} int32 values. Got {} of {}.".format(B, n_voxels.numel(), n_voxels.dtype))
+    out = torch.empty((B, int(M_max), C), dtype=torch.float32, device=x.device)
+    ws = workspace(ws_bytes("gs_voxel_reduce_ws_bytes", B, int(M_max), C), x.device, "voxel_reduce")
+    call("gs_voxel_reduce", ptr(x), ptr(counts), N, C, B, ptr(voxel_of), ptr(n_voxels.contiguous()), ptr(voxel_count), int(M_max),
+         int(mode), ptr(out), ptr(ws), ws.numel(), stream())
+    return out
+
+
+def voxel_reduce_backward_raw(g_out, counts_i32, voxel_of, voxel_count, N, mode=VOXEL_MEAN):
+    """Adjoint of voxel_reduce_raw: g_out (B,M_max,C) -> g_x (B,N,C), a gather (zero rows for padding and dropped points)."""
+    g_out, counts = _voxel_rows(g_out, counts_i32, "voxel_reduce_backward")
+    B, M_max, C = g_out.shape
+    g_x = torch.empty((B, int(N), C), dtype=torch.float32, device=g_out.device)
+    voxel_of, voxel_count = _voxel_index_args(g_x, voxel_of, voxel_count, M_max, "voxel_reduce_backward")
+    call("gs_voxel_reduce_backward", ptr(g_out), ptr(counts), int(N), C, B, ptr(voxel_of), ptr(voxel_count), M_max, int(mode),
+         ptr(g_x), stream())
+    return g_x
+
+
+class _VoxelReduceFn(torch.autograd.Function):
+    """(x | counts, voxel_of, n_voxels, voxel_count: constants) -> per-voxel sum or mean.  The voxel of a point is a constant of
+    the graph, like a nearest-neighbour index: the gradient is that of the sum / mean over fixed members."""
+
+    @staticmethod
+    def forward(ctx, x, counts, voxel_of, n_voxels, voxel_count, M_max, mode):
+        out = voxel_reduce_raw(x, counts, voxel_of, n_voxels, voxel_count, M_max, mode)
+        ctx.save_for_backward(counts, voxel_of, voxel_count)
+        ctx.shape, ctx.dtype, ctx.mode = tuple(x.shape), x.dtype, mode
+        return out
+
+    @staticmethod
+    def backward(ctx, g_out):
+        counts, voxel_of, voxel_count = ctx.saved_tensors
+        g_x = voxel_reduce_backward_raw(g_out, counts, voxel_of, voxel_count, ctx.shape[1], ctx.mode & VOXEL_MEAN)
+        return g_x.view(ctx.shape).to(ctx.dtype), None, None, None, None, None, None
+
+
+def voxel_reduce(x, counts_i32, voxel_of, n_voxels, voxel_count, M_max, mean=True):
+    """Autograd-aware voxel_reduce_raw over the assignment of `voxel_assign`: (B,N,C) -> (B,M_max,C), gradients reach x."""
+    return _VoxelReduceFn.apply(x, counts_i32, voxel_of, n_voxels, voxel_count, int(M_max), VOXEL_MEAN if mean else VOXEL_SUM)

@@ -13,6 +13,7 @@ Differences that are deliberate and invisible through the API:
   per-batch `.item()` loop (reference :1419-1427);
 * the four attribute families share one implementation instead of four copies.
 """
+import warnings
 from typing import List, Optional, Union
 
 import torch
@@ -500,6 +501,49 @@ class Pointclouds(object):
         return self
 
     # ------------------------------------------------------------------ export (out of scope: viewers)
+    def voxel_downsample(self, voxel_size, origin=None, feature_reduction: str = "mean", return_index: bool = False):
+        r"""Voxel-grid downsample: a NEW Pointclouds with one point per occupied voxel of edge `voxel_size` (grid through
+        `origin`, default 0), holding the mean of the voxel's points, normals (not re-normalised) and colours, and the mean or
+        the sum (`feature_reduction`: "mean" | "sum") of its features -- a PointFusion map's features are confidence counts,
+        which accumulate.  Voxels come in order of first appearance.  Every sum is exact and rounded once, so the result
+        does not depend on the order of the points and is the same bits from run to run; it is differentiable w.r.t. every
+        attribute carried (the voxel of a point is a constant of the graph).  Points with a non-finite coordinate or more than
+        2^20 voxels from the origin are dropped with a RuntimeWarning.  One host synchronisation (the new sizes).
+
+        With `return_index=True` also returns (voxel_of (B,N), voxel_count (B,M), voxel_first (B,M)) as int64, padded:
+        the voxel of every input row (-1: padding or dropped), the members of every voxel (0 beyond a cloud's voxels) and
+        its lowest member row (-1 beyond)."""
+        from .. import ops
+
+        voxel_size = ops._voxel_size(voxel_size, "voxel_downsample")
+        if feature_reduction not in ("mean", "sum"):
+            raise ValueError('feature_reduction should be "mean" or "sum". Got {!r}.'.format(feature_reduction))
+        if not self.has_points or self._B == 0:
+            raise ValueError("cannot voxel_downsample an empty pointclouds object")
+        points = self.points_padded
+        counts = self._counts_i32()
+        voxel_of, n_voxels, n_dropped, voxel_count, voxel_first = ops.voxel_assign(points, counts, voxel_size, origin)
+        host = torch.cat([n_voxels, n_dropped]).tolist()  # the one host synchronisation
+        n_vox, dropped = host[: self._B], sum(host[self._B:])
+        if min(n_vox) < 0:
+            raise RuntimeError("voxel_downsample: the voxel hash table overflowed (internal capacity bound violated)")
+        if dropped > 0:
+            warnings.warn("voxel_downsample: {} points were dropped (non-finite coordinates, or more than 2^20 voxels from "
+                          "the origin)".format(dropped), RuntimeWarning)
+        M = max(n_vox)
+        if M > 0:
+            red = lambda x, mean=True: None if x is None else ops.voxel_reduce(x, counts, voxel_of, n_voxels, voxel_count, M, mean)
+        else:  # no cloud keeps a point (empty clouds, or every row dropped): padded attributes without rows, like the counts
+            red = lambda x, mean=True: None if x is None else torch.zeros((self._B, 0, x.shape[-1]), dtype=torch.float32, device=x.device)
+        out = Pointclouds(device=self.device)
+        out._B = self._B
+        out._adopt_padded(red(points), red(self.normals_padded), red(self.colors_padded),
+                          red(self.features_padded, feature_reduction == "mean"))
+        out._set_counts(n_vox)
+        if return_index:
+            return out, (voxel_of.long(), voxel_count[:, :M].long(), voxel_first[:, :M].long())
+        return out
+
     def open3d(self, index: int, include_colors: bool = True, max_num_points: Optional[int] = None,
                include_normals: bool = False):
         """`index`-th cloud as an `open3d.geometry.PointCloud` (reference :1239-1294): a device-to-host copy;

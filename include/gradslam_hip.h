@@ -616,6 +616,58 @@ int gs_chamfer_backward_det(const float *a, const int32_t *a_counts, int Na_max,
                             const uint64_t *keys_ba, const float *g2, const float *g1, float *g_a, float *g_b,
                             void *ws, size_t ws_bytes, gs_stream_t stream);
 
+/* ---------------------------------------------------------------- V: voxel downsampling (one row per occupied voxel)
+ * The reference has no counterpart.  points (B,N_max,3): a padded fp32 batch; counts (B,) int32 on the device; voxel_size > 0
+ * and origin (three floats in HOST memory, read during the call) define the grid.
+ * Assignment, for batch element b and rows i < counts[b]:
+ *   k = floorf((p - origin) / voxel_size) per axis: one fp32 subtraction, one IEEE fp32 division (numpy's
+ *       np.floor((p - o) / v) in float32, bit for bit; floor, not truncation).  A row is valid if its three coordinates are
+ *       finite and |k| < 2^20 on every axis; its key is the three biased 21-bit coordinates packed into 63 bits.
+ *   Voxels are numbered 0 .. M_b - 1 in ascending order of their lowest member row (order of first appearance): a property
+ *       of the input alone, not of scheduling.
+ *   voxel_of (B,N_max): the voxel of every row; -1 for invalid rows (counted in n_dropped[b]) and for rows >= counts[b] (not
+ *       counted).  n_voxels (B,) = M_b.  voxel_count (B,N_max): members per voxel, 0 beyond M_b.  voxel_first (B,N_max): lowest
+ *       member row per voxel, -1 beyond M_b.  Every element of all five outputs is written.
+ *   A hash grid per batch element: S = the smallest power of two >= 2 N_max slots, open addressing with linear probing, 64-bit
+ *       compare-and-swap on the key, atomic minimum on the slot's lowest-row word; leaders (lowest member rows) are numbered by
+ *       the stable compaction.  N_max <= 2^29, B <= 65535.  Every probe loop is bounded by S; should one ever run through the
+ *       whole table (impossible at load <= 0.5 short of a bug) the error word is set and n_voxels is returned as -1 for every b.
+ *   Five launches (six above 2^20 rows), whatever the counts and B.  Nothing synchronises the host.
+ * Workspace, every piece rounded up to 256 bytes:  4 B (error word) | 8 B B S (keys) | 4 B B S (lowest rows) | 4 B B N_max
+ *   (the slot of every row) | 4 B B ceil(N_max/1024) | 4 B B ceil(N_max/1024) (the compaction's block counts and offsets). */
+size_t gs_voxel_assign_ws_bytes(int B, int N_max);
+int gs_voxel_assign(const float *points, const int32_t *counts, int N_max, int B, float voxel_size,
+                    const float *origin, int32_t *voxel_of, int32_t *n_voxels, int32_t *n_dropped,
+                    int32_t *voxel_count, int32_t *voxel_first, void *ws, size_t ws_bytes, gs_stream_t stream);
+
+/* Reduction of a per-point attribute x (B,N_max,C) fp32, 1 <= C <= 64, over the voxels of gs_voxel_assign (voxel_of, n_voxels,
+ * voxel_count as it wrote them) into out (B,M_max,C), M_max >= max_b n_voxels[b] chosen by the caller (M_max <= N_max; voxels at
+ * or beyond M_max are left out).  mode: GS_VOXEL_SUM or GS_VOXEL_MEAN.  (GS_VOXEL_NO_PREAGG may be or-ed in by the timing tool:
+ * the same bits without the kernel's pre-aggregation.  It is a measurement switch, NOT part of the stable contract, and may go.)
+ *   sum:  out[b,m,c] = the EXACT sum of the members' values rounded once to fp32 (nearest, ties to even);
+ *   mean: that fp32 value divided (IEEE fp32) by float(voxel_count[b,m]).
+ *   The sum is carried in 128-bit fixed point (integer atomics), so the result does not depend on row order, arrival order or
+ *   the kernel's pre-aggregation of neighbouring lanes.  Exactness domain: with lg = ceil(log2 N_max), bits more than 102 - lg
+ *   binary places below the largest finite |x| among the call's members are truncated toward zero.  Non-finite members give what
+ *   a float sum gives: NaN for a NaN or both infinities, else the infinity.  Rows m >= n_voxels[b] of out are written as zero:
+ *   every element of out is written.  One memset and three launches.
+ * Workspace, every piece rounded up to 256 bytes:  16 B B M_max C ((lo, hi) words of the sums) | 4 B B M_max ceil(C/10)
+ *   (non-finite flags, 3 bits per component) | 4 B (float bits of the maximum). */
+#define GS_VOXEL_SUM 0
+#define GS_VOXEL_MEAN 1
+#define GS_VOXEL_NO_PREAGG 2
+size_t gs_voxel_reduce_ws_bytes(int B, int M_max, int C);
+int gs_voxel_reduce(const float *x, const int32_t *counts, int N_max, int C, int B, const int32_t *voxel_of,
+                    const int32_t *n_voxels, const int32_t *voxel_count, int M_max, int mode, float *out, void *ws,
+                    size_t ws_bytes, gs_stream_t stream);
+
+/* Reverse pass of the reduction: g_x[b,i,c] = g_out[b,m,c] (sum) or g_out[b,m,c] / float(voxel_count[b,m]) (mean) with
+ * m = voxel_of[b,i]; zero where voxel_of < 0 and for rows >= counts[b]: every element of g_x (B,N_max,C) is written.  One gather
+ * launch, no atomics, no workspace: the same bits from run to run.  The assignment is a constant of the graph. */
+int gs_voxel_reduce_backward(const float *g_out, const int32_t *counts, int N_max, int C, int B,
+                             const int32_t *voxel_of, const int32_t *voxel_count, int M_max, int mode, float *g_x,
+                             gs_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,621 @@
+"""Voxel downsampling (gs_voxel_assign / gs_voxel_reduce / Pointclouds.voxel_downsample): exact, order-independent, differentiable.
+
+The references are written here in numpy and Python integers, not taken from the code under test:
+* assignment: keys from np.floor((p - o) / v) in float32, np.unique on the int64 keys, voxels ranked by their first row;
+* sums: every fp32 value taken apart into mantissa * 2^e as a Python integer (unit 2^-149, the smallest fp32 quantum), added
+  exactly and rounded ONCE to 24 bits with ties to even; the mean is that fp32 value divided in fp32 by the member count.
+The kernels carry at least 102 - ceil(log2 N) >= 87 binary places below the largest member, the test data spread over at most
+2^40 plus 24 mantissa bits: nothing is truncated, so the comparison is bitwise (torch.equal on the int32 view).
+"""
+import ctypes
+import math
+import warnings
+from functools import lru_cache
+
+import numpy as np
+import pytest
+import torch
+
+import gradslam_amd as gs
+from gradslam_amd import _native as nv
+from gradslam_amd import ops
+from gradslam_amd.structures.utils import pointclouds_from_rgbdimages
+from gradslam_amd.synthetic import make_sequence
+
+DEV = "cuda:0"
+U = 2.0 ** -24  # unit roundoff of fp32
+SENT32 = 0x5A5A5A5A
+NEW_SYMBOLS = {"gs_voxel_assign_ws_bytes": 2, "gs_voxel_assign": 14, "gs_voxel_reduce_ws_bytes": 3, "gs_voxel_reduce": 14,
+               "gs_voxel_reduce_backward": 11}
+
+
+def _align256(n):
+    return -(-n // 256) * 256
+
+
+# ------------------------------------------------------------------ the references
+def ref_assign(pts, counts, v, origin=(0.0, 0.0, 0.0)):
+    """pts (B, N, 3) float32, counts (B,) -> (voxel_of, n_voxels, n_dropped, voxel_count, voxel_first, keys) as numpy int arrays;
+    keys (B, N) int64 holds the packed key of every valid row (-1 elsewhere)."""
+    B, N = pts.shape[:2]
+    o = np.asarray(origin, dtype=np.float32)
+    voxel_of = np.full((B, N), -1, np.int32)
+    voxel_count = np.zeros((B, N), np.int32)
+    voxel_first = np.full((B, N), -1, np.int32)
+    keys = np.full((B, N), -1, np.int64)
+    n_voxels, n_dropped = np.zeros(B, np.int32), np.zeros(B, np.int32)
+    for b in range(B):
+        n = int(counts[b])
+        p = pts[b, :n]
+        with np.errstate(all="ignore"):
+            q = np.floor((p - o) / np.float32(v))
+            assert q.dtype == np.float32
+            valid = np.isfinite(p).all(1) & (np.abs(q) < 2.0 ** 20).all(1)
+        rows = np.nonzero(valid)[0]
+        n_dropped[b] = n - len(rows)
+        if len(rows) == 0:
+            continue
+        k = q[rows].astype(np.int64) + (1 << 20)
+        key = k[:, 0] | (k[:, 1] << 21) | (k[:, 2] << 42)
+        keys[b, rows] = key
+        _, first, inv = np.unique(key, return_index=True, return_inverse=True)
+        order = np.argsort(first, kind="stable")  # voxels in ascending order of their lowest member row
+        rank = np.empty(len(first), np.int64)
+        rank[order] = np.arange(len(first))
+        m = rank[inv.reshape(-1)]
+        voxel_of[b, rows] = m
+        M = len(first)
+        n_voxels[b] = M
+        voxel_count[b, :M] = np.bincount(m, minlength=M)
+        voxel_first[b, :M] = rows[first[order]]
+    return voxel_of, n_voxels, n_dropped, voxel_count, voxel_first, keys
+
+
+def f32_to_int(bits):
+    """fp32 bit patterns (finite) -> Python integers in units of 2^-149 (exact)."""
+    bits = np.asarray(bits, dtype=np.uint32).astype(np.int64)
+    e, m = (bits >> 23) & 0xFF, bits & 0x7FFFFF
+    mant = np.where(e > 0, m | 0x800000, m)
+    shift = np.maximum(e, 1) - 1
+    sign = np.where(bits >> 31, -1, 1)
+    return [int(s) * (int(a) << int(k)) for s, a, k in zip(sign.ravel(), mant.ravel(), shift.ravel())]
+
+
+def int_to_f32(t, unit=-149):
+    """A Python integer in units of 2^unit (default 2^-149) -> the nearest fp32 (ties to even), rounded once.  (Other units: for
+    results that are normal numbers only.)"""
+    if t == 0:
+        return np.float32(0.0)
+    a = abs(t)
+    nb = a.bit_length()
+    mant, sh = a, 0
+    if nb > 24:
+        sh = nb - 24
+        mant = a >> sh
+        rem, half = a & ((1 << sh) - 1), 1 << (sh - 1)
+        if rem > half or (rem == half and (mant & 1)):
+            mant += 1
+    val = math.ldexp(mant, sh + unit) if sh + unit + mant.bit_length() <= 128 else math.inf  # (exact in float64 below 2^128)
+    with np.errstate(over="ignore"):
+        return np.float32(-val if t < 0 else val)
+
+
+def exact_sum_f32(values):
+    """The exact sum of fp32 values rounded once to fp32; non-finite members give what a float sum gives."""
+    values = np.asarray(values, dtype=np.float32).ravel()
+    fin = np.isfinite(values)
+    if not fin.all():
+        bad = values[~fin]
+        if np.isnan(bad).any() or (np.isposinf(bad).any() and np.isneginf(bad).any()):
+            return np.float32(np.nan)
+        return np.float32(np.inf if np.isposinf(bad).any() else -np.inf)
+    return int_to_f32(sum(f32_to_int(values.view(np.uint32))))
+
+
+def ref_reduce(x, voxel_of, n_voxels, M_max):
+    """x (B, N, C) float32 -> exact per-voxel sums (B, M_max, C) float32, zeros beyond n_voxels."""
+    B, N, C = x.shape
+    out = np.zeros((B, M_max, C), np.float32)
+    for b in range(B):
+        rows = np.nonzero(voxel_of[b] >= 0)[0]
+        vals = x[b, rows]
+        fin = np.isfinite(vals)
+        ints = f32_to_int(np.where(fin, vals, np.float32(0)).view(np.uint32))
+        acc = [[0] * C for _ in range(int(n_voxels[b]))]
+        ms = voxel_of[b, rows]
+        for r in range(len(rows)):
+            a = acc[ms[r]]
+            for c in range(C):
+                a[c] += ints[r * C + c]
+        for m in range(int(n_voxels[b])):
+            for c in range(C):
+                out[b, m, c] = int_to_f32(acc[m][c])
+        for r, c in zip(*np.nonzero(~fin)):  # voxels with a non-finite member: the float rule
+            m = ms[r]
+            out[b, m, c] = exact_sum_f32(vals[ms == m, c])
+    return out
+
+
+def ref_mean(sums, voxel_count, M_max):
+    with np.errstate(all="ignore"):
+        cnt = voxel_count[:, :M_max].astype(np.float32)[..., None]
+        return np.where(cnt > 0, sums / np.where(cnt > 0, cnt, np.float32(1)), np.float32(0)).astype(np.float32)
+
+
+def make_points(n, seed):
+    rng = np.random.RandomState(seed)
+    p = (1.5 * rng.randn(n, 3)).astype(np.float32)
+    p[::7] = np.round(p[::7] / 0.25) * 0.25  # exactly on voxel faces of the 0.25 grid
+    return p
+
+
+# ------------------------------------------------------------------ CPU: ABI, layouts, error contracts, the rounding helper
+def test_voxel_symbols_load():
+    lib = nv.lib()
+    for name, nargs in NEW_SYMBOLS.items():
+        assert hasattr(lib, name) and name in nv.SIGNATURES, name
+        assert len(nv.SIGNATURES[name][1]) == nargs, name
+    assert lib.gs_abi_version() == 3
+    assert hasattr(ops, "voxel_assign") and hasattr(ops, "_VoxelReduceFn") and hasattr(gs.Pointclouds, "voxel_downsample")
+
+
+@pytest.mark.parametrize("B,N", [(1, 1), (1, 130), (3, 4099), (1, 307200)])
+def test_voxel_workspace_sizes_follow_the_layout(B, N):
+    """The layouts documented in include/gradslam_hip.h, piece by piece, each rounded up to 256 bytes."""
+    lib = nv.lib()
+    S = 1
+    while S < 2 * N:
+        S *= 2
+    nb = -(-N // 1024)
+    want = _align256(4) + _align256(8 * B * S) + _align256(4 * B * S) + _align256(4 * B * N) + 2 * _align256(4 * B * nb)
+    assert lib.gs_voxel_assign_ws_bytes(B, N) == want
+    for C in (1, 3, 10, 11, 64):
+        M = max(1, N // 3)
+        want = _align256(16 * B * M * C) + _align256(4 * B * M * -(-C // 10)) + _align256(4)
+        assert lib.gs_voxel_reduce_ws_bytes(B, M, C) == want
+    for bad in (0, -1):
+        assert lib.gs_voxel_assign_ws_bytes(bad, N) == 0 and lib.gs_voxel_reduce_ws_bytes(bad, N, 3) == 0
+    assert lib.gs_voxel_assign_ws_bytes(1, (1 << 29) + 1) == 0 and lib.gs_voxel_assign_ws_bytes(1, 0) == 0
+    assert lib.gs_voxel_reduce_ws_bytes(1, N, 0) == 0 and lib.gs_voxel_reduce_ws_bytes(1, N, 65) == 0
+
+
+def test_voxel_refuses_bad_arguments_before_any_device_work():
+    """NULL pointers, non-positive sizes and a bad voxel_size return -1, a missing or short workspace -2 (the device pointers
+    below are never read: every check happens on the host before the first launch; the origin is host memory)."""
+    lib = nv.lib()
+    P = 4096  # a non-NULL stand-in
+    org = (ctypes.c_float * 3)(0.0, 0.0, 0.0)
+    ok = [P, P, 10, 1, 0.5, org, P, P, P, P, P, P, 1 << 20, None]
+    for pos in (0, 1, 5, 6, 7, 8, 9, 10):
+        args = list(ok)
+        args[pos] = None
+        assert lib.gs_voxel_assign(*args) == -1, pos
+    for pos, bad in ((2, 0), (2, -4), (2, (1 << 29) + 1), (3, 0), (3, -1), (4, 0.0), (4, -1.0), (4, float("inf")), (4, float("nan"))):
+        args = list(ok)
+        args[pos] = bad
+        assert lib.gs_voxel_assign(*args) == -1, (pos, bad)
+    args = list(ok)
+    args[11], args[12] = None, 0
+    assert lib.gs_voxel_assign(*args) == -2
+    args = list(ok)
+    args[12] = lib.gs_voxel_assign_ws_bytes(1, 10) - 1
+    assert lib.gs_voxel_assign(*args) == -2
+    assert b"gs_voxel_assign" in lib.gs_last_error()
+
+    ok = [P, P, 10, 3, 1, P, P, P, 4, 1, P, P, 1 << 20, None]
+    for pos in (0, 1, 5, 6, 7, 10):
+        args = list(ok)
+        args[pos] = None
+        assert lib.gs_voxel_reduce(*args) == -1, pos
+    for pos, bad in ((2, 0), (3, 0), (3, 65), (4, 0), (8, 0), (8, 11), (9, -1), (9, 4)):
+        args = list(ok)
+        args[pos] = bad
+        assert lib.gs_voxel_reduce(*args) == -1, (pos, bad)
+    args = list(ok)
+    args[11], args[12] = None, 0
+    assert lib.gs_voxel_reduce(*args) == -2
+    args = list(ok)
+    args[12] = lib.gs_voxel_reduce_ws_bytes(1, 4, 3) - 1
+    assert lib.gs_voxel_reduce(*args) == -2
+    assert b"gs_voxel_reduce" in lib.gs_last_error()
+
+    ok = [P, P, 10, 3, 1, P, P, 4, 1, P, None]
+    for pos in (0, 1, 5, 6, 9):
+        args = list(ok)
+        args[pos] = None
+        assert lib.gs_voxel_reduce_backward(*args) == -1, pos
+    for pos, bad in ((2, 0), (3, 0), (3, 65), (4, -1), (7, 0), (8, 7)):
+        args = list(ok)
+        args[pos] = bad
+        assert lib.gs_voxel_reduce_backward(*args) == -1, (pos, bad)
+    assert b"gs_voxel_reduce_backward" in lib.gs_last_error()
+
+
+def test_voxel_python_error_contracts():
+    pts = torch.rand(1, 10, 3)
+    counts = torch.full((1,), 10, dtype=torch.int32)
+    idx = torch.zeros(1, 10, dtype=torch.int32)
+    with pytest.raises(RuntimeError, match="no CPU fallback"):
+        ops.voxel_assign(pts, counts, 0.1)
+    with pytest.raises(RuntimeError, match="no CPU fallback"):
+        ops.voxel_reduce(pts, counts, idx, counts, idx, 4)
+    pc = gs.Pointclouds(points=pts)
+    with pytest.raises(RuntimeError, match="no CPU fallback"):
+        pc.voxel_downsample(0.1)
+    for bad in (0.0, -1.0, float("inf"), float("nan"), 1e-60, "x", None):
+        with pytest.raises(ValueError, match="voxel_size"):
+            pc.voxel_downsample(bad)
+        with pytest.raises(ValueError, match="voxel_size"):
+            ops.voxel_assign(pts, counts, bad)
+    with pytest.raises(ValueError, match="feature_reduction"):
+        pc.voxel_downsample(0.1, feature_reduction="max")
+    with pytest.raises(ValueError, match="empty"):
+        gs.Pointclouds().voxel_downsample(0.1)
+    with pytest.raises(ValueError, match="origin"):
+        ops.voxel_assign(pts, counts, 0.1, origin=(0.0, float("nan"), 0.0))
+
+
+def test_reference_rounding_helper_on_hand_cases():
+    """The test's own exact sum: a tie to even at 2^24, a cancellation to zero, a subnormal."""
+    f = lambda *xs: exact_sum_f32(np.array(xs, np.float32))
+    assert f(16777216.0, 1.0) == np.float32(16777216.0)                    # 2^24 + 1: tie, the even neighbour is below
+    assert f(16777216.0, 1.0, 2.0) == np.float32(16777220.0)               # 2^24 + 3: tie, the even neighbour is above
+    assert f(16777216.0, 1.0, 2.0 ** -20) == np.float32(16777218.0)        # just above the tie
+    assert f(1e10, 1.0, -1e10) == np.float32(1.0)                          # a float sum in this order gives 0
+    assert f(3.25, -3.25) == np.float32(0.0) and f() == np.float32(0.0)
+    tiny = np.array([1, 1, 3], np.uint32).view(np.float32)                 # subnormals: 5 * 2^-149, exact
+    assert exact_sum_f32(tiny).view(np.uint32) == 5
+    assert f(2.0 ** -126, -(2.0 ** -149)).view(np.uint32) == 0x007FFFFF    # the largest subnormal
+    assert np.isnan(f(1.0, np.nan)) and np.isnan(f(np.inf, -np.inf)) and f(1.0, -np.inf) == -np.inf
+    assert int_to_f32(f32_to_int(np.array([0x3F800001], np.uint32))[0]).view(np.uint32) == 0x3F800001
+    # and not fsum-then-cast, which rounds twice: 2^24 + 1 + 2^-30 is above the tie in exact arithmetic
+    assert f(16777216.0, 1.0, 2.0 ** -30) == np.float32(16777218.0)
+
+
+# ------------------------------------------------------------------ GPU helpers
+def assign_raw(pts, counts, v, origin=(0.0, 0.0, 0.0)):
+    """gs_voxel_assign into sentinel-filled buffers: (voxel_of, n_voxels, n_dropped, voxel_count, voxel_first) on the device."""
+    pts = torch.as_tensor(pts, dtype=torch.float32).to(DEV).contiguous()
+    counts = torch.as_tensor(np.asarray(counts), dtype=torch.int32).to(DEV)
+    B, N = pts.shape[:2]
+    bufs = [torch.full(s, SENT32, dtype=torch.int32, device=DEV) for s in ((B, N), (B,), (B,), (B, N), (B, N))]
+    ws = torch.full((nv.ws_bytes("gs_voxel_assign_ws_bytes", B, N),), 0x5A, dtype=torch.uint8, device=DEV)
+    nv.call("gs_voxel_assign", nv.ptr(pts), nv.ptr(counts), N, B, float(v), (ctypes.c_float * 3)(*origin), *[nv.ptr(t) for t in bufs],
+            nv.ptr(ws), ws.numel(), nv.stream())
+    torch.cuda.synchronize()
+    return bufs
+
+
+def check_assign(pts, counts, v, origin=(0.0, 0.0, 0.0), want=None):
+    got = assign_raw(pts, counts, v, origin)
+    want = ref_assign(np.asarray(pts, np.float32), counts, v, origin) if want is None else want
+    for name, g, w in zip(("voxel_of", "n_voxels", "n_dropped", "voxel_count", "voxel_first"), got, want):
+        assert torch.equal(g.cpu(), torch.from_numpy(w)), name
+    return got, want
+
+
+def bits(t):
+    return t.contiguous().view(torch.int32)
+
+
+# ------------------------------------------------------------------ GPU 1: assignment
+@pytest.mark.gpu
+@pytest.mark.parametrize("v", [1e-4, 0.25, 100.0])
+@pytest.mark.parametrize("N", [1, 63, 64, 65, 257, 4099])
+def test_assignment_matches_the_numpy_reference(N, v):
+    """All five outputs, torch.equal.  v = 1e-4: nearly every point its own voxel (long probe chains at load 0.5); 0.25: mixed,
+    every seventh point exactly on a face; 100: the eight octants at the origin (floor of negative coordinates, every row
+    contending for eight slots)."""
+    pts = make_points(N, seed=N)[None]
+    (_, n_voxels, _, _, _), want = check_assign(pts, [N], v)
+    if v == 100.0 and N >= 257:
+        assert int(n_voxels[0]) == 8
+    if v == 1e-4 and N >= 257:
+        assert int(n_voxels[0]) > N // 2
+
+
+@pytest.mark.gpu
+def test_assignment_with_an_origin_and_through_ops():
+    pts = make_points(4099, seed=3)[None]
+    org = (0.1, -0.2, 0.3)
+    got, _ = check_assign(pts, [4099], 0.25, org)
+    via_ops = ops.voxel_assign(torch.from_numpy(pts).to(DEV), torch.tensor([4099], dtype=torch.int32, device=DEV), 0.25, org)
+    for g, o in zip(got, via_ops):
+        assert torch.equal(g, o)
+    shifted = ref_assign(pts, [4099], 0.25)  # the origin matters: another partition
+    assert not np.array_equal(shifted[0], got[0].cpu().numpy())
+
+
+# Above 2^20 rows the compaction's block counts take a scan launch of their own (six launches), and every row-parallel grid
+# (capped at 4096 blocks of 256 threads) takes a second trip through its loop: the smallest size at which those paths run.
+BIG_N = (1 << 20) + 77
+
+
+@lru_cache(maxsize=None)
+def big_scene():
+    """(pts (1, BIG_N, 3), v, reference assignment), computed once and shared (never written to)."""
+    pts = make_points(BIG_N, seed=77)[None]
+    return pts, 0.25, ref_assign(pts, [BIG_N], 0.25)
+
+
+@pytest.mark.gpu
+def test_assignment_above_2_to_the_20_rows():
+    pts, v, ref = big_scene()
+    (_, n_voxels, _, voxel_count, _), _ = check_assign(pts, [BIG_N], v, want=ref)
+    assert int(n_voxels[0]) > 10000 and int(voxel_count.max()) > 64
+
+
+@pytest.mark.gpu
+def test_sum_above_2_to_the_20_rows():
+    """C = 1, sum mode.  The values are integers q, -2^18 <= q <= 2^20, times 2^-10, so that int64 holds every exact sum (np.add.at on
+    integers); voxels with more than 16 members sum beyond 24 bits, so the single rounding is exercised."""
+    pts, v, ref = big_scene()
+    M = int(ref[1][0])
+    q = np.random.RandomState(78).randint(-(1 << 18), (1 << 20) + 1, size=BIG_N).astype(np.int64)
+    x = (q.astype(np.float64) * 2.0 ** -10).astype(np.float32)
+    assert np.array_equal(x.astype(np.float64) * 2.0 ** 10, q)  # exact in fp32
+    sums = np.zeros(M, np.int64)
+    np.add.at(sums, ref[0][0], q)
+    assert int((np.abs(sums) > 1 << 24).sum()) > 1000  # (sums that do not fit 24 bits: rounded)
+    want = np.array([int_to_f32(int(t), unit=-10) for t in sums], np.float32).reshape(1, M, 1)
+    got = reduce_on_gpu(x.reshape(1, BIG_N, 1), ref, M, mean=False)
+    assert torch.equal(bits(got).cpu(), torch.from_numpy(want).view(torch.int32))
+
+
+# ------------------------------------------------------------------ GPU 2: ragged batch
+@pytest.mark.gpu
+def test_ragged_batch_ignores_padding_and_writes_every_output():
+    N, counts = 4099, [0, 700, 4099]
+    pts = np.stack([make_points(N, seed=10 + b) for b in range(3)])
+    for b, n in enumerate(counts):
+        pts[b, n:] = np.nan  # padding rows must not matter
+    got, want = check_assign(pts, counts, 0.25)  # (equality with the reference leaves no sentinel anywhere)
+    for g in got:
+        assert not bool((g == SENT32).any())
+    assert got[1].tolist()[0] == 0 and got[2].tolist() == [0, 0, 0]
+    alone = assign_raw(pts[1:2, :700], [700], 0.25)  # the same cloud on its own: the same numbering
+    assert torch.equal(alone[0][0], got[0][1, :700]) and int(alone[1][0]) == int(got[1][1])
+
+
+# ------------------------------------------------------------------ GPU 3: dropped rows
+@pytest.mark.gpu
+def test_dropped_rows_are_counted_and_do_not_disturb_the_numbering():
+    N, v = 257, 0.25
+    clean = make_points(N, seed=5)
+    pts = clean.copy()
+    bad = {3: (np.nan, 0, 0), 64: (0, np.inf, 0), 65: (0, 0, -np.inf), 100: (v * 2 ** 20, 0, 0), 101: (0, -v * (2 ** 20 + 1), 0),
+           200: (1e30, 1e30, 1e30), 256: (np.nan, np.nan, np.nan)}
+    for r, p in bad.items():
+        pts[r] = p
+    pts[7] = (v * (2 ** 20 - 1), 0, -v * (2 ** 20 - 1) + 0.5 * v)  # the outermost voxels still inside
+    (voxel_of, n_voxels, n_dropped, _, _), _ = check_assign(pts[None], [N], v)
+    assert int(n_dropped[0]) == len(bad) and bool((voxel_of[0, list(bad)] == -1).all())
+    assert int(voxel_of[0, 7]) >= 0
+    keep = np.array([r for r in range(N) if r not in bad])
+    (vo2, nv2, nd2, _, _), _ = check_assign(pts[keep][None], [len(keep)], v)  # without the bad rows: the same numbering
+    assert torch.equal(vo2[0], voxel_of[0, torch.from_numpy(keep).to(DEV)]) and int(nv2[0]) == int(n_voxels[0]) and int(nd2[0]) == 0
+    pc = gs.Pointclouds(points=torch.from_numpy(pts)[None].to(DEV))
+    with pytest.warns(RuntimeWarning, match="points were dropped"):
+        down = pc.voxel_downsample(v)
+    assert down.num_points_per_pointcloud.tolist() == [int(n_voxels[0])]
+    with warnings.catch_warnings(record=True) as seen:
+        warnings.simplefilter("always")
+        gs.Pointclouds(points=torch.from_numpy(clean)[None].to(DEV)).voxel_downsample(v)  # nothing dropped: no warning
+    assert not [w for w in seen if "dropped" in str(w.message)]
+    # every row dropped: a cloud without points, padded attributes without rows
+    nothing = gs.Pointclouds(points=torch.full((2, 5, 3), float("nan"), device=DEV), colors=torch.ones(2, 5, 3, device=DEV))
+    with pytest.warns(RuntimeWarning, match="10 points were dropped"):
+        none, (vo, vc, vf) = nothing.voxel_downsample(v, return_index=True)
+    assert none.num_points_per_pointcloud.tolist() == [0, 0] and tuple(none.points_padded.shape) == (2, 0, 3)
+    assert tuple(none.colors_padded.shape) == (2, 0, 3) and none.normals_padded is None
+    assert bool((vo == -1).all()) and tuple(vc.shape) == tuple(vf.shape) == (2, 0)
+
+
+# ------------------------------------------------------------------ GPU 4: reduction, bitwise
+def spread_values(n, C, seed):
+    """Mixed signs, magnitudes spread over 2^-20 .. 2^20."""
+    rng = np.random.RandomState(seed)
+    return (rng.randn(n, C) * np.exp2(rng.randint(-20, 21, size=(n, C)))).astype(np.float32)
+
+
+@lru_cache(maxsize=None)
+def scene(name):
+    """(pts (1, N, 3), v, reference assignment), computed once and shared (never written to)."""
+    rng = np.random.RandomState(42)
+    if name == "one_voxel":  # N = 4096 in one voxel: every add wraps the low word, negative values carry into the high one
+        pts, v = rng.rand(1, 4096, 3).astype(np.float32), 100.0
+    elif name == "room":     # N = 20 000 on the walls of a 4 x 3 x 2.5 m room, 5 cm voxels
+        p = rng.rand(20000, 3) * np.array([4.0, 3.0, 2.5])
+        wall = rng.randint(0, 3, 20000)
+        p[np.arange(20000), wall] = np.round(rng.rand(20000)) * np.array([4.0, 3.0, 2.5])[wall]
+        pts, v = (p - np.array([2.0, 1.5, 0.0])).astype(np.float32)[None], 0.05
+    else:
+        raise KeyError(name)
+    return pts, v, ref_assign(pts, [pts.shape[1]], v)
+
+
+@lru_cache(maxsize=None)
+def scene_sums(name, C):
+    pts, v, ref = scene(name)
+    N = pts.shape[1]
+    x = pts.copy() if (name == "room" and C == 3) else spread_values(N, C, seed=C)[None]
+    return x, ref_reduce(x, ref[0], ref[1], int(ref[1].max()))
+
+
+def reduce_on_gpu(x, ref, M, mean, mode_bits=0):
+    counts = torch.tensor([x.shape[1]] * x.shape[0], dtype=torch.int32, device=DEV)
+    t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
+    return ops.voxel_reduce_raw(t(x), counts, t(ref[0]), t(ref[1]), t(ref[3]), M, (1 if mean else 0) | mode_bits)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("mean", [False, True], ids=["sum", "mean"])
+@pytest.mark.parametrize("C", [1, 3, 4])
+@pytest.mark.parametrize("name", ["one_voxel", "room"])
+def test_reduction_is_the_exact_sum_rounded_once(name, C, mean):
+    pts, v, ref = scene(name)
+    got_assign = assign_raw(pts, [pts.shape[1]], v)
+    assert torch.equal(got_assign[0].cpu(), torch.from_numpy(ref[0]))  # the kernel's own assignment is the reference's
+    x, sums = scene_sums(name, C)
+    M = int(ref[1].max())
+    want = ref_mean(sums, ref[3], M) if mean else sums
+    for mode_bits in (0, ops.VOXEL_NO_PREAGG):  # with and without the pre-aggregation of neighbouring lanes: the same bits
+        got = reduce_on_gpu(x, ref, M, mean, mode_bits)
+        assert torch.equal(bits(got).cpu(), torch.from_numpy(want).view(torch.int32)), mode_bits
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("mean", [False, True], ids=["sum", "mean"])
+def test_reduction_with_non_finite_members_and_padding_rows(mean):
+    """A member with NaN, one with +inf (both -> what a float sum gives, the other components and voxels untouched); rows of out
+    beyond n_voxels are written as zero over a sentinel-free fresh buffer of M_max > n_voxels rows."""
+    N, C, v = 257, 3, 0.25
+    pts = make_points(N, seed=8)[None]
+    ref = ref_assign(pts, [N], v)
+    x = spread_values(N, C, seed=9)[None]
+    vo = ref[0][0]
+    big = np.nonzero(ref[3][0] >= 2)[0]  # voxels with at least two members
+    r_nan, r_inf = np.nonzero(vo == big[0])[0][0], np.nonzero(vo == big[1])[0][1]
+    r_pos, r_neg = np.nonzero(vo == big[2])[0][:2]  # +inf and -inf meet in one voxel: NaN
+    x[0, r_nan, 1], x[0, r_inf, 2], x[0, r_pos, 0], x[0, r_neg, 0] = np.nan, np.inf, np.inf, -np.inf
+    M = int(ref[1][0]) + 5
+    sums = ref_reduce(x, ref[0], ref[1], M)
+    want = ref_mean(sums, ref[3], M) if mean else sums
+    got = reduce_on_gpu(x, ref, M, mean)
+    assert torch.equal(bits(got).cpu(), torch.from_numpy(want).view(torch.int32))
+    g = got[0].cpu().numpy()
+    assert np.isnan(g[big[0], 1]) and np.isposinf(g[big[1], 2]) and np.isnan(g[big[2], 0])
+    assert np.isfinite(g[big[0], 0]) and np.isfinite(g[big[2], 1]) and not g[int(ref[1][0]):].any()
+
+
+# ------------------------------------------------------------------ GPU 5: order independence
+def voxel_map(pts, x, v):
+    """{key -> (count, mean bits)} from the ops-level calls on one cloud."""
+    N = pts.shape[0]
+    counts = torch.tensor([N], dtype=torch.int32, device=DEV)
+    P, X = torch.from_numpy(pts)[None].to(DEV), torch.from_numpy(x)[None].to(DEV)
+    voxel_of, n_voxels, n_dropped, voxel_count, voxel_first = ops.voxel_assign(P, counts, v)
+    M = int(n_voxels[0])
+    mean = ops.voxel_reduce(X, counts, voxel_of, n_voxels, voxel_count, M, mean=True)
+    keys = ref_assign(pts[None], [N], v)[5][0]
+    first = voxel_first[0, :M].cpu().numpy()
+    mb, cnt = bits(mean)[0].cpu().numpy(), voxel_count[0, :M].cpu().numpy()
+    return {int(keys[first[m]]): (int(cnt[m]), tuple(mb[m].tolist())) for m in range(M)}, bits(mean).clone()
+
+
+@pytest.mark.gpu
+def test_result_does_not_depend_on_row_order_nor_on_the_run():
+    N, v = 4099, 0.25
+    pts, x = make_points(N, seed=21), spread_values(N, 4, seed=22)
+    base, bits0 = voxel_map(pts, x, v)
+    assert len(base) > 100 and sum(c for c, _ in base.values()) == N
+    _, bits1 = voxel_map(pts, x, v)
+    assert torch.equal(bits0, bits1)  # two repeats of one call: identical bits
+    rng = np.random.RandomState(23)
+    for perm in (np.arange(N)[::-1].copy(), rng.permutation(N), np.argsort(pts[:, 0], kind="stable")):
+        other, _ = voxel_map(pts[perm], x[perm], v)
+        assert other == base
+
+
+# ------------------------------------------------------------------ GPU 6: reverse pass
+@pytest.mark.gpu
+@pytest.mark.parametrize("mean", [False, True], ids=["sum", "mean"])
+def test_reverse_pass_is_a_gather(mean):
+    B, N, C, v = 2, 257, 3, 0.25
+    counts_l = [257, 200]
+    pts = np.stack([make_points(N, seed=30 + b) for b in range(B)])
+    pts[0, 5] = np.nan  # a dropped row
+    P = torch.from_numpy(pts).to(DEV)
+    counts = torch.tensor(counts_l, dtype=torch.int32, device=DEV)
+    voxel_of, n_voxels, n_dropped, voxel_count, voxel_first = ops.voxel_assign(P, counts, v)
+    M = int(n_voxels.max())
+    x = torch.from_numpy(np.stack([spread_values(N, C, seed=40 + b) for b in range(B)])).to(DEV)
+    g_out = torch.from_numpy(spread_values(B * M, C, seed=50).reshape(B, M, C)).to(DEV)
+    grads = []
+    for det in (False, True):
+        torch.use_deterministic_algorithms(det)
+        try:
+            xr = x.clone().requires_grad_(True)
+            out = ops.voxel_reduce(xr, counts, voxel_of, n_voxels, voxel_count, M, mean=mean)
+            out.backward(g_out)
+        finally:
+            torch.use_deterministic_algorithms(False)
+        grads.append(xr.grad)
+    assert torch.equal(bits(grads[0]), bits(grads[1]))  # a gather: the same bits with the deterministic flag on and off
+    idx = voxel_of.long().clamp(min=0)
+    want = torch.gather(g_out, 1, idx[..., None].expand(B, N, C))
+    if mean:
+        want = want / torch.gather(voxel_count, 1, idx).to(torch.float32)[..., None]
+    want = torch.where((voxel_of >= 0)[..., None], want, torch.zeros_like(want))
+    assert torch.equal(bits(grads[0]), bits(want))
+    assert not grads[0][0, 5].any() and not grads[0][1, 200:].any() and bool((voxel_of[1, 200:] == -1).all())
+
+
+@pytest.mark.gpu
+def test_reverse_pass_against_autograd_through_a_float64_restatement():
+    """N = 257: d(sum_m <w_m, mean_m>) / dx by the kernels against torch autograd through index_add_ / counts in float64.
+    Bound 4 * 2^-24 relative per element: one fp32 division and one rounding of the sum."""
+    N, C, v = 257, 3, 0.25
+    pts = make_points(N, seed=60)
+    P = torch.from_numpy(pts)[None].to(DEV)
+    counts = torch.tensor([N], dtype=torch.int32, device=DEV)
+    voxel_of, n_voxels, _, voxel_count, _ = ops.voxel_assign(P, counts, v)
+    M = int(n_voxels[0])
+    w = torch.randn(1, M, C, generator=torch.Generator().manual_seed(61)).to(DEV)
+    for mean in (True, False):
+        xr = P.clone().requires_grad_(True)
+        out = ops.voxel_reduce(xr, counts, voxel_of, n_voxels, voxel_count, M, mean=mean)
+        (out * w).sum().backward()
+        x64 = P.double().clone().requires_grad_(True)
+        acc = torch.zeros(M, C, dtype=torch.float64, device=DEV).index_add_(0, voxel_of[0].long(), x64[0])
+        if mean:
+            acc = acc / voxel_count[0, :M].double()[:, None]
+        (acc * w[0].double()).sum().backward()
+        err = (xr.grad.double() - x64.grad).abs()
+        assert bool((err <= 4 * U * x64.grad.abs()).all()), float((err / x64.grad.abs().clamp(min=1e-300)).max())
+        ferr = (out[0].double() - acc.detach()).abs()
+        assert bool((ferr <= 4 * U * acc.detach().abs() + 1e-300).all())
+
+
+# ------------------------------------------------------------------ GPU 7: Pointclouds level
+@pytest.mark.gpu
+def test_pointclouds_voxel_downsample_on_a_frame():
+    c, d, K, P = make_sequence(1, 1, 120, 160, seed=0)
+    frame = gs.RGBDImages(c.to(DEV), d.to(DEV), K.to(DEV), P.to(DEV))
+    pc = pointclouds_from_rgbdimages(frame)
+    N, v = int(pc.num_points_per_pointcloud[0]), 0.05
+    feats = torch.rand(1, N, 2, generator=torch.Generator().manual_seed(1)).to(DEV) + 0.5
+    pc = gs.Pointclouds(points=pc.points_padded, normals=pc.normals_padded, colors=pc.colors_padded, features=feats)
+    down, (voxel_of, voxel_count, voxel_first) = pc.voxel_downsample(v, return_index=True)
+    assert isinstance(down, gs.Pointclouds) and down is not pc and pc.points_padded.shape[1] == N  # never in place
+    M = int(down.num_points_per_pointcloud[0])
+    assert 0 < M < N and int(voxel_count.sum()) == N and voxel_of.dtype == voxel_count.dtype == voxel_first.dtype == torch.int64
+    assert voxel_count.shape == voxel_first.shape == (1, M) and voxel_of.shape == (1, N)
+    # attributes equal the ops-level results
+    counts = pc._counts_i32()
+    a = ops.voxel_assign(pc.points_padded, counts, v)
+    assert torch.equal(a[0].long(), voxel_of) and int(a[1][0]) == M
+    for name in ("points", "normals", "colors", "features"):
+        want = ops.voxel_reduce(getattr(pc, name + "_padded"), counts, a[0], a[1], a[3], M, mean=True)
+        assert torch.equal(bits(getattr(down, name + "_padded")), bits(want)), name
+    # and the numpy reference's assignment
+    ref = ref_assign(pc.points_padded.cpu().numpy(), [N], v)
+    assert torch.equal(a[0].cpu(), torch.from_numpy(ref[0])) and torch.equal(voxel_first.cpu()[0], torch.from_numpy(ref[4][0, :M]).long())
+    # feature_reduction="sum" keeps the total of the features to fp32 rounding: each voxel sum is rounded once (relative U),
+    # and both totals are taken in float64
+    summed = pc.voxel_downsample(v, feature_reduction="sum")
+    assert torch.equal(bits(summed.points_padded), bits(down.points_padded))
+    tot, tot_in = summed.features_padded.double().sum(1), feats.double().sum(1)
+    assert bool(((tot - tot_in).abs() <= U * tot_in.abs()).all())
+    # a voxel's mean lies inside the voxel: every original point is within sqrt(3) v (1 + 2^-20) of its nearest downsampled point
+    d2, idx = gs.metrics.nearest_neighbor(pc, down)
+    assert bool((idx[0] >= 0).all())
+    assert float(d2.double().sqrt().max()) <= math.sqrt(3.0) * v * (1 + 2.0 ** -20)
+    # differentiable with respect to every attribute it carries
+    leaves = {n: getattr(pc, n + "_padded").clone().requires_grad_(True) for n in ("points", "normals", "colors", "features")}
+    pcg = gs.Pointclouds(points=leaves["points"], normals=leaves["normals"], colors=leaves["colors"], features=leaves["features"])
+    dg = pcg.voxel_downsample(v)
+    (dg.points_padded.sum() + dg.normals_padded.sum() + dg.colors_padded.sum() + dg.features_padded.sum()).backward()
+    inv = 1.0 / voxel_count[0][voxel_of[0]].to(torch.float32)
+    for n, leaf in leaves.items():
+        assert leaf.grad is not None and torch.equal(leaf.grad[0], inv[:, None].expand_as(leaf.grad[0]).contiguous()), n

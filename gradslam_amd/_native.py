@@ -137,6 +137,12 @@ SIGNATURES = {
     "gs_voxel_reduce_ws_bytes": (c_sz, [c_i, c_i, c_i]),
     "gs_voxel_reduce": (c_i, [c_p, c_p, c_i, c_i, c_i, c_p, c_p, c_p, c_i, c_i, c_p, c_p, c_sz, c_p]),
     "gs_voxel_reduce_backward": (c_i, [c_p, c_p, c_i, c_i, c_i, c_p, c_p, c_i, c_i, c_p, c_p]),
+    "gs_set_knn_grid": (None, [c_i]),
+    "gs_knn_ws_bytes": (c_sz, [c_i, c_i, c_i, c_i]),
+    "gs_knn": (c_i, [c_p, c_p, c_i, c_p, c_p, c_i, c_i, c_i, c_p, c_p, c_sz, c_p]),
+    "gs_knn_backward_ws_bytes": (c_sz, [c_i, c_i, c_i, c_i]),
+    "gs_knn_backward": (c_i, [c_p, c_p, c_i, c_p, c_p, c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_sz, c_p]),
+    "gs_knn_normals": (c_i, [c_p, c_p, c_i, c_p, c_p, c_i, c_i, c_i, c_p, c_i, c_p, c_p, c_p, c_p]),
 }
 
 _lib = None

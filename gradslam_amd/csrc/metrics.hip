@@ -23,6 +23,7 @@
 // Launch counts do not depend on the counts nor (the deterministic fold apart) on B; nothing synchronises the host.
 #include <stddef.h>
 
+#include "gs_cellgrid.hpp"
 #include "gs_metrics.hpp"
 
 namespace gs {
@@ -41,48 +42,12 @@ __host__ __device__ static inline int cham_g(int n) {
 __host__ __device__ static inline int cham_nbox(int cap) { return (cap + CHUNK - 1) / CHUNK; }  // boxes per batch element
 static inline int cham_cells_cap(int cap) { const int g = cham_g(cap); return g * g * g; }
 
-// order-preserving float -> uint32 (all finite values and the infinities) and back
-__device__ __forceinline__ uint32_t ord_bits(float f) {
-    const uint32_t u = __float_as_uint(f);
-    return u ^ ((uint32_t)((int32_t)u >> 31) | 0x80000000u);
-}
-__device__ __forceinline__ float ord_float(uint32_t o) { return __uint_as_float((o & 0x80000000u) ? (o ^ 0x80000000u) : ~o); }
-
-// The cell grid of one cloud: cubic cells of side h = (longest extent) / g, g = cham_g(n); an axis of extent e gets
-// floor(e / h) + 1 cells, at most g (a flat or degenerate axis: one).  No extent at all (one point, all points equal, no
-// point): one cell.  Every value is clamped, so a non-finite coordinate lands in some cell and never outside the table.
-struct ChamGrid {
-    float lo[3], inv_h;
-    int g[3], ncells;
-};
+// The cell grid of one cloud (gs_cellgrid.hpp) with chamfer's rule for the cells per axis, g = cham_g(n).
+using ChamGrid = CellGrid;
 __device__ __forceinline__ ChamGrid cham_grid(const uint32_t *__restrict__ acc /* max x y z | ~min x y z */, int n) {
-    ChamGrid G;
-    G.lo[0] = G.lo[1] = G.lo[2] = 0.0f;
-    G.inv_h = 0.0f;
-    G.g[0] = G.g[1] = G.g[2] = 1;
-    G.ncells = 1;
-    if (n <= 0) return G;
-    float ext[3], emax = 0.0f;
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-        G.lo[a] = ord_float(~acc[3 + a]);
-        ext[a] = ord_float(acc[a]) - G.lo[a];
-        emax = fmaxf(emax, ext[a]);
-    }
-    if (!(emax > 0.0f) || !(emax < INFINITY)) return G;
-    const int g = cham_g(n);
-    G.inv_h = (float)g / emax;
-#pragma unroll
-    for (int a = 0; a < 3; ++a) G.g[a] = min((int)fminf(ext[a] * G.inv_h, (float)(g - 1)), g - 1) + 1;
-    G.ncells = G.g[0] * G.g[1] * G.g[2];
-    return G;
+    return cell_grid(acc, n, cham_g(n));
 }
-__device__ __forceinline__ int cham_cell(const ChamGrid &G, const f3 p) {
-    const int cx = min(max((int)((p.x - G.lo[0]) * G.inv_h), 0), G.g[0] - 1);
-    const int cy = min(max((int)((p.y - G.lo[1]) * G.inv_h), 0), G.g[1] - 1);
-    const int cz = min(max((int)((p.z - G.lo[2]) * G.inv_h), 0), G.g[2] - 1);
-    return (cz * G.g[1] + cy) * G.g[0] + cx;
-}
+__device__ __forceinline__ int cham_cell(const ChamGrid &G, const f3 p) { return cell_of(G, p); }
 
 // ------------------------------------------------------------------ workspace
 struct ChamWs {

@@ -1175,3 +1175,128 @@ class _VoxelReduceFn(torch.autograd.Function):
 def voxel_reduce(x, counts_i32, voxel_of, n_voxels, voxel_count, M_max, mean=True):
     """Autograd-aware voxel_reduce_raw over the assignment of `voxel_assign`: (B,N,C) -> (B,M_max,C), gradients reach x."""
     return _VoxelReduceFn.apply(x, counts_i32, voxel_of, n_voxels, voxel_count, int(M_max), VOXEL_MEAN if mean else VOXEL_SUM)
+
+
+# ---------------------------------------------------------------------------------------------- N
+KNN_KMAX = 32
+
+
+def _knn_args(src, tgt, src_counts, tgt_counts, K, op):
+    require_hip(src, tgt, src_counts, tgt_counts, op=op)
+    same = src is tgt
+    src = _f32c(src)
+    tgt = src if same else _f32c(tgt)
+    for name, x in (("src", src), ("tgt", tgt)):
+        if x.ndim != 3 or x.shape[-1] != 3 or x.shape[1] == 0:
+            raise ValueError("{}: {} should have shape (B, N, 3) with N > 0. Got {}.".format(op, name, tuple(x.shape)))
+    B = src.shape[0]
+    if tgt.shape[0] != B or B == 0:
+        raise ValueError("{}: src and tgt should share a batch size B > 0. Got {} and {}.".format(op, src.shape[0], tgt.shape[0]))
+    for name, c in (("src_counts", src_counts), ("tgt_counts", tgt_counts)):
+        if c.dtype != torch.int32 or c.numel() != B:
+            raise ValueError("{}: {} should be {} int32 values. Got {} of {}.".format(op, name, B, c.numel(), c.dtype))
+    if isinstance(K, bool) or not isinstance(K, int) or not 1 <= K <= KNN_KMAX:
+        raise ValueError("{}: K should be an int in [1, {}]. Got {!r}.".format(op, KNN_KMAX, K))
+    return src, tgt, src_counts.contiguous(), tgt_counts.contiguous()
+
+
+def knn_raw(src, tgt, src_counts, tgt_counts, K: int, out=None) -> torch.Tensor:
+    """Exact K nearest neighbours of every row of src (B,Ns,3) in tgt (B,Nt,3), padded clouds with int32 device counts ->
+    keys (B,Ns,K) int64, every element written: slot k of a row below its count holds the k-th smallest (d2, j) packed as
+    dist2_bits << 32 | j (d2 in fp32 without FMA, the lowest row wins ties); KEY_NONE beyond min(K, tgt_counts) and in the
+    rows beyond src_counts.  `src is tgt` is the self-query.  `out`: a (B,Ns,K) int64 buffer to write into."""
+    src, tgt, cs, ct = _knn_args(src, tgt, src_counts, tgt_counts, K, "knn")
+    B, Ns, Nt = src.shape[0], src.shape[1], tgt.shape[1]
+    keys = torch.empty((B, Ns, K), dtype=torch.int64, device=src.device) if out is None else out
+    ws = workspace(ws_bytes("gs_knn_ws_bytes", B, Ns, Nt, K), src.device, "knn")
+    call("gs_knn", ptr(src), ptr(cs), Ns, ptr(tgt), ptr(ct), Nt, B, K, ptr(keys), ptr(ws), ws.numel(), stream())
+    return keys
+
+
+def knn_unpack(keys: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """keys int64 -> (d2 fp32, idx int64); KEY_NONE slots give d2 = 0, idx = -1."""
+    none = keys == KEY_NONE
+    d2 = (keys >> 32).to(torch.int32).view(torch.float32).masked_fill(none, 0.0)
+    idx = (keys & 0xFFFFFFFF).masked_fill(none, -1)
+    return d2, idx
+
+
+def knn_backward_raw(src, tgt, src_counts, tgt_counts, keys, g_d2):
+    """Adjoint of knn's distances: g_d2 (B,Ns,K) -> (g_src (B,Ns,3), g_tgt (B,Nt,3)), both fully written; the keys are constants.
+    g_src is the fp32 sum in slot order, g_tgt the exact sum rounded once: one path, the same bits from run to run."""
+    require_hip(keys, g_d2, op="knn_backward")
+    if keys.ndim != 3 or keys.dtype != torch.int64:
+        raise ValueError("knn_backward: keys should be (B, Ns, K) int64. Got {} of {}.".format(tuple(keys.shape), keys.dtype))
+    K = int(keys.shape[-1])
+    src, tgt, cs, ct = _knn_args(src, tgt, src_counts, tgt_counts, K, "knn_backward")
+    B, Ns, Nt = src.shape[0], src.shape[1], tgt.shape[1]
+    if tuple(keys.shape) != (B, Ns, K) or tuple(g_d2.shape) != (B, Ns, K):
+        raise ValueError("knn_backward: keys and g_d2 should have shape {}. Got {} and {}.".format(
+            (B, Ns, K), tuple(keys.shape), tuple(g_d2.shape)))
+    keys, g_d2 = keys.contiguous(), _f32c(g_d2)
+    g_src = torch.empty((B, Ns, 3), dtype=torch.float32, device=src.device)
+    g_tgt = torch.empty((B, Nt, 3), dtype=torch.float32, device=src.device)
+    ws = workspace(ws_bytes("gs_knn_backward_ws_bytes", B, Ns, Nt, K), src.device, "knn_bwd")
+    call("gs_knn_backward", ptr(src), ptr(cs), Ns, ptr(tgt), ptr(ct), Nt, B, K, ptr(keys), ptr(g_d2), ptr(g_src), ptr(g_tgt),
+         ptr(ws), ws.numel(), stream())
+    return g_src, g_tgt
+
+
+class _KnnFn(torch.autograd.Function):
+    """(src, tgt | counts, K) -> (d2 (B,Ns,K) fp32, idx (B,Ns,K) int64: a constant).  The neighbours are constants of the graph,
+    as in _ChamferFn: the gradient is that of the distances to them."""
+
+    @staticmethod
+    def forward(ctx, src, tgt, src_counts, tgt_counts, K, same):
+        keys = knn_raw(src, src if same else tgt, src_counts, tgt_counts, K)
+        d2, idx = knn_unpack(keys)
+        ctx.save_for_backward(src, tgt, src_counts, tgt_counts, keys)
+        ctx.same = same
+        ctx.mark_non_differentiable(idx)
+        return d2, idx
+
+    @staticmethod
+    def backward(ctx, g_d2, _g_idx):
+        src, tgt, src_counts, tgt_counts, keys = ctx.saved_tensors
+        g_src, g_tgt = knn_backward_raw(src, src if ctx.same else tgt, src_counts, tgt_counts, keys, g_d2)
+        if ctx.same:  # one cloud: both roles' adjoints, added once
+            return (g_src + g_tgt).view_as(src).to(src.dtype), None, None, None, None, None
+        return (g_src.view_as(src).to(src.dtype) if ctx.needs_input_grad[0] else None,
+                g_tgt.view_as(tgt).to(tgt.dtype) if ctx.needs_input_grad[1] else None, None, None, None, None)
+
+
+def knn(src, tgt, src_counts, tgt_counts, K: int):
+    """Autograd-aware knn_raw -> (d2 (B,Ns,K) fp32, idx (B,Ns,K) int64).  KEY_NONE slots give d2 = 0, idx = -1.  Gradients of
+    d2 reach both clouds' points (for `src is tgt`, the cloud receives the sum of both roles)."""
+    _knn_args(src, tgt, src_counts, tgt_counts, K, "knn")
+    return _KnnFn.apply(src, tgt, src_counts, tgt_counts, K, src is tgt)
+
+
+def knn_normals_raw(src, tgt, src_counts, tgt_counts, keys, mode: int = 0, orient=None, want_variation: bool = False):
+    """Normals of the rows of src from the covariance of their neighbours in tgt (keys of knn_raw) -> (normals (B,Ns,3),
+    variation (B,Ns) or None).  mode 0: unoriented; 1: orient (B,3) viewpoints, normals face them; 2: orient (B,Ns,3) reference
+    normals, n . ref >= 0.  Rows with fewer than three neighbours and rows beyond the count: zeros.  Not differentiable."""
+    require_hip(keys, orient, op="knn_normals")
+    if keys.ndim != 3 or keys.dtype != torch.int64:
+        raise ValueError("knn_normals: keys should be (B, Ns, K) int64. Got {} of {}.".format(tuple(keys.shape), keys.dtype))
+    K = int(keys.shape[-1])
+    src, tgt, cs, ct = _knn_args(src, tgt, src_counts, tgt_counts, K, "knn_normals")
+    B, Ns, Nt = src.shape[0], src.shape[1], tgt.shape[1]
+    if tuple(keys.shape) != (B, Ns, K):
+        raise ValueError("knn_normals: keys should have shape {}. Got {}.".format((B, Ns, K), tuple(keys.shape)))
+    if mode not in (0, 1, 2):
+        raise ValueError("knn_normals: mode should be 0, 1 or 2. Got {!r}.".format(mode))
+    if mode:
+        want = (B, 3) if mode == 1 else (B, Ns, 3)
+        if orient is None or tuple(orient.shape) != want:
+            raise ValueError("knn_normals: mode {} needs orient of shape {}. Got {}.".format(
+                mode, want, None if orient is None else tuple(orient.shape)))
+        orient = _f32c(orient)
+    else:
+        orient = None
+    keys = keys.contiguous()
+    normals = torch.empty((B, Ns, 3), dtype=torch.float32, device=src.device)
+    variation = torch.empty((B, Ns), dtype=torch.float32, device=src.device) if want_variation else None
+    call("gs_knn_normals", ptr(src), ptr(cs), Ns, ptr(tgt), ptr(ct), Nt, B, K, ptr(keys), int(mode), ptr(orient), ptr(normals),
+         ptr(variation), stream())
+    return normals, variation

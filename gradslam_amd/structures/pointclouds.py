@@ -13,6 +13,7 @@ Differences that are deliberate and invisible through the API:
   per-batch `.item()` loop (reference :1419-1427);
 * the four attribute families share one implementation instead of four copies.
 """
+import math
 import warnings
 from typing import List, Optional, Union
 
@@ -543,6 +544,146 @@ class Pointclouds(object):
         if return_index:
             return out, (voxel_of.long(), voxel_count[:, :M].long(), voxel_first[:, :M].long())
         return out
+
+    # ------------------------------------------------------------------ neighbours
+    def knn(self, K: int, other: Optional["Pointclouds"] = None):
+        r"""The exact K nearest neighbours (1 <= K <= 32) of every point among the points of `other` (default: this cloud, the
+        self-query, in which every point's first neighbour is itself or a duplicate with a lower row), on the padded layout:
+        (d2 (B,N,K) fp32, idx (B,N,K) int64), ascending in (d2, idx), the lowest row winning ties.  Slots without a neighbour
+        (fewer than K points, padding rows) hold d2 = 0, idx = -1.  d2 is differentiable w.r.t. both clouds' points; the
+        neighbours are constants of the graph."""
+        from .. import ops
+
+        if not self.has_points or self._B == 0 or self._N == 0:
+            raise ValueError("cannot search the neighbours of an empty pointclouds object")
+        if other is None or other is self:
+            pts = self.points_padded
+            return ops.knn(pts, pts, self._counts_i32(), self._counts_i32(), K)
+        if not isinstance(other, type(self)):
+            raise TypeError("other must be of type gradslam.Pointclouds, but was of type {}.".format(type(other)))
+        if not other.has_points or other._N == 0:
+            raise ValueError("cannot search neighbours in an empty pointclouds object")
+        if len(other) != len(self):
+            raise ValueError("Batch size of the two pointclouds must match: ({0} != {1})".format(len(other), len(self)))
+        return ops.knn(self.points_padded, other.points_padded, self._counts_i32(), other._counts_i32(), K)
+
+    def _self_keys(self, K: int) -> torch.Tensor:
+        from .. import ops
+
+        pts = self.points_padded.detach()
+        return ops.knn_raw(pts, pts, self._counts_i32(), self._counts_i32(), K)
+
+    def estimate_normals(self, K: int = 16, viewpoint=None, orient: str = "auto", return_variation: bool = False):
+        r"""A NEW Pointclouds with the same points / colours / features and normals estimated from every point's K nearest
+        neighbours (3 <= K <= 32, the point itself included): the unit eigenvector of the smallest eigenvalue of the
+        neighbourhood's covariance (fp64).  `orient`: "viewpoint" turns every normal towards `viewpoint` ((3,) or (B,3),
+        default the origin); "normals" keeps the side of the cloud's existing normals; "none" leaves the sign to the
+        decomposition; "auto" is "normals" where the cloud has normals, else "viewpoint".  Points with fewer than three
+        neighbours get a zero normal.  The normals are NOT differentiable (points, colours and features pass through).
+        With `return_variation=True` also returns the surface variation l0 / (l0 + l1 + l2) per point, (B,N) padded."""
+        from .. import ops
+
+        if isinstance(K, bool) or not isinstance(K, int) or not 3 <= K <= ops.KNN_KMAX:
+            raise ValueError("estimate_normals: K should be an int in [3, {}]. Got {!r}.".format(ops.KNN_KMAX, K))
+        if orient not in ("auto", "viewpoint", "normals", "none"):
+            raise ValueError('orient should be "auto", "viewpoint", "normals" or "none". Got {!r}.'.format(orient))
+        if orient == "normals" and not self.has_normals:
+            raise ValueError('orient="normals" needs a pointclouds object that has normals')
+        if not self.has_points or self._B == 0 or self._N == 0:
+            return (self, None) if return_variation else self
+        points = self.points_padded
+        if orient == "auto":
+            orient = "normals" if self.has_normals else "viewpoint"
+        mode, ref = 0, None
+        if orient == "viewpoint":
+            mode = 1
+            ref = torch.zeros(3, device=self.device) if viewpoint is None else torch.as_tensor(viewpoint, dtype=torch.float32, device=self.device)
+            if ref.shape not in ((3,), (self._B, 3)):
+                raise ValueError("viewpoint should have shape (3,) or ({}, 3). Got {}.".format(self._B, tuple(ref.shape)))
+            ref = ref.expand(self._B, 3).contiguous()
+        elif orient == "normals":
+            mode, ref = 2, self.normals_padded.detach()
+        counts = self._counts_i32()
+        keys = self._self_keys(K)
+        pts = points.detach()
+        normals, variation = ops.knn_normals_raw(pts, pts, counts, counts, keys, mode, ref, return_variation)
+        out = Pointclouds(device=self.device)
+        out._B = self._B
+        out._adopt_padded(points, normals, self.colors_padded, self.features_padded)
+        out._set_counts(self._counts)
+        return (out, variation) if return_variation else out
+
+    def _keep_rows(self, keep: torch.Tensor, return_mask: bool):
+        """A NEW Pointclouds with the rows of `keep` (B,N) bool, order preserved, every attribute carried (differentiable)."""
+        from .. import ops
+
+        names = [a for a in _ATTRS if self._has(a)]
+        lists = {a: [] for a in names}
+        counts = []
+        for b in range(self._B):
+            n = self._counts[b]
+            xs = [self._get_padded(a)[b, :n] for a in names]
+            if n == 0:
+                sel = xs
+            else:
+                sel = ops.select_rows_multi(xs, keep[b, :n])
+            for a, x in zip(names, sel):
+                lists[a].append(x)
+            counts.append(int(sel[0].shape[0]))
+        out = Pointclouds(device=self.device)
+        out._B = self._B
+        for a in _ATTRS:
+            setattr(out, "_%s_list" % a, lists.get(a))
+            setattr(out, "_%s_padded" % a, None)
+            setattr(out, "_has_%s" % a, a in lists)
+        out._set_counts(counts)
+        return (out, keep) if return_mask else out
+
+    def remove_radius_outliers(self, radius, min_neighbors: int, return_mask: bool = False):
+        r"""A NEW Pointclouds without the points that have fewer than `min_neighbors` points (themselves included,
+        1 <= min_neighbors <= 32) within `radius`: a point is kept iff its `min_neighbors`-th nearest neighbour exists and its
+        squared distance (fp32, as `knn`) is <= fp32(radius) * fp32(radius), exactly.  The kept points keep their order and
+        all their attributes; gradients flow to the kept rows.  With `return_mask=True` also returns the (B,N) bool mask."""
+        from .. import ops
+
+        if isinstance(min_neighbors, bool) or not isinstance(min_neighbors, int) or not 1 <= min_neighbors <= ops.KNN_KMAX:
+            raise ValueError("remove_radius_outliers: min_neighbors should be an int in [1, {}]. Got {!r}.".format(
+                ops.KNN_KMAX, min_neighbors))
+        r = torch.tensor(float(radius), dtype=torch.float32)
+        if not bool(torch.isfinite(r)) or float(r) <= 0.0:
+            raise ValueError("remove_radius_outliers: radius should be finite and positive. Got {!r}.".format(radius))
+        if not self.has_points or self._B == 0 or self._N == 0:
+            return (self, None) if return_mask else self
+        keys = self._self_keys(min_neighbors)[..., min_neighbors - 1]
+        # the key's high word is the distance's bit pattern; non-negative floats order as their bits do
+        r2_bits = int((r * r).view(torch.int32).item())
+        keep = (keys != ops.KEY_NONE) & ((keys >> 32) <= r2_bits)
+        return self._keep_rows(keep, return_mask)
+
+    def remove_statistical_outliers(self, K: int, std_ratio, return_mask: bool = False):
+        r"""A NEW Pointclouds without the points whose mean distance to their K nearest other points (1 <= K <= 31) exceeds
+        the cloud's mean of that quantity by more than `std_ratio` population standard deviations (statistics per cloud, in
+        fp64).  The kept points keep their order and all their attributes; gradients flow to the kept rows.  With
+        `return_mask=True` also returns the (B,N) bool mask."""
+        from .. import ops
+
+        if isinstance(K, bool) or not isinstance(K, int) or not 1 <= K <= ops.KNN_KMAX - 1:
+            raise ValueError("remove_statistical_outliers: K should be an int in [1, {}]. Got {!r}.".format(ops.KNN_KMAX - 1, K))
+        std_ratio = float(std_ratio)
+        if not math.isfinite(std_ratio):
+            raise ValueError("remove_statistical_outliers: std_ratio should be finite. Got {!r}.".format(std_ratio))
+        if not self.has_points or self._B == 0 or self._N == 0:
+            return (self, None) if return_mask else self
+        d2, idx = ops.knn_unpack(self._self_keys(K + 1)[..., 1:])
+        have = idx >= 0
+        m = have.sum(-1)
+        mean_i = (d2.double().sqrt() * have).sum(-1) / m.clamp(min=1)
+        valid = self.nonpad_mask & (m > 0)
+        nv = valid.sum(-1).clamp(min=1)
+        mu = (mean_i * valid).sum(-1) / nv
+        sigma = ((((mean_i - mu.unsqueeze(-1)) ** 2) * valid).sum(-1) / nv).sqrt()
+        keep = self.nonpad_mask & ((mean_i <= (mu + std_ratio * sigma).unsqueeze(-1)) | (m == 0))
+        return self._keep_rows(keep, return_mask)
 
     def open3d(self, index: int, include_colors: bool = True, max_num_points: Optional[int] = None,
                include_normals: bool = False):

@@ -668,6 +668,63 @@ int gs_voxel_reduce_backward(const float *g_out, const int32_t *counts, int N_ma
                              const int32_t *voxel_of, const int32_t *voxel_count, int M_max, int mode, float *g_x,
                              gs_stream_t stream);
 
+/* ---------------------------------------------------------------- N: neighbours (exact K nearest neighbours of every row)
+ * The reference's chamferdist.knn_points takes a K and is only ever called with 1; this contract is ours.
+ * src (B,Ns_max,3), tgt (B,Nt_max,3): padded fp32 clouds; src_counts / tgt_counts: (B,) int32 on the device; rows at or beyond a
+ * count are never read.  1 <= K <= 32.  src == tgt (the same pointer) is the self-query: every row's first key is itself (or a
+ * duplicate with a lower row).
+ *   keys (B,Ns_max,K) 64-bit, EVERY element written.  For i < src_counts[b], slot k holds the k-th smallest of
+ *       {(d2(i,j), j) : j < tgt_counts[b]} in lexicographic order, packed dist2_bits << 32 | j, where
+ *       d2 = (dx*dx + dy*dy) + dz*dz in fp32 without FMA: the bits of gs_knn1 / gs_knn1_bruteforce, the lowest row wins ties.
+ *       Slots beyond min(K, tgt_counts[b]) and all slots of rows >= src_counts[b] hold all ones (no neighbour).
+ *   Search: both clouds are bucketed in one cell grid over the targets' bounding box (g cells along the longest axis, the
+ *       smallest g <= 128 with kb g^2 >= tgt_counts[b], kb = K rounded up to 8 / 16 / 32); one thread per query, in the sources'
+ *       cell order, keeps its sorted top K in LDS and examines a growing box of cells.  It stops only when the K-th distance is
+ *       STRICTLY below a lower bound of every unexamined target (per face: the squared fp32 gap to the nearest coordinate of
+ *       any target beyond it, exact by monotone rounding; no epsilon), or when nothing is left.  No result depends on g:
+ *       gs_set_knn_grid(g_max) caps the cells per axis (0 = the rule) so that tests can prove it.
+ *   No float atomics: the same bits from run to run, whatever the row order of either cloud.  One memset and five launches,
+ *       whatever the counts, B and K.  Nothing synchronises the host.  Non-finite coordinates inside the counts: the result is
+ *       undefined (nothing is written out of bounds, the search terminates).  B <= 65535.
+ * Workspace, every piece rounded up to 256 bytes, with cells = g^3 for the rule's g at Nt_max:
+ *   16 B B Nt_max | 4 B B Ns_max | 4 B B Ns_max | 4 B B Nt_max | 3096 B B (face tables) | 32 B B | 3072 B B (layer extremes) |
+ *   4 B B cells | 4 B B cells (the two histograms).
+ * Errors: GS_ERR_INVALID_ARG for a NULL pointer or a bad shape / K, GS_ERR_WORKSPACE_TOO_SMALL; a *_ws_bytes query with a bad
+ * argument returns 0. */
+void gs_set_knn_grid(int g_max);
+size_t gs_knn_ws_bytes(int B, int Ns_max, int Nt_max, int K);
+int gs_knn(const float *src, const int32_t *src_counts, int Ns_max, const float *tgt, const int32_t *tgt_counts,
+           int Nt_max, int B, int K, uint64_t *keys, void *ws, size_t ws_bytes, gs_stream_t stream);
+
+/* Adjoint of the K distances; the keys are constants of the graph.  g_d2 (B,Ns_max,K) fp32.  A slot (i,k) is valid when its
+ * key is not all ones and its row j < tgt_counts[b]; its term is v = c delta with c = 2 g_d2[i,k], delta = s_i - t_j, each
+ * operation in fp32.
+ *   g_src (B,Ns_max,3): ((0 + v_0) + v_1) + ... over the valid slots, k ascending, in fp32.
+ *   g_tgt (B,Nt_max,3): the EXACT sum of -v over every valid slot whose neighbour is j, rounded once to fp32 (128-bit fixed
+ *       point, integer atomics, as gs_voxel_reduce: with lg = ceil(log2(Ns_max K)), bits more than 102 - lg binary places below
+ *       the call's largest finite |v| are truncated toward zero).  Non-finite terms give what a float sum gives.
+ *   Rows beyond the counts and target rows no slot points to receive zeros: every element of both outputs is written.
+ *   g_src and g_tgt must be distinct buffers, for a self-query too (the caller adds them).  One path, the same bits from run
+ *   to run and under any permutation of the source rows (for g_tgt).  One memset and three launches.
+ * Workspace, every piece rounded up to 256 bytes:  48 B B Nt_max | 4 B B Nt_max | 4 B. */
+size_t gs_knn_backward_ws_bytes(int B, int Ns_max, int Nt_max, int K);
+int gs_knn_backward(const float *src, const int32_t *src_counts, int Ns_max, const float *tgt,
+                    const int32_t *tgt_counts, int Nt_max, int B, int K, const uint64_t *keys, const float *g_d2,
+                    float *g_src, float *g_tgt, void *ws, size_t ws_bytes, gs_stream_t stream);
+
+/* Normals from the neighbourhoods, one thread per source row; not differentiable.  With x_k the target rows of the row's
+ * m valid slots: m < 3 gives normal (0,0,0) and variation 0; otherwise mu = (1/m) sum x_k and C = (1/m) sum (x_k - mu)(x_k - mu)^T
+ * accumulated in fp64, k ascending; the eigen-decomposition of C in fp64 by cyclic Jacobi (8 sweeps); n = the unit eigenvector of
+ * the smallest eigenvalue l0, oriented, then rounded to fp32.
+ *   mode 0: no orientation (the sign is whatever the decomposition gives; orient may be NULL).
+ *   mode 1: orient = viewpoints (B,3); n is flipped iff n . (view_b - s_i) < 0, evaluated in fp64.
+ *   mode 2: orient = reference normals (B,Ns_max,3); n is flipped iff n . ref_i < 0 (a zero reference does not flip).
+ *   normals (B,Ns_max,3); variation (B,Ns_max) = l0 / (l0 + l1 + l2), 0 when the trace is 0; skipped when NULL.
+ *   Rows beyond src_counts[b]: zeros.  One launch, no workspace. */
+int gs_knn_normals(const float *src, const int32_t *src_counts, int Ns_max, const float *tgt,
+                   const int32_t *tgt_counts, int Nt_max, int B, int K, const uint64_t *keys, int mode,
+                   const float *orient, float *normals, float *variation, gs_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,515 @@
+// libgradslam_hip -- TSDF volumes (T): fuse posed RGB-D frames into a dense truncated signed-distance grid, take the surface out.
+//
+//   I  gs_tsdf_integrate: one launch per chunk of up to 32 frames.  One thread per 4 consecutive x-voxels: their tsdf, weight
+//      and colour stay in registers while the chunk's frames are applied in order (gs_tsdf.hpp: centre, observe, average), the
+//      chunk's cameras sit in LDS; the volume is read and written once per chunk.  Every voxel is read and written by one thread:
+//      the outputs may alias the inputs.  No workspace, no atomics, nothing synchronises the host.
+//      gs_tsdf_integrate_backward: chunks in reverse order, one thread per voxel.  The thread re-takes the forward's decisions
+//      (a 32-bit update mask of the chunk, the number of updates before the chunk), then walks the chunk's frames backwards with
+//      the weight rebuilt from the mask.  The depth / rgb adjoints of a pixel are sums over many voxels: the exact fixed-point
+//      fold of gs_fixed128.hpp, per chunk   memset -> tsdf_bwd_k<MAX> -> tsdf_bwd_k<ACC> -> tsdf_fold_finish_k
+//      (the two passes compute the same terms: storing them would take 16 B per voxel and frame).
+//   E  gs_tsdf_extract: the stable compaction of gs_compact.hpp over the 3 nx ny nz edge slots:
+//        tsdf_count_k -> tsdf_scan_k -> tsdf_write_k (skipped when cap == 0)
+//      gs_tsdf_extract_backward: a memset and six (axis, end) passes over the rows; within a pass no two rows share a voxel, so
+//      the adds are plain read-modify-writes in a fixed order.
+// Batch elements ride in grid.y.
+#include <cmath>
+#include <stddef.h>
+
+#include <algorithm>
+
+#include "gs_compact.hpp"
+#include "gs_fixed128.hpp"
+#include "gs_tsdf.hpp"
+
+namespace gs {
+
+// ------------------------------------------------------------------ I: integration.  grid (x: quads of x-voxels, y: batch element)
+template <bool VEC>
+__device__ __forceinline__ void tsdf_ld4(const float *p, int nv, float *r) {
+    if (VEC) {
+        const float4 t = *reinterpret_cast<const float4 *>(p);
+        r[0] = t.x; r[1] = t.y; r[2] = t.z; r[3] = t.w;
+    } else {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) r[k] = k < nv ? p[k] : 0.0f;
+    }
+}
+template <bool VEC>
+__device__ __forceinline__ void tsdf_st4(float *p, int nv, const float *r) {
+    if (VEC) {
+        *reinterpret_cast<float4 *>(p) = make_float4(r[0], r[1], r[2], r[3]);
+    } else {
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+            if (k < nv) p[k] = r[k];
+    }
+}
+
+// VEC: nx is a multiple of 4 and every pointer is 16-byte aligned, so a thread's 4 voxels move as one 16-byte access
+// (in / out are not __restrict__: they may alias)
+template <bool VEC, bool COLOR>
+__global__ __launch_bounds__(TSDF_T) void tsdf_integrate_k(TsdfVol vol, TsdfFrames fr, const float *tsdf_in, const float *weight_in,
+                                                           const float *color_in, float *tsdf_out, float *weight_out, float *color_out) {
+    __shared__ Cam cams[TSDF_CHUNK];
+    const int b = blockIdx.y;
+    tsdf_load_cams(cams, fr, b, fr.l0, fr.Lc);
+    const int nx4 = (vol.nx + 3) >> 2;
+    const int64_t nq = (int64_t)nx4 * vol.ny * vol.nz;
+    const int64_t q = (int64_t)blockIdx.x * TSDF_T + threadIdx.x;
+    if (q >= nq) return;
+    const int row = (int)(q / nx4), x0 = (int)(q - (int64_t)row * nx4) * 4;
+    const int iz = row / vol.ny, iy = row - iz * vol.ny;
+    const int nv = min(4, vol.nx - x0);
+    const int64_t at = (int64_t)b * tsdf_nvox(vol) + (int64_t)row * vol.nx + x0;
+    const float *o = vol.origin + 3 * b;
+    const float cy = tsdf_centre1(o[1], iy, vol.v), cz = tsdf_centre1(o[2], iz, vol.v);
+    float cx[4], f[4], wt[4], col[12];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) cx[k] = tsdf_centre1(o[0], x0 + k, vol.v);
+    tsdf_ld4<VEC>(tsdf_in + at, nv, f);
+    tsdf_ld4<VEC>(weight_in + at, nv, wt);
+    if (COLOR) {
+#pragma unroll
+        for (int k = 0; k < 3; ++k) tsdf_ld4<VEC>(color_in + 3 * at + 4 * k, 3 * nv - 4 * k, col + 4 * k);
+    }
+    const int64_t HW = (int64_t)fr.H * fr.W;
+    for (int l = 0; l < fr.Lc; ++l) {
+        const int64_t frame = ((int64_t)b * fr.L + fr.l0 + l) * HW;
+        const float *dl = fr.depth + frame;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            int pix;
+            float sdf;
+            if (k >= nv || !tsdf_observe(cams[l], f3{cx[k], cy, cz}, dl, fr, vol.trunc, pix, sdf)) continue;
+            const float t = tsdf_sample(sdf, vol.trunc);
+            f[k] = tsdf_average(wt[k], f[k], t);
+            if (COLOR) {
+                const f3 c = ld3(fr.rgb, frame + pix);
+                col[3 * k] = tsdf_average(wt[k], col[3 * k], c.x);
+                col[3 * k + 1] = tsdf_average(wt[k], col[3 * k + 1], c.y);
+                col[3 * k + 2] = tsdf_average(wt[k], col[3 * k + 2], c.z);
+            }
+            wt[k] = tsdf_next_weight(wt[k], vol.maxw);
+        }
+    }
+    tsdf_st4<VEC>(tsdf_out + at, nv, f);
+    tsdf_st4<VEC>(weight_out + at, nv, wt);
+    if (COLOR) {
+#pragma unroll
+        for (int k = 0; k < 3; ++k) tsdf_st4<VEC>(color_out + 3 * at + 4 * k, 3 * nv - 4 * k, col + 4 * k);
+    }
+}
+
+// ------------------------------------------------------------------ reverse pass of the integration
+// the fold of one chunk: per pixel (b, l, h, w) of the chunk 4 sums (depth, r, g, b), each a (lo, hi) pair of 64-bit words
+struct TsdfFold {
+    uint32_t *maxbits;        // 1
+    uint32_t *flags;          // npix: 3 bits per sum (NaN, +inf, -inf)
+    unsigned long long *acc;  // npix x 4 x (lo, hi)
+};
+static inline size_t tsdf_fold_layout(int B, int L, int H, int W, void *ws, TsdfFold *out) {
+    const size_t npix = (size_t)B * std::min(L, TSDF_CHUNK) * H * W;
+    Carve c{(char *)ws};
+    uint32_t *maxbits = c.take<uint32_t>(4);
+    uint32_t *flags = c.take<uint32_t>(4 * npix);
+    unsigned long long *acc = c.take<unsigned long long>(64 * npix);
+    if (out) *out = TsdfFold{maxbits, flags, acc};
+    return c.off;
+}
+
+__device__ __forceinline__ uint32_t tsdf_fold_max(uint32_t mx, float x) {
+    const uint32_t u = __float_as_uint(x) & 0x7fffffffu;
+    return (u < 0x7f800000u && u > mx) ? u : mx;
+}
+__device__ __forceinline__ void tsdf_fold_add(const TsdfFold &fold, int64_t p, int ch, float x, int E) {
+    const uint32_t bits = __float_as_uint(x);
+    if ((bits & 0x7fffffffu) >= 0x7f800000u) {
+        const uint32_t code = (bits & 0x7fffffu) ? 1u : ((bits >> 31) ? 4u : 2u);
+        atomicOr(fold.flags + p, code << (3 * ch));
+        return;
+    }
+    const __int128 v = det_to_fixed(bits, E);
+    if (v == 0) return;
+    unsigned long long *a = fold.acc + (p * 4 + ch) * 2;
+    const unsigned long long lo = (unsigned long long)v;
+    unsigned long long hi = (unsigned long long)(v >> 64);
+    const unsigned long long old = atomicAdd(a, lo);
+    hi += (old + lo < old) ? 1ull : 0ull;  // the carry out of the low word, counted once by the adder that caused it
+    if (hi) atomicAdd(a + 1, hi);
+}
+
+// grid (x: voxels, y: batch element).  ACC = false: the largest finite |term| of the chunk; ACC = true: the terms go into the
+// fold and the adjoints carried to the frames before the chunk are written (g_*_src -> g_*_dst: the same thread reads and writes
+// a voxel, so they may alias).  No thread leaves early: the camera loads are block-wide.
+template <bool ACC>
+__global__ __launch_bounds__(TSDF_T) void tsdf_bwd_k(TsdfVol vol, TsdfFrames fr, const float *__restrict__ weight_in, const float *g_tsdf_src,
+                                                     const float *g_color_src, float *g_tsdf_dst, float *g_color_dst, TsdfFold fold, int lg) {
+    __shared__ Cam cams[TSDF_CHUNK];
+    const int b = blockIdx.y;
+    const int64_t nvox = tsdf_nvox(vol), j = (int64_t)blockIdx.x * TSDF_T + threadIdx.x;
+    const bool live = j < nvox;
+    const int64_t at = (int64_t)b * nvox + (live ? j : 0);
+    int ix, iy, iz;
+    tsdf_unflatten(vol, live ? (int)j : 0, ix, iy, iz);
+    const f3 c = tsdf_centre(vol.origin + 3 * b, ix, iy, iz, vol.v);
+    const int64_t HW = (int64_t)fr.H * fr.W;
+    int pix;
+    float sdf;
+    int n0 = 0;  // updates of this voxel by the frames before the chunk
+    for (int s = 0; s < fr.l0; s += TSDF_CHUNK) {
+        const int n = min(TSDF_CHUNK, fr.l0 - s);
+        __syncthreads();
+        tsdf_load_cams(cams, fr, b, s, n);
+        if (live)
+            for (int l = 0; l < n; ++l)
+                if (tsdf_observe(cams[l], c, fr.depth + ((int64_t)b * fr.L + s + l) * HW, fr, vol.trunc, pix, sdf)) ++n0;
+    }
+    __syncthreads();
+    tsdf_load_cams(cams, fr, b, fr.l0, fr.Lc);
+    uint32_t mask = 0;
+    if (live)
+        for (int l = 0; l < fr.Lc; ++l)
+            if (tsdf_observe(cams[l], c, fr.depth + ((int64_t)b * fr.L + fr.l0 + l) * HW, fr, vol.trunc, pix, sdf)) mask |= 1u << l;
+    const bool color = g_color_src != nullptr;
+    float g = live ? g_tsdf_src[at] : 0.0f;
+    f3 gc = (live && color) ? ld3(g_color_src, at) : f3{0.0f, 0.0f, 0.0f};
+    const float W0 = live ? weight_in[at] : 0.0f;
+    const int E = ACC ? det_scale(*fold.maxbits, lg) : 0;
+    uint32_t mx = 0;
+    for (int l = fr.Lc - 1; l >= 0; --l) {
+        if (!((mask >> l) & 1u)) continue;
+        tsdf_observe(cams[l], c, fr.depth + ((int64_t)b * fr.L + fr.l0 + l) * HW, fr, vol.trunc, pix, sdf);
+        const float W = tsdf_weight_after(W0, n0 + __popc(mask & ((1u << l) - 1u)), vol.maxw);
+        const float den = W + 1.0f, keep = W / den;
+        const float gd = sdf < vol.trunc ? (g / den) / vol.trunc : 0.0f;  // t = 1 beyond trunc: no gradient
+        const f3 gr{gc.x / den, gc.y / den, gc.z / den};
+        g = g * keep;
+        gc = f3{gc.x * keep, gc.y * keep, gc.z * keep};
+        if (ACC) {
+            const int64_t p = ((int64_t)b * fr.Lc + l) * HW + pix;
+            tsdf_fold_add(fold, p, 0, gd, E);
+            if (color) {
+                tsdf_fold_add(fold, p, 1, gr.x, E);
+                tsdf_fold_add(fold, p, 2, gr.y, E);
+                tsdf_fold_add(fold, p, 3, gr.z, E);
+            }
+        } else {
+            mx = tsdf_fold_max(mx, gd);
+            if (color) mx = tsdf_fold_max(tsdf_fold_max(tsdf_fold_max(mx, gr.x), gr.y), gr.z);
+        }
+    }
+    if (ACC) {
+        if (live) {
+            g_tsdf_dst[at] = g;
+            if (color) st3(g_color_dst, at, gc);
+        }
+    } else {
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) mx = max(mx, (uint32_t)__shfl_xor((int)mx, off, kWave));
+        if ((threadIdx.x & 63) == 0 && mx > 0) atomicMax(fold.maxbits, mx);
+    }
+}
+
+// every pixel of the chunk's frames: each sum rounded once to fp32.  g_rgb may be NULL
+__global__ __launch_bounds__(TSDF_T) void tsdf_fold_finish_k(TsdfFold fold, int lg, int B, int L, int l0, int Lc, int64_t HW,
+                                                             float *__restrict__ g_depth, float *__restrict__ g_rgb) {
+    const int E = det_scale(*fold.maxbits, lg);
+    const int64_t total = (int64_t)B * Lc * HW;
+    for (int64_t p = (int64_t)blockIdx.x * TSDF_T + threadIdx.x; p < total; p += (int64_t)gridDim.x * TSDF_T) {
+        const int64_t bl = p / HW, pix = p - bl * HW;
+        const int b = (int)(bl / Lc), l = (int)(bl - (int64_t)b * Lc);
+        const int64_t out = ((int64_t)b * L + l0 + l) * HW + pix;
+        const uint32_t fl = fold.flags[p];
+        for (int ch = 0; ch < (g_rgb ? 4 : 1); ++ch) {
+            const uint32_t f = (fl >> (3 * ch)) & 7u;
+            float r;
+            if (f) r = ((f & 1u) || (f & 6u) == 6u) ? __int_as_float(0x7fc00000) : __int_as_float((f & 2u) ? 0x7f800000 : (int)0xff800000);
+            else r = det_to_float(fold.acc[(p * 4 + ch) * 2], fold.acc[(p * 4 + ch) * 2 + 1], E);
+            if (ch == 0) g_depth[out] = r;
+            else g_rgb[3 * out + ch - 1] = r;
+        }
+    }
+}
+
+// ------------------------------------------------------------------ E: extraction.  grid (x: compaction blocks, y: batch element)
+struct TsdfState {
+    const float *tsdf, *weight, *color;  // of ONE batch element; color may be NULL
+    float minw;
+};
+struct TsdfCrossPred {
+    TsdfVol vol;
+    TsdfState s;
+    __device__ bool operator()(int64_t e) const {
+        TsdfEdge ed;
+        if (!tsdf_edge(vol, e, ed)) return false;
+        return tsdf_crosses(s.tsdf[ed.j], s.weight[ed.j], s.tsdf[ed.j1], s.weight[ed.j1], s.minw);
+    }
+};
+// D_k(j): the difference of tsdf along one axis over the observed neighbours inside the grid (i: the voxel's index on that axis,
+// n: the grid's size, stride: the neighbour's distance in voxels)
+__device__ __forceinline__ float tsdf_diff(const TsdfState &s, int j, int i, int n, int stride) {
+    const bool hp = i + 1 < n && s.weight[j + stride] >= s.minw, hm = i > 0 && s.weight[j - stride] >= s.minw;
+    if (hp && hm) return 0.5f * (s.tsdf[j + stride] - s.tsdf[j - stride]);
+    if (hp) return s.tsdf[j + stride] - s.tsdf[j];
+    if (hm) return s.tsdf[j] - s.tsdf[j - stride];
+    return 0.0f;
+}
+__device__ __forceinline__ f3 tsdf_grad(const TsdfVol &g, const TsdfState &s, int j, int ix, int iy, int iz) {
+    return f3{tsdf_diff(s, j, ix, g.nx, 1), tsdf_diff(s, j, iy, g.ny, g.nx), tsdf_diff(s, j, iz, g.nz, g.nx * g.ny)};
+}
+struct TsdfRowWriter {
+    TsdfVol vol;
+    TsdfState s;
+    const float *origin;  // of this batch element
+    float *points, *normals, *colors;  // (cap, 3) of this batch element; colors may be NULL
+    int32_t *edge;
+    int cap;
+    __device__ void operator()(int64_t e, int64_t pos) const {
+        if (pos >= cap) return;
+        TsdfEdge ed;
+        tsdf_edge(vol, e, ed);
+        const float f0 = s.tsdf[ed.j], f1 = s.tsdf[ed.j1];
+        const float t = tsdf_cross_s(f0, f1);
+        f3 p = tsdf_centre(origin, ed.ix, ed.iy, ed.iz, vol.v);
+        if (ed.a == 0) p.x = p.x + t * vol.v;
+        else if (ed.a == 1) p.y = p.y + t * vol.v;
+        else p.z = p.z + t * vol.v;
+        st3(points, pos, p);
+        const f3 d0 = tsdf_grad(vol, s, ed.j, ed.ix, ed.iy, ed.iz);
+        const f3 d1 = tsdf_grad(vol, s, ed.j1, ed.ix + (ed.a == 0), ed.iy + (ed.a == 1), ed.iz + (ed.a == 2));
+        f3 n{d0.x + t * (d1.x - d0.x), d0.y + t * (d1.y - d0.y), d0.z + t * (d1.z - d0.z)};
+        float nn = sqrtf(__fmaf_rn(n.z, n.z, __fmaf_rn(n.y, n.y, n.x * n.x)));  // (_compute_normal_map's rule: zero stays zero)
+        nn = (nn == 0.0f) ? 1.0f : nn;
+        st3(normals, pos, f3{n.x / nn, n.y / nn, n.z / nn});
+        if (colors) {
+            const f3 c0 = ld3(s.color, ed.j), c1 = ld3(s.color, ed.j1);
+            st3(colors, pos, f3{c0.x + t * (c1.x - c0.x), c0.y + t * (c1.y - c0.y), c0.z + t * (c1.z - c0.z)});
+        }
+        edge[pos] = (int32_t)e;
+    }
+};
+struct TsdfExtractWs {
+    int *bcount, *boffset;  // B x nb each
+    int nb;
+};
+static inline size_t tsdf_extract_layout(int B, int64_t nvox, void *ws, TsdfExtractWs *out) {
+    const int nb = compact_blocks(3 * nvox);
+    Carve c{(char *)ws};
+    int *bcount = c.take<int>(sizeof(int) * (size_t)B * nb);
+    int *boffset = c.take<int>(sizeof(int) * (size_t)B * nb);
+    if (out) *out = TsdfExtractWs{bcount, boffset, nb};
+    return c.off;
+}
+__device__ __forceinline__ TsdfState tsdf_state_of(const float *tsdf, const float *weight, const float *color, float minw, int b, int64_t nvox) {
+    return TsdfState{tsdf + b * nvox, weight + b * nvox, color ? color + 3 * b * nvox : nullptr, minw};
+}
+
+__global__ __launch_bounds__(kCT) void tsdf_count_k(TsdfVol vol, const float *__restrict__ tsdf, const float *__restrict__ weight, float minw,
+                                                    TsdfExtractWs w) {
+    const int b = blockIdx.y;
+    const int64_t nvox = tsdf_nvox(vol);
+    const TsdfCrossPred pred{vol, tsdf_state_of(tsdf, weight, nullptr, minw, b, nvox)};
+    compact_count_body(3 * nvox, pred, w.bcount + (int64_t)b * w.nb, (unsigned char *)nullptr, (int)blockIdx.x, w.nb);
+}
+// grid (x: batch element), one block each; the total is n_points[b]
+__global__ __launch_bounds__(1024) void tsdf_scan_k(TsdfExtractWs w, int32_t *__restrict__ n_points) {
+    const int b = blockIdx.x;
+    compact_scan_body(w.bcount + (int64_t)b * w.nb, w.nb, w.boffset + (int64_t)b * w.nb, (int *)(n_points + b));
+}
+__global__ __launch_bounds__(kCT) void tsdf_write_k(TsdfVol vol, const float *__restrict__ tsdf, const float *__restrict__ weight,
+                                                    const float *__restrict__ color, float minw, TsdfExtractWs w, int cap,
+                                                    float *__restrict__ points, float *__restrict__ normals, float *__restrict__ colors,
+                                                    int32_t *__restrict__ edge) {
+    const int b = blockIdx.y;
+    const int64_t nvox = tsdf_nvox(vol), row0 = (int64_t)b * cap;
+    const TsdfState s = tsdf_state_of(tsdf, weight, color, minw, b, nvox);
+    const TsdfCrossPred pred{vol, s};
+    const TsdfRowWriter wr{vol, s, vol.origin + 3 * b, points + 3 * row0, normals + 3 * row0, (colors && color) ? colors + 3 * row0 : nullptr,
+                           edge + row0, cap};
+    compact_write_body<TsdfCrossPred, TsdfRowWriter, false>(3 * nvox, pred, wr, w.boffset + (int64_t)b * w.nb, (int *)nullptr,
+                                                            (const unsigned char *)nullptr, (int)blockIdx.x, w.nb);
+}
+
+// One (axis, end) pass of the reverse pass: rows whose edge runs along `axis` add into the voxel at their end `end`.  A voxel is
+// end 0 of at most one edge per axis and end 1 of at most one: no two rows of a pass meet.  grid (x: rows, y: batch element)
+__global__ __launch_bounds__(TSDF_T) void tsdf_extract_bwd_k(TsdfVol vol, const float *__restrict__ tsdf, const float *__restrict__ color,
+                                                             const int32_t *__restrict__ edge, const int32_t *__restrict__ n_points, int cap,
+                                                             const float *__restrict__ g_points, const float *__restrict__ g_colors, int axis,
+                                                             int end, float *g_tsdf, float *g_color) {
+    const int b = blockIdx.y, n = min(max(n_points[b], 0), cap);
+    const int r = blockIdx.x * TSDF_T + threadIdx.x;
+    if (r >= n) return;
+    const int64_t nvox = tsdf_nvox(vol), row = (int64_t)b * cap + r;
+    const int64_t e = edge[row];
+    TsdfEdge ed;
+    if (e < 0 || e >= 3 * nvox || !tsdf_edge(vol, e, ed) || ed.a != axis) return;
+    const float *f = tsdf + b * nvox;
+    const float f0 = f[ed.j], f1 = f[ed.j1];
+    const float t = tsdf_cross_s(f0, f1), den = (f0 - f1) * (f0 - f1);
+    const f3 gp = g_points ? ld3(g_points, row) : f3{0.0f, 0.0f, 0.0f};
+    float gs = vol.v * (axis == 0 ? gp.x : (axis == 1 ? gp.y : gp.z));
+    const int64_t at = b * nvox + (end ? ed.j1 : ed.j);
+    if (g_colors && color) {
+        const f3 gc = ld3(g_colors, row);
+        const f3 c0 = ld3(color, b * nvox + ed.j), c1 = ld3(color, b * nvox + ed.j1);
+        gs = ((gs + gc.x * (c1.x - c0.x)) + gc.y * (c1.y - c0.y)) + gc.z * (c1.z - c0.z);
+        const float m = end ? t : (-f1) / (f0 - f1);  // 1 - s, without the cancellation of 1.0f - t near s = 1
+        const f3 old = ld3(g_color, at);
+        st3(g_color, at, f3{old.x + m * gc.x, old.y + m * gc.y, old.z + m * gc.z});
+    }
+    g_tsdf[at] = g_tsdf[at] + gs * (end ? f0 / den : (-f1) / den);
+}
+
+static inline bool tsdf_vol_ok(int B, int nx, int ny, int nz) {
+    return B > 0 && B <= 65535 && nx > 0 && ny > 0 && nz > 0 && (int64_t)nx * ny * nz <= TSDF_NMAX;
+}
+static inline bool tsdf_pos(float x) { return x > 0.0f && x < INFINITY; }
+static inline int tsdf_lg(int64_t n) {  // ceil(log2(n)): a pixel receives at most one term per voxel
+    int lg = 0;
+    while (((int64_t)1 << lg) < n) ++lg;
+    return lg;
+}
+static inline bool tsdf_aligned16(const void *p) { return ((uintptr_t)p & 15u) == 0; }
+static inline TsdfFrames tsdf_frames(const float *depth, const float *rgb, const float *K, const float *poses, int L, int H, int W) {
+    return TsdfFrames{depth, rgb, K, poses, L, H, W, 0, 0, (float)((double)W - 0.999), (float)((double)H - 0.999)};
+}
+
+}  // namespace gs
+
+using namespace gs;
+
+#define TSDF_REQUIRE_VOLUME(name)                                                                                                       \
+    GS_REQUIRE(tsdf_vol_ok(B, nx, ny, nz), name ": bad volume B=%d dims=(%d, %d, %d) (1 <= B <= 65535, nx ny nz <= 2^29)", B, nx, ny, nz); \
+    GS_REQUIRE(tsdf_pos(voxel_size), name ": voxel_size must be finite and positive, got %g", (double)voxel_size)
+#define TSDF_REQUIRE_FRAMES(name)                                                                                        \
+    GS_REQUIRE(L > 0 && H > 0 && W > 0 && (int64_t)H * W <= INT32_MAX, name ": bad frames L=%d H=%d W=%d", L, H, W);      \
+    GS_REQUIRE(tsdf_pos(trunc) && tsdf_pos(max_weight), name ": trunc and max_weight must be finite and positive, got %g and %g", \
+               (double)trunc, (double)max_weight)
+
+extern "C" {
+
+int gs_tsdf_integrate(const float *depth, const float *rgb, const float *intrinsics, const float *poses, int B, int L, int H, int W, int nx,
+                      int ny, int nz, float voxel_size, const float *origin, float trunc, float max_weight, const float *tsdf_in,
+                      const float *weight_in, const float *color_in, float *tsdf_out, float *weight_out, float *color_out,
+                      gs_stream_t stream) {
+    GS_REQUIRE(depth && intrinsics && poses && origin && tsdf_in && weight_in && tsdf_out && weight_out, "gs_tsdf_integrate: NULL argument");
+    GS_REQUIRE((color_in != nullptr) == (color_out != nullptr) && (!color_in || rgb),
+               "gs_tsdf_integrate: color_in, color_out and rgb go together");
+    TSDF_REQUIRE_VOLUME("gs_tsdf_integrate");
+    TSDF_REQUIRE_FRAMES("gs_tsdf_integrate");
+    const TsdfVol vol{nx, ny, nz, voxel_size, trunc, max_weight, origin};
+    TsdfFrames fr = tsdf_frames(depth, color_in ? rgb : nullptr, intrinsics, poses, L, H, W);
+    const bool vec = nx % 4 == 0 && tsdf_aligned16(tsdf_in) && tsdf_aligned16(weight_in) && tsdf_aligned16(color_in) &&
+                     tsdf_aligned16(tsdf_out) && tsdf_aligned16(weight_out) && tsdf_aligned16(color_out);
+    const dim3 grid(cdiv((int64_t)((nx + 3) / 4) * ny * nz, TSDF_T), B);
+    for (int l0 = 0; l0 < L; l0 += TSDF_CHUNK) {  // later chunks continue on the outputs
+        fr.l0 = l0;
+        fr.Lc = std::min(TSDF_CHUNK, L - l0);
+        const float *ti = l0 ? tsdf_out : tsdf_in, *wi = l0 ? weight_out : weight_in, *ci = l0 ? color_out : color_in;
+        auto k = color_in ? (vec ? tsdf_integrate_k<true, true> : tsdf_integrate_k<false, true>)
+                          : (vec ? tsdf_integrate_k<true, false> : tsdf_integrate_k<false, false>);
+        hipLaunchKernelGGL(k, grid, dim3(TSDF_T), 0, (hipStream_t)stream, vol, fr, ti, wi, ci, tsdf_out, weight_out, color_out);
+        GS_LAUNCH_CHECK("gs_tsdf_integrate");
+    }
+    return GS_OK;
+}
+
+size_t gs_tsdf_integrate_backward_ws_bytes(int B, int L, int H, int W) {
+    if (B <= 0 || B > 65535 || L <= 0 || H <= 0 || W <= 0) return 0;
+    return tsdf_fold_layout(B, L, H, W, nullptr, nullptr);
+}
+
+int gs_tsdf_integrate_backward(const float *depth, const float *intrinsics, const float *poses, int B, int L, int H, int W, int nx, int ny,
+                               int nz, float voxel_size, const float *origin, float trunc, float max_weight, const float *weight_in,
+                               const float *g_tsdf_out, const float *g_color_out, float *g_tsdf_in, float *g_color_in, float *g_depth,
+                               float *g_rgb, void *ws, size_t ws_bytes, gs_stream_t stream) {
+    GS_REQUIRE(depth && intrinsics && poses && origin && weight_in && g_tsdf_out && g_tsdf_in && g_depth,
+               "gs_tsdf_integrate_backward: NULL argument");
+    GS_REQUIRE((g_color_out != nullptr) == (g_color_in != nullptr) && (g_color_out != nullptr) == (g_rgb != nullptr),
+               "gs_tsdf_integrate_backward: g_color_out, g_color_in and g_rgb go together");
+    TSDF_REQUIRE_VOLUME("gs_tsdf_integrate_backward");
+    TSDF_REQUIRE_FRAMES("gs_tsdf_integrate_backward");
+    const size_t need = gs_tsdf_integrate_backward_ws_bytes(B, L, H, W);
+    if (!ws || ws_bytes < need) {
+        set_error("gs_tsdf_integrate_backward: workspace too small (%zu < %zu)", ws_bytes, need);
+        return GS_ERR_WORKSPACE_TOO_SMALL;
+    }
+    hipStream_t st = (hipStream_t)stream;
+    const TsdfVol vol{nx, ny, nz, voxel_size, trunc, max_weight, origin};
+    TsdfFrames fr = tsdf_frames(depth, nullptr, intrinsics, poses, L, H, W);
+    TsdfFold fold;
+    tsdf_fold_layout(B, L, H, W, ws, &fold);
+    const int64_t nvox = tsdf_nvox(vol), HW = (int64_t)H * W;
+    const int lg = tsdf_lg(nvox);
+    const dim3 grid(cdiv(nvox, TSDF_T), B);
+    const int last = (L - 1) / TSDF_CHUNK * TSDF_CHUNK;
+    for (int l0 = last; l0 >= 0; l0 -= TSDF_CHUNK) {  // the last chunk starts from the upstream adjoints, the others from the carried ones
+        fr.l0 = l0;
+        fr.Lc = std::min(TSDF_CHUNK, L - l0);
+        const float *gt = l0 == last ? g_tsdf_out : g_tsdf_in, *gc = l0 == last ? g_color_out : g_color_in;
+        GS_HIP(hipMemsetAsync(ws, 0, need, st), "gs_tsdf_integrate_backward/zero");
+        hipLaunchKernelGGL(tsdf_bwd_k<false>, grid, dim3(TSDF_T), 0, st, vol, fr, weight_in, gt, gc, g_tsdf_in, g_color_in, fold, lg);
+        hipLaunchKernelGGL(tsdf_bwd_k<true>, grid, dim3(TSDF_T), 0, st, vol, fr, weight_in, gt, gc, g_tsdf_in, g_color_in, fold, lg);
+        GS_LAUNCH_CHECK("gs_tsdf_integrate_backward/fold");
+        hipLaunchKernelGGL(tsdf_fold_finish_k, dim3(std::min(cdiv((int64_t)B * fr.Lc * HW, TSDF_T), 4096)), dim3(TSDF_T), 0, st, fold, lg, B, L,
+                           l0, fr.Lc, HW, g_depth, g_rgb);
+        GS_LAUNCH_CHECK("gs_tsdf_integrate_backward/finish");
+    }
+    return GS_OK;
+}
+
+size_t gs_tsdf_extract_ws_bytes(int B, int nx, int ny, int nz) {
+    if (!tsdf_vol_ok(B, nx, ny, nz)) return 0;
+    return tsdf_extract_layout(B, (int64_t)nx * ny * nz, nullptr, nullptr);
+}
+
+int gs_tsdf_extract(const float *tsdf, const float *weight, const float *color, int B, int nx, int ny, int nz, float voxel_size,
+                    const float *origin, float min_weight, int cap, float *points, float *normals, float *colors, int32_t *edge,
+                    int32_t *n_points, void *ws, size_t ws_bytes, gs_stream_t stream) {
+    GS_REQUIRE(tsdf && weight && origin && n_points, "gs_tsdf_extract: NULL argument");
+    GS_REQUIRE(cap >= 0 && (cap == 0 || (points && normals && edge)), "gs_tsdf_extract: cap = %d rows need points, normals and edge", cap);
+    TSDF_REQUIRE_VOLUME("gs_tsdf_extract");
+    GS_REQUIRE(min_weight == min_weight, "gs_tsdf_extract: min_weight must be a number");
+    const size_t need = gs_tsdf_extract_ws_bytes(B, nx, ny, nz);
+    if (!ws || ws_bytes < need) {
+        set_error("gs_tsdf_extract: workspace too small (%zu < %zu)", ws_bytes, need);
+        return GS_ERR_WORKSPACE_TOO_SMALL;
+    }
+    hipStream_t st = (hipStream_t)stream;
+    const TsdfVol vol{nx, ny, nz, voxel_size, 0.0f, 0.0f, origin};
+    TsdfExtractWs w;
+    tsdf_extract_layout(B, tsdf_nvox(vol), ws, &w);
+    hipLaunchKernelGGL(tsdf_count_k, dim3(w.nb, B), dim3(kCT), 0, st, vol, tsdf, weight, min_weight, w);
+    hipLaunchKernelGGL(tsdf_scan_k, dim3(B), dim3(1024), 0, st, w, n_points);
+    GS_LAUNCH_CHECK("gs_tsdf_extract/count");
+    if (cap > 0) {
+        hipLaunchKernelGGL(tsdf_write_k, dim3(w.nb, B), dim3(kCT), 0, st, vol, tsdf, weight, color, min_weight, w, cap, points, normals, colors,
+                           edge);
+        GS_LAUNCH_CHECK("gs_tsdf_extract/write");
+    }
+    return GS_OK;
+}
+
+int gs_tsdf_extract_backward(const float *tsdf, const float *color, int B, int nx, int ny, int nz, float voxel_size, const int32_t *edge,
+                             const int32_t *n_points, int cap, const float *g_points, const float *g_colors, float *g_tsdf, float *g_color,
+                             gs_stream_t stream) {
+    GS_REQUIRE(tsdf && edge && n_points && g_tsdf, "gs_tsdf_extract_backward: NULL argument");
+    GS_REQUIRE((g_color == nullptr) || color, "gs_tsdf_extract_backward: g_color needs color");
+    GS_REQUIRE(cap > 0, "gs_tsdf_extract_backward: cap must be positive, got %d", cap);
+    TSDF_REQUIRE_VOLUME("gs_tsdf_extract_backward");
+    hipStream_t st = (hipStream_t)stream;
+    const TsdfVol vol{nx, ny, nz, voxel_size, 0.0f, 0.0f, nullptr};
+    const int64_t n = (int64_t)B * tsdf_nvox(vol);
+    GS_HIP(hipMemsetAsync(g_tsdf, 0, sizeof(float) * n, st), "gs_tsdf_extract_backward/zero");
+    if (g_color) GS_HIP(hipMemsetAsync(g_color, 0, sizeof(float) * 3 * n, st), "gs_tsdf_extract_backward/zero");
+    for (int axis = 0; axis < 3; ++axis)
+        for (int end = 0; end < 2; ++end)
+            hipLaunchKernelGGL(tsdf_extract_bwd_k, dim3(cdiv(cap, TSDF_T), B), dim3(TSDF_T), 0, st, vol, tsdf, g_color ? color : nullptr, edge,
+                               n_points, cap, g_points, g_color ? g_colors : nullptr, axis, end, g_tsdf, g_color);
+    GS_LAUNCH_CHECK("gs_tsdf_extract_backward");
+    return GS_OK;
+}
+
+}  // extern "C"

@@ -1300,3 +1300,258 @@ def knn_normals_raw(src, tgt, src_counts, tgt_counts, keys, mode: int = 0, orien
     call("gs_knn_normals", ptr(src), ptr(cs), Ns, ptr(tgt), ptr(ct), Nt, B, K, ptr(keys), int(mode), ptr(orient), ptr(normals),
          ptr(variation), stream())
     return normals, variation
+
+
+# ---------------------------------------------------------------------------------------------- T
+TSDF_NMAX = 1 << 29  # voxels per batch element: edge ids 3 j + a are int32
+TSDF_CHUNK = 32      # frames per integration launch
+
+
+def _tsdf_on_device(op, *tensors):
+    for t in tensors:
+        if t is not None and not torch.is_tensor(t):
+            raise TypeError("{}: expected a tensor; got {}".format(op, type(t)))
+        if t is not None and not t.is_cuda:
+            raise ValueError("{}: tensor is on {}; TSDF volumes only live on a HIP device (no CPU fallback is provided).".format(
+                op, t.device))
+    require_hip(*tensors, op=op)
+
+
+def _tsdf_positive(value, name, op):
+    try:
+        x = float(value)
+    except (TypeError, ValueError):
+        x = float("nan")
+    x32 = float(torch.tensor(x, dtype=torch.float32)) if math.isfinite(x) else x  # what the kernels compute with
+    if not (math.isfinite(x32) and x32 > 0.0):
+        raise ValueError("{}: {} should be a finite positive number. Got {!r}.".format(op, name, value))
+    return x
+
+
+def _tsdf_dims(dims, op):
+    try:
+        d = tuple(dims)
+        ok = len(d) == 3 and all(isinstance(n, int) and not isinstance(n, bool) and n > 0 for n in d)
+    except TypeError:
+        d, ok = dims, False
+    if not ok:
+        raise ValueError("{}: dims should be three positive integers (nx, ny, nz). Got {!r}.".format(op, dims))
+    if d[0] * d[1] * d[2] > TSDF_NMAX:
+        raise ValueError("{}: at most 2^29 voxels per batch element are supported. Got dims {} = {} voxels.".format(
+            op, d, d[0] * d[1] * d[2]))
+    return d
+
+
+def tsdf_origin(origin, B: int, device, op: str = "tsdf_origin") -> torch.Tensor:
+    """The (B,3) fp32 device tensor the kernels read: `origin` given as three numbers or B rows of three (host values, checked
+    to be finite, then uploaded), or a (B,3) / (3,) device tensor that is taken as it is (no host synchronisation)."""
+    if torch.is_tensor(origin) and origin.is_cuda:
+        o = _f32c(origin.detach())
+        if o.shape == (3,):
+            o = o.expand(B, 3).contiguous()
+        if tuple(o.shape) != (B, 3):
+            raise ValueError("{}: origin should have shape (3,) or ({}, 3). Got {}.".format(op, B, tuple(origin.shape)))
+        return o
+    try:
+        o = torch.as_tensor(origin, dtype=torch.float32)
+    except (TypeError, ValueError, RuntimeError):
+        raise ValueError("{}: origin should be three finite numbers, or one such row per batch element. Got {!r}.".format(op, origin))
+    if o.shape == (3,):
+        o = o.expand(B, 3)
+    if tuple(o.shape) != (B, 3) or not bool(torch.isfinite(o).all()):
+        raise ValueError("{}: origin should be finite, of shape (3,) or ({}, 3). Got {!r}.".format(op, B, origin))
+    return o.contiguous().to(device)
+
+
+def _tsdf_state(tsdf, weight, color, origin, voxel_size, op):
+    """Checks one volume's tensors -> (tsdf, weight, color, origin (B,3), (nx, ny, nz), voxel_size)."""
+    _tsdf_on_device(op, tsdf, weight, color)
+    if tsdf.ndim != 4 or tsdf.shape[0] == 0 or tsdf.shape[0] > 65535:
+        raise ValueError("{}: tsdf should have shape (B, nz, ny, nx) with 1 <= B <= 65535. Got {}.".format(op, tuple(tsdf.shape)))
+    B, nz, ny, nx = (int(n) for n in tsdf.shape)
+    dims = _tsdf_dims((nx, ny, nz), op)
+    if weight.shape != tsdf.shape:
+        raise ValueError("{}: weight should have the shape of tsdf {}. Got {}.".format(op, tuple(tsdf.shape), tuple(weight.shape)))
+    if color is not None and tuple(color.shape) != (B, nz, ny, nx, 3):
+        raise ValueError("{}: color should have shape {}. Got {}.".format(op, (B, nz, ny, nx, 3), tuple(color.shape)))
+    v = _tsdf_positive(voxel_size, "voxel_size", op)
+    origin = tsdf_origin(origin, B, tsdf.device, op)
+    _tsdf_on_device(op, origin)
+    return _f32c(tsdf), _f32c(weight), _f32c(color), origin, dims, v
+
+
+def _tsdf_frames(depth, rgb, K, poses, B, want_rgb, op):
+    if poses is None:
+        raise ValueError("{}: the frames need poses (camera-to-world, (B, L, 4, 4)).".format(op))
+    _tsdf_on_device(op, depth, rgb, K, poses)
+    if depth.ndim == 5 and depth.shape[-1] == 1:
+        depth = depth[..., 0]
+    if depth.ndim != 4 or depth.shape[0] != B or 0 in depth.shape:
+        raise ValueError("{}: depth should have shape ({}, L, H, W[, 1]) with L, H, W > 0. Got {}.".format(op, B, tuple(depth.shape)))
+    L, H, W = (int(n) for n in depth.shape[1:])
+    if want_rgb and (rgb is None or tuple(rgb.shape) != (B, L, H, W, 3)):
+        raise ValueError("{}: a volume with colours needs rgb of shape {}. Got {}.".format(
+            op, (B, L, H, W, 3), None if rgb is None else tuple(rgb.shape)))
+    if K.numel() != 16 * B or K.shape[-2:] != (4, 4):
+        raise ValueError("{}: intrinsics should hold one 4x4 matrix per batch element (B = {}). Got {}.".format(op, B, tuple(K.shape)))
+    if tuple(poses.shape) != (B, L, 4, 4):
+        raise ValueError("{}: poses should have shape {}. Got {}.".format(op, (B, L, 4, 4), tuple(poses.shape)))
+    return _f32c(depth), (_f32c(rgb) if want_rgb else None), _f32c(K), _f32c(poses), L, H, W
+
+
+def tsdf_integrate_raw(depth, rgb, K, poses, tsdf, weight, color, origin, voxel_size, trunc, max_weight, inplace: bool = False):
+    """Fuse the frames depth (B,L,H,W[,1]) / rgb (B,L,H,W,3) with intrinsics K (B,1,4,4) and camera-to-world poses (B,L,4,4) into
+    the volume tsdf / weight (B,nz,ny,nx), color (B,nz,ny,nx,3) or None -> the new (tsdf, weight, color).  Per voxel the frames
+    are applied in order (the rule: include/gradslam_hip.h, T); one launch per 32 frames; the result is what L single-frame calls
+    give, bit for bit.  `inplace` writes into the given tensors (which must then be contiguous fp32).  origin: see tsdf_origin."""
+    op = "tsdf_integrate"
+    if poses is None:
+        raise ValueError("{}: the frames need poses (camera-to-world, (B, L, 4, 4)).".format(op))
+    t_in, w_in, c_in, origin, (nx, ny, nz), v = _tsdf_state(tsdf, weight, color, origin, voxel_size, op)
+    B = t_in.shape[0]
+    depth, rgb, K, poses, L, H, W = _tsdf_frames(depth, rgb, K, poses, B, c_in is not None, op)
+    trunc, max_weight = _tsdf_positive(trunc, "trunc", op), _tsdf_positive(max_weight, "max_weight", op)
+    if inplace:
+        if any(a is not b for a, b in ((t_in, tsdf), (w_in, weight), (c_in, color))):
+            raise ValueError("{}: inplace needs contiguous float32 state tensors.".format(op))
+        t_out, w_out, c_out = t_in, w_in, c_in
+    else:
+        t_out, w_out = torch.empty_like(t_in), torch.empty_like(w_in)
+        c_out = None if c_in is None else torch.empty_like(c_in)
+    call("gs_tsdf_integrate", ptr(depth), ptr(rgb), ptr(K), ptr(poses), B, L, H, W, nx, ny, nz, v, ptr(origin), trunc, max_weight,
+         ptr(t_in), ptr(w_in), ptr(c_in), ptr(t_out), ptr(w_out), ptr(c_out), stream())
+    return t_out, w_out, c_out
+
+
+def tsdf_integrate_backward_raw(depth, K, poses, weight, origin, voxel_size, trunc, max_weight, g_tsdf, g_color=None):
+    """Adjoint of tsdf_integrate_raw: the adjoints g_tsdf (B,nz,ny,nx) / g_color (B,nz,ny,nx,3 or None) of the new state ->
+    (g_tsdf_in, g_color_in, g_depth (B,L,H,W), g_rgb (B,L,H,W,3)); `weight` is the weight BEFORE the integration.  The pixel sums
+    are exact and rounded once: the same bits from run to run (one path, with or without torch.use_deterministic_algorithms)."""
+    op = "tsdf_integrate_backward"
+    g_t, w_in, g_c, origin, (nx, ny, nz), v = _tsdf_state(g_tsdf, weight, g_color, origin, voxel_size, op)
+    B = g_t.shape[0]
+    depth, _, K, poses, L, H, W = _tsdf_frames(depth, None, K, poses, B, False, op)
+    trunc, max_weight = _tsdf_positive(trunc, "trunc", op), _tsdf_positive(max_weight, "max_weight", op)
+    dev = g_t.device
+    o_t = torch.empty_like(g_t)
+    o_c = None if g_c is None else torch.empty_like(g_c)
+    g_depth = torch.empty((B, L, H, W), dtype=torch.float32, device=dev)
+    g_rgb = None if g_c is None else torch.empty((B, L, H, W, 3), dtype=torch.float32, device=dev)
+    ws = workspace(ws_bytes("gs_tsdf_integrate_backward_ws_bytes", B, L, H, W), dev, "tsdf_bwd")
+    call("gs_tsdf_integrate_backward", ptr(depth), ptr(K), ptr(poses), B, L, H, W, nx, ny, nz, v, ptr(origin), trunc, max_weight,
+         ptr(w_in), ptr(g_t), ptr(g_c), ptr(o_t), ptr(o_c), ptr(g_depth), ptr(g_rgb), ptr(ws), ws.numel(), stream())
+    return o_t, o_c, g_depth, g_rgb
+
+
+class _TsdfIntegrateFn(torch.autograd.Function):
+    """(depth, rgb, tsdf, color | weight, K, poses, origin: constants) -> (tsdf', color', weight').  The pixel of a voxel, the three
+    skips, the t = 1 branch and the weight cap are constants of the graph; weight, poses and intrinsics receive None."""
+
+    @staticmethod
+    def forward(ctx, depth, rgb, tsdf, color, weight, K, poses, origin, voxel_size, trunc, max_weight):
+        t, w, c = tsdf_integrate_raw(depth, rgb, K, poses, tsdf, weight, color, origin, voxel_size, trunc, max_weight)
+        ctx.save_for_backward(depth, K, poses, weight, origin)
+        ctx.cfg = (voxel_size, trunc, max_weight)
+        ctx.depth_shape, ctx.has_color = tuple(depth.shape), color is not None
+        ctx.mark_non_differentiable(w)
+        return t, c, w
+
+    @staticmethod
+    def backward(ctx, g_t, g_c, _g_w):
+        depth, K, poses, weight, origin = ctx.saved_tensors
+        if g_t is None:
+            g_t = torch.zeros_like(weight)
+        if ctx.has_color and g_c is None:
+            g_c = torch.zeros(tuple(weight.shape) + (3,), dtype=torch.float32, device=weight.device)
+        o_t, o_c, g_depth, g_rgb = tsdf_integrate_backward_raw(depth, K, poses, weight, origin, *ctx.cfg, g_t, g_c if ctx.has_color else None)
+        need = ctx.needs_input_grad
+        return (g_depth.view(ctx.depth_shape) if need[0] else None, g_rgb if need[1] else None, o_t if need[2] else None,
+                o_c if need[3] else None, None, None, None, None, None, None, None)
+
+
+def tsdf_integrate(depth, rgb, K, poses, tsdf, weight, color, origin, voxel_size, trunc, max_weight):
+    """Autograd-aware tsdf_integrate_raw -> (tsdf, weight, color): gradients reach the old tsdf / color, depth and rgb."""
+    origin = tsdf_origin(origin, tsdf.shape[0], tsdf.device, "tsdf_integrate") if torch.is_tensor(tsdf) and tsdf.ndim == 4 else origin
+    t, c, w = _TsdfIntegrateFn.apply(depth, rgb, tsdf, color, weight, K, poses, origin, voxel_size, trunc, max_weight)
+    return t, w, c
+
+
+def tsdf_extract_raw(tsdf, weight, color, origin, voxel_size, min_weight: float = 1.0, cap: int = 0):
+    """The surface points of a volume: one per grid edge whose ends are observed (weight >= min_weight) and differ in the sign of
+    tsdf -> (points, normals, colors (B,cap,3), edge (B,cap) int32, n_points (B,) int32).  Rows come in ascending edge id
+    e = 3 j + axis; the first min(n_points, cap) rows are written (the others hold zeros, edge -1), n_points is the full count.
+    cap = 0 only counts (the arrays are None): size with it first.  colors is None for a volume without colours."""
+    op = "tsdf_extract"
+    t, w, c, origin, (nx, ny, nz), v = _tsdf_state(tsdf, weight, color, origin, voxel_size, op)
+    try:
+        mw = float(min_weight)
+    except (TypeError, ValueError):
+        mw = float("nan")
+    if math.isnan(mw):
+        raise ValueError("{}: min_weight should be a number. Got {!r}.".format(op, min_weight))
+    cap = int(cap)
+    if cap < 0 or cap > 3 * TSDF_NMAX:
+        raise ValueError("{}: cap should lie in 0 .. 3 * 2^29. Got {}.".format(op, cap))
+    B, dev = t.shape[0], t.device
+    n_points = torch.empty((B,), dtype=torch.int32, device=dev)
+    rows = lambda have: torch.zeros((B, cap, 3), dtype=torch.float32, device=dev) if (have and cap) else None
+    points, normals, colors = rows(True), rows(True), rows(c is not None)
+    edge = torch.full((B, cap), -1, dtype=torch.int32, device=dev) if cap else None
+    ws = workspace(ws_bytes("gs_tsdf_extract_ws_bytes", B, nx, ny, nz), dev, "tsdf_extract")
+    call("gs_tsdf_extract", ptr(t), ptr(w), ptr(c), B, nx, ny, nz, v, ptr(origin), mw, cap, ptr(points), ptr(normals), ptr(colors),
+         ptr(edge), ptr(n_points), ptr(ws), ws.numel(), stream())
+    return points, normals, colors, edge, n_points
+
+
+def tsdf_extract_backward_raw(tsdf, color, voxel_size, edge, n_points, g_points=None, g_colors=None):
+    """Adjoint of tsdf_extract_raw for the rows in edge / n_points (constants): -> (g_tsdf, g_color or None), written in full.
+    No float atomics, a fixed order of addition: bit-reproducible."""
+    op = "tsdf_extract_backward"
+    _tsdf_on_device(op, tsdf, color, edge, n_points, g_points, g_colors)
+    if tsdf.ndim != 4:
+        raise ValueError("{}: tsdf should have shape (B, nz, ny, nx). Got {}.".format(op, tuple(tsdf.shape)))
+    B, nz, ny, nx = (int(n) for n in tsdf.shape)
+    _tsdf_dims((nx, ny, nz), op)
+    v = _tsdf_positive(voxel_size, "voxel_size", op)
+    if edge.dtype != torch.int32 or edge.ndim != 2 or edge.shape[0] != B or edge.shape[1] == 0:
+        raise ValueError("{}: edge should be int32 of shape ({}, cap) with cap > 0. Got {} of {}.".format(op, B, tuple(edge.shape), edge.dtype))
+    cap = int(edge.shape[1])
+    if n_points.dtype != torch.int32 or n_points.numel() != B:
+        raise ValueError("{}: n_points should be {} int32 values. Got {} of {}.".format(op, B, n_points.numel(), n_points.dtype))
+    for name, g in (("g_points", g_points), ("g_colors", g_colors)):
+        if g is not None and tuple(g.shape) != (B, cap, 3):
+            raise ValueError("{}: {} should have shape {}. Got {}.".format(op, name, (B, cap, 3), tuple(g.shape)))
+    t, c = _f32c(tsdf), _f32c(color)
+    g_tsdf = torch.empty_like(t)
+    g_color = None if c is None else torch.empty_like(c)
+    call("gs_tsdf_extract_backward", ptr(t), ptr(c), B, nx, ny, nz, v, ptr(edge.contiguous()), ptr(n_points.contiguous()), cap,
+         ptr(_f32c(g_points)), ptr(_f32c(g_colors)), ptr(g_tsdf), ptr(g_color), stream())
+    return g_tsdf, g_color
+
+
+class _TsdfExtractFn(torch.autograd.Function):
+    """(tsdf, color | weight, origin: constants) -> (points, normals, colors, edge, n_points).  Which edges cross is a constant of
+    the graph; normals carry no gradient (like knn_normals)."""
+
+    @staticmethod
+    def forward(ctx, tsdf, color, weight, origin, voxel_size, min_weight, cap):
+        points, normals, colors, edge, n_points = tsdf_extract_raw(tsdf, weight, color, origin, voxel_size, min_weight, cap)
+        ctx.save_for_backward(tsdf, color, edge, n_points)
+        ctx.voxel_size = voxel_size
+        ctx.mark_non_differentiable(normals, edge, n_points)
+        return points, normals, colors, edge, n_points
+
+    @staticmethod
+    def backward(ctx, g_points, _g_normals, g_colors, _g_edge, _g_n):
+        tsdf, color, edge, n_points = ctx.saved_tensors
+        g_tsdf, g_color = tsdf_extract_backward_raw(tsdf, color, ctx.voxel_size, edge, n_points, g_points, g_colors)
+        return (g_tsdf if ctx.needs_input_grad[0] else None, g_color if ctx.needs_input_grad[1] else None, None, None, None, None, None)
+
+
+def tsdf_extract(tsdf, weight, color, origin, voxel_size, min_weight: float = 1.0, cap: int = 0):
+    """Autograd-aware tsdf_extract_raw (cap > 0): gradients of points and colors reach tsdf and color."""
+    if int(cap) <= 0:
+        raise ValueError("tsdf_extract: cap should be positive (size it with tsdf_extract_raw(..., cap=0)). Got {}.".format(cap))
+    if torch.is_tensor(tsdf) and tsdf.ndim == 4:
+        origin = tsdf_origin(origin, tsdf.shape[0], tsdf.device, "tsdf_extract")
+    return _TsdfExtractFn.apply(tsdf, color, weight, origin, voxel_size, min_weight, int(cap))

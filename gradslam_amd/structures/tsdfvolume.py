@@ -1,0 +1,121 @@
+"""TSDFVolume: a dense truncated signed-distance grid per batch element, the volumetric map of KinectFusion-style dense SLAM.
+
+Posed RGB-D frames are fused into it (`integrate`), a surface is taken out of it as a `Pointclouds` (`extract_pointcloud`);
+both steps are differentiable.  The reference ships no counterpart (the paper describes one).  All arithmetic runs in the HIP
+kernels of csrc/tsdf.hip; nothing here computes on the CPU.
+"""
+from typing import Optional
+
+import torch
+
+from .. import ops
+from .pointclouds import Pointclouds
+from .rgbdimages import RGBDImages
+
+__all__ = ["TSDFVolume"]
+
+
+class TSDFVolume(object):
+    r"""A batch of B dense volumes of `dims = (nx, ny, nz)` voxels of edge `voxel_size`; `origin` ((3,) or (B, 3)) is the corner
+    of voxel (0, 0, 0), so voxel i has its centre at origin + (i + 0.5) voxel_size.
+
+    State, fp32, x fastest: `tsdf` (B, nz, ny, nx), 1 where unobserved; `weight` (B, nz, ny, nx), 0 where unobserved; `color`
+    (B, nz, ny, nx, 3), 0 where unobserved (None with `color=False`).  `trunc` (default 4 voxel_size) is the truncation distance,
+    `max_weight` (default 128) caps the running average's weight.  B is the number of origins given, or `batch_size`."""
+
+    def __init__(self, dims, voxel_size, origin=(0.0, 0.0, 0.0), trunc=None, max_weight=128.0, batch_size: Optional[int] = None,
+                 color: bool = True, device="cuda"):
+        op = "TSDFVolume"
+        self.dims = ops._tsdf_dims(dims, op)
+        self.voxel_size = ops._tsdf_positive(voxel_size, "voxel_size", op)
+        self.trunc = ops._tsdf_positive(4.0 * self.voxel_size if trunc is None else trunc, "trunc", op)
+        self.max_weight = ops._tsdf_positive(max_weight, "max_weight", op)
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise ValueError("{}: device is {}; TSDF volumes only live on a HIP device (no CPU fallback is provided).".format(op, self.device))
+        if batch_size is None:
+            shape = tuple(origin.shape) if torch.is_tensor(origin) else None
+            if shape is None:
+                try:
+                    shape = tuple(torch.as_tensor(origin, dtype=torch.float32).shape)
+                except (TypeError, ValueError, RuntimeError):
+                    shape = ()
+            batch_size = shape[0] if len(shape) == 2 else 1
+        if not isinstance(batch_size, int) or isinstance(batch_size, bool) or not 1 <= batch_size <= 65535:
+            raise ValueError("{}: batch_size should be an integer in 1 .. 65535. Got {!r}.".format(op, batch_size))
+        self._B = batch_size
+        self.origin = ops.tsdf_origin(origin, self._B, self.device, op)
+        nx, ny, nz = self.dims
+        self.tsdf = torch.ones((self._B, nz, ny, nx), dtype=torch.float32, device=self.device)
+        self.weight = torch.zeros((self._B, nz, ny, nx), dtype=torch.float32, device=self.device)
+        self.color = torch.zeros((self._B, nz, ny, nx, 3), dtype=torch.float32, device=self.device) if color else None
+
+    def __len__(self):
+        return self._B
+
+    @property
+    def has_colors(self) -> bool:
+        return self.color is not None
+
+    def _with_state(self, tsdf, weight, color):
+        out = object.__new__(type(self))
+        out.__dict__.update(self.__dict__)
+        out.tsdf, out.weight, out.color = tsdf, weight, color
+        return out
+
+    def detach(self):
+        return self._with_state(self.tsdf.detach(), self.weight, None if self.color is None else self.color.detach())
+
+    # ------------------------------------------------------------------ integration
+    def integrate(self, rgbdimages: RGBDImages, inplace: bool = False):
+        r"""Fuse a (B, L) batch of posed frames: per voxel and frame, in order, the voxel's centre is projected with the map's own
+        rule (the pixel `find_active_map_points` would put a map point on); with d the pixel's depth and z the centre's depth,
+        sdf = d - z; frames with no pixel, no depth or sdf < -trunc leave the voxel alone, the others update
+
+            tsdf <- (W tsdf + min(1, sdf / trunc)) / (W + 1),   color likewise with the pixel's rgb,   W <- min(W + 1, max_weight).
+
+        Exactly what integrating the frames one at a time gives.  Returns a NEW TSDFVolume, or this one updated with
+        `inplace=True` (when a gradient is being recorded the state is written to fresh tensors either way).  Differentiable
+        w.r.t. the depth and rgb images and the previous tsdf / color; not w.r.t. the poses and intrinsics."""
+        if not isinstance(rgbdimages, RGBDImages):
+            raise TypeError("Expected rgbdimages to be of type gradslam.RGBDImages. Got {}.".format(type(rgbdimages)))
+        if not rgbdimages.has_poses:
+            raise ValueError("TSDFVolume.integrate: the frames need poses (rgbdimages.poses is None).")
+        if len(rgbdimages) != self._B:
+            raise ValueError("Batch size of the frames and of the volume must match: ({0} != {1})".format(len(rgbdimages), self._B))
+        depth, rgb = rgbdimages._cl(rgbdimages.depth_image), rgbdimages._cl(rgbdimages.rgb_image)
+        args = (depth, rgb if self.has_colors else None, rgbdimages.intrinsics, rgbdimages.poses)
+        cfg = (self.origin, self.voxel_size, self.trunc, self.max_weight)
+        grad = torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (depth, rgb, self.tsdf, self.color))
+        if grad:
+            tsdf, weight, color = ops.tsdf_integrate(*args, self.tsdf, self.weight, self.color, *cfg)
+        else:
+            tsdf, weight, color = ops.tsdf_integrate_raw(*args, self.tsdf, self.weight, self.color, *cfg, inplace=inplace)
+        if inplace:
+            self.tsdf, self.weight, self.color = tsdf, weight, color
+            return self
+        return self._with_state(tsdf, weight, color)
+
+    # ------------------------------------------------------------------ extraction
+    def extract_pointcloud(self, min_weight: float = 1.0) -> Pointclouds:
+        r"""The surface as a Pointclouds with points, normals and (for a volume with colours) colours: one point on every grid
+        edge whose two voxels are observed (weight >= min_weight) and lie on different sides of the surface, placed by linear
+        interpolation of tsdf; colours interpolated the same way; normals from the tsdf differences of the observed
+        neighbours, pointing into free space.  Points come in ascending edge order (voxel, then axis).  Differentiable w.r.t.
+        tsdf and color (which edges cross is a constant of the graph; normals carry no gradient).  One host synchronisation
+        (the sizes)."""
+        state = (self.tsdf, self.weight, self.color, self.origin, self.voxel_size, min_weight)
+        with torch.no_grad():
+            n_points = ops.tsdf_extract_raw(*state, cap=0)[4]
+        counts = n_points.tolist()  # the one host synchronisation
+        cap = max(counts)
+        out = Pointclouds(device=self.device)
+        out._B = self._B
+        if cap > 0:
+            points, normals, colors, _, _ = ops.tsdf_extract(*state, cap=cap)
+        else:  # nothing observed yet: padded attributes without rows, like the counts
+            empty = lambda: torch.zeros((self._B, 0, 3), dtype=torch.float32, device=self.device)
+            points, normals, colors = empty(), empty(), (empty() if self.has_colors else None)
+        out._adopt_padded(points, normals, colors, None)
+        out._set_counts(counts)
+        return out

@@ -725,6 +725,68 @@ int gs_knn_normals(const float *src, const int32_t *src_counts, int Ns_max, cons
                    const int32_t *tgt_counts, int Nt_max, int B, int K, const uint64_t *keys, int mode,
                    const float *orient, float *normals, float *variation, gs_stream_t stream);
 
+/* ---------------------------------------------------------------- T: TSDF volumes (fuse posed RGB-D frames, extract the surface)
+ * The reference has no counterpart.  A dense grid per batch element: dims (nx, ny, nz) with nx ny nz <= 2^29, edge voxel_size > 0,
+ * origin (B,3) fp32 ON THE DEVICE (the corner of voxel (0,0,0)).  State, fp32, x fastest: tsdf (B,nz,ny,nx), 1 where unobserved;
+ * weight (B,nz,ny,nx), 0 where unobserved; color (B,nz,ny,nx,3), optional (NULL).  B <= 65535.
+ *   The centre of voxel i along axis k is  c_k = o_k + ((float)i_k + 0.5f) * voxel_size  (one rounded product, one rounded sum).
+ * Integration of frames depth (B,L,H,W), rgb (B,L,H,W,3), intrinsics (B,4,4), poses (B,L,4,4); for every voxel the frames
+ * l = 0 .. L-1 are applied in order:
+ *   1. the centre is projected with the rule of gs_project_active (same device body): not active -> the frame is skipped;
+ *   2. d = depth[b,l,h,w]; !(d > 0) -> skipped;     3. sdf = d - z (z: camera-frame depth of the centre); sdf < -trunc -> skipped;
+ *   4. t = fminf(1, sdf / trunc);                   5. tsdf = (W tsdf + t) / (W + 1), every colour component the same way with
+ *      rgb[b,l,h,w,k], then W = fminf(W + 1, max_weight).  IEEE fp32, no contraction.
+ *   One launch per chunk of up to 32 frames (one thread per 4 consecutive x-voxels, the state in registers, the chunk's cameras in
+ *   LDS; 16-byte accesses when nx is a multiple of 4 and the pointers are 16-byte aligned).  The result is what L single-frame
+ *   calls give, bit for bit.  The outputs may alias the inputs.  color_in / color_out / rgb go together (all three or NULL
+ *   colours).  No workspace, no atomics, nothing synchronises the host. */
+int gs_tsdf_integrate(const float *depth, const float *rgb, const float *intrinsics, const float *poses, int B, int L,
+                      int H, int W, int nx, int ny, int nz, float voxel_size, const float *origin, float trunc,
+                      float max_weight, const float *tsdf_in, const float *weight_in, const float *color_in,
+                      float *tsdf_out, float *weight_out, float *color_out, gs_stream_t stream);
+
+/* Reverse pass of the integration.  Constants of the graph: the pixel of a voxel, the three skips, the t = 1 branch, the weight
+ * cap.  Per applied frame, with W the weight before it (= weight_in, or fminf(weight_in + n, max_weight) after n >= 1 earlier updates):
+ *   g_t = g / (W + 1),  g <- g (W / (W + 1)),  and g_t / trunc goes to depth[b,l,h,w] iff sdf < trunc; colours the same with rgb.
+ *   g_tsdf_in (B,nz,ny,nx), g_color_in: what is left after frame 0.  g_depth (B,L,H,W), g_rgb (B,L,H,W,3): per pixel the EXACT
+ *   sum of its voxels' terms rounded once to fp32 (128-bit fixed point, integer atomics, as gs_voxel_reduce: with
+ *   lg = ceil(log2(nx ny nz)), bits more than 102 - lg places below the chunk's largest finite |term| are truncated toward
+ *   zero; non-finite terms give what a float sum gives).  Every element of all four outputs is written; the same bits from run to
+ *   run.  g_color_out / g_color_in / g_rgb go together (all three or NULL).  g_*_in may alias g_*_out.
+ *   Chunks of 32 frames in reverse order, per chunk one memset and three launches; a chunk re-projects the frames before it
+ *   to count its voxels' earlier updates.
+ * Workspace, every piece rounded up to 256 bytes, with P = B min(L, 32) H W:  4 B (maximum) | 4 B P (flags) | 64 B P (sums). */
+size_t gs_tsdf_integrate_backward_ws_bytes(int B, int L, int H, int W);
+int gs_tsdf_integrate_backward(const float *depth, const float *intrinsics, const float *poses, int B, int L, int H, int W,
+                               int nx, int ny, int nz, float voxel_size, const float *origin, float trunc,
+                               float max_weight, const float *weight_in, const float *g_tsdf_out,
+                               const float *g_color_out, float *g_tsdf_in, float *g_color_in, float *g_depth,
+                               float *g_rgb, void *ws, size_t ws_bytes, gs_stream_t stream);
+
+/* Surface extraction.  A voxel is observed iff weight >= min_weight.  Edge slot e = 3 j + a runs from voxel j to its +1
+ * neighbour j+ along axis a (0: x, 1: y, 2: z) and exists iff that neighbour is inside the grid; it carries a point iff both
+ * ends are observed and (f0 < 0) != (f1 < 0), f0 = tsdf[j], f1 = tsdf[j+].  Then s = f0 / (f0 - f1); the point is the centre of
+ * j with component a moved by s voxel_size; color = col0 + s (col1 - col0); normal = g / |g| (a zero g stays zero) with
+ * g = D(j) + s (D(j+) - D(j)), D_k = the difference of tsdf along axis k over the observed neighbours inside the grid
+ * (central halved, else one-sided, else 0).  Rows come in ascending e per batch element (stable compaction):
+ *   points, normals, colors (B,cap,3), edge (B,cap) int32: the first min(n, cap) rows are written, nothing else;
+ *   n_points (B,): the full count, whatever cap.  cap = 0 (outputs may be NULL) only counts.  colors needs color.
+ * Two launches for the count, one more for the rows; nothing synchronises the host.
+ * Workspace, every piece rounded up to 256 bytes:  4 B B ceil(3 nx ny nz / 1024), twice (block counts and offsets). */
+size_t gs_tsdf_extract_ws_bytes(int B, int nx, int ny, int nz);
+int gs_tsdf_extract(const float *tsdf, const float *weight, const float *color, int B, int nx, int ny, int nz,
+                    float voxel_size, const float *origin, float min_weight, int cap, float *points, float *normals,
+                    float *colors, int32_t *edge, int32_t *n_points, void *ws, size_t ws_bytes, gs_stream_t stream);
+
+/* Reverse pass of the extraction for the rows in edge / n_points (constants): with g_s = voxel_size g_point_a +
+ * sum_k g_col_k (col1_k - col0_k):  g_f0 = g_s (-f1 / (f0 - f1)^2), g_f1 = g_s (f0 / (f0 - f1)^2), g_col0 = (1 - s) g_col,
+ * g_col1 = s g_col.  Normals carry no gradient.  g_tsdf (B,nz,ny,nx) and g_color (optional) are written in full: a memset, then
+ * six (axis, end) passes of plain read-modify-writes (no two rows of a pass share a voxel): the same bits from run to run.
+ * g_points / g_colors (B,cap,3) may be NULL (zero). */
+int gs_tsdf_extract_backward(const float *tsdf, const float *color, int B, int nx, int ny, int nz, float voxel_size,
+                             const int32_t *edge, const int32_t *n_points, int cap, const float *g_points,
+                             const float *g_colors, float *g_tsdf, float *g_color, gs_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

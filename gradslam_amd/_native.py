@@ -151,6 +151,11 @@ SIGNATURES = {
     "gs_tsdf_extract_ws_bytes": (c_sz, [c_i, c_i, c_i, c_i]),
     "gs_tsdf_extract": (c_i, [c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_f, c_p, c_f, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_sz, c_p]),
     "gs_tsdf_extract_backward": (c_i, [c_p, c_p, c_i, c_i, c_i, c_i, c_f, c_p, c_p, c_i, c_p, c_p, c_p, c_p, c_p]),
+    "gs_tsdf_raycast": (c_i, [c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_f, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_f, c_f, c_f, c_f, c_p, c_p, c_p,
+                              c_p, c_p]),
+    "gs_tsdf_raycast_backward_ws_bytes": (c_sz, [c_i, c_i, c_i, c_i, c_i]),
+    "gs_tsdf_raycast_backward": (c_i, [c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_f, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_f, c_f, c_p, c_p, c_p,
+                                       c_p, c_p, c_p, c_sz, c_p]),
 }
 
 _lib = None

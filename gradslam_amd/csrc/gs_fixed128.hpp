@@ -1,4 +1,4 @@
-// gs_fixed128.hpp -- the 128-bit fixed-point arithmetic of the order-independent sums: three device functions, no kernels, so
+// gs_fixed128.hpp -- the 128-bit fixed-point arithmetic of the order-independent sums: device functions, no kernels, so
 // that every translation unit that folds a scattered sum (gs_detfold.hpp in icp.hip, voxel.hip) states it once.
 //
 // With M = the largest finite |x| of a fold (float bits mbits, biased exponent eb) and at most 2^lg terms per sum,
@@ -44,6 +44,35 @@ __device__ __forceinline__ float det_to_float(unsigned long long lo, unsigned lo
     }
     const float r = ldexpf((float)mant, sh - E);
     return neg ? -r : r;
+}
+
+// ------------------------------------------------------------------ one term of a fold (the max pass, then the accumulate pass)
+// the largest finite |x| so far, as float bits
+__device__ __forceinline__ uint32_t fold_max(uint32_t mx, float x) {
+    const uint32_t u = __float_as_uint(x) & 0x7fffffffu;
+    return (u < 0x7f800000u && u > mx) ? u : mx;
+}
+// x joins the sum held in the two 64-bit words at a; a non-finite x sets one of 3 bits (NaN, +inf, -inf) at `shift` of *flags
+__device__ __forceinline__ void fold_add_at(uint32_t *flags, int shift, unsigned long long *a, float x, int E) {
+    const uint32_t bits = __float_as_uint(x);
+    if ((bits & 0x7fffffffu) >= 0x7f800000u) {
+        const uint32_t code = (bits & 0x7fffffu) ? 1u : ((bits >> 31) ? 4u : 2u);
+        atomicOr(flags, code << shift);
+        return;
+    }
+    const __int128 v = det_to_fixed(bits, E);
+    if (v == 0) return;
+    const unsigned long long lo = (unsigned long long)v;
+    unsigned long long hi = (unsigned long long)(v >> 64);
+    const unsigned long long old = atomicAdd(a, lo);
+    hi += (old + lo < old) ? 1ull : 0ull;  // the carry out of the low word, counted once by the adder that caused it
+    if (hi) atomicAdd(a + 1, hi);
+}
+// what the flags of a sum make of it: true -> r is the NaN or infinity a float sum would give
+__device__ __forceinline__ bool fold_flagged(uint32_t f, float &r) {
+    if (!f) return false;
+    r = ((f & 1u) || (f & 6u) == 6u) ? __int_as_float(0x7fc00000) : __int_as_float((f & 2u) ? 0x7f800000 : (int)0xff800000);
+    return true;
 }
 
 }  // namespace gs

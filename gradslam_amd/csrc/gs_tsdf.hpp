@@ -89,4 +89,104 @@ __device__ __forceinline__ bool tsdf_crosses(float f0, float w0, float f1, float
 }
 __device__ __forceinline__ float tsdf_cross_s(float f0, float f1) { return f0 / (f0 - f1); }
 
+// ------------------------------------------------------------------ the ray-cast rule (tsdf_raycast.hip: forward and reverse)
+// Output pixel (i, j) of the strided grid is full-resolution pixel (h, w) = (i s, j s).  Its ray, fp32 in this order:
+//   dx = ((float)w - cx) / fx,  dy = ((float)h - cy) / fy,  dw_i = (R_i0 dx + R_i1 dy) + R_i2,
+//   len = sqrtf((dx dx + dy dy) + 1),  dz = step / len.
+// Sample k (1 <= k < 2^30: the tape is int32) lies at camera depth z_k = (float)k * dz -- one rounded product, never a running
+// sum, so the reverse pass and a reference find sample k without walking the ray -- at p_i = t_i + z_k dw_i, and belongs to
+// the ray iff near <= z_k <= far.  Consecutive samples are exactly `step` apart in space.
+struct TsdfRay {
+    f3 t, dw;
+    float dz;
+};
+__device__ __forceinline__ TsdfRay tsdf_ray(const float *__restrict__ K, const float *__restrict__ P, int h, int w, float step) {
+    const float dx = ((float)w - K[2]) / K[0], dy = ((float)h - K[6]) / K[5];
+    TsdfRay r;
+    r.t = f3{P[3], P[7], P[11]};
+    r.dw = f3{(P[0] * dx + P[1] * dy) + P[2], (P[4] * dx + P[5] * dy) + P[6], (P[8] * dx + P[9] * dy) + P[10]};
+    r.dz = step / sqrtf((dx * dx + dy * dy) + 1.0f);
+    return r;
+}
+__device__ __forceinline__ float tsdf_ray_z(const TsdfRay &r, int k) { return (float)k * r.dz; }
+__device__ __forceinline__ f3 tsdf_ray_at(const TsdfRay &r, float z) { return f3{r.t.x + z * r.dw.x, r.t.y + z * r.dw.y, r.t.z + z * r.dw.z}; }
+
+// The cell of a position: per axis g = (p - o) / v - 0.5f, i = floorf(g), a = g - i; inside iff 0 <= i and i + 1 <= n - 1 on all
+// three axes (the 8 corners i, i + 1 exist).  Written so that a NaN or an infinity is outside; every gather below follows it.
+struct TsdfCell {
+    int j;  // the corner (ix, iy, iz) within one batch element
+    float ax, ay, az;
+};
+__device__ __forceinline__ bool tsdf_cell1(float p, float o, float v, int n, int &i, float &a) {
+    const float g = (p - o) / v - 0.5f, fi = floorf(g);
+    if (!(fi >= 0.0f && fi + 1.0f <= (float)(n - 1))) return false;
+    i = (int)fi;
+    a = g - fi;
+    return true;
+}
+__device__ __forceinline__ bool tsdf_cell(const TsdfVol &g, const float *__restrict__ o, f3 p, TsdfCell &c) {
+    int ix, iy, iz;
+    if (!tsdf_cell1(p.x, o[0], g.v, g.nx, ix, c.ax) || !tsdf_cell1(p.y, o[1], g.v, g.ny, iy, c.ay) ||
+        !tsdf_cell1(p.z, o[2], g.v, g.nz, iz, c.az))
+        return false;
+    c.j = (iz * g.ny + iy) * g.nx + ix;
+    return true;
+}
+// corner c = x + 2 y + 4 z of the cell at j
+__device__ __forceinline__ int tsdf_corner(const TsdfVol &g, int j, int c) {
+    return j + (c & 1) + ((c >> 1) & 1) * g.nx + (c >> 2) * g.nx * g.ny;
+}
+// observed iff all 8 corner weights are >= minw (tested before the 8 tsdf values are fetched: unobserved space costs half)
+__device__ __forceinline__ bool tsdf_cell_observed(const TsdfVol &g, const float *__restrict__ weight, int j, float minw) {
+    bool ok = true;
+#pragma unroll
+    for (int c = 0; c < 8; ++c) ok = ok && weight[tsdf_corner(g, j, c)] >= minw;
+    return ok;
+}
+__device__ __forceinline__ float tsdf_lerp(float p, float q, float s) { return p + s * (q - p); }
+// four times along x, twice along y, once along z
+__device__ __forceinline__ float tsdf_trilerp(const float *f, const TsdfCell &c) {
+    const float c00 = tsdf_lerp(f[0], f[1], c.ax), c10 = tsdf_lerp(f[2], f[3], c.ax);
+    const float c01 = tsdf_lerp(f[4], f[5], c.ax), c11 = tsdf_lerp(f[6], f[7], c.ax);
+    return tsdf_lerp(tsdf_lerp(c00, c10, c.ay), tsdf_lerp(c01, c11, c.ay), c.az);
+}
+// the gradient of the interpolant in voxel units: differences along the axis, lerped over the other two (x before y before z)
+__device__ __forceinline__ f3 tsdf_trigrad(const float *f, const TsdfCell &c) {
+    const float gx = tsdf_lerp(tsdf_lerp(f[1] - f[0], f[3] - f[2], c.ay), tsdf_lerp(f[5] - f[4], f[7] - f[6], c.ay), c.az);
+    const float gy = tsdf_lerp(tsdf_lerp(f[2] - f[0], f[3] - f[1], c.ax), tsdf_lerp(f[6] - f[4], f[7] - f[5], c.ax), c.az);
+    const float gz = tsdf_lerp(tsdf_lerp(f[4] - f[0], f[5] - f[1], c.ax), tsdf_lerp(f[6] - f[2], f[7] - f[3], c.ax), c.ay);
+    return f3{gx, gy, gz};
+}
+// the weight of corner c in the interpolant: (wx wy) wz with w = a at the far end of an axis, 1 - a at the near end
+__device__ __forceinline__ float tsdf_corner_weight(const TsdfCell &c, int k) {
+    const float wx = (k & 1) ? c.ax : 1.0f - c.ax, wy = (k & 2) ? c.ay : 1.0f - c.ay, wz = (k & 4) ? c.az : 1.0f - c.az;
+    return (wx * wy) * wz;
+}
+__device__ __forceinline__ void tsdf_gather8(const TsdfVol &g, const float *__restrict__ x, int j, float *f) {
+#pragma unroll
+    for (int c = 0; c < 8; ++c) f[c] = x[tsdf_corner(g, j, c)];
+}
+__device__ __forceinline__ void tsdf_gather8c(const TsdfVol &g, const float *__restrict__ col, int j, int ch, float *f) {
+#pragma unroll
+    for (int c = 0; c < 8; ++c) f[c] = col[3 * (int64_t)tsdf_corner(g, j, c) + ch];
+}
+// One sample of one batch element's volume: observed -> its value.
+__device__ __forceinline__ bool tsdf_sample_at(const TsdfVol &g, const float *__restrict__ o, const float *__restrict__ tsdf,
+                                               const float *__restrict__ weight, float minw, f3 p, TsdfCell &c, float &f) {
+    if (!tsdf_cell(g, o, p, c) || !tsdf_cell_observed(g, weight, c.j, minw)) return false;
+    float f8[8];
+    tsdf_gather8(g, tsdf, c.j, f8);
+    f = tsdf_trilerp(f8, c);
+    return true;
+}
+// The march ends at the first observed sample k with f < 0 (zero counts as outside, as in tsdf_crosses); it is a hit iff sample
+// k - 1 belongs to the ray, is observed and has f_prev >= 0.  Then s = f_prev / (f_prev - f), z* = ((float)(k - 1) + s) dz,
+// p* = t + z* dw, and p* must be observed too.
+__device__ __forceinline__ bool tsdf_hit_at(const TsdfVol &g, const float *__restrict__ o, const float *__restrict__ weight, float minw,
+                                            const TsdfRay &r, int k, float f_prev, float f, float &z, TsdfCell &c) {
+    const float s = f_prev / (f_prev - f);
+    z = ((float)(k - 1) + s) * r.dz;
+    return tsdf_cell(g, o, tsdf_ray_at(r, z), c) && tsdf_cell_observed(g, weight, c.j, minw);
+}
+
 }  // namespace gs

@@ -13,7 +13,13 @@
 //        tsdf_count_k -> tsdf_scan_k -> tsdf_write_k (skipped when cap == 0)
 //      gs_tsdf_extract_backward: a memset and six (axis, end) passes over the rows; within a pass no two rows share a voxel, so
 //      the adds are plain read-modify-writes in a fixed order.
-// Batch elements ride in grid.y.
+//   R  gs_tsdf_raycast: the volume seen from a camera (the rule: gs_tsdf.hpp).  One launch, one thread per output pixel, a wave
+//      per 8x8 tile; the ray is clipped against the box, then marched sample by sample: 8 weights, then 8 tsdf values.  No
+//      workspace, no atomics, nothing synchronises the host.
+//      gs_tsdf_raycast_backward: one thread per pixel recomputes its two samples and its hit from the tape k_end; a voxel's
+//      adjoint is a sum over many pixels: the same fold, over the voxels
+//        memset -> tsdf_raycast_bwd_k<MAX> -> tsdf_raycast_bwd_k<ACC> -> tsdf_cast_finish_k
+// Batch elements ride in grid.y (R: frames in grid.y, batch elements in grid.z).
 #include <cmath>
 #include <stddef.h>
 
@@ -119,25 +125,8 @@ static inline size_t tsdf_fold_layout(int B, int L, int H, int W, void *ws, Tsdf
     return c.off;
 }
 
-__device__ __forceinline__ uint32_t tsdf_fold_max(uint32_t mx, float x) {
-    const uint32_t u = __float_as_uint(x) & 0x7fffffffu;
-    return (u < 0x7f800000u && u > mx) ? u : mx;
-}
 __device__ __forceinline__ void tsdf_fold_add(const TsdfFold &fold, int64_t p, int ch, float x, int E) {
-    const uint32_t bits = __float_as_uint(x);
-    if ((bits & 0x7fffffffu) >= 0x7f800000u) {
-        const uint32_t code = (bits & 0x7fffffu) ? 1u : ((bits >> 31) ? 4u : 2u);
-        atomicOr(fold.flags + p, code << (3 * ch));
-        return;
-    }
-    const __int128 v = det_to_fixed(bits, E);
-    if (v == 0) return;
-    unsigned long long *a = fold.acc + (p * 4 + ch) * 2;
-    const unsigned long long lo = (unsigned long long)v;
-    unsigned long long hi = (unsigned long long)(v >> 64);
-    const unsigned long long old = atomicAdd(a, lo);
-    hi += (old + lo < old) ? 1ull : 0ull;  // the carry out of the low word, counted once by the adder that caused it
-    if (hi) atomicAdd(a + 1, hi);
+    fold_add_at(fold.flags + p, 3 * ch, fold.acc + (p * 4 + ch) * 2, x, E);
 }
 
 // grid (x: voxels, y: batch element).  ACC = false: the largest finite |term| of the chunk; ACC = true: the terms go into the
@@ -196,8 +185,8 @@ __global__ __launch_bounds__(TSDF_T) void tsdf_bwd_k(TsdfVol vol, TsdfFrames fr,
                 tsdf_fold_add(fold, p, 3, gr.z, E);
             }
         } else {
-            mx = tsdf_fold_max(mx, gd);
-            if (color) mx = tsdf_fold_max(tsdf_fold_max(tsdf_fold_max(mx, gr.x), gr.y), gr.z);
+            mx = fold_max(mx, gd);
+            if (color) mx = fold_max(fold_max(fold_max(mx, gr.x), gr.y), gr.z);
         }
     }
     if (ACC) {
@@ -225,8 +214,7 @@ __global__ __launch_bounds__(TSDF_T) void tsdf_fold_finish_k(TsdfFold fold, int 
         for (int ch = 0; ch < (g_rgb ? 4 : 1); ++ch) {
             const uint32_t f = (fl >> (3 * ch)) & 7u;
             float r;
-            if (f) r = ((f & 1u) || (f & 6u) == 6u) ? __int_as_float(0x7fc00000) : __int_as_float((f & 2u) ? 0x7f800000 : (int)0xff800000);
-            else r = det_to_float(fold.acc[(p * 4 + ch) * 2], fold.acc[(p * 4 + ch) * 2 + 1], E);
+            if (!fold_flagged(f, r)) r = det_to_float(fold.acc[(p * 4 + ch) * 2], fold.acc[(p * 4 + ch) * 2 + 1], E);
             if (ch == 0) g_depth[out] = r;
             else g_rgb[3 * out + ch - 1] = r;
         }
@@ -360,6 +348,216 @@ __global__ __launch_bounds__(TSDF_T) void tsdf_extract_bwd_k(TsdfVol vol, const 
         st3(g_color, at, f3{old.x + m * gc.x, old.y + m * gc.y, old.z + m * gc.z});
     }
     g_tsdf[at] = g_tsdf[at] + gs * (end ? f0 / den : (-f1) / den);
+}
+
+// ------------------------------------------------------------------ R: ray casting.  grid (x: 16x16 tiles of output pixels, y: frame, z: batch element)
+struct TsdfCast {
+    const float *K, *poses;  // (B,4,4), (B,L,4,4)
+    int L, Ho, Wo, s, kmax;  // kmax: the most samples a thread visits
+    float step, near, far, minw;
+};
+constexpr int TSDF_KMAX = 1 << 30;  // samples per ray: the tape is int32
+constexpr int TSDF_CAST_TILES = 1 << 22;  // 16x16 tiles per image: grid.x x 256 threads stays below 2^32
+
+// A block of 256 threads covers 16x16 output pixels and each of its 4 waves a compact 8x8 tile, not a 64x1 row: neighbouring rays
+// read neighbouring voxels, so the 16 gathers of a sample share cache lines.
+__device__ __forceinline__ bool tsdf_cast_pixel(const TsdfCast &c, int &i, int &j) {
+    const int tx = (c.Wo + 15) >> 4, by = blockIdx.x / tx, bx = blockIdx.x - by * tx;
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    i = by * 16 + (wave >> 1) * 8 + (lane >> 3);
+    j = bx * 16 + (wave & 1) * 8 + (lane & 7);
+    return i < c.Ho && j < c.Wo;
+}
+
+// The samples [ka, kb] outside of which none is inside the grid: the ray clipped against the three slabs of the box
+// [o, o + n v], which is half a voxel wider on every side than the positions with a cell, so that the rounding of (lo - t) (far
+// less than v / 2 unless |t| > 2^20 v) cannot cut a cell off however small dw is; then widened by one sample and 2^-21 of the
+// index on each side for the roundings of the divisions and of k dz.  A ray parallel to an axis (dw_i == 0) is inside that slab
+// for every z or for none: no division, and no infinity or NaN decides anything (fminf / fmaxf drop a NaN, the conversions clamp
+// in float first and send a NaN to the empty side).  At most kmax samples are visited whatever the arithmetic gave: samples are
+// `step` apart and the box's longest chord is below (nx + ny + nz) v.
+__device__ __forceinline__ void tsdf_cast_range(const TsdfVol &g, const float *__restrict__ o, const TsdfRay &r, const TsdfCast &c, int &ka,
+                                                int &kb) {
+    const float t[3] = {r.t.x, r.t.y, r.t.z}, d[3] = {r.dw.x, r.dw.y, r.dw.z};
+    const int n[3] = {g.nx, g.ny, g.nz};
+    float zin = c.near, zout = c.far;
+    bool any = true;
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+        const float lo = o[a], hi = o[a] + (float)n[a] * g.v;
+        if (d[a] == 0.0f) {
+            any = any && t[a] >= lo && t[a] <= hi;
+        } else {
+            const float z0 = (lo - t[a]) / d[a], z1 = (hi - t[a]) / d[a];
+            zin = fmaxf(zin, fminf(z0, z1));
+            zout = fminf(zout, fmaxf(z0, z1));
+        }
+    }
+    ka = 1;
+    kb = 0;
+    if (!any || !(zin <= zout)) return;
+    const float qa = zin / r.dz, qb = zout / r.dz;
+    const float fa = floorf(qa - qa * 0x1p-21f) - 1.0f, fb = ceilf(qb + qb * 0x1p-21f) + 1.0f;
+    ka = fa >= 1.0f ? (fa < (float)TSDF_KMAX ? (int)fa : TSDF_KMAX) : 1;
+    kb = fb >= 0.0f ? (fb < (float)TSDF_KMAX ? (int)fb : TSDF_KMAX - 1) : 0;
+    kb = min(kb, TSDF_KMAX - 1);
+    if (kb - ka >= c.kmax) kb = ka + c.kmax - 1;
+}
+
+template <bool COLOR>
+__global__ __launch_bounds__(TSDF_T) void tsdf_raycast_k(TsdfVol vol, TsdfCast cast, const float *__restrict__ tsdf, const float *__restrict__ weight,
+                                                         const float *__restrict__ color, float *__restrict__ depth, float *__restrict__ normal,
+                                                         float *__restrict__ rgb, int32_t *__restrict__ k_end) {
+    int i, j;
+    if (!tsdf_cast_pixel(cast, i, j)) return;
+    const int l = blockIdx.y, b = blockIdx.z;
+    const int64_t nvox = tsdf_nvox(vol), pix = (((int64_t)b * cast.L + l) * cast.Ho + i) * cast.Wo + j;
+    const float *o = vol.origin + 3 * b, *f_b = tsdf + b * nvox, *w_b = weight + b * nvox;
+    const TsdfRay ray = tsdf_ray(cast.K + 16 * b, cast.poses + ((int64_t)b * cast.L + l) * 16, i * cast.s, j * cast.s, cast.step);
+    int ka, kb;
+    tsdf_cast_range(vol, o, ray, cast, ka, kb);
+    bool prev_ok = false;  // sample k - 1 belongs to the ray, is observed and has f >= 0 (a skipped sample is an unobserved one)
+    float f_prev = 0.0f, z = 0.0f;
+    int kend = 0;
+    TsdfCell c, hc;
+    for (int k = ka; k <= kb; ++k) {
+        const float zk = tsdf_ray_z(ray, k);
+        if (!(zk >= cast.near)) continue;
+        if (!(zk <= cast.far)) break;
+        float f;
+        if (!tsdf_sample_at(vol, o, f_b, w_b, cast.minw, tsdf_ray_at(ray, zk), c, f)) {
+            prev_ok = false;
+            continue;
+        }
+        if (f < 0.0f) {
+            if (prev_ok && tsdf_hit_at(vol, o, w_b, cast.minw, ray, k, f_prev, f, z, hc)) kend = k;
+            break;
+        }
+        prev_ok = f >= 0.0f;
+        f_prev = f;
+    }
+    f3 nrm{0.0f, 0.0f, 0.0f}, col{0.0f, 0.0f, 0.0f};
+    if (kend) {
+        float f8[8];
+        tsdf_gather8(vol, f_b, hc.j, f8);
+        const f3 g = tsdf_trigrad(f8, hc);  // +grad f: the tsdf is positive in free space
+        const float nn = sqrtf((g.x * g.x + g.y * g.y) + g.z * g.z);
+        if (nn > 0.0f) nrm = f3{g.x / nn, g.y / nn, g.z / nn};
+        else kend = 0;  // a zero (or NaN) gradient: a miss
+    }
+    if (COLOR && kend) {
+        const float *c_b = color + 3 * b * nvox;
+        float c8[8];
+        tsdf_gather8c(vol, c_b, hc.j, 0, c8);
+        col.x = tsdf_trilerp(c8, hc);
+        tsdf_gather8c(vol, c_b, hc.j, 1, c8);
+        col.y = tsdf_trilerp(c8, hc);
+        tsdf_gather8c(vol, c_b, hc.j, 2, c8);
+        col.z = tsdf_trilerp(c8, hc);
+    }
+    depth[pix] = kend ? z : 0.0f;
+    st3(normal, pix, nrm);
+    if (COLOR) st3(rgb, pix, col);
+    k_end[pix] = kend;
+}
+
+// the fold of the reverse pass: per voxel (b, j) nch sums (tsdf; r, g, b), each a (lo, hi) pair of 64-bit words
+struct TsdfCastFold {
+    uint32_t *maxbits;        // 1
+    uint32_t *flags;          // B nvox: 3 bits per sum (NaN, +inf, -inf)
+    unsigned long long *acc;  // B nvox x nch x (lo, hi)
+    int nch;
+};
+static inline size_t tsdf_cast_fold_layout(int B, int64_t nvox, int nch, void *ws, TsdfCastFold *out) {
+    const size_t n = (size_t)B * nvox;
+    Carve c{(char *)ws};
+    uint32_t *maxbits = c.take<uint32_t>(4);
+    uint32_t *flags = c.take<uint32_t>(4 * n);
+    unsigned long long *acc = c.take<unsigned long long>(16 * n * nch);
+    if (out) *out = TsdfCastFold{maxbits, flags, acc, nch};
+    return c.off;
+}
+template <bool ACC>
+__device__ __forceinline__ void tsdf_cast_term(const TsdfCastFold &fold, int64_t p, int ch, float x, int E, uint32_t &mx) {
+    if (ACC) fold_add_at(fold.flags + p, 3 * ch, fold.acc + (p * fold.nch + ch) * 2, x, E);
+    else mx = fold_max(mx, x);
+}
+
+// One thread per output pixel: the two samples and the hit are recomputed from the tape k_end through the forward's bodies.
+// ACC = false: the largest finite |term|; ACC = true: the terms go into the fold.  No thread leaves before the wave's reduction.
+template <bool ACC>
+__global__ __launch_bounds__(TSDF_T) void tsdf_raycast_bwd_k(TsdfVol vol, TsdfCast cast, const float *__restrict__ tsdf,
+                                                             const float *__restrict__ weight, const float *__restrict__ color,
+                                                             const int32_t *__restrict__ k_end, const float *__restrict__ g_depth,
+                                                             const float *__restrict__ g_rgb, TsdfCastFold fold, int lg) {
+    int i, j;
+    const bool live = tsdf_cast_pixel(cast, i, j);
+    const int l = blockIdx.y, b = blockIdx.z;
+    const int64_t nvox = tsdf_nvox(vol), pix = (((int64_t)b * cast.L + l) * cast.Ho + i) * cast.Wo + j;
+    const float *o = vol.origin + 3 * b, *f_b = tsdf + b * nvox, *w_b = weight + b * nvox;
+    const int E = ACC ? det_scale(*fold.maxbits, lg) : 0;
+    uint32_t mx = 0;
+    const int k = live ? k_end[pix] : 0;
+    if (k >= 2 && k < TSDF_KMAX) {
+        const TsdfRay ray = tsdf_ray(cast.K + 16 * b, cast.poses + ((int64_t)b * cast.L + l) * 16, i * cast.s, j * cast.s, cast.step);
+        TsdfCell c0, c1, hc;
+        float f0, f1, z;
+        // (a tape that does not belong to this volume fails these tests; every gather stays behind tsdf_cell's bounds)
+        if (tsdf_sample_at(vol, o, f_b, w_b, cast.minw, tsdf_ray_at(ray, tsdf_ray_z(ray, k - 1)), c0, f0) &&
+            tsdf_sample_at(vol, o, f_b, w_b, cast.minw, tsdf_ray_at(ray, tsdf_ray_z(ray, k)), c1, f1) && f0 >= 0.0f && f1 < 0.0f &&
+            tsdf_hit_at(vol, o, w_b, cast.minw, ray, k, f0, f1, z, hc)) {
+            float gz = g_depth ? g_depth[pix] : 0.0f;
+            const bool col = fold.nch == 4 && g_rgb != nullptr;
+            f3 gc{0.0f, 0.0f, 0.0f};
+            if (col) {
+                const float *c_b = color + 3 * b * nvox;
+                gc = ld3(g_rgb, pix);
+                const float gch[3] = {gc.x, gc.y, gc.z};
+#pragma unroll
+                for (int ch = 0; ch < 3; ++ch) {  // g_z = g_depth + sum_ch g_rgb_ch (grad C_ch(p*) . dw) / v
+                    float c8[8];
+                    tsdf_gather8c(vol, c_b, hc.j, ch, c8);
+                    const f3 g = tsdf_trigrad(c8, hc);
+                    gz = gz + gch[ch] * (((g.x * ray.dw.x + g.y * ray.dw.y) + g.z * ray.dw.z) / vol.v);
+                }
+            }
+            const float den = f0 - f1, den2 = den * den, gs = gz * ray.dz;
+            const float a0 = gs * ((-f1) / den2), a1 = gs * (f0 / den2);
+            const int64_t at = b * nvox;
+#pragma unroll
+            for (int c = 0; c < 8; ++c) {
+                tsdf_cast_term<ACC>(fold, at + tsdf_corner(vol, c0.j, c), 0, a0 * tsdf_corner_weight(c0, c), E, mx);
+                tsdf_cast_term<ACC>(fold, at + tsdf_corner(vol, c1.j, c), 0, a1 * tsdf_corner_weight(c1, c), E, mx);
+                if (col) {
+                    const float w = tsdf_corner_weight(hc, c);
+                    const int64_t p = at + tsdf_corner(vol, hc.j, c);
+                    tsdf_cast_term<ACC>(fold, p, 1, gc.x * w, E, mx);
+                    tsdf_cast_term<ACC>(fold, p, 2, gc.y * w, E, mx);
+                    tsdf_cast_term<ACC>(fold, p, 3, gc.z * w, E, mx);
+                }
+            }
+        }
+    }
+    if (!ACC) {
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) mx = max(mx, (uint32_t)__shfl_xor((int)mx, off, kWave));
+        if ((threadIdx.x & 63) == 0 && mx > 0) atomicMax(fold.maxbits, mx);
+    }
+}
+
+// every voxel: each sum rounded once to fp32.  g_color may be NULL
+__global__ __launch_bounds__(TSDF_T) void tsdf_cast_finish_k(TsdfCastFold fold, int lg, int64_t total, float *__restrict__ g_tsdf,
+                                                             float *__restrict__ g_color) {
+    const int E = det_scale(*fold.maxbits, lg);
+    for (int64_t p = (int64_t)blockIdx.x * TSDF_T + threadIdx.x; p < total; p += (int64_t)gridDim.x * TSDF_T) {
+        const uint32_t fl = fold.flags[p];
+        for (int ch = 0; ch < fold.nch; ++ch) {
+            float r;
+            if (!fold_flagged((fl >> (3 * ch)) & 7u, r)) r = det_to_float(fold.acc[(p * fold.nch + ch) * 2], fold.acc[(p * fold.nch + ch) * 2 + 1], E);
+            if (ch == 0) g_tsdf[p] = r;
+            else if (g_color) g_color[3 * p + ch - 1] = r;
+        }
+    }
 }
 
 static inline bool tsdf_vol_ok(int B, int nx, int ny, int nz) {
@@ -509,6 +707,72 @@ int gs_tsdf_extract_backward(const float *tsdf, const float *color, int B, int n
             hipLaunchKernelGGL(tsdf_extract_bwd_k, dim3(cdiv(cap, TSDF_T), B), dim3(TSDF_T), 0, st, vol, tsdf, g_color ? color : nullptr, edge,
                                n_points, cap, g_points, g_color ? g_colors : nullptr, axis, end, g_tsdf, g_color);
     GS_LAUNCH_CHECK("gs_tsdf_extract_backward");
+    return GS_OK;
+}
+
+// the arguments a cast and its reverse pass share; kmax: the bound of a thread's loop
+#define TSDF_REQUIRE_CAST(name)                                                                                                             \
+    GS_REQUIRE(L > 0 && L <= 65535 && height > 0 && width > 0 && (int64_t)height * width <= INT32_MAX, name ": bad frames L=%d H=%d W=%d", L, \
+               height, width);                                                                                                              \
+    GS_REQUIRE(stride >= 1, name ": stride must be at least 1, got %d", stride);                                                            \
+    const int Ho = (int)(((int64_t)height + stride - 1) / stride), Wo = (int)(((int64_t)width + stride - 1) / stride);                      \
+    GS_REQUIRE((int64_t)cdiv(Ho, 16) * cdiv(Wo, 16) <= TSDF_CAST_TILES, name ": %d x %d output pixels need more than 2^22 tiles of 16 x 16", \
+               Ho, Wo);                                                                                                                     \
+    GS_REQUIRE(tsdf_pos(step), name ": step must be finite and positive, got %g", (double)step);                                            \
+    GS_REQUIRE(min_weight == min_weight, name ": min_weight must be a number");                                                             \
+    const double span = ((double)nx + ny + nz) * (double)voxel_size / (double)step;                                                         \
+    GS_REQUIRE(span <= 1048576.0, name ": (nx + ny + nz) voxel_size / step = %g exceeds 2^20 samples per ray", span)
+
+int gs_tsdf_raycast(const float *tsdf, const float *weight, const float *color, int B, int nx, int ny, int nz, float voxel_size,
+                    const float *origin, const float *intrinsics, const float *poses, int L, int height, int width, int stride, float step,
+                    float near, float far, float min_weight, float *depth, float *normal, float *rgb, int32_t *k_end, gs_stream_t stream) {
+    GS_REQUIRE(tsdf && weight && origin && intrinsics && poses && depth && normal && k_end, "gs_tsdf_raycast: NULL argument");
+    GS_REQUIRE((color != nullptr) == (rgb != nullptr), "gs_tsdf_raycast: color and rgb go together");
+    TSDF_REQUIRE_VOLUME("gs_tsdf_raycast");
+    TSDF_REQUIRE_CAST("gs_tsdf_raycast");
+    GS_REQUIRE(near >= 0.0f && far == far, "gs_tsdf_raycast: near must be a number >= 0 and far a number, got %g and %g", (double)near,
+               (double)far);
+    const TsdfVol vol{nx, ny, nz, voxel_size, 0.0f, 0.0f, origin};
+    const TsdfCast cast{intrinsics, poses, L, Ho, Wo, stride, (int)span + 1040, step, near, far, min_weight};
+    const dim3 grid(cdiv(Ho, 16) * cdiv(Wo, 16), L, B);
+    hipLaunchKernelGGL(color ? tsdf_raycast_k<true> : tsdf_raycast_k<false>, grid, dim3(TSDF_T), 0, (hipStream_t)stream, vol, cast, tsdf,
+                       weight, color, depth, normal, rgb, k_end);
+    GS_LAUNCH_CHECK("gs_tsdf_raycast");
+    return GS_OK;
+}
+
+size_t gs_tsdf_raycast_backward_ws_bytes(int B, int nx, int ny, int nz, int has_color) {
+    if (!tsdf_vol_ok(B, nx, ny, nz)) return 0;
+    return tsdf_cast_fold_layout(B, (int64_t)nx * ny * nz, has_color ? 4 : 1, nullptr, nullptr);
+}
+
+int gs_tsdf_raycast_backward(const float *tsdf, const float *weight, const float *color, int B, int nx, int ny, int nz, float voxel_size,
+                             const float *origin, const float *intrinsics, const float *poses, int L, int height, int width, int stride,
+                             float step, float min_weight, const int32_t *k_end, const float *g_depth, const float *g_rgb, float *g_tsdf,
+                             float *g_color, void *ws, size_t ws_bytes, gs_stream_t stream) {
+    GS_REQUIRE(tsdf && weight && origin && intrinsics && poses && k_end && g_tsdf, "gs_tsdf_raycast_backward: NULL argument");
+    GS_REQUIRE((color != nullptr) == (g_color != nullptr) && (!g_rgb || color), "gs_tsdf_raycast_backward: color and g_color go together, g_rgb needs them");
+    TSDF_REQUIRE_VOLUME("gs_tsdf_raycast_backward");
+    TSDF_REQUIRE_CAST("gs_tsdf_raycast_backward");
+    const size_t need = gs_tsdf_raycast_backward_ws_bytes(B, nx, ny, nz, color != nullptr);
+    if (!ws || ws_bytes < need) {
+        set_error("gs_tsdf_raycast_backward: workspace too small (%zu < %zu)", ws_bytes, need);
+        return GS_ERR_WORKSPACE_TOO_SMALL;
+    }
+    hipStream_t st = (hipStream_t)stream;
+    const TsdfVol vol{nx, ny, nz, voxel_size, 0.0f, 0.0f, origin};
+    const TsdfCast cast{intrinsics, poses, L, Ho, Wo, stride, 0, step, 0.0f, 0.0f, min_weight};
+    TsdfCastFold fold;
+    tsdf_cast_fold_layout(B, tsdf_nvox(vol), color ? 4 : 1, ws, &fold);
+    const int lg = tsdf_lg(2 * (int64_t)L * Ho * Wo);  // a voxel receives at most two terms per pixel of its batch element
+    const int64_t total = (int64_t)B * tsdf_nvox(vol);
+    const dim3 grid(cdiv(Ho, 16) * cdiv(Wo, 16), L, B);
+    GS_HIP(hipMemsetAsync(ws, 0, need, st), "gs_tsdf_raycast_backward/zero");
+    hipLaunchKernelGGL(tsdf_raycast_bwd_k<false>, grid, dim3(TSDF_T), 0, st, vol, cast, tsdf, weight, color, k_end, g_depth, g_rgb, fold, lg);
+    hipLaunchKernelGGL(tsdf_raycast_bwd_k<true>, grid, dim3(TSDF_T), 0, st, vol, cast, tsdf, weight, color, k_end, g_depth, g_rgb, fold, lg);
+    GS_LAUNCH_CHECK("gs_tsdf_raycast_backward/fold");
+    hipLaunchKernelGGL(tsdf_cast_finish_k, dim3(std::min(cdiv(total, TSDF_T), 65536)), dim3(TSDF_T), 0, st, fold, lg, total, g_tsdf, g_color);
+    GS_LAUNCH_CHECK("gs_tsdf_raycast_backward/finish");
     return GS_OK;
 }
 

@@ -196,9 +196,9 @@ class _MultiMaskSelectFn(torch.autograd.Function):
     sync for the length) forward, one expansion kernel backward."""
 
     @staticmethod
-    def forward(ctx, mask, *xs):
+    def forward(ctx, mask, n, *xs):
         outs, cnt = compact_multi_raw(list(xs), mask)
-        n = int(cnt.item())
+        n = int(cnt.item()) if n is None else n
         ctx.save_for_backward(mask)
         ctx.shapes = [x.shape for x in xs]
         return tuple(o[:n] for o in outs)
@@ -213,7 +213,7 @@ class _MultiMaskSelectFn(torch.autograd.Function):
         dev = mask.device
         outs = [torch.empty(shape, dtype=torch.float32, device=dev) for shape in ctx.shapes]
         if n == 0:
-            return (None, *outs)
+            return (None, None, *outs)
         m8 = mask.contiguous().view(torch.uint8) if mask.dtype == torch.bool else mask.contiguous()
         k = len(gs)
         # an empty selection leaves nothing to read: give the kernel a valid (unused) pointer
@@ -222,12 +222,13 @@ class _MultiMaskSelectFn(torch.autograd.Function):
         a_w = (ctypes.c_int * k)(*[o.numel() // n for o in outs])
         ws = workspace(ws_bytes("gs_compact_ws_bytes", n), dev, "compact")
         call("gs_expand_multi", k, a_g, a_w, a_out, ptr(m8), n, ptr(ws), ws.numel(), stream())
-        return (None, *outs)
+        return (None, None, *outs)
 
 
-def mask_select_multi(xs, mask: torch.Tensor):
-    """[x[mask] for x in xs] (<= 4 arrays, (n, C_a) float32 each), differentiable, one scan and one sync."""
-    return list(_MultiMaskSelectFn.apply(mask, *xs))
+def mask_select_multi(xs, mask: torch.Tensor, n: Optional[int] = None):
+    """[x[mask] for x in xs] (<= 4 arrays, (n, C_a) float32 each), differentiable, one scan and one sync -- none when the caller
+    already knows n = mask.sum()."""
+    return list(_MultiMaskSelectFn.apply(mask, n, *xs))
 
 
 def select_rows_multi(xs, mask: torch.Tensor):
@@ -1555,3 +1556,118 @@ def tsdf_extract(tsdf, weight, color, origin, voxel_size, min_weight: float = 1.
     if torch.is_tensor(tsdf) and tsdf.ndim == 4:
         origin = tsdf_origin(origin, tsdf.shape[0], tsdf.device, "tsdf_extract")
     return _TsdfExtractFn.apply(tsdf, color, weight, origin, voxel_size, min_weight, int(cap))
+
+
+def _tsdf_number(value, name, op):
+    try:
+        x = float(value)
+    except (TypeError, ValueError):
+        x = float("nan")
+    if math.isnan(x):
+        raise ValueError("{}: {} should be a number. Got {!r}.".format(op, name, value))
+    return x
+
+
+def _tsdf_cast(K, poses, B, dims, v, height, width, stride, step, min_weight, op):
+    """Checks the cameras and the sampling of a cast -> (K, poses, L, height, width, stride, step, min_weight)."""
+    if poses is None:
+        raise ValueError("{}: the cameras need poses (camera-to-world, (B, L, 4, 4)).".format(op))
+    _tsdf_on_device(op, K, poses)
+    if K.numel() != 16 * B or K.shape[-2:] != (4, 4):
+        raise ValueError("{}: intrinsics should hold one 4x4 matrix per batch element (B = {}). Got {}.".format(op, B, tuple(K.shape)))
+    if poses.ndim != 4 or poses.shape[0] != B or poses.shape[1] == 0 or poses.shape[1] > 65535 or poses.shape[2:] != (4, 4):
+        raise ValueError("{}: poses should have shape ({}, L, 4, 4) with 1 <= L <= 65535. Got {}.".format(op, B, tuple(poses.shape)))
+    for name, n in (("height", height), ("width", width), ("stride", stride)):
+        if not isinstance(n, int) or isinstance(n, bool) or n < 1:
+            raise ValueError("{}: {} should be a positive integer. Got {!r}.".format(op, name, n))
+    if height * width > 2 ** 31 - 1:
+        raise ValueError("{}: at most 2^31 - 1 pixels per image are supported. Got {} x {}.".format(op, height, width))
+    if -(-height // (16 * stride)) * -(-width // (16 * stride)) > 2 ** 22:
+        raise ValueError("{}: at most 2^22 tiles of 16 x 16 output pixels per image are supported. Got {} x {} at stride {}.".format(
+            op, height, width, stride))
+    step = _tsdf_positive(step, "step", op)
+    if sum(dims) * v / step > 2 ** 20:
+        raise ValueError("{}: (nx + ny + nz) voxel_size / step should be at most 2^20 samples per ray. Got {:g}.".format(
+            op, sum(dims) * v / step))
+    return _f32c(K), _f32c(poses), int(poses.shape[1]), height, width, stride, step, _tsdf_number(min_weight, "min_weight", op)
+
+
+def tsdf_raycast_raw(tsdf, weight, color, origin, voxel_size, K, poses, height: int, width: int, stride: int, step: float,
+                     near: float = 0.0, far: float = float("inf"), min_weight: float = 1.0):
+    """Cast the volume into the cameras K (B,1,4,4), poses (B,L,4,4) of height x width images, on the [::stride, ::stride] pixel
+    grid -> (depth (B,L,Ho,Wo), normal (B,L,Ho,Wo,3), rgb (B,L,Ho,Wo,3) or None without colours, k_end (B,L,Ho,Wo) int32).  The
+    rule (ray, sample, march, hit) is stated in include/gradslam_hip.h, T; `stride` and `step` are required here
+    (TSDFVolume.raycast defaults them to 1 and trunc / 2).  Misses hold zeros; k_end is the tape of tsdf_raycast_backward_raw.  One launch, no host synchronisation."""
+    op = "tsdf_raycast"
+    t, w, c, origin, dims, v = _tsdf_state(tsdf, weight, color, origin, voxel_size, op)
+    B, dev = t.shape[0], t.device
+    K, poses, L, height, width, stride, step, mw = _tsdf_cast(K, poses, B, dims, v, height, width, stride, step, min_weight, op)
+    near, far = _tsdf_number(near, "near", op), _tsdf_number(far, "far", op)
+    if near < 0.0:
+        raise ValueError("{}: near should not be negative. Got {!r}.".format(op, near))
+    Ho, Wo = -(-height // stride), -(-width // stride)
+    depth = torch.empty((B, L, Ho, Wo), dtype=torch.float32, device=dev)
+    normal = torch.empty((B, L, Ho, Wo, 3), dtype=torch.float32, device=dev)
+    rgb = None if c is None else torch.empty((B, L, Ho, Wo, 3), dtype=torch.float32, device=dev)
+    k_end = torch.empty((B, L, Ho, Wo), dtype=torch.int32, device=dev)
+    call("gs_tsdf_raycast", ptr(t), ptr(w), ptr(c), B, *dims, v, ptr(origin), ptr(K), ptr(poses), L, height, width, stride, step, near,
+         far, mw, ptr(depth), ptr(normal), ptr(rgb), ptr(k_end), stream())
+    return depth, normal, rgb, k_end
+
+
+def tsdf_raycast_backward_raw(tsdf, weight, color, origin, voxel_size, K, poses, height: int, width: int, stride, step, min_weight,
+                              k_end, g_depth=None, g_rgb=None):
+    """Adjoint of tsdf_raycast_raw for the tape k_end (a constant): g_depth (B,L,Ho,Wo), g_rgb (B,L,Ho,Wo,3) (None: zero) ->
+    (g_tsdf, g_color or None), written in full.  Every voxel's sum over its pixels is exact and rounded once: the same bits from
+    run to run (one path, with or without torch.use_deterministic_algorithms).  Poses, intrinsics and weights get no gradient."""
+    op = "tsdf_raycast_backward"
+    t, w, c, origin, dims, v = _tsdf_state(tsdf, weight, color, origin, voxel_size, op)
+    B, dev = t.shape[0], t.device
+    K, poses, L, height, width, stride, step, mw = _tsdf_cast(K, poses, B, dims, v, height, width, stride, step, min_weight, op)
+    Ho, Wo = -(-height // stride), -(-width // stride)
+    _tsdf_on_device(op, k_end, g_depth, g_rgb)
+    if k_end.dtype != torch.int32 or tuple(k_end.shape) != (B, L, Ho, Wo):
+        raise ValueError("{}: k_end should be int32 of shape {}. Got {} of {}.".format(op, (B, L, Ho, Wo), tuple(k_end.shape), k_end.dtype))
+    if g_depth is not None and g_depth.ndim == 5 and g_depth.shape[-1] == 1:
+        g_depth = g_depth[..., 0]
+    if g_depth is not None and tuple(g_depth.shape) != (B, L, Ho, Wo):
+        raise ValueError("{}: g_depth should have shape {}. Got {}.".format(op, (B, L, Ho, Wo), tuple(g_depth.shape)))
+    if g_rgb is not None and (c is None or tuple(g_rgb.shape) != (B, L, Ho, Wo, 3)):
+        raise ValueError("{}: g_rgb needs a volume with colours and the shape {}. Got {}.".format(op, (B, L, Ho, Wo, 3), tuple(g_rgb.shape)))
+    g_tsdf = torch.empty_like(t)
+    g_color = None if c is None else torch.empty_like(c)
+    ws = workspace(ws_bytes("gs_tsdf_raycast_backward_ws_bytes", B, *dims, int(c is not None)), dev, "tsdf_cast_bwd")
+    call("gs_tsdf_raycast_backward", ptr(t), ptr(w), ptr(c), B, *dims, v, ptr(origin), ptr(K), ptr(poses), L, height, width, stride, step,
+         mw, ptr(k_end.contiguous()), ptr(_f32c(g_depth)), ptr(_f32c(g_rgb)), ptr(g_tsdf), ptr(g_color), ptr(ws), ws.numel(), stream())
+    return g_tsdf, g_color
+
+
+class _TsdfRaycastFn(torch.autograd.Function):
+    """(tsdf, color | weight, origin, K, poses: constants) -> (depth, normal, rgb, k_end).  Which sample ends a ray and whether it
+    hits are constants of the graph; normals carry no gradient; poses, intrinsics and weights receive None."""
+
+    @staticmethod
+    def forward(ctx, tsdf, color, weight, origin, voxel_size, K, poses, height, width, stride, step, near, far, min_weight):
+        depth, normal, rgb, k_end = tsdf_raycast_raw(tsdf, weight, color, origin, voxel_size, K, poses, height, width, stride, step, near,
+                                                     far, min_weight)
+        ctx.save_for_backward(tsdf, color, weight, origin, K, poses, k_end)
+        ctx.cfg = (voxel_size, height, width, stride, step, min_weight)
+        ctx.mark_non_differentiable(normal, k_end)
+        return depth, normal, rgb, k_end
+
+    @staticmethod
+    def backward(ctx, g_depth, _g_normal, g_rgb, _g_k):
+        tsdf, color, weight, origin, K, poses, k_end = ctx.saved_tensors
+        voxel_size, height, width, stride, step, min_weight = ctx.cfg
+        g_tsdf, g_color = tsdf_raycast_backward_raw(tsdf, weight, color, origin, voxel_size, K, poses, height, width, stride, step,
+                                                    min_weight, k_end, g_depth, g_rgb if color is not None else None)
+        need = ctx.needs_input_grad
+        return (g_tsdf if need[0] else None, g_color if need[1] else None) + (None,) * 12
+
+
+def tsdf_raycast(tsdf, weight, color, origin, voxel_size, K, poses, height: int, width: int, stride: int, step: float,
+                 near: float = 0.0, far: float = float("inf"), min_weight: float = 1.0):
+    """Autograd-aware tsdf_raycast_raw, one node: gradients of depth and rgb reach tsdf and color."""
+    if torch.is_tensor(tsdf) and tsdf.ndim == 4:
+        origin = tsdf_origin(origin, tsdf.shape[0], tsdf.device, "tsdf_raycast")
+    return _TsdfRaycastFn.apply(tsdf, color, weight, origin, voxel_size, K, poses, height, width, stride, step, near, far, min_weight)

@@ -1,0 +1,124 @@
+"""KinectFusion: frame loop = ray-cast the volume from the previous pose, ICP against the cast surface, integrate
+(the paper's volumetric pipeline; the reference ships no counterpart)."""
+import warnings
+from typing import Optional, Union
+
+import torch
+import torch.nn as nn
+
+from ..geometry.geometryutils import compose_transformations
+from ..odometry.gradicp import GradICPOdometryProvider
+from ..odometry.icp import ICPOdometryProvider
+from ..odometry.icputils import downsample_rgbdimages
+from ..structures.rgbdimages import RGBDImages
+from ..structures.tsdfvolume import TSDFVolume
+
+__all__ = ["KinectFusion"]
+
+
+class KinectFusion(nn.Module):
+    r"""Volumetric SLAM: the map is a TSDFVolume of `dims` voxels of edge `voxel_size` at `origin` (`trunc`, `max_weight`, `color`
+    as in TSDFVolume).  Per frame s >= 1 with an ICP odometry (`odom` "icp" or "gradicp", parameters as in ICPSLAM):
+
+        target = volume.raycast_pointcloud(K, pose_{s-1}, H, W, stride=dsratio, step=step, min_weight=min_weight)
+        source = downsample_rgbdimages(live frame carrying pose_{s-1}, dsratio)
+        pose_s = compose_transformations(odomprov.provide(target, source), pose_{s-1})
+
+    and the frame is integrated under pose_s.  Frame 0 takes `frames.poses[:, 0]` if given, else the identity.  With
+    `odom="gt"` the frames' poses are used.  Under autograd every piece is a node of its own: gradients reach the depths and
+    colours through raycast, ICP and integrate (not the poses given, nor the intrinsics).  The volume should hold what the
+    cameras see (or `dist_thresh` be set): ICP pairs every frame point with its nearest cast point, and frame points beyond the
+    volume pair with the rim of the cast surface."""
+
+    def __init__(self, *, dims, voxel_size, origin=(0.0, 0.0, 0.0), trunc=None, max_weight: float = 128.0, color: bool = True,
+                 odom: str = "gradicp", dsratio: int = 4, numiters: int = 20, damp: float = 1e-8,
+                 dist_thresh: Union[float, int, None] = None, lambda_max: Union[float, int] = 2.0, B: Union[float, int] = 1.0,
+                 B2: Union[float, int] = 1.0, nu: Union[float, int] = 200.0, step: Optional[float] = None, min_weight: float = 1.0,
+                 device: Union[torch.device, str, None] = None):
+        super().__init__()
+        if odom not in ["gt", "icp", "gradicp"]:
+            msg = "odometry method ({}) not supported for KinectFusion. ".format(odom)
+            msg += "Currently supported odometry modules for KinectFusion are: 'gt', 'icp', 'gradicp'"
+            raise ValueError(msg)
+        if not isinstance(dsratio, int) or isinstance(dsratio, bool) or dsratio < 1:
+            raise ValueError("KinectFusion: dsratio should be a positive integer. Got {!r}.".format(dsratio))
+        odomprov = None
+        if odom == "icp":
+            odomprov = ICPOdometryProvider(numiters, damp, dist_thresh)
+        elif odom == "gradicp":
+            odomprov = GradICPOdometryProvider(numiters, damp, dist_thresh, lambda_max, B, B2, nu)
+        self.odom = odom
+        self.odomprov = odomprov
+        self.dsratio = dsratio
+        self.step_size = step
+        self.min_weight = min_weight
+        self.volume_args = dict(dims=dims, voxel_size=voxel_size, origin=origin, trunc=trunc, max_weight=max_weight, color=color)
+        self.device = torch.device(device) if device is not None else torch.device("cuda")
+
+    def new_volume(self, batch_size: int) -> TSDFVolume:
+        """An empty volume for `batch_size` sequences (raises for a device that is no HIP device)."""
+        return TSDFVolume(batch_size=batch_size, device=self.device, **self.volume_args)
+
+    def forward(self, frames: RGBDImages):
+        """frames (B, L, ...) -> (TSDFVolume, recovered poses (B, L, 4, 4))."""
+        if not isinstance(frames, RGBDImages):
+            raise TypeError("Expected frames to be of type gradslam.RGBDImages. Got {0}.".format(type(frames)))
+        batch_size, seq_len = frames.shape[:2]
+        volume = self.new_volume(batch_size)
+        recovered = []
+        prev_frame = None
+        for s in range(seq_len):  # true serial dependence: pose s needs the volume of the frames before it
+            live_frame = frames[:, s].to(self.device)
+            if s == 0 and live_frame.poses is None:
+                live_frame.poses = torch.eye(4, dtype=torch.float, device=self.device).view(1, 1, 4, 4).repeat(batch_size, 1, 1, 1)
+            volume, live_frame.poses = self._step(volume, live_frame, prev_frame, "frame {}, ".format(s))
+            prev_frame = live_frame if self.odom != "gt" else None
+            recovered.append(live_frame.poses[:, 0])
+        return volume, torch.stack(recovered, dim=1)
+
+    def step(self, volume: TSDFVolume, live_frame: RGBDImages, prev_frame: Optional[RGBDImages] = None):
+        """One step on `live_frame` (sequence length 1) -> (the volume with the frame integrated, live poses (B, 1, 4, 4)).
+        `live_frame.poses` is set to the recovered poses once they exist: a step that raises leaves the frame as it was."""
+        return self._step(volume, live_frame, prev_frame, "")
+
+    def _step(self, volume, live_frame, prev_frame, where):
+        if not isinstance(volume, TSDFVolume):
+            raise TypeError("Expected volume to be of type gradslam.TSDFVolume. Got {0}.".format(type(volume)))
+        if not isinstance(live_frame, RGBDImages):
+            raise TypeError("Expected live_frame to be of type gradslam.RGBDImages. Got {0}.".format(type(live_frame)))
+        live_frame.poses = self._localize(volume, live_frame, prev_frame, where)
+        return volume.integrate(live_frame), live_frame.poses
+
+    def _localize(self, volume: TSDFVolume, live_frame: RGBDImages, prev_frame: Optional[RGBDImages], where: str = ""):
+        if not isinstance(prev_frame, (RGBDImages, type(None))):
+            raise TypeError("Expected prev_frame to be of type gradslam.RGBDImages or None. Got {0}.".format(type(prev_frame)))
+        if live_frame.shape[1] != 1:
+            raise ValueError("Sequence length of live_frame must be 1, but was {0}.".format(live_frame.shape[1]))
+        if len(live_frame) != len(volume):
+            raise ValueError("Batch size of the frames and of the volume must match: ({0} != {1})".format(len(live_frame), len(volume)))
+        if prev_frame is not None:
+            if self.odom == "gt":
+                warnings.warn("`prev_frame` is not used when using `odom='gt'` (should be None)")
+            elif not prev_frame.has_poses:
+                raise ValueError("`prev_frame` should have poses, but did not.")
+        if prev_frame is None or self.odom == "gt":
+            if not live_frame.has_poses:
+                raise ValueError("`live_frame` must have poses when `prev_frame` is None or `odom='gt'`.")
+            return live_frame.poses
+
+        if live_frame.channels_first:
+            live_frame = live_frame.to_channels_last()
+        H, W = live_frame.shape[2:4]
+        target = volume.raycast_pointcloud(live_frame.intrinsics, prev_frame.poses, H, W, stride=self.dsratio, step=self.step_size,
+                                           min_weight=self.min_weight)
+        # the frame under the previous pose, as a frame of its own: the caller's keeps its poses until the step has succeeded
+        source = downsample_rgbdimages(RGBDImages(live_frame.rgb_image, live_frame.depth_image, live_frame.intrinsics, prev_frame.poses),
+                                       self.dsratio)
+        for b in range(len(volume)):  # never ICP on an empty cloud
+            if target._counts[b] == 0:
+                raise RuntimeError("KinectFusion: {}batch element {}: the camera of the previous pose sees nothing of the "
+                                   "volume (no ray hits an observed surface).".format(where, b))
+            if source._counts[b] == 0:
+                raise RuntimeError("KinectFusion: {}batch element {}: the frame has no valid pixel.".format(where, b))
+        transform = self.odomprov.provide(target, source)
+        return compose_transformations(transform.squeeze(1), prev_frame.poses.squeeze(1)).unsqueeze(1)

@@ -119,3 +119,69 @@ class TSDFVolume(object):
         out._adopt_padded(points, normals, colors, None)
         out._set_counts(counts)
         return out
+
+    # ------------------------------------------------------------------ ray casting
+    def _cast(self, intrinsics, poses, height, width, stride, step, near, far, min_weight):
+        op = "TSDFVolume.raycast"
+        for name, t in (("intrinsics", intrinsics), ("poses", poses)):
+            if not torch.is_tensor(t):
+                raise TypeError("{}: expected {} to be a tensor; got {}".format(op, name, type(t)))
+        if poses.ndim != 4 or poses.shape[0] != self._B:
+            raise ValueError("Batch size of the poses and of the volume must match: poses {} for a volume of {}.".format(
+                tuple(poses.shape), self._B))
+        if intrinsics.numel() != 16 * self._B:
+            raise ValueError("Batch size of the intrinsics and of the volume must match: intrinsics {} for a volume of {}.".format(
+                tuple(intrinsics.shape), self._B))
+        step = 0.5 * self.trunc if step is None else step
+        far = float("inf") if far is None else far
+        state = (self.tsdf, self.weight, self.color, self.origin, self.voxel_size, intrinsics, poses, height, width, stride, step, near,
+                 far, min_weight)
+        if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (self.tsdf, self.color)):
+            return ops.tsdf_raycast(*state)
+        return ops.tsdf_raycast_raw(*state)
+
+    def raycast(self, intrinsics, poses, height: int, width: int, *, stride: int = 1, step: Optional[float] = None, near: float = 0.0,
+                far: Optional[float] = None, min_weight: float = 1.0, return_normals: bool = False):
+        r"""The volume seen from the cameras `intrinsics` (B, 1, 4, 4), `poses` (B, L, 4, 4) (camera-to-world) of height x width
+        images, on the [::stride, ::stride] pixel grid: per pixel the ray is sampled every `step` (default trunc / 2) of space,
+        at depths near <= z <= far; a sample is observed iff the 8 voxels around it have weight >= min_weight, its value is
+        their trilinear interpolant; the first observed sample behind the surface (tsdf < 0) ends the ray, which hits iff the
+        sample before it is observed and in front (a ray that comes out of unobserved space, or starts inside, misses); the hit
+        is placed by linear interpolation between the two.  Returns a channels-last RGBDImages of the cast depth (z, not range;
+        0 on a miss) and colour (zero for a volume without colours) with the given poses and the intrinsics of the strided grid
+        (fx, fy, cx, cy divided by stride), so that its vertex maps are the hit points.  `return_normals=True` also returns the
+        (B, L, Ho, Wo, 3) image of global normals (the gradient of the interpolant, pointing into free space; 0 on a miss).
+        Differentiable w.r.t. tsdf and color (which sample ends a ray is a constant of the graph; normals carry no gradient);
+        not w.r.t. the poses, the intrinsics and the weights.  No host synchronisation."""
+        depth, normal, rgb, _ = self._cast(intrinsics, poses, height, width, stride, step, near, far, min_weight)
+        if rgb is None:
+            rgb = torch.zeros(tuple(depth.shape) + (3,), dtype=torch.float32, device=depth.device)
+        K = intrinsics.detach().to(torch.float32).reshape(self._B, 1, 4, 4).clone()
+        K[..., 0, 0] /= stride
+        K[..., 1, 1] /= stride
+        K[..., 0, 2] /= stride
+        K[..., 1, 2] /= stride
+        frames = RGBDImages(rgb, depth.unsqueeze(-1), K, poses.detach().to(torch.float32))
+        return (frames, normal) if return_normals else frames
+
+    def raycast_pointcloud(self, intrinsics, poses, height: int, width: int, *, stride: int = 1, step: Optional[float] = None,
+                           near: float = 0.0, far: Optional[float] = None, min_weight: float = 1.0) -> Pointclouds:
+        r"""The hit pixels of `raycast` from ONE camera per batch element (poses (B, 1, 4, 4)) as a Pointclouds, in pixel order:
+        global points (the global vertex map of the cast image), normals and, for a volume with colours, colours.
+        Differentiable w.r.t. tsdf and color, through the depth.  One host synchronisation (the sizes)."""
+        if torch.is_tensor(poses) and poses.ndim == 4 and poses.shape[1] != 1:
+            raise ValueError("TSDFVolume.raycast_pointcloud: one camera per batch element (L = 1). Got poses {}.".format(tuple(poses.shape)))
+        frames, normal = self.raycast(intrinsics, poses, height, width, stride=stride, step=step, near=near, far=far,
+                                      min_weight=min_weight, return_normals=True)
+        B = self._B
+        mask = (frames.depth_image > 0).reshape(-1)  # the hits: z* > 0
+        xs = [frames.global_vertex_map.reshape(-1, 3), normal.reshape(-1, 3)] + ([frames.rgb_image.reshape(-1, 3)] if self.has_colors else [])
+        counts = mask.view(B, -1).sum(1)
+        n = counts.tolist()  # the one host synchronisation
+        if torch.is_grad_enabled() and any(x.requires_grad for x in xs):
+            rows = ops.mask_select_multi(xs, mask, n=sum(n))
+        else:
+            rows, _ = ops.compact_multi_raw(xs, mask)
+        at = [sum(n[:b]) for b in range(B + 1)]
+        split = lambda x: [x[at[b]: at[b + 1]] for b in range(B)]
+        return Pointclouds(points=split(rows[0]), normals=split(rows[1]), colors=split(rows[2]) if self.has_colors else None)

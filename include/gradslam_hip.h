@@ -787,6 +787,54 @@ int gs_tsdf_extract_backward(const float *tsdf, const float *color, int B, int n
                              const int32_t *edge, const int32_t *n_points, int cap, const float *g_points,
                              const float *g_colors, float *g_tsdf, float *g_color, gs_stream_t stream);
 
+/* Ray casting: the volume seen from the cameras intrinsics (B,4,4), poses (B,L,4,4) (camera-to-world) of height x width images,
+ * on the strided grid: output pixel (i, j) of Ho = ceil(height / stride) rows and Wo = ceil(width / stride) columns is
+ * full-resolution pixel (h, w) = (i stride, j stride).  IEEE fp32 in the order written, no contraction:
+ *   ray     dx = ((float)w - cx) / fx, dy = ((float)h - cy) / fy, dw_i = (R_i0 dx + R_i1 dy) + R_i2,
+ *           len = sqrtf((dx dx + dy dy) + 1), dz = step / len.  Sample k (1 <= k < 2^30) lies at camera depth
+ *           z_k = (float)k * dz (one rounded product, never a running sum) at p_i = t_i + z_k dw_i; the ray's samples are the k
+ *           with near <= z_k <= far.  Depth is z, not range.  Consecutive samples are exactly `step` apart in space.
+ *   sample  per axis g = (p - o) / v - 0.5f, i = floorf(g), a = g - i; inside iff 0 <= i and i + 1 <= n - 1 on all three axes;
+ *           observed iff inside and all 8 corner weights are >= min_weight.  Its value f: lerp(p, q, s) = p + s (q - p), four
+ *           times along x, twice along y, once along z.  Colour the same way per component.
+ *   march   in ascending k; it ends at the first observed sample with f < 0 (zero counts as outside).  The end is a hit iff
+ *           sample k - 1 belongs to the ray, is observed and has f_prev >= 0; otherwise, and when no sample ends it, a miss.
+ *   hit     s = f_prev / (f_prev - f), z* = ((float)(k - 1) + s) * dz, p* = t + z* dw; p* not observed -> a miss.  Colour: the
+ *           interpolant at p*.  Normal: the gradient of the interpolant at p* (differences along the axis, lerped over the
+ *           other two, x before y before z), divided by sqrtf((gx gx + gy gy) + gz gz); it points into free space; a zero
+ *           gradient -> a miss.
+ *   depth (B,L,Ho,Wo): z*, 0 on a miss; normal (B,L,Ho,Wo,3): 0 on a miss; rgb (B,L,Ho,Wo,3): 0 on a miss, goes together with
+ *   color (both or neither); k_end (B,L,Ho,Wo) int32: the ending sample of a hit, 0 on a miss -- the tape of the reverse pass.
+ * A thread skips the samples that the ray's clip against the box [o, o + n v] (half a voxel wider than the positions that have
+ * a cell, then one sample and 2^-21 of the index wider on each side) proves to be outside; a skipped sample and an unobserved one
+ * mean the same to the march, so skipping changes no result.  A ray parallel to an axis divides by nothing.  Refused before any
+ * device work: stride < 1, a step that is not finite and positive, near < 0 or NaN, far NaN, L > 65535, more than 2^22 tiles of
+ * 16 x 16 output pixels per image, and
+ * (nx + ny + nz) voxel_size / step > 2^20 -- the bound of a thread's loop, which visits at most that many samples (+ 1040).
+ * One launch, one thread per output pixel, a wave per 8x8 tile; no workspace, no atomics, nothing synchronises the host. */
+int gs_tsdf_raycast(const float *tsdf, const float *weight, const float *color, int B, int nx, int ny, int nz,
+                    float voxel_size, const float *origin, const float *intrinsics, const float *poses, int L, int height,
+                    int width, int stride, float step, float near, float far, float min_weight, float *depth,
+                    float *normal, float *rgb, int32_t *k_end, gs_stream_t stream);
+
+/* Reverse pass of the cast for the tape k_end (the decisions are constants of the graph; normals carry no gradient; poses,
+ * intrinsics and weights receive none).  Per hit pixel the samples k - 1 and k and the hit are recomputed by the forward's
+ * bodies (a tape entry whose recomputation is no hit is skipped).  With
+ *   g_z = g_depth + sum_ch g_rgb_ch (grad C_ch(p*) . dw) / voxel_size
+ * the 8 corners of sample k - 1 receive g_z dz (-f) / (f_prev - f)^2 times their trilinear weight (wx wy) wz, those of sample k
+ * g_z dz f_prev / (f_prev - f)^2 times theirs, and the 8 corners of p* receive g_rgb times their weight into g_color.
+ * g_tsdf (B,nz,ny,nx) and g_color (B,nz,ny,nx,3; goes together with color) are written in full: per voxel the EXACT sum of its
+ * pixels' terms rounded once to fp32 (the fold of gs_tsdf_integrate_backward with lg = ceil(log2(2 L Ho Wo))): the same bits
+ * from run to run, whatever the order.  g_depth / g_rgb may be NULL (zero).  One memset and three launches.
+ * Workspace, every piece rounded up to 256 bytes, with N = B nx ny nz and C = 4 with colours, else 1:
+ *   4 B (maximum) | 4 B N (flags) | 16 B N C (sums). */
+size_t gs_tsdf_raycast_backward_ws_bytes(int B, int nx, int ny, int nz, int has_color);
+int gs_tsdf_raycast_backward(const float *tsdf, const float *weight, const float *color, int B, int nx, int ny, int nz,
+                             float voxel_size, const float *origin, const float *intrinsics, const float *poses, int L,
+                             int height, int width, int stride, float step, float min_weight, const int32_t *k_end,
+                             const float *g_depth, const float *g_rgb, float *g_tsdf, float *g_color, void *ws,
+                             size_t ws_bytes, gs_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

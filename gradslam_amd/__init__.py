@@ -14,4 +14,4 @@ __version__ = "0.1.0"
 
 from . import geometry, metrics, odometry, slam, structures  # noqa: F401,E402
 from .geometry.projutils import *  # noqa: F401,F403,E402  (reference __init__.py:6)
-from .structures import Pointclouds, RGBDImages, TSDFVolume  # noqa: F401,E402
+from .structures import Meshes, Pointclouds, RGBDImages, TSDFVolume  # noqa: F401,E402

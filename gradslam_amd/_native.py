@@ -156,6 +156,8 @@ SIGNATURES = {
     "gs_tsdf_raycast_backward_ws_bytes": (c_sz, [c_i, c_i, c_i, c_i, c_i]),
     "gs_tsdf_raycast_backward": (c_i, [c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_f, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_f, c_f, c_p, c_p, c_p,
                                        c_p, c_p, c_p, c_sz, c_p]),
+    "gs_tsdf_faces_ws_bytes": (c_sz, [c_i, c_i, c_i, c_i]),
+    "gs_tsdf_faces": (c_i, [c_p, c_p, c_i, c_i, c_i, c_i, c_f, c_p, c_p, c_i, c_i, c_p, c_p, c_p, c_sz, c_p]),
 }
 
 _lib = None

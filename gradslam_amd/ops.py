@@ -1558,6 +1558,56 @@ def tsdf_extract(tsdf, weight, color, origin, voxel_size, min_weight: float = 1.
     return _TsdfExtractFn.apply(tsdf, color, weight, origin, voxel_size, min_weight, int(cap))
 
 
+MESH_NMAX = 1 << 28  # voxels per batch element of a meshed volume: face counts are int32, 5 per cube
+
+
+def tsdf_faces_raw(tsdf, weight, min_weight, edge, n_points, fcap: int = 0, points_fit: bool = False):
+    """The triangles of a volume's surface over the rows of tsdf_extract_raw (marching cubes; the case table is generated by
+    tools/gen_mc_table.py) -> (faces (B,fcap,3) int32, n_faces (B,) int32).  A cube of 8 voxels emits iff all its corners are
+    observed (weight >= min_weight); faces come in ascending cube id, then table order, counter-clockwise seen from free space,
+    and index the rows of `edge` (B,vcap) / `n_points` (B,) -- the edge list and count tsdf_extract_raw returned for the same
+    volume and min_weight.  The first min(n_faces, fcap) rows are written, the others hold -1; n_faces is the full count.
+    fcap = 0 only counts (faces is None; edge and n_points may be None): size with it first.  A truncated edge list
+    (vcap < n_points) is refused: the counts are read back for that (one host synchronisation) unless the caller, who sized
+    vcap from them, passes points_fit=True.  Integers only: no autograd node."""
+    op = "tsdf_faces"
+    _tsdf_on_device(op, tsdf, weight, edge, n_points)
+    if tsdf.ndim != 4 or tsdf.shape[0] == 0 or tsdf.shape[0] > 65535:
+        raise ValueError("{}: tsdf should have shape (B, nz, ny, nx) with 1 <= B <= 65535. Got {}.".format(op, tuple(tsdf.shape)))
+    B, nz, ny, nx = (int(n) for n in tsdf.shape)
+    _tsdf_dims((nx, ny, nz), op)
+    if nx * ny * nz > MESH_NMAX:
+        raise ValueError("{}: at most 2^28 voxels per batch element can be meshed. Got dims {} = {} voxels.".format(
+            op, (nx, ny, nz), nx * ny * nz))
+    if weight.shape != tsdf.shape:
+        raise ValueError("{}: weight should have the shape of tsdf {}. Got {}.".format(op, tuple(tsdf.shape), tuple(weight.shape)))
+    mw = _tsdf_number(min_weight, "min_weight", op)
+    fcap = int(fcap)
+    if fcap < 0 or fcap > 5 * MESH_NMAX:
+        raise ValueError("{}: fcap should lie in 0 .. 5 * 2^28. Got {}.".format(op, fcap))
+    vcap = 0
+    if fcap:
+        if edge is None or n_points is None:
+            raise ValueError("{}: fcap = {} rows need the edge list and n_points of tsdf_extract_raw.".format(op, fcap))
+        if edge.dtype != torch.int32 or edge.ndim != 2 or edge.shape[0] != B:
+            raise ValueError("{}: edge should be int32 of shape ({}, vcap). Got {} of {}.".format(op, B, tuple(edge.shape), edge.dtype))
+        if n_points.dtype != torch.int32 or n_points.numel() != B:
+            raise ValueError("{}: n_points should be {} int32 values. Got {} of {}.".format(op, B, n_points.numel(), n_points.dtype))
+        vcap = int(edge.shape[1])
+        if not points_fit and int(n_points.max()) > vcap:
+            raise ValueError("{}: the edge list is truncated: it holds {} rows per batch element, n_points is up to {}.".format(
+                op, vcap, int(n_points.max())))
+        edge, n_points = edge.contiguous(), n_points.contiguous()
+    t, w = _f32c(tsdf.detach()), _f32c(weight.detach())
+    dev = t.device
+    n_faces = torch.empty((B,), dtype=torch.int32, device=dev)
+    faces = torch.empty((B, fcap, 3), dtype=torch.int32, device=dev) if fcap else None
+    ws = workspace(ws_bytes("gs_tsdf_faces_ws_bytes", B, nx, ny, nz), dev, "tsdf_faces")
+    call("gs_tsdf_faces", ptr(t), ptr(w), B, nx, ny, nz, mw, ptr(edge) if (fcap and vcap) else None, ptr(n_points) if fcap else None, vcap,
+         fcap, ptr(faces), ptr(n_faces), ptr(ws), ws.numel(), stream())
+    return faces, n_faces
+
+
 def _tsdf_number(value, name, op):
     try:
         x = float(value)

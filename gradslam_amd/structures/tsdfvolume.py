@@ -1,14 +1,15 @@
 """TSDFVolume: a dense truncated signed-distance grid per batch element, the volumetric map of KinectFusion-style dense SLAM.
 
-Posed RGB-D frames are fused into it (`integrate`), a surface is taken out of it as a `Pointclouds` (`extract_pointcloud`);
-both steps are differentiable.  The reference ships no counterpart (the paper describes one).  All arithmetic runs in the HIP
-kernels of csrc/tsdf.hip; nothing here computes on the CPU.
+Posed RGB-D frames are fused into it (`integrate`), a surface is taken out of it as a `Pointclouds` (`extract_pointcloud`) or
+as a triangle mesh (`extract_mesh`); all of it is differentiable.  The reference ships no counterpart (the paper describes one).  All arithmetic runs in the HIP
+kernels of csrc/tsdf.hip and csrc/mesh.hip; nothing here computes on the CPU.
 """
 from typing import Optional
 
 import torch
 
 from .. import ops
+from .meshes import Meshes
 from .pointclouds import Pointclouds
 from .rgbdimages import RGBDImages
 
@@ -119,6 +120,34 @@ class TSDFVolume(object):
         out._adopt_padded(points, normals, colors, None)
         out._set_counts(counts)
         return out
+
+    def extract_mesh(self, min_weight: float = 1.0) -> Meshes:
+        r"""The surface as a Meshes (marching cubes).  The vertices, normals and colours are `extract_pointcloud(min_weight)`'s,
+        bit for bit and in its order (the same call, the same autograd node); the faces index those rows.  A cube of 8
+        neighbouring voxels emits triangles iff all 8 are observed, so a vertex on the rim of the observed region may be
+        referenced by no face: such vertices are kept (the rows stay the point cloud's).  Faces come in ascending cube id and
+        run counter-clockwise seen from free space: the face normals point the way the vertex normals do.  Where the volume
+        is observed the mesh is closed and manifold (the case table resolves an ambiguous cube face from that face's signs
+        alone, so neighbouring cubes agree).  Anything computed from `verts` or `colors` is differentiable w.r.t. tsdf and
+        color (which edges cross and which cubes emit are constants of the graph).  One host synchronisation (both sizes).
+        An empty volume gives B meshes without vertices and faces."""
+        state = (self.tsdf, self.weight, self.color, self.origin, self.voxel_size, min_weight)
+        with torch.no_grad():
+            n_points = ops.tsdf_extract_raw(*state, cap=0)[4]
+            n_faces = ops.tsdf_faces_raw(self.tsdf, self.weight, min_weight, None, None, fcap=0)[1]
+        sizes = torch.stack([n_points, n_faces]).tolist()  # the one host synchronisation
+        vcap, fcap = max(sizes[0]), max(sizes[1])
+        B = self._B
+        if vcap > 0:
+            verts, normals, colors, edge, n_pts = ops.tsdf_extract(*state, cap=vcap)
+        else:
+            empty = lambda: torch.zeros((B, 0, 3), dtype=torch.float32, device=self.device)
+            verts, normals, colors = empty(), empty(), (empty() if self.has_colors else None)
+        if fcap > 0:
+            faces, _ = ops.tsdf_faces_raw(self.tsdf, self.weight, min_weight, edge, n_pts, fcap=fcap, points_fit=True)
+        else:
+            faces = torch.full((B, 0, 3), -1, dtype=torch.int32, device=self.device)
+        return Meshes._from_padded(verts, faces, normals, colors, sizes[0], sizes[1])
 
     # ------------------------------------------------------------------ ray casting
     def _cast(self, intrinsics, poses, height, width, stride, step, near, far, min_weight):

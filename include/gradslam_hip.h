@@ -835,6 +835,26 @@ int gs_tsdf_raycast_backward(const float *tsdf, const float *weight, const float
                              const float *g_depth, const float *g_rgb, float *g_tsdf, float *g_color, void *ws,
                              size_t ws_bytes, gs_stream_t stream);
 
+/* Triangle meshes (marching cubes over the rows of gs_tsdf_extract).  A cube is the 8 voxels whose lowest corner is voxel j
+ * (corner c = dx + 2 dy + 4 dz); it emits iff all 8 corners are observed (weight >= min_weight); its case has bit c set iff
+ * tsdf < 0 at corner c (zero counts as outside, as for the edges).  The case table is generated by tools/gen_mc_table.py
+ * (csrc/gs_mc_table.hpp): cube edge k = 4 a + o1 + 2 o2 runs along axis a from the corner with offsets o1, o2 on the two other
+ * axes (ascending); its vertex is edge slot e = 3 j' + a of the extraction, j' the voxel at its lower end.  On an ambiguous
+ * face the two segments each go round one inside corner, which the face's four signs alone decide: the two cubes sharing the
+ * face agree, so the mesh is closed wherever the volume is observed.  Triangles run counter-clockwise seen from free space.
+ *   edge (B,vcap) int32, n_points (B,): the rows of gs_tsdf_extract for the same volume and min_weight; a triangle's corner is
+ *   the row r with edge[b,r] = e, found by binary search of edge[b, 0 .. min(n_points[b], vcap)); an e that is not there (a
+ *   truncated list, vcap < n_points[b]) gives -1; nothing is read past vcap.
+ *   faces (B,fcap,3) int32: ascending cube id, then table order; the first min(n, fcap) rows are written, the others hold -1;
+ *   n_faces (B,): the full count, whatever fcap.  fcap = 0 (faces, edge, n_points may be NULL) only counts.
+ * Refused: nx ny nz > 2^28 (5 faces per cube must fit int32).  One memset (with fcap > 0) and three launches (per-block counts,
+ * per-batch-element scan, ordered write); no float atomics, nothing synchronises the host.
+ * Workspace, every piece rounded up to 256 bytes:  4 B B ceil(nx ny nz / 1024), twice (block counts and offsets). */
+size_t gs_tsdf_faces_ws_bytes(int B, int nx, int ny, int nz);
+int gs_tsdf_faces(const float *tsdf, const float *weight, int B, int nx, int ny, int nz, float min_weight,
+                  const int32_t *edge, const int32_t *n_points, int vcap, int fcap, int32_t *faces, int32_t *n_faces,
+                  void *ws, size_t ws_bytes, gs_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -18,11 +18,12 @@ def inverse_intrinsics(K: torch.Tensor, eps: float = 1e-6) -> torch.Tensor:
     return Kinv
 
 
-def pixel_grid(B: int, L: int, H: int, W: int) -> torch.Tensor:
+def pixel_grid(B: int, L: int, H: int, W: int, dtype=torch.float32) -> torch.Tensor:
     """(w, h, 1) per pixel: reference structures/rgbdimages.py:647-661 with the float32
-    linspace meshgrid of geometry/geometryutils.py:599-608."""
-    hs = torch.linspace(0, H - 1, H)
-    ws = torch.linspace(0, W - 1, W)
+    linspace meshgrid of geometry/geometryutils.py:599-608.  `dtype` is the reference's float32 unless a test
+    runs the whole oracle in float64 (the integers 0 .. H-1, 0 .. W-1 are exact in either)."""
+    hs = torch.linspace(0, H - 1, H, dtype=dtype)
+    ws = torch.linspace(0, W - 1, W, dtype=dtype)
     hh, ww = torch.meshgrid([hs, ws], indexing="ij")
     pix = torch.stack([ww, hh, torch.ones_like(ww)], -1)
     return pix.view(1, 1, H, W, 3).repeat(B, L, 1, 1, 1)

@@ -1,4 +1,5 @@
-"""Depth -> vertex / normal maps (local + global), channels-last.  fp32 torch CPU ops."""
+"""Depth -> vertex / normal maps (local + global), channels-last.  torch CPU ops in the dtype of the depth map: float32
+like the reference, or float64 when a test wants the same statements at higher precision."""
 import torch
 
 from .geometry import inverse_intrinsics, pixel_grid
@@ -8,7 +9,7 @@ def vertex_map(depth: torch.Tensor, K: torch.Tensor) -> torch.Tensor:
     """depth (B,L,H,W,1), K (B,1,4,4) -> (B,L,H,W,3).  reference
     structures/rgbdimages.py:643-679 (einsum then *depth then *valid)."""
     B, L, H, W, _ = depth.shape
-    pix = pixel_grid(B, L, H, W).to(depth.device)
+    pix = pixel_grid(B, L, H, W, depth.dtype).to(depth.device)
     Kinv = inverse_intrinsics(K)[..., :3, :3].repeat(1, L, 1, 1)
     V = torch.einsum("bsjc,bshwc->bshwj", Kinv, pix) * depth
     return V * (depth > 0).to(V.dtype)

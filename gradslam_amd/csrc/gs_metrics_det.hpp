@@ -27,8 +27,7 @@ __global__ __launch_bounds__(256) void cham_bwd_rows_k(ChamIn in, const unsigned
 
 struct ChamDetWs {
     float *rows[2];  // per direction: (B, cap[d], DET_ROW)
-    uint32_t *maxbits, *flags;
-    unsigned long long *acc;  // one fold's accumulators, reused by the folds in stream order
+    Fold fold;       // one fold's workspace (max(cap) x DET_NCH), reused by the folds in stream order
 };
 static size_t cham_det_layout(int B, int cap0, int cap1, void *ws, ChamDetWs *out) {
     Carve c{(char *)ws};
@@ -36,9 +35,7 @@ static size_t cham_det_layout(int B, int cap0, int cap1, void *ws, ChamDetWs *ou
     const size_t capm = (size_t)std::max(cap0, cap1);
     r.rows[0] = c.take<float>((size_t)B * cap0 * DET_ROW * 4);
     r.rows[1] = c.take<float>((size_t)B * cap1 * DET_ROW * 4);
-    r.maxbits = c.take<uint32_t>(4);
-    r.flags = c.take<uint32_t>(capm * 4);
-    r.acc = c.take<unsigned long long>(capm * 6 * 16);
+    r.fold = fold_carve(c, capm, DET_NCH);
     return c.off;
 }
 
@@ -55,7 +52,7 @@ int chamfer_det_scatter(const ChamIn &in, int B, const unsigned long long *keys_
     for (int b = 0; b < B; ++b)
         for (int d = 0; d < 2; ++d) {
             const int t = 1 - d;
-            const DetWs dw{w.rows[d] + (int64_t)b * in.cap[d] * DET_ROW, w.maxbits, w.flags, w.acc};
+            const DetWs dw{w.rows[d] + (int64_t)b * in.cap[d] * DET_ROW, w.fold};
             const int rc = det_fold_run(dw, 1, in.cap[d], in.cnt[d] + b, in.cnt[t] + b, in.cap[t], g_pts[t] + (int64_t)b * in.cap[t] * 3,
                                         nullptr, st, name);
             if (rc != GS_OK) return rc;

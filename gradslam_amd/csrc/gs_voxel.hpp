@@ -4,6 +4,7 @@
 // Clouds come as the renderer and the metrics take them: points (B, N_max, 3) fp32, padded, with (B,) int32 device counts.
 #pragma once
 #include "gs_common.hpp"
+#include "gs_fixed128.hpp"
 
 namespace gs {
 
@@ -12,7 +13,6 @@ constexpr int VOX_NMAX = 1 << 29;                   // rows per batch element at
 constexpr int VOX_CMAX = 64;                        // components per attribute at most
 constexpr int VOX_KBIAS = 1 << 20;                  // |k| < 2^20 per axis: 21 biased bits, three axes in 63
 constexpr unsigned long long VOX_EMPTY = ~0ull;     // bit 63 set: no valid key
-constexpr int VOX_FLAGS_PER_WORD = 10;              // 3 bits (NaN, +inf, -inf) per component, ten components per flag word
 
 // slots per batch element: the smallest power of two >= 2 N_max (load <= 0.5)
 static inline int64_t vox_slots(int N_max) {
@@ -21,12 +21,6 @@ static inline int64_t vox_slots(int N_max) {
     return s;
 }
 static inline int vox_blocks(int N_max) { return cdiv(N_max, 1024); }  // = compact_blocks(N_max): rows per compaction block
-static inline int vox_flag_words(int C) { return (C + VOX_FLAGS_PER_WORD - 1) / VOX_FLAGS_PER_WORD; }
-static inline int vox_lg(int N_max) {  // ceil(log2 N_max): no voxel has more members
-    int lg = 0;
-    while (((int64_t)1 << lg) < N_max) ++lg;
-    return lg;
-}
 
 // The voxel of a point: k = floorf((p - o) / v) per axis, one fp32 subtraction and one IEEE fp32 division (no fast-math, no
 // contraction).  False for a non-finite coordinate and for |k| >= 2^20 on any axis (a NaN or infinite quotient included).
@@ -73,18 +67,12 @@ static size_t vox_assign_layout(int B, int N_max, void *ws, VoxWs *out) {
     return c.off;
 }
 
-// ------------------------------------------------------------------ workspace of gs_voxel_reduce (zeroed as one piece)
-struct VoxRedWs {
-    unsigned long long *acc;  // (B, M_max, C, 2) the (lo, hi) words of the 128-bit sums
-    uint32_t *flags;          // (B, M_max, ceil(C / 10)) non-finite members: 3 bits per component
-    uint32_t *maxbits;        // 1: float bits of the largest finite |x| among the members
-};
-static size_t vox_reduce_layout(int B, int M_max, int C, void *ws, VoxRedWs *out) {
+// ------------------------------------------------------------------ workspace of gs_voxel_reduce (zeroed as one piece): the
+// fold of gs_fixed128.hpp over B M_max rows of C sums
+static size_t vox_reduce_layout(int B, int M_max, int C, void *ws, Fold *out) {
     Carve c{(char *)ws};
-    VoxRedWs scratch, &r = out ? *out : scratch;
-    r.acc = c.take<unsigned long long>((size_t)B * M_max * C * 16);
-    r.flags = c.take<uint32_t>((size_t)B * M_max * vox_flag_words(C) * 4);
-    r.maxbits = c.take<uint32_t>(4);
+    const Fold f = fold_carve(c, (size_t)B * M_max, C, true);  // sums | flags | maximum
+    if (out) *out = f;
     return c.off;
 }
 

@@ -20,8 +20,7 @@
 //      face's bound (a target at equal distance may have a lower row), or when no face has a target beyond it.  Otherwise the
 //      faces whose bound is not above the K-th distance grow by one layer and only the new cells are examined.
 //      The result is a property of the key set alone: it does not depend on g, on either cloud's row order or on arrival order.
-//   R  gs_knn_backward: g_src in fp32 in slot order; g_tgt as the exact sum in 128-bit fixed point (gs_fixed128.hpp), the
-//      three steps of voxel.hip's reduction: maximum, integer atomics, one rounding.
+//   R  gs_knn_backward: g_src in fp32 in slot order; g_tgt by the exact fold of gs_fixed128.hpp (the rule is stated there).
 //   E  gs_knn_normals: fp64 covariance of the neighbours, cyclic Jacobi, the eigenvector of the smallest eigenvalue.
 // No float atomic, no allocation, no host synchronisation; launch counts do not depend on the counts, B or K.
 #include <stddef.h>
@@ -325,23 +324,14 @@ struct NbBwd {
     const unsigned long long *keys;  // (B, cap0, K)
     const float *g_d2;               // (B, cap0, K)
     float *g_src, *g_tgt;            // (B, cap0, 3), (B, cap1, 3)
-    unsigned long long *acc;         // (B, cap1, 3, 2) the (lo, hi) words of the sums     } zeroed together
-    uint32_t *flags;                 // (B, cap1) non-finite terms: 3 bits per component   }
-    uint32_t *maxbits;               // 1: float bits of the largest finite |v|            }
+    Fold fold;                       // (B cap1) x 3: the sums of g_tgt (gs_fixed128.hpp), zeroed as one piece
     int lg;
 };
 static size_t nb_bwd_layout(int B, int cap1, void *ws, NbBwd *out) {
     Carve c{(char *)ws};
-    NbBwd scratch, &r = out ? *out : scratch;
-    r.acc = c.take<unsigned long long>((size_t)B * cap1 * 3 * 16);
-    r.flags = c.take<uint32_t>((size_t)B * cap1 * 4);
-    r.maxbits = c.take<uint32_t>(4);
+    const Fold f = fold_carve(c, (size_t)B * cap1, 3, true);  // sums | flags | maximum
+    if (out) out->fold = f;
     return c.off;
-}
-static inline int nb_lg(int cap0, int K) {  // ceil(log2(cap0 K)): no target row receives more terms
-    int lg = 0;
-    while (((int64_t)1 << lg) < (int64_t)cap0 * K) ++lg;
-    return lg;
 }
 
 // The term of slot (i, k): with j its neighbour, c = 2 g_d2[i, k], delta = s_i - t_j, v = c delta, all fp32.  False (v = 0)
@@ -376,63 +366,39 @@ __global__ __launch_bounds__(NB_T) void nb_bwd_src_k(NbBwd a) {
                 int j;
                 if (!nb_term(a, b, nt, i, k, v, j)) continue;
                 g = f3{g.x + v.x, g.y + v.y, g.z + v.z};
-                const uint32_t ux = fbits(v.x) & 0x7fffffffu, uy = fbits(v.y) & 0x7fffffffu, uz = fbits(v.z) & 0x7fffffffu;
-                if (ux < 0x7f800000u) mx = max(mx, ux);
-                if (uy < 0x7f800000u) mx = max(mx, uy);
-                if (uz < 0x7f800000u) mx = max(mx, uz);
+                mx = fold_max(fold_max(fold_max(mx, v.x), v.y), v.z);
             }
         st3(g_src, i, g);
     }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) mx = max(mx, (uint32_t)__shfl_xor((int)mx, off, kWave));
-    if ((threadIdx.x & 63) == 0 && mx > 0) atomicMax(a.maxbits, mx);
+    fold_max_commit(a.fold.maxbits, mx);
 }
 
 // grid (x: slots (i, k), y: batch element): -v of every slot into its target's 128-bit sums
 __global__ __launch_bounds__(NB_T) void nb_bwd_acc_k(NbBwd a) {
     const int b = blockIdx.y, ns = nb_count(a.in, 0, b), nt = nb_count(a.in, 1, b), K = a.in.K;
-    const int E = det_scale(*a.maxbits, a.lg);
+    const int E = det_scale(*a.fold.maxbits, a.lg);
     const int64_t total = (int64_t)ns * K;
     for (int64_t e = (int64_t)blockIdx.x * NB_T + threadIdx.x; e < total; e += (int64_t)gridDim.x * NB_T) {
         const int i = (int)(e / K), k = (int)(e - (int64_t)i * K);
         f3 v;
         int j;
         if (!nb_term(a, b, nt, i, k, v, j)) continue;
-        const uint32_t nbits[3] = {fbits(v.x) ^ 0x80000000u, fbits(v.y) ^ 0x80000000u, fbits(v.z) ^ 0x80000000u};
         const int64_t row = (int64_t)b * a.in.cap[1] + j;
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-            const uint32_t bits = nbits[c];
-            if ((bits & 0x7fffffffu) >= 0x7f800000u) {
-                const uint32_t code = (bits & 0x7fffffu) ? 1u : ((bits >> 31) ? 4u : 2u);
-                atomicOr(a.flags + row, code << (3 * c));
-                continue;
-            }
-            const __int128 x = det_to_fixed(bits, E);
-            const unsigned long long lo = (unsigned long long)x;
-            unsigned long long hi = (unsigned long long)(x >> 64);
-            if ((lo | hi) == 0ull) continue;
-            unsigned long long *p = a.acc + (row * 3 + c) * 2;
-            const unsigned long long old = atomicAdd(p, lo);
-            hi += (old + lo < old) ? 1ull : 0ull;  // the carry out of the low word, counted once by the adder that caused it
-            if (hi) atomicAdd(p + 1, hi);
-        }
+        fold_add(a.fold, row, 0, -v.x, E);
+        fold_add(a.fold, row, 1, -v.y, E);
+        fold_add(a.fold, row, 2, -v.z, E);
     }
 }
 
 // grid (x: elements of g_tgt, y: batch element): every element of g_tgt is written
 __global__ __launch_bounds__(NB_T) void nb_bwd_finish_k(NbBwd a) {
     const int b = blockIdx.y, nt = nb_count(a.in, 1, b);
-    const int E = det_scale(*a.maxbits, a.lg);
+    const int E = det_scale(*a.fold.maxbits, a.lg);
     const int64_t total = (int64_t)a.in.cap[1] * 3, base = (int64_t)b * total;
     for (int64_t t = (int64_t)blockIdx.x * NB_T + threadIdx.x; t < total; t += (int64_t)gridDim.x * NB_T) {
         const int j = (int)(t / 3), c = (int)(t - (int64_t)j * 3);
         float r = 0.0f;
-        if (j < nt) {
-            const uint32_t fl = (a.flags[(int64_t)b * a.in.cap[1] + j] >> (3 * c)) & 7u;
-            if (fl) r = ((fl & 1u) || (fl & 6u) == 6u) ? __int_as_float(0x7fc00000) : __int_as_float((fl & 2u) ? 0x7f800000 : (int)0xff800000);
-            else r = det_to_float(a.acc[2 * (base + t)], a.acc[2 * (base + t) + 1], E);
-        }
+        if (j < nt) r = fold_result(a.fold, (int64_t)b * a.in.cap[1] + j, c, E);
         a.g_tgt[base + t] = r;
     }
 }
@@ -598,7 +564,7 @@ int gs_knn_backward(const float *src, const int32_t *src_counts, int Ns_max, con
     a.g_d2 = g_d2;
     a.g_src = g_src;
     a.g_tgt = g_tgt;
-    a.lg = nb_lg(Ns_max, K);
+    a.lg = fold_lg((int64_t)Ns_max * K);  // no target row receives more terms
     GS_HIP(hipMemsetAsync(ws, 0, bytes, st), "gs_knn_backward/zero");
     hipLaunchKernelGGL(nb_bwd_src_k, dim3(nb_rows_grid(Ns_max), B), dim3(NB_T), 0, st, a);
     hipLaunchKernelGGL(nb_bwd_acc_k, dim3(nb_rows_grid((int64_t)Ns_max * K), B), dim3(NB_T), 0, st, a);

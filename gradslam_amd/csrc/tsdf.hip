@@ -109,24 +109,12 @@ __global__ __launch_bounds__(TSDF_T) void tsdf_integrate_k(TsdfVol vol, TsdfFram
 }
 
 // ------------------------------------------------------------------ reverse pass of the integration
-// the fold of one chunk: per pixel (b, l, h, w) of the chunk 4 sums (depth, r, g, b), each a (lo, hi) pair of 64-bit words
-struct TsdfFold {
-    uint32_t *maxbits;        // 1
-    uint32_t *flags;          // npix: 3 bits per sum (NaN, +inf, -inf)
-    unsigned long long *acc;  // npix x 4 x (lo, hi)
-};
-static inline size_t tsdf_fold_layout(int B, int L, int H, int W, void *ws, TsdfFold *out) {
-    const size_t npix = (size_t)B * std::min(L, TSDF_CHUNK) * H * W;
+// the fold of one chunk: per pixel (b, l, h, w) of the chunk 4 sums (depth, r, g, b)
+static inline size_t tsdf_fold_layout(int B, int L, int H, int W, void *ws, Fold *out) {
     Carve c{(char *)ws};
-    uint32_t *maxbits = c.take<uint32_t>(4);
-    uint32_t *flags = c.take<uint32_t>(4 * npix);
-    unsigned long long *acc = c.take<unsigned long long>(64 * npix);
-    if (out) *out = TsdfFold{maxbits, flags, acc};
+    const Fold f = fold_carve(c, (size_t)B * std::min(L, TSDF_CHUNK) * H * W, 4);
+    if (out) *out = f;
     return c.off;
-}
-
-__device__ __forceinline__ void tsdf_fold_add(const TsdfFold &fold, int64_t p, int ch, float x, int E) {
-    fold_add_at(fold.flags + p, 3 * ch, fold.acc + (p * 4 + ch) * 2, x, E);
 }
 
 // grid (x: voxels, y: batch element).  ACC = false: the largest finite |term| of the chunk; ACC = true: the terms go into the
@@ -134,7 +122,7 @@ __device__ __forceinline__ void tsdf_fold_add(const TsdfFold &fold, int64_t p, i
 // a voxel, so they may alias).  No thread leaves early: the camera loads are block-wide.
 template <bool ACC>
 __global__ __launch_bounds__(TSDF_T) void tsdf_bwd_k(TsdfVol vol, TsdfFrames fr, const float *__restrict__ weight_in, const float *g_tsdf_src,
-                                                     const float *g_color_src, float *g_tsdf_dst, float *g_color_dst, TsdfFold fold, int lg) {
+                                                     const float *g_color_src, float *g_tsdf_dst, float *g_color_dst, Fold fold, int lg) {
     __shared__ Cam cams[TSDF_CHUNK];
     const int b = blockIdx.y;
     const int64_t nvox = tsdf_nvox(vol), j = (int64_t)blockIdx.x * TSDF_T + threadIdx.x;
@@ -178,11 +166,11 @@ __global__ __launch_bounds__(TSDF_T) void tsdf_bwd_k(TsdfVol vol, TsdfFrames fr,
         gc = f3{gc.x * keep, gc.y * keep, gc.z * keep};
         if (ACC) {
             const int64_t p = ((int64_t)b * fr.Lc + l) * HW + pix;
-            tsdf_fold_add(fold, p, 0, gd, E);
+            fold_add(fold, p, 0, gd, E);
             if (color) {
-                tsdf_fold_add(fold, p, 1, gr.x, E);
-                tsdf_fold_add(fold, p, 2, gr.y, E);
-                tsdf_fold_add(fold, p, 3, gr.z, E);
+                fold_add(fold, p, 1, gr.x, E);
+                fold_add(fold, p, 2, gr.y, E);
+                fold_add(fold, p, 3, gr.z, E);
             }
         } else {
             mx = fold_max(mx, gd);
@@ -195,14 +183,12 @@ __global__ __launch_bounds__(TSDF_T) void tsdf_bwd_k(TsdfVol vol, TsdfFrames fr,
             if (color) st3(g_color_dst, at, gc);
         }
     } else {
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) mx = max(mx, (uint32_t)__shfl_xor((int)mx, off, kWave));
-        if ((threadIdx.x & 63) == 0 && mx > 0) atomicMax(fold.maxbits, mx);
+        fold_max_commit(fold.maxbits, mx);
     }
 }
 
 // every pixel of the chunk's frames: each sum rounded once to fp32.  g_rgb may be NULL
-__global__ __launch_bounds__(TSDF_T) void tsdf_fold_finish_k(TsdfFold fold, int lg, int B, int L, int l0, int Lc, int64_t HW,
+__global__ __launch_bounds__(TSDF_T) void tsdf_fold_finish_k(Fold fold, int lg, int B, int L, int l0, int Lc, int64_t HW,
                                                              float *__restrict__ g_depth, float *__restrict__ g_rgb) {
     const int E = det_scale(*fold.maxbits, lg);
     const int64_t total = (int64_t)B * Lc * HW;
@@ -210,11 +196,8 @@ __global__ __launch_bounds__(TSDF_T) void tsdf_fold_finish_k(TsdfFold fold, int 
         const int64_t bl = p / HW, pix = p - bl * HW;
         const int b = (int)(bl / Lc), l = (int)(bl - (int64_t)b * Lc);
         const int64_t out = ((int64_t)b * L + l0 + l) * HW + pix;
-        const uint32_t fl = fold.flags[p];
         for (int ch = 0; ch < (g_rgb ? 4 : 1); ++ch) {
-            const uint32_t f = (fl >> (3 * ch)) & 7u;
-            float r;
-            if (!fold_flagged(f, r)) r = det_to_float(fold.acc[(p * 4 + ch) * 2], fold.acc[(p * 4 + ch) * 2 + 1], E);
+            const float r = fold_result(fold, p, ch, E);
             if (ch == 0) g_depth[out] = r;
             else g_rgb[3 * out + ch - 1] = r;
         }
@@ -461,25 +444,17 @@ __global__ __launch_bounds__(TSDF_T) void tsdf_raycast_k(TsdfVol vol, TsdfCast c
     k_end[pix] = kend;
 }
 
-// the fold of the reverse pass: per voxel (b, j) nch sums (tsdf; r, g, b), each a (lo, hi) pair of 64-bit words
-struct TsdfCastFold {
-    uint32_t *maxbits;        // 1
-    uint32_t *flags;          // B nvox: 3 bits per sum (NaN, +inf, -inf)
-    unsigned long long *acc;  // B nvox x nch x (lo, hi)
-    int nch;
-};
-static inline size_t tsdf_cast_fold_layout(int B, int64_t nvox, int nch, void *ws, TsdfCastFold *out) {
-    const size_t n = (size_t)B * nvox;
+// the fold of the reverse pass: per voxel (b, j) nch sums (tsdf; r, g, b)
+static inline size_t tsdf_cast_fold_layout(int B, int64_t nvox, int nch, void *ws, Fold *out) {
     Carve c{(char *)ws};
-    uint32_t *maxbits = c.take<uint32_t>(4);
-    uint32_t *flags = c.take<uint32_t>(4 * n);
-    unsigned long long *acc = c.take<unsigned long long>(16 * n * nch);
-    if (out) *out = TsdfCastFold{maxbits, flags, acc, nch};
+    const Fold f = fold_carve(c, (size_t)B * nvox, nch);
+    if (out) *out = f;
     return c.off;
 }
+// one term of voxel p: into the maximum, or into the sums
 template <bool ACC>
-__device__ __forceinline__ void tsdf_cast_term(const TsdfCastFold &fold, int64_t p, int ch, float x, int E, uint32_t &mx) {
-    if (ACC) fold_add_at(fold.flags + p, 3 * ch, fold.acc + (p * fold.nch + ch) * 2, x, E);
+__device__ __forceinline__ void tsdf_cast_term(const Fold &fold, int64_t p, int ch, float x, int E, uint32_t &mx) {
+    if (ACC) fold_add(fold, p, ch, x, E);
     else mx = fold_max(mx, x);
 }
 
@@ -489,7 +464,7 @@ template <bool ACC>
 __global__ __launch_bounds__(TSDF_T) void tsdf_raycast_bwd_k(TsdfVol vol, TsdfCast cast, const float *__restrict__ tsdf,
                                                              const float *__restrict__ weight, const float *__restrict__ color,
                                                              const int32_t *__restrict__ k_end, const float *__restrict__ g_depth,
-                                                             const float *__restrict__ g_rgb, TsdfCastFold fold, int lg) {
+                                                             const float *__restrict__ g_rgb, Fold fold, int lg) {
     int i, j;
     const bool live = tsdf_cast_pixel(cast, i, j);
     const int l = blockIdx.y, b = blockIdx.z;
@@ -538,22 +513,16 @@ __global__ __launch_bounds__(TSDF_T) void tsdf_raycast_bwd_k(TsdfVol vol, TsdfCa
             }
         }
     }
-    if (!ACC) {
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) mx = max(mx, (uint32_t)__shfl_xor((int)mx, off, kWave));
-        if ((threadIdx.x & 63) == 0 && mx > 0) atomicMax(fold.maxbits, mx);
-    }
+    if (!ACC) fold_max_commit(fold.maxbits, mx);
 }
 
 // every voxel: each sum rounded once to fp32.  g_color may be NULL
-__global__ __launch_bounds__(TSDF_T) void tsdf_cast_finish_k(TsdfCastFold fold, int lg, int64_t total, float *__restrict__ g_tsdf,
+__global__ __launch_bounds__(TSDF_T) void tsdf_cast_finish_k(Fold fold, int lg, int64_t total, float *__restrict__ g_tsdf,
                                                              float *__restrict__ g_color) {
     const int E = det_scale(*fold.maxbits, lg);
     for (int64_t p = (int64_t)blockIdx.x * TSDF_T + threadIdx.x; p < total; p += (int64_t)gridDim.x * TSDF_T) {
-        const uint32_t fl = fold.flags[p];
         for (int ch = 0; ch < fold.nch; ++ch) {
-            float r;
-            if (!fold_flagged((fl >> (3 * ch)) & 7u, r)) r = det_to_float(fold.acc[(p * fold.nch + ch) * 2], fold.acc[(p * fold.nch + ch) * 2 + 1], E);
+            const float r = fold_result(fold, p, ch, E);
             if (ch == 0) g_tsdf[p] = r;
             else if (g_color) g_color[3 * p + ch - 1] = r;
         }
@@ -564,11 +533,6 @@ static inline bool tsdf_vol_ok(int B, int nx, int ny, int nz) {
     return B > 0 && B <= 65535 && nx > 0 && ny > 0 && nz > 0 && (int64_t)nx * ny * nz <= TSDF_NMAX;
 }
 static inline bool tsdf_pos(float x) { return x > 0.0f && x < INFINITY; }
-static inline int tsdf_lg(int64_t n) {  // ceil(log2(n)): a pixel receives at most one term per voxel
-    int lg = 0;
-    while (((int64_t)1 << lg) < n) ++lg;
-    return lg;
-}
 static inline bool tsdf_aligned16(const void *p) { return ((uintptr_t)p & 15u) == 0; }
 static inline TsdfFrames tsdf_frames(const float *depth, const float *rgb, const float *K, const float *poses, int L, int H, int W) {
     return TsdfFrames{depth, rgb, K, poses, L, H, W, 0, 0, (float)((double)W - 0.999), (float)((double)H - 0.999)};
@@ -637,10 +601,10 @@ int gs_tsdf_integrate_backward(const float *depth, const float *intrinsics, cons
     hipStream_t st = (hipStream_t)stream;
     const TsdfVol vol{nx, ny, nz, voxel_size, trunc, max_weight, origin};
     TsdfFrames fr = tsdf_frames(depth, nullptr, intrinsics, poses, L, H, W);
-    TsdfFold fold;
+    Fold fold;
     tsdf_fold_layout(B, L, H, W, ws, &fold);
     const int64_t nvox = tsdf_nvox(vol), HW = (int64_t)H * W;
-    const int lg = tsdf_lg(nvox);
+    const int lg = fold_lg(nvox);  // a pixel receives at most one term per voxel
     const dim3 grid(cdiv(nvox, TSDF_T), B);
     const int last = (L - 1) / TSDF_CHUNK * TSDF_CHUNK;
     for (int l0 = last; l0 >= 0; l0 -= TSDF_CHUNK) {  // the last chunk starts from the upstream adjoints, the others from the carried ones
@@ -762,9 +726,9 @@ int gs_tsdf_raycast_backward(const float *tsdf, const float *weight, const float
     hipStream_t st = (hipStream_t)stream;
     const TsdfVol vol{nx, ny, nz, voxel_size, 0.0f, 0.0f, origin};
     const TsdfCast cast{intrinsics, poses, L, Ho, Wo, stride, 0, step, 0.0f, 0.0f, min_weight};
-    TsdfCastFold fold;
+    Fold fold;
     tsdf_cast_fold_layout(B, tsdf_nvox(vol), color ? 4 : 1, ws, &fold);
-    const int lg = tsdf_lg(2 * (int64_t)L * Ho * Wo);  // a voxel receives at most two terms per pixel of its batch element
+    const int lg = fold_lg(2 * (int64_t)L * Ho * Wo);  // a voxel receives at most two terms per pixel of its batch element
     const int64_t total = (int64_t)B * tsdf_nvox(vol);
     const dim3 grid(cdiv(Ho, 16) * cdiv(Wo, 16), L, B);
     GS_HIP(hipMemsetAsync(ws, 0, need, st), "gs_tsdf_raycast_backward/zero");

@@ -12,13 +12,12 @@
 //                       that share a voxel)
 //      The numbering is a property of the input alone: it depends on the lowest member row of every voxel, which atomicMin
 //      finds whatever the arrival order, never on which slot a key landed in.
-//   R  gs_voxel_reduce: the 128-bit fixed-point fold of gs_fixed128.hpp over the members of every voxel:
-//        (memset)       accumulators, flags and the maximum := 0
-//        vred_max_k     M = max finite |x| over the members (integer atomicMax on the float bits)
-//        vred_acc_k     x 2^E as a signed 128-bit integer, added into a (lo, hi) pair of 64-bit words per (voxel, component) with
-//                       integer atomics, the low word's carry counted by the adder that caused it.  One lane per row: runs of
-//                       lanes that share a voxel are summed in registers first (integer addition is associative: same bits)
-//        vred_finish_k  per (voxel, component): the sum rounded once to fp32, divided by float(count) in mean mode; rows beyond
+//   R  gs_voxel_reduce: the exact fold of gs_fixed128.hpp (the rule is stated there) over the members of every voxel:
+//        (memset)       the fold's workspace := 0
+//        vred_max_k     the max pass over the members
+//        vred_acc_k     the accumulate pass, one lane per row: runs of lanes that share a voxel are summed in registers first
+//                       (integer addition is associative: same bits) and the run's first lane adds the total
+//        vred_finish_k  per (voxel, component): the fold's result, divided by float(count) in mean mode; rows beyond
 //                       n_voxels := 0
 //      gs_voxel_reduce_backward: one gather launch.
 // Every probe loop is bounded by the table size; nothing spins, nothing is handed from one workgroup to another inside a launch,
@@ -197,33 +196,28 @@ struct VredIn {
 };
 __device__ __forceinline__ int vred_nvox(const VredIn &in, int b) { return min(max(in.n_voxels[b], 0), in.M); }
 
-__global__ __launch_bounds__(VOX_T) void vred_max_k(VredIn in, uint32_t *__restrict__ maxbits) {
+__global__ __launch_bounds__(VOX_T) void vred_max_k(VredIn in, Fold f) {
     const int b = blockIdx.y, n = vox_count(in.counts, b, in.N), nv = vred_nvox(in, b);
-    const uint32_t *x = reinterpret_cast<const uint32_t *>(in.x) + (int64_t)b * in.N * in.C;
+    const float *x = in.x + (int64_t)b * in.N * in.C;
     const int32_t *vof = in.voxel_of + (int64_t)b * in.N;
     const int64_t total = (int64_t)n * in.C;
     uint32_t mx = 0;
     for (int64_t e = (int64_t)blockIdx.x * VOX_T + threadIdx.x; e < total; e += (int64_t)gridDim.x * VOX_T) {
-        const uint32_t u = x[e] & 0x7fffffffu;
-        if (u >= 0x7f800000u || u <= mx) continue;
-        if ((uint32_t)vof[e / in.C] < (uint32_t)nv) mx = u;
+        const uint32_t u = fold_max(mx, x[e]);
+        if (u != mx && (uint32_t)vof[e / in.C] < (uint32_t)nv) mx = u;  // (the voxel is looked up for a new maximum only)
     }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) mx = max(mx, (uint32_t)__shfl_xor((int)mx, off, kWave));
-    if ((threadIdx.x & 63) == 0 && mx > 0) atomicMax(maxbits, mx);
+    fold_max_commit(f.maxbits, mx);
 }
 
 // PREAGG: runs of lanes that share a voxel are summed in registers and the run's first lane adds the total
 template <bool PREAGG>
-__global__ __launch_bounds__(VOX_T) void vred_acc_k(VredIn in, VoxRedWs w, int lg) {
+__global__ __launch_bounds__(VOX_T) void vred_acc_k(VredIn in, Fold f, int lg) {
     const int b = blockIdx.y, lane = threadIdx.x & 63, C = in.C;
     const int n = vox_count(in.counts, b, in.N), nv = vred_nvox(in, b);
-    const int E = det_scale(*w.maxbits, lg);
+    const int E = det_scale(*f.maxbits, lg);
     const uint32_t *x = reinterpret_cast<const uint32_t *>(in.x) + (int64_t)b * in.N * C;
     const int32_t *vof = in.voxel_of + (int64_t)b * in.N;
-    unsigned long long *acc = w.acc + (int64_t)b * in.M * C * 2;
-    const int fw = (C + VOX_FLAGS_PER_WORD - 1) / VOX_FLAGS_PER_WORD;
-    uint32_t *flags = w.flags + (int64_t)b * in.M * fw;
+    const int64_t row0 = (int64_t)b * in.M;
     for (int64_t i0 = (int64_t)blockIdx.x * VOX_T; i0 < n; i0 += (int64_t)gridDim.x * VOX_T) {  // (block-uniform trip count)
         const int64_t i = i0 + threadIdx.x;
         int m = i < n ? vof[i] : -1;
@@ -237,12 +231,7 @@ __global__ __launch_bounds__(VOX_T) void vred_acc_k(VredIn in, VoxRedWs w, int l
             __int128 v = 0;
             if (m >= 0) {
                 const uint32_t bits = x[i * C + c];
-                if ((bits & 0x7fffffffu) >= 0x7f800000u) {
-                    const uint32_t code = (bits & 0x7fffffu) ? 1u : ((bits >> 31) ? 4u : 2u);
-                    atomicOr(flags + (int64_t)m * fw + c / VOX_FLAGS_PER_WORD, code << (3 * (c % VOX_FLAGS_PER_WORD)));
-                } else {
-                    v = det_to_fixed(bits, E);
-                }
+                if (fold_finite(f, row0 + m, c, bits)) v = det_to_fixed(bits, E);
             }
             unsigned long long lo = (unsigned long long)v, hi = (unsigned long long)(v >> 64);
             if (PREAGG && !lone) {
@@ -256,32 +245,23 @@ __global__ __launch_bounds__(VOX_T) void vred_acc_k(VredIn in, VoxRedWs w, int l
                     }
                 }
             }
-            if (!head || m < 0 || (lo | hi) == 0ull) continue;
-            unsigned long long *p = acc + ((int64_t)m * C + c) * 2;
-            const unsigned long long old = atomicAdd(p, lo);
-            hi += (old + lo < old) ? 1ull : 0ull;  // the carry out of the low word, counted once by the adder that caused it
-            if (hi) atomicAdd(p + 1, hi);
+            if (head && m >= 0) fold_add_words(fold_sum(f, row0 + m, c), lo, hi);
         }
     }
 }
 
 // grid (x: elements of out, y: batch element): every element of out is written
-__global__ __launch_bounds__(VOX_T) void vred_finish_k(VredIn in, VoxRedWs w, int lg, int mean, float *__restrict__ out) {
+__global__ __launch_bounds__(VOX_T) void vred_finish_k(VredIn in, Fold f, int lg, int mean, float *__restrict__ out) {
     const int b = blockIdx.y, C = in.C, nv = vred_nvox(in, b);
-    const int E = det_scale(*w.maxbits, lg);
-    const unsigned long long *acc = w.acc + (int64_t)b * in.M * C * 2;
-    const int fw = (C + VOX_FLAGS_PER_WORD - 1) / VOX_FLAGS_PER_WORD;
-    const uint32_t *flags = w.flags + (int64_t)b * in.M * fw;
+    const int E = det_scale(*f.maxbits, lg);
     const int32_t *cnt = in.voxel_count + (int64_t)b * in.N;
     float *o = out + (int64_t)b * in.M * C;
-    const int64_t total = (int64_t)in.M * C;
+    const int64_t total = (int64_t)in.M * C, row0 = (int64_t)b * in.M;
     for (int64_t t = (int64_t)blockIdx.x * VOX_T + threadIdx.x; t < total; t += (int64_t)gridDim.x * VOX_T) {
         const int m = (int)(t / C), c = (int)(t - (int64_t)m * C);
         float r = 0.0f;
         if (m < nv) {
-            const uint32_t fl = (flags[(int64_t)m * fw + c / VOX_FLAGS_PER_WORD] >> (3 * (c % VOX_FLAGS_PER_WORD))) & 7u;
-            if (fl) r = ((fl & 1u) || (fl & 6u) == 6u) ? __int_as_float(0x7fc00000) : __int_as_float((fl & 2u) ? 0x7f800000 : (int)0xff800000);
-            else r = det_to_float(acc[2 * t], acc[2 * t + 1], E);
+            r = fold_result(f, row0 + m, c, E);
             if (mean) r = r / (float)cnt[m];
         }
         o[t] = r;
@@ -378,12 +358,12 @@ int gs_voxel_reduce(const float *x, const int32_t *counts, int N_max, int C, int
         return GS_ERR_WORKSPACE_TOO_SMALL;
     }
     hipStream_t st = (hipStream_t)stream;
-    VoxRedWs w;
+    Fold w;
     const size_t bytes = vox_reduce_layout(B, M_max, C, ws, &w);
     const VredIn in{x, counts, voxel_of, n_voxels, voxel_count, N_max, C, M_max};
-    const int lg = vox_lg(N_max);
+    const int lg = fold_lg(N_max);  // no voxel has more members
     GS_HIP(hipMemsetAsync(ws, 0, bytes, st), "gs_voxel_reduce/zero");
-    hipLaunchKernelGGL(vred_max_k, dim3(vox_grid((int64_t)N_max * C), B), dim3(VOX_T), 0, st, in, w.maxbits);
+    hipLaunchKernelGGL(vred_max_k, dim3(vox_grid((int64_t)N_max * C), B), dim3(VOX_T), 0, st, in, w);
     const dim3 rows(vox_grid(N_max), B);
     if (mode & GS_VOXEL_NO_PREAGG) hipLaunchKernelGGL(vred_acc_k<false>, rows, dim3(VOX_T), 0, st, in, w, lg);
     else hipLaunchKernelGGL(vred_acc_k<true>, rows, dim3(VOX_T), 0, st, in, w, lg);

@@ -298,6 +298,48 @@ def test_linearize_node_is_bitwise_reproducible(gs, det_flag):
 
 
 @pytest.mark.gpu
+def test_linearize_fold_with_non_finite_upstream_entries(gs, det_flag):
+    """gs_icp_linearize_backward_det with 130 sources on 40 targets, +inf in the upstream gH[0][1] and NaN in gH[1][1].  With
+    a = [n ; s x n] the row adjoint is a_bar_u = sum_w (gH[u][w] + gH[w][u]) a_w + ..., and a_bar_0, a_bar_1 are added to the
+    x and y of the target normal's adjoint: every source of target j contributes (inf) n_j.y to x and a NaN to y.  So x of an
+    associated target is the infinity of the sign of n_j.y, y is NaN, and every other element (z, the target adjoint, the rows
+    of targets without a source) holds the bits of the same call with the two entries set to zero."""
+    ns, nt = 130, 40
+    g = torch.Generator().manual_seed(9)
+    src = torch.rand(ns, 3, generator=g)
+    tgt = torch.rand(nt, 3, generator=g)
+    nrm = torch.randn(nt, 3, generator=g)
+    nrm = nrm / nrm.norm(dim=-1, keepdim=True)
+    gH, gg, ge = torch.randn(6, 6, generator=g), torch.randn(6, 1, generator=g), torch.tensor(0.5)
+    bad, zero = gH.clone(), gH.clone()
+    bad[0, 1], bad[1, 1], zero[0, 1], zero[1, 1] = float("inf"), float("nan"), 0.0, 0.0
+
+    def run(up):
+        s, tg, n = (x.to(DEV).clone().requires_grad_(True) for x in (src, tgt, nrm))
+        best = gs.ops.knn1_raw(s.detach(), tg.detach())
+        torch.autograd.backward(list(gs.ops.icp_linearize(s, tg, n, best, None)), [up.to(DEV), gg.to(DEV), ge.to(DEV)])
+        return [x.grad.cpu().numpy() for x in (s, tg, n)], (best & 0xFFFFFFFF).cpu().numpy()
+
+    with det_flag(True):
+        (got_s, got_t, got_n), j = run(bad)
+        (ref_s, ref_t, ref_n), _ = run(zero)
+    assoc = np.zeros(nt, bool)
+    assoc[j] = True
+    assert 20 < assoc.sum() < nt and (np.bincount(j) > 1).any()  # shared targets, and targets without a source
+    hit = np.zeros((nt, 3), bool)
+    hit[assoc, :2] = True
+    n_y = nrm.numpy()[:, 1]
+    assert (n_y != 0).all()
+    want_x = np.where(n_y > 0, np.float32(np.inf), np.float32(-np.inf))
+    assert np.array_equal(got_n[assoc, 0], want_x[assoc]) and np.isnan(got_n[assoc, 1]).all()
+    assert np.isposinf(got_n[hit]).any() and np.isneginf(got_n[hit]).any() and np.isnan(got_n[hit]).any()
+    bits = lambda x: x.view(np.uint32)
+    assert np.array_equal(bits(got_n)[~hit], bits(ref_n)[~hit]) and np.array_equal(bits(got_t), bits(ref_t))
+    assert np.array_equal(bits(got_s), bits(ref_s))  # (gH's upper-left block reaches the normals only)
+    assert (ref_n[assoc] != 0).all() and (ref_t[assoc] != 0).all() and not ref_n[~assoc].any()
+
+
+@pytest.mark.gpu
 def test_scheduling_independence(gs, det_flag):
     """The contention backward while a side stream keeps the GPU busy with matmuls: the same bits as the quiet run."""
     src, tgt, nrm, T0, W = _contention_scene()

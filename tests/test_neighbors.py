@@ -13,7 +13,7 @@ import torch
 import gradslam_amd as gs
 from gradslam_amd import _native as nv
 from gradslam_amd import ops
-from tests.test_voxel_downsample import f32_to_int, int_to_f32
+from tests.helpers import exact_sum_f32, f32_to_int, int_to_f32
 
 DEV = "cuda:0"
 U = 2.0 ** -24  # unit roundoff of fp32
@@ -436,6 +436,59 @@ def test_target_adjoint_does_not_depend_on_the_order_of_the_query_rows():
     b = ops.knn_backward_raw(dev(src[:, p]), dev(tgt), dev(cs), dev(ct), dev(keys_np[:, p]), dev(g[:, p]))
     assert torch.equal(bits(a[1]), bits(b[1]))
     assert torch.equal(bits(a[0][:, p]), bits(b[0]))
+
+
+@pytest.mark.gpu
+def test_reverse_pass_with_non_finite_upstream_entries():
+    """g_d2 = NaN at one slot, +inf at another, +inf and -inf at two slots of one target.  A target element that receives a
+    non-finite term holds what a float sum of its terms gives; every other element holds the bits of the same call with those
+    four entries set to zero (non-finite terms stay out of the maximum, a zero term adds nothing to an exact sum)."""
+    B, Ns, Nt, K = 2, 300, 70, 3
+    rs = np.random.RandomState(23)
+    cs, ct = np.array([300, 137], np.int32), np.array([41, 70], np.int32)
+    src = np.stack([_pad(rs.rand(n, 3), Ns) for n in cs])
+    tgt = np.stack([_pad(rs.rand(n, 3), Nt) for n in ct])
+    keys = oracle_keys(src, tgt, cs, ct, K)
+    idx = keys & 0xFFFFFFFF
+    g = ((0.5 + rs.rand(B, Ns, K)) * rs.choice([-1.0, 1.0], (B, Ns, K))).astype(np.float32)
+    # the pair: two slots of the target that the last slot of batch element 0 (row 299: another block) points to, whose
+    # coordinate differences agree in sign on some axes (there both infinities meet) and not on the others
+    j_pair = int(idx[0, 299, K - 1])
+    slots = [tuple(s) for s in np.argwhere(idx[0] == j_pair)]
+    up = (src[0, :, None, :] - tgt[0][idx[0]]) > 0
+    pair = next(((p, q) for p in slots for q in slots if p != q and 0 < (up[p] == up[q]).sum() < 3), None)
+    assert pair is not None, "no two slots of target %d agree in sign on some axes only: choose another seed" % j_pair
+    bad = {(0,) + pair[0]: np.inf, (0,) + pair[1]: -np.inf, (0, 70, 1): np.nan, (1, 130, 0): np.inf}
+    rows = {(0, j_pair), (0, int(idx[0, 70, 1])), (1, int(idx[1, 130, 0]))}
+    assert len(bad) == 4 and len(rows) == 3
+    g_bad, g_zero = g.copy(), g.copy()
+    for at, val in bad.items():
+        g_bad[at], g_zero[at] = val, 0.0
+    dev = lambda x: torch.from_numpy(np.ascontiguousarray(x)).to(DEV)
+    args = (dev(src), dev(tgt), dev(cs), dev(ct), dev(keys))
+    got_src, got_tgt = (x.cpu().numpy() for x in ops.knn_backward_raw(*args, dev(g_bad)))
+    ref_src, ref_tgt = (x.cpu().numpy() for x in ops.knn_backward_raw(*args, dev(g_zero)))
+    hit = np.zeros((B, Nt, 3), bool)
+    for b in range(B):
+        ns, nt = int(cs[b]), int(ct[b])
+        with np.errstate(invalid="ignore"):
+            v = (np.float32(2.0) * g_bad[b, :ns])[..., None] * (src[b, :ns, None, :] - tgt[b][idx[b, :ns]])  # (ns, K, 3)
+        assert v.dtype == np.float32 and (idx[b, :ns] < nt).all()
+        for j in np.unique(idx[b, :ns][~np.isfinite(v).all(-1)]):
+            terms = -v[idx[b, :ns] == j]  # (slots of j, 3)
+            for c in range(3):
+                if not np.isfinite(terms[:, c]).all():
+                    hit[b, j, c] = True
+                    want, have = exact_sum_f32(terms[:, c]), got_tgt[b, j, c]
+                    assert (np.isnan(want) and np.isnan(have)) or want.view(np.uint32) == have.view(np.uint32), (b, j, c, want, have)
+    assert {(b, j) for b, j, _ in np.argwhere(hit)} == rows and hit.sum() == 9  # (no coordinate difference is zero)
+    assert np.isnan(got_tgt[hit]).any() and np.isposinf(got_tgt[hit]).any() and np.isneginf(got_tgt[hit]).any()
+    assert np.isnan(got_tgt[0, j_pair]).any() and np.isinf(got_tgt[0, j_pair]).any()
+    assert np.array_equal(got_tgt.view(np.uint32)[~hit], ref_tgt.view(np.uint32)[~hit])
+    touched = np.zeros((B, Ns), bool)
+    for b, i, _ in bad:
+        touched[b, i] = True
+    assert (~np.isfinite(got_src[touched])).all() and np.array_equal(got_src.view(np.uint32)[~touched], ref_src.view(np.uint32)[~touched])
 
 
 @pytest.mark.gpu

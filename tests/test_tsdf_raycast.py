@@ -36,6 +36,7 @@ from gradslam_amd import ops
 from gradslam_amd.metrics import chamfer_distance
 from gradslam_amd.structures.utils import pointclouds_from_rgbdimages
 from gradslam_amd.synthetic import make_sequence
+from tests.helpers import exact_sum_f32
 
 DEV = "cuda:0"
 U = 2.0 ** -24
@@ -605,11 +606,8 @@ def test_volume_without_colours():
 
 
 # ------------------------------------------------------------------ GPU 3: tiny volumes
-@pytest.mark.gpu
-@pytest.mark.parametrize("dims", [(2, 2, 2), (3, 2, 2), (1, 1, 1), (5, 1, 1)])
-def test_tiny_volumes(dims):
-    """One cell, two cells, none: with a single voxel along an axis no position has 8 corners, every pixel is a miss and no
-    voxel is read (the tensors hold exactly the volume: the first read beyond it is outside the allocation's data)."""
+def tiny_host_volume(dims):
+    """A tilted plane through a volume of half-metre voxels in front of the identity camera, as the reference's dict."""
     v, trunc = 0.5, 1.0
     origin = (-0.5 * dims[0] * v + 0.013, -0.5 * dims[1] * v - 0.021, 1.0)
     nx, ny, nz = dims
@@ -617,9 +615,24 @@ def test_tiny_volumes(dims):
     z, y, x = np.meshgrid(ax[2], ax[1], ax[0], indexing="ij")
     tsdf = np.clip((origin[2] + 0.55 * nz * v + 0.2 * x - 0.1 * y - z) / trunc, -1, 1).astype(F32)
     color = np.stack([0.5 + 0.3 * x, 0.5 - 0.3 * y, 0.1 * z], -1).astype(F32)
-    hv = dict(tsdf=tsdf, weight=np.ones_like(tsdf), color=color, origin=origin, v=v, dims=dims)
-    vol = gs.TSDFVolume(dims, v, origin=[origin], trunc=trunc, device=DEV)
+    return dict(tsdf=tsdf, weight=np.ones_like(tsdf), color=color, origin=origin, v=v, dims=dims)
+
+
+def tiny_volume(dims):
+    """-> (the reference's dict, the TSDFVolume that holds the same state)."""
+    hv = tiny_host_volume(dims)
+    vol = gs.TSDFVolume(dims, hv["v"], origin=[hv["origin"]], trunc=1.0, device=DEV)
     vol.tsdf, vol.weight, vol.color = (torch.from_numpy(hv[k][None].copy()).to(DEV) for k in ("tsdf", "weight", "color"))
+    return hv, vol
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("dims", [(2, 2, 2), (3, 2, 2), (1, 1, 1), (5, 1, 1)])
+def test_tiny_volumes(dims):
+    """One cell, two cells, none: with a single voxel along an axis no position has 8 corners, every pixel is a miss and no
+    voxel is read (the tensors hold exactly the volume: the first read beyond it is outside the allocation's data)."""
+    hv, vol = tiny_volume(dims)
+    v = hv["v"]
     K, poses = cameras(1, ["identity"])
     out = ops.tsdf_raycast_raw(vol.tsdf, vol.weight, vol.color, vol.origin, v, K, poses, H, W, 1, 0.25)
     ref = ref_cast(hv, make_K(), POSES["identity"], H, W, 1, 0.25)
@@ -741,6 +754,72 @@ def test_cast_gradients_match_the_explicit_formulas_and_repeat_bitwise(stride):
         check_gradient(flat(g_t, ()), want_t, A_t, "b %d stride %d g_tsdf" % (b, stride))
         check_gradient(flat(g_c, (3,)), want_c, A_c, "b %d stride %d g_color" % (b, stride))
         check_gradient(flat(g_t0, ()), want_0, A_0, "b %d stride %d g_tsdf of g_depth alone" % (b, stride))
+
+
+def cast_terms_f32(hv, rec, p, gd, gc):
+    """The terms of hit pixel p in float32 in the kernel's order: -> [(voxel, channel (0: tsdf, 1..3: colour), term)]."""
+    dims, v = hv["dims"], F32(hv["v"])
+    f0, f1, dz, dw = F32(rec["f0"][p]), F32(rec["f1"][p]), F32(rec["dz"][p]), rec["dw"][p].astype(F32)
+    a0, a1, ah = (rec[k][p: p + 1].astype(F32) for k in ("a0", "a1", "ah"))
+    ids0, ids1, idsh = (corner_ids(rec[k][p], dims) for k in ("i0", "i1", "ih"))
+    col = hv["color"].reshape(-1, 3)
+    with np.errstate(invalid="ignore"):
+        gz = F32(gd)
+        for ch in range(3):
+            g = trigrad(col[:, ch][idsh][None], ah)[0]
+            gz = gz + F32(gc[ch]) * (((g[0] * dw[0] + g[1] * dw[1]) + g[2] * dw[2]) / v)
+        den = f0 - f1
+        den2, gs_ = den * den, gz * dz
+        t0, t1 = gs_ * ((-f1) / den2), gs_ * (f0 / den2)
+        w0, w1, wh = corner_w(a0)[0], corner_w(a1)[0], corner_w(ah)[0]
+        out = [(int(ids0[c]), 0, t0 * w0[c]) for c in range(8)] + [(int(ids1[c]), 0, t1 * w1[c]) for c in range(8)]
+        out += [(int(idsh[c]), 1 + ch, F32(gc[ch]) * wh[c]) for c in range(8) for ch in range(3)]
+    assert all(t.dtype == F32 for _, _, t in out)
+    return out
+
+
+@pytest.mark.gpu
+def test_cast_reverse_with_non_finite_upstream_entries():
+    """g_depth = +inf at one hit pixel and g_rgb = NaN (one channel) at another, on the 12 x 16 grid of the stride-4 camera over
+    a (5, 4, 3) volume.  A voxel sum that receives a non-finite term holds what a float sum of its terms gives (the terms formed
+    in float32 in the kernel's order: inf times a zero weight is NaN); every other element of g_tsdf and g_color holds the bits of
+    the same call with the two entries set to zero."""
+    dims, stride, step = (5, 4, 3), 4, 0.25
+    hv, vol = tiny_volume(dims)
+    K, poses = cameras(1, ["identity"])
+    r64 = ref_cast(hv, make_K(), POSES["identity"], H, W, stride, step)
+    r32 = ref_cast(hv, make_K(), POSES["identity"], H, W, stride, step, dt=np.float32)
+    good = ~r64["tie"] & (r64["k_end"] > 0)
+    assert np.array_equal(r64["k_end"][good], r32["k_end"][good])
+    tape = np.where(good, r32["k_end"], 0).astype(np.int32)
+    Ho, Wo = tape.shape
+    assert (Ho, Wo) == (12, 16)
+    hits = np.nonzero(tape.reshape(-1))[0]
+    assert len(hits) > 20
+    p_inf, p_nan = int(hits[0]), int(hits[-1])
+    rng = np.random.RandomState(6)
+    gd, gc = rng.randn(Ho * Wo).astype(F32), rng.randn(Ho * Wo, 3).astype(F32)
+    gd_bad, gc_bad, gd_zero, gc_zero = gd.copy(), gc.copy(), gd.copy(), gc.copy()
+    gd_bad[p_inf], gc_bad[p_nan, 1], gd_zero[p_inf], gc_zero[p_nan, 1] = np.inf, np.nan, 0.0, 0.0
+    dev = lambda x, s: torch.from_numpy(x).reshape(s).to(DEV)
+    run = lambda d, c: ops.tsdf_raycast_backward_raw(vol.tsdf, vol.weight, vol.color, vol.origin, hv["v"], K, poses, H, W, stride, step, 1.0,
+                                                     dev(tape, (1, 1, Ho, Wo)), dev(d, (1, 1, Ho, Wo)), dev(c, (1, 1, Ho, Wo, 3)))
+    got, want = run(gd_bad, gc_bad), run(gd_zero, gc_zero)
+    nvox = dims[0] * dims[1] * dims[2]
+    flat = lambda x: np.concatenate([x[0].reshape(nvox, 1).cpu().numpy(), x[1].reshape(nvox, 3).cpu().numpy()], 1)  # (voxel, channel)
+    g, z = flat(got), flat(want)
+    terms = {}
+    for p in (p_inf, p_nan):
+        for j, ch, t in cast_terms_f32(hv, r32["rec"], p, gd_bad[p], gc_bad[p]):
+            if not np.isfinite(t):
+                terms.setdefault((j, ch), []).append(t)
+    hit = np.zeros((nvox, 4), bool)
+    for (j, ch), ts in terms.items():
+        hit[j, ch] = True
+        w, h = exact_sum_f32(ts), g[j, ch]
+        assert (np.isnan(w) and np.isnan(h)) or w.view(np.uint32) == h.view(np.uint32), (j, ch, w, h)
+    assert 0 < hit.sum() <= 2 * 16 + 8 and np.isposinf(g[hit]).any() and np.isnan(g[hit]).any()
+    assert np.array_equal(g.view(np.uint32)[~hit], z.view(np.uint32)[~hit]) and (z != 0).sum() > 50
 
 
 @pytest.mark.gpu

@@ -21,6 +21,7 @@ from gradslam_amd import _native as nv
 from gradslam_amd import ops
 from gradslam_amd.structures.utils import pointclouds_from_rgbdimages
 from gradslam_amd.synthetic import make_sequence
+from tests.helpers import exact_sum_f32, f32_to_int, int_to_f32
 
 DEV = "cuda:0"
 U = 2.0 ** -24  # unit roundoff of fp32
@@ -69,47 +70,6 @@ def ref_assign(pts, counts, v, origin=(0.0, 0.0, 0.0)):
         voxel_count[b, :M] = np.bincount(m, minlength=M)
         voxel_first[b, :M] = rows[first[order]]
     return voxel_of, n_voxels, n_dropped, voxel_count, voxel_first, keys
-
-
-def f32_to_int(bits):
-    """fp32 bit patterns (finite) -> Python integers in units of 2^-149 (exact)."""
-    bits = np.asarray(bits, dtype=np.uint32).astype(np.int64)
-    e, m = (bits >> 23) & 0xFF, bits & 0x7FFFFF
-    mant = np.where(e > 0, m | 0x800000, m)
-    shift = np.maximum(e, 1) - 1
-    sign = np.where(bits >> 31, -1, 1)
-    return [int(s) * (int(a) << int(k)) for s, a, k in zip(sign.ravel(), mant.ravel(), shift.ravel())]
-
-
-def int_to_f32(t, unit=-149):
-    """A Python integer in units of 2^unit (default 2^-149) -> the nearest fp32 (ties to even), rounded once.  (Other units: for
-    results that are normal numbers only.)"""
-    if t == 0:
-        return np.float32(0.0)
-    a = abs(t)
-    nb = a.bit_length()
-    mant, sh = a, 0
-    if nb > 24:
-        sh = nb - 24
-        mant = a >> sh
-        rem, half = a & ((1 << sh) - 1), 1 << (sh - 1)
-        if rem > half or (rem == half and (mant & 1)):
-            mant += 1
-    val = math.ldexp(mant, sh + unit) if sh + unit + mant.bit_length() <= 128 else math.inf  # (exact in float64 below 2^128)
-    with np.errstate(over="ignore"):
-        return np.float32(-val if t < 0 else val)
-
-
-def exact_sum_f32(values):
-    """The exact sum of fp32 values rounded once to fp32; non-finite members give what a float sum gives."""
-    values = np.asarray(values, dtype=np.float32).ravel()
-    fin = np.isfinite(values)
-    if not fin.all():
-        bad = values[~fin]
-        if np.isnan(bad).any() or (np.isposinf(bad).any() and np.isneginf(bad).any()):
-            return np.float32(np.nan)
-        return np.float32(np.inf if np.isposinf(bad).any() else -np.inf)
-    return int_to_f32(sum(f32_to_int(values.view(np.uint32))))
 
 
 def ref_reduce(x, voxel_of, n_voxels, M_max):

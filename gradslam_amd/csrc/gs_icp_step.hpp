@@ -192,12 +192,11 @@ __device__ __forceinline__ double shfl_d(double v, int src) {
     const int lo = __shfl(__double2loint(v), src, kWave), hi = __shfl(__double2hiint(v), src, kWave);
     return __hiloint2double(hi, lo);
 }
-__device__ void solve6_wave(const float *H, const float *g, float damp, float *x, double *lu_buf) {
+// (the elimination itself: `a` = the lane's element of the augmented system, element (i, k) in lane 8 i + k; returns the
+// lane's element of the result -- column 6 is the solution -- and whether every pivot was a positive finite number)
+__device__ __forceinline__ double solve6_wave_elim(double a, bool &ok) {
     const int lane = threadIdx.x & 63, i = lane >> 3, k = lane & 7;
-    double a = 0.0;
-    if (i < 6 && k < 6) a = (double)(i == k ? H[6 * i + k] + damp : H[6 * i + k]);
-    if (i < 6 && k == 6) a = (double)g[i];
-    bool ok = true;
+    ok = true;
 #pragma unroll
     for (int j = 0; j < 6; ++j) {
         const double piv = shfl_d(a, 8 * j + j);
@@ -207,8 +206,52 @@ __device__ void solve6_wave(const float *H, const float *g, float damp, float *x
         const double inv = 1.0 / piv;
         a = (i == j) ? pr * inv : a - (col * inv) * pr;
     }
+    return a;
+}
+__device__ void solve6_wave(const float *H, const float *g, float damp, float *x, double *lu_buf) {
+    const int lane = threadIdx.x & 63, i = lane >> 3, k = lane & 7;
+    double a = 0.0;
+    if (i < 6 && k < 6) a = (double)(i == k ? H[6 * i + k] + damp : H[6 * i + k]);
+    if (i < 6 && k == 6) a = (double)g[i];
+    bool ok;
+    a = solve6_wave_elim(a, ok);
     if (i < 6 && k == 6) x[i] = (float)a;
     if (!ok && lane == 0) solve6_lu(H, g, damp, x, lu_buf);     // `ok` is wave-uniform: every lane saw the same pivots
+}
+
+// se3_exp_dev by one wave: the lane's element (threadIdx.x & 15, row-major) of the 4 x 4 transform.  Lane m < 9 forms
+// element m of R and of V, the translation's lanes fetch their row of V with lane permutes; sin / cos / A / Bc / C are
+// computed once (by every lane, on the same operands).  Every element is the result of exactly se3_exp_dev's operations in
+// se3_exp_dev's order: same bits.  All 64 lanes must call this.
+__device__ __forceinline__ float se3_exp_wave(const float (&xi)[6]) {
+    const int lane = threadIdx.x & 63;
+    const float v0 = xi[0], v1 = xi[1], v2 = xi[2], w0 = xi[3], w1 = xi[4], w2 = xi[5];
+    // Wh = {0, -w2, w1, w2, 0, -w0, -w1, w0, 0}
+    auto wh = [&](int q) {
+        float r = 0.0f;
+        r = q == 1 ? -w2 : r; r = q == 2 ? w1 : r; r = q == 3 ? w2 : r;
+        r = q == 5 ? -w0 : r; r = q == 6 ? -w1 : r; r = q == 7 ? w0 : r;
+        return r;
+    };
+    const float th = sqrtf(__fmaf_rn(w2, w2, __fmaf_rn(w1, w1, w0 * w0)));
+    const int m = min(lane, 8), mi = m / 3, mj = m - 3 * mi;
+    const float e = (m % 4 == 0) ? 1.0f : 0.0f, whm = wh(m);
+    float Rm, Vm;
+    if (th < 1e-6f) {  // (wave-uniform)
+        Rm = e + whm; Vm = Rm;
+    } else {
+        const float s = sinf(th), c = cosf(th);
+        const float W2m = dot3_fma(wh(3 * mi), wh(3 * mi + 1), wh(3 * mi + 2), wh(mj), wh(3 + mj), wh(6 + mj));
+        const float A = s / th, Bc = (1.0f - c) / (th * th), C = (th - s) / (th * th * th);
+        Rm = (e + A * whm) + Bc * W2m;
+        Vm = (e + Bc * whm) + C * W2m;
+    }
+    const int t = lane & 15, i = min(t >> 2, 2), j = t & 3;
+    const float r = __shfl(Rm, 3 * i + min(j, 2), kWave);
+    const float va = __shfl(Vm, 3 * i, kWave), vb = __shfl(Vm, 3 * i + 1, kWave), vc = __shfl(Vm, 3 * i + 2, kWave);
+    const float tr = dot3_fma(va, vb, vc, v0, v1, v2);
+    if (t >= 12) return t == 15 ? 1.0f : 0.0f;
+    return j == 3 ? tr : r;
 }
 
 // The O(1) step by ONE wave (S and acc in LDS).  The work is spread
@@ -219,6 +262,11 @@ __device__ void solve6_wave(const float *H, const float *g, float damp, float *x
 //   STEP_LM    : look-ahead cloud: accept (adopt, damp/2, T = dT T) or reject (damp*2) -> solve ; dT
 //   STEP_GRAD_B: look-ahead error -> damp, sigma ; dT = exp(sigma xi) ; T = dT T ; look-ahead discarded
 // `solve` = false for a loop's very last step, whose xi / dT nothing consumes.
+// ORDER.  The chain that the block waits for is  sums -> decision -> solve -> exp.  So the solve takes its operands
+// straight from the sums and the old state (lane (i, k): its element of either, selected on the decision; the new damping
+// formed in a register), one LDS trip after the sums are there, and the exponential takes xi from the solve's registers.
+// The bookkeeping -- adopting the 44 values, T = dT . T, the state words, the tape / trace records -- consists of stores
+// whose values are in registers by then; nothing on the chain reads them back.  Same operands, same operations: same bits.
 __device__ __forceinline__ float expand_elem(const float *acc, int t) {  // element t of the 44 from the 29 sums
     if (t < 36) {
         int u = t / 6, v = t % 6;
@@ -237,33 +285,26 @@ __device__ __forceinline__ void wave_sync() {
 }
 // Called by the block's FIRST WAVE only (all 64 lanes of it): no block barrier inside, so the other waves are free to
 // do something else meanwhile (the grid search's staging); the caller synchronises the block afterwards.
+// Three sections: everything the step reads of the sums and of the OLD state, into registers (with the whole of a gradLM
+// step's gates and damped exponential: one lane, rare, and T = dT . T) ; the chain, in registers ; the stores.
 __device__ __forceinline__ void step_wave0(IcpState *S, const float *acc, int mode, GradParams gp, float *trace, float *out_T,
                                            int look_slot, float *rec, double *lu_buf, bool solve) {
-    __shared__ float lin[44];
     __shared__ float sx[6];
+    __shared__ float lu_hg[42];  // H | g as the solve saw them, for the pivoted elimination (rare)
     const int t = threadIdx.x;
-    if (t < 44) lin[t] = expand_elem(acc, t);
-    wave_sync();
-    const float err = S->cur[42], new_err = lin[42];
+    // ---- reads
+    const float err = S->cur[42], new_err = acc[27], damp0 = S->damp, cur43 = S->cur[43];
+    const int it0 = S->it;
+    const float lin_t = expand_elem(acc, min(t, 43)), cur_t = S->cur[min(t, 43)];
+    const int si = t >> 3, sk = t & 7;
+    const bool s_in = si < 6 && sk <= 6;  // the lane holds an element of the augmented system: H (sk < 6) or g (sk = 6)
+    const int s_e = s_in ? (sk < 6 ? 6 * si + sk : 36 + si) : 0;
+    const float s_new = expand_elem(acc, s_e), s_old = S->cur[s_e];
     const bool lm_accept = new_err < err;
     const bool adopt = mode == STEP_ADOPT || (mode == STEP_LM && lm_accept);
-    if (rec) {  // tape: what the look-ahead launch measured, where it wrote, what this step is
-        if (t < 44) rec[REC_LIN + t] = lin[t];
-        if (t == 44) {
-            rec[REC_SLOT] = (float)look_slot;
-            rec[REC_MODE] = (float)mode;
-            rec[REC_ACCEPT] = (mode == STEP_LM) ? (lm_accept ? 1.0f : 0.0f) : 1.0f;
-        }
-    }
-    if (trace && mode != STEP_ADOPT) {
-        float *tr = trace + 48 * S->it;
-        if (t < 42) tr[t] = S->cur[t];
-        if (t == 42) {
-            tr[42] = err; tr[43] = new_err; tr[44] = S->damp; tr[45] = (mode == STEP_LM && !lm_accept) ? 0.0f : 1.0f;
-            tr[46] = S->cur[43]; tr[47] = 0.0f;
-        }
-    }
+    const float damp1 = (mode == STEP_LM) ? (lm_accept ? damp0 / 2.0f : damp0 * 2.0f) : damp0;
     if (mode == STEP_GRAD_B) {  // the gates and the damped step: a few scalars, one lane
+        wave_sync();
         if (t == 0) {
             float diff = new_err - err;
             diff = fminf(fmaxf(diff, -70.0f), 70.0f);
@@ -277,9 +318,9 @@ __device__ __forceinline__ void step_wave0(IcpState *S, const float *acc, int mo
     }
     // T = dT . T  (accepted LM step, every gradLM step): one lane per element, torch.mm's fma chain over k
     const bool mul_T = mode == STEP_GRAD_B || (mode == STEP_LM && lm_accept);
-    float new_T = 0.0f;
-    if (mul_T && t < 16) {
-        const int i = t >> 2, j = t & 3;
+    float new_T = S->T[t & 15];
+    if (mul_T) {
+        const int i = (t & 15) >> 2, j = t & 3;
         float v = S->dT[4 * i] * S->T[j];
         v = __fmaf_rn(S->dT[4 * i + 1], S->T[4 + j], v);
         v = __fmaf_rn(S->dT[4 * i + 2], S->T[8 + j], v);
@@ -287,7 +328,52 @@ __device__ __forceinline__ void step_wave0(IcpState *S, const float *acc, int mo
         new_T = v;
     }
     wave_sync();  // the old state has been read
-    if (adopt && t < 44) S->cur[t] = lin[t];
+    // ---- the chain: solve, exponential -- in registers; writes xi and dT only (a gradLM step has none: its exponential is above)
+    if (solve && mode != STEP_GRAD_B) {  // wave-uniform
+        const float h = adopt ? s_new : s_old;
+        double a = 0.0;
+        if (s_in) a = (double)((sk < 6 && si == sk) ? h + damp1 : h);
+        bool ok;
+        a = solve6_wave_elim(a, ok);
+        const float x_l = (float)a;
+        GS_STAMP(14);  // (diagnostic build, wave 0: solved)
+        float xi[6];
+        if (ok) {  // wave-uniform: every lane saw the same pivots
+#pragma unroll
+            for (int q = 0; q < 6; ++q) xi[q] = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(x_l), 8 * q + 6));
+        } else {  // a pivot that is not a positive finite number: the pivoted elimination, on the same H | g and damping
+            if (s_in) lu_hg[s_e] = h;
+            wave_sync();
+            if (t == 0) solve6_lu(lu_hg, lu_hg + 36, damp1, lu_hg + 36, lu_buf);  // (x overwrites g: solve6_lu has copied g by then)
+            wave_sync();
+#pragma unroll
+            for (int q = 0; q < 6; ++q) xi[q] = lu_hg[36 + q];
+        }
+        const float dT_l = se3_exp_wave(xi);
+        float xv = xi[0];
+#pragma unroll
+        for (int q = 1; q < 6; ++q) xv = t == q ? xi[q] : xv;
+        if (t < 6) S->xi[t] = xv;
+        if (t < 16) S->dT[t] = dT_l;
+    }
+    // ---- the bookkeeping: stores
+    if (rec) {  // tape: what the look-ahead launch measured, where it wrote, what this step is
+        if (t < 44) rec[REC_LIN + t] = lin_t;
+        if (t == 44) {
+            rec[REC_SLOT] = (float)look_slot;
+            rec[REC_MODE] = (float)mode;
+            rec[REC_ACCEPT] = (mode == STEP_LM) ? (lm_accept ? 1.0f : 0.0f) : 1.0f;
+        }
+    }
+    if (trace && mode != STEP_ADOPT) {
+        float *tr = trace + 48 * it0;
+        if (t < 42) tr[t] = cur_t;
+        if (t == 42) {
+            tr[42] = err; tr[43] = new_err; tr[44] = damp0; tr[45] = (mode == STEP_LM && !lm_accept) ? 0.0f : 1.0f;
+            tr[46] = cur43; tr[47] = 0.0f;
+        }
+    }
+    if (adopt && t < 44) S->cur[t] = lin_t;
     if (mul_T && t < 16) S->T[t] = new_T;
     if (t == 0) {
         if (mode != STEP_ADOPT) S->b_first = S->b_cur;  // the neighbour array the iteration's first solve used
@@ -296,18 +382,11 @@ __device__ __forceinline__ void step_wave0(IcpState *S, const float *acc, int mo
             S->b_cur = look_slot >= 0 ? look_slot : 1 - S->b_cur;
         }
         if (mode == STEP_ADOPT) S->b_first = S->b_cur;
-        if (mode == STEP_LM) S->damp = lm_accept ? S->damp / 2.0f : S->damp * 2.0f;
-        if (mode != STEP_ADOPT) S->it += 1;
+        if (mode == STEP_LM) S->damp = damp1;
+        if (mode != STEP_ADOPT) S->it = it0 + 1;
     }
-    wave_sync();
-    GS_STAMP(13);  // (diagnostic build, wave 0: decision taken, state updated)
-    if (out_T && t < 16) out_T[t] = S->T[t];
-    if (solve && mode != STEP_GRAD_B) {  // wave-uniform
-        solve6_wave(S->cur, S->cur + 36, S->damp, S->xi, lu_buf);
-        wave_sync();
-        GS_STAMP(14);  // (solved)
-        if (t == 0) se3_exp_dev(S->xi, S->dT);
-    }
+    if (out_T && t < 16) out_T[t] = new_T;
+    GS_STAMP(13);  // (diagnostic build, wave 0: the books are written -- after 14 on this wave)
     wave_sync();
 }
 

@@ -4,7 +4,7 @@ the ICP target grown to the downsampled active map (needs make -C gradslam_amd/c
 
 Stamp slots per wave (16 x 8 bytes per wave, GS_STAMP / GS_COUNT in csrc/gs_icp_assoc.hpp; times are s_memrealtime ticks of 10 ns):
   6 kernel entry | 8 first batch of requests arrived | 9 row sums handed over (wave 0: sums ready) | 7 prologue barrier passed
-  wave 0 (the folded step): 13 decision taken + state updated | 14 6x6 system solved | 10 step done
+  wave 0 (the folded step): 14 6x6 system solved | 13 exponential done, books written (state, tape, trace) | 10 step done
   wave 1 (planner): 13 window centres + majority displacement known | 14 plan published | 15 its share staged
   waves 2.. : 14 plan seen | 15 staged (wave 2, the lanes' wave: rows packed)
   0 / 1 / 2 / 3 search start / window scan done / proof + fallbacks done / end ; 5 (wave 0) HW_ID | XCC_ID: which CU
@@ -125,8 +125,8 @@ if (a[..., 9] > 0).any():
         m = share == k
         r = lambda arr: np.percentile(((arr - a[..., 6]) * tick)[m], 50)
         w0r = lambda slot: np.percentile(((w0[..., slot] - w0[..., 6]) * tick)[m], 50)
-        print("  %d block(s) on the CU: first batch arrived %.2f | rows summed %.2f | wave 0: sums ready %.2f, decision + state %.2f, solved %.2f, step done %.2f (us after kernel entry, p50)" % (
-            k, r(a[..., 8]), r(a[..., 9]), w0r(9), w0r(13), w0r(14), w0r(10)))
+        print("  %d block(s) on the CU: first batch arrived %.2f | rows summed %.2f | wave 0: sums ready %.2f, solved %.2f, exponential + books %.2f, step done %.2f (us after kernel entry, p50)" % (
+            k, r(a[..., 8]), r(a[..., 9]), w0r(9), w0r(14), w0r(13), w0r(10)))
 if (a[..., 15] > 0).any() and a.shape[1] > 3:
     solo = share == min(set(share))
     wrel = lambda w, slot: np.percentile(((a[:, w, slot] - a[:, w, 6]) * tick)[solo & (a[:, w, slot] > 0)], 50)

@@ -158,6 +158,10 @@ SIGNATURES = {
                                        c_p, c_p, c_p, c_sz, c_p]),
     "gs_tsdf_faces_ws_bytes": (c_sz, [c_i, c_i, c_i, c_i]),
     "gs_tsdf_faces": (c_i, [c_p, c_p, c_i, c_i, c_i, c_i, c_f, c_p, c_p, c_i, c_i, c_p, c_p, c_p, c_sz, c_p]),
+    "gs_rgbd_odometry_ws_bytes": (c_sz, [c_i, c_i, c_i, c_i]),
+    "gs_rgbd_odometry": (c_i, [c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_p, c_p, c_i, c_p, c_f, c_f, c_f, c_f, c_p, c_p, c_p, c_sz, c_p]),
+    "gs_rgbd_rows": (c_i, [c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_p, c_p, c_f, c_f, c_f, c_p, c_p, c_p, c_p, c_sz, c_p]),
+    "gs_rgbd_pyramid": (c_i, [c_p, c_p, c_i, c_i, c_i, c_i, c_f, c_f, c_p, c_p]),
 }
 
 _lib = None

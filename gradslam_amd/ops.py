@@ -1721,3 +1721,129 @@ def tsdf_raycast(tsdf, weight, color, origin, voxel_size, K, poses, height: int,
     if torch.is_tensor(tsdf) and tsdf.ndim == 4:
         origin = tsdf_origin(origin, tsdf.shape[0], tsdf.device, "tsdf_raycast")
     return _TsdfRaycastFn.apply(tsdf, color, weight, origin, voxel_size, K, poses, height, width, stride, step, near, far, min_weight)
+
+
+# ------------------------------------------------------------------ dense RGB-D odometry (csrc/rgbd.hip)
+def _rgbd_frame(depth, rgb, which, op, B=None, H=None, W=None):
+    """depth (B,H,W) or (B,H,W,1), rgb (B,H,W,3) -> contiguous fp32 (B,H,W), (B,H,W,3)."""
+    for name, t in (("depth", depth), ("rgb", rgb)):
+        if not torch.is_tensor(t):
+            raise TypeError("{}: expected {}_{} to be a tensor; got {}".format(op, which, name, type(t)))
+    if depth.ndim == 4 and depth.shape[-1] == 1:
+        depth = depth[..., 0]
+    if depth.ndim != 3:
+        raise ValueError("{}: {}_depth should have shape (B, H, W) or (B, H, W, 1). Got {}.".format(op, which, tuple(depth.shape)))
+    if tuple(rgb.shape) != tuple(depth.shape) + (3,):
+        raise ValueError("{}: {}_rgb should have shape {}. Got {}.".format(op, which, tuple(depth.shape) + (3,), tuple(rgb.shape)))
+    if B is not None and tuple(depth.shape) != (B, H, W):
+        raise ValueError("{}: both frames should have the same batch size and image size ({} != {}).".format(
+            op, tuple(depth.shape), (B, H, W)))
+    return _f32c(depth.detach()), _f32c(rgb.detach())
+
+
+def _rgbd_K(K, B, op):
+    if not torch.is_tensor(K):
+        raise TypeError("{}: expected intrinsics to be a tensor; got {}".format(op, type(K)))
+    if K.numel() != B * 16:
+        raise ValueError("{}: intrinsics should have shape ({}, 4, 4) or ({}, 1, 4, 4). Got {}.".format(op, B, B, tuple(K.shape)))
+    return _f32c(K.detach().reshape(B, 4, 4))
+
+
+def _rgbd_T(T, B, name, op):
+    if not torch.is_tensor(T):
+        raise TypeError("{}: expected {} to be a tensor; got {}".format(op, name, type(T)))
+    if T.numel() != B * 16 or tuple(T.shape[-2:]) != (4, 4):
+        raise ValueError("{}: {} should have shape ({}, 4, 4) or ({}, 1, 4, 4). Got {}.".format(op, name, B, B, tuple(T.shape)))
+    return _f32c(T.detach().reshape(B, 16))
+
+
+def _rgbd_params(levels, lambda_geo, depth_diff_max, rgb_scale, H, W, op):
+    if not isinstance(levels, int) or isinstance(levels, bool) or levels < 1 or levels > 8:
+        raise ValueError("{}: levels should be an integer in [1, 8]. Got {!r}.".format(op, levels))
+    if (H >> (levels - 1)) < 4 or (W >> (levels - 1)) < 4:
+        raise ValueError("{}: the coarsest of {} levels of a {} x {} image would be smaller than 4 x 4.".format(op, levels, H, W))
+    lam, ddm, scale = (_tsdf_number(x, n, op) for x, n in ((lambda_geo, "lambda_geo"), (depth_diff_max, "depth_diff_max"),
+                                                           (rgb_scale, "rgb_scale")))
+    if not 0.0 <= lam <= 1.0:
+        raise ValueError("{}: lambda_geo should be in [0, 1]. Got {!r}.".format(op, lambda_geo))
+    if not (0.0 < ddm < math.inf):
+        raise ValueError("{}: depth_diff_max should be finite and positive. Got {!r}.".format(op, depth_diff_max))
+    if not math.isfinite(scale):
+        raise ValueError("{}: rgb_scale should be finite. Got {!r}.".format(op, rgb_scale))
+    return lam, ddm, scale
+
+
+def rgbd_level_sizes(H: int, W: int, levels: int):
+    """[(H_l, W_l)] of the pyramid: every level halves the one before, rounding down."""
+    return [(H >> l, W >> l) for l in range(levels)]
+
+
+def rgbd_pyramid_raw(depth, rgb, levels: int, depth_diff_max: float = 0.07, rgb_scale: float = 1.0 / 255.0):
+    """The (intensity, depth) pyramid of one frame, the rule of include/gradslam_hip.h: a list of `levels` tensors (B, H_l, W_l, 2),
+    views of one allocation.  Depth 0 = not valid."""
+    op = "rgbd_pyramid"
+    depth, rgb = _rgbd_frame(depth, rgb, "frame", op)
+    B, H, W = depth.shape
+    _, ddm, scale = _rgbd_params(levels, 0.5, depth_diff_max, rgb_scale, H, W, op)
+    require_hip(depth, rgb, op=op)
+    sizes = rgbd_level_sizes(H, W, levels)
+    out = torch.empty(2 * B * sum(h * w for h, w in sizes), dtype=torch.float32, device=depth.device)
+    call("gs_rgbd_pyramid", ptr(depth), ptr(rgb), B, H, W, levels, ddm, scale, ptr(out), stream())
+    pyr, o = [], 0
+    for h, w in sizes:
+        pyr.append(out[o:o + 2 * B * h * w].view(B, h, w, 2))
+        o += 2 * B * h * w
+    return pyr
+
+
+def rgbd_rows_raw(tgt_depth, tgt_rgb, src_depth, src_rgb, intrinsics, T, lambda_geo: float = 0.968, depth_diff_max: float = 0.07,
+                  rgb_scale: float = 1.0 / 255.0):
+    """One level-0 linearisation of the RGB-D alignment at T (B,4,4) (source camera -> target camera) -> (valid (B,H,W) int32,
+    rows (B,H,W,14) = J_I | r_I | J_D | r_D, sums (B,29) = H upper triangle | g | err | cnt).  The seam the tests check."""
+    op = "rgbd_rows"
+    td, tc = _rgbd_frame(tgt_depth, tgt_rgb, "target", op)
+    B, H, W = td.shape
+    sd, sc = _rgbd_frame(src_depth, src_rgb, "source", op, B, H, W)
+    K, T = _rgbd_K(intrinsics, B, op), _rgbd_T(T, B, "T", op)
+    lam, ddm, scale = _rgbd_params(1, lambda_geo, depth_diff_max, rgb_scale, H, W, op)
+    require_hip(td, tc, sd, sc, K, T, op=op)
+    dev = td.device
+    valid = torch.empty((B, H, W), dtype=torch.int32, device=dev)
+    rows = torch.empty((B, H, W, 14), dtype=torch.float32, device=dev)
+    sums = torch.empty((B, 29), dtype=torch.float32, device=dev)
+    ws = workspace(ws_bytes("gs_rgbd_odometry_ws_bytes", B, H, W, 1), dev, "rgbd")
+    call("gs_rgbd_rows", ptr(td), ptr(tc), ptr(sd), ptr(sc), B, H, W, ptr(K), ptr(T), lam, ddm, scale, ptr(valid), ptr(rows), ptr(sums),
+         ptr(ws), ws.numel(), stream())
+    return valid, rows, sums
+
+
+def rgbd_odometry(tgt_depth, tgt_rgb, src_depth, src_rgb, intrinsics, init=None, numiters=(10, 5, 3), levels: int = 3,
+                  lambda_geo: float = 0.968, depth_diff_max: float = 0.07, damp: float = 1e-8, rgb_scale: float = 1.0 / 255.0):
+    """Dense RGB-D odometry, coarse to fine (the rule of include/gradslam_hip.h): frames as depth (B,H,W[,1]) and rgb (B,H,W,3) with
+    shared intrinsics -> (T (B,4,4) taking source-camera to target-camera coordinates, info (B,levels,4) = cnt, err, status bits,
+    iterations per level).  `numiters`: iterations per level, finest first (an int: that count at every level).  No gradients;
+    no host synchronisation."""
+    op = "rgbd_odometry"
+    td, tc = _rgbd_frame(tgt_depth, tgt_rgb, "target", op)
+    B, H, W = td.shape
+    sd, sc = _rgbd_frame(src_depth, src_rgb, "source", op, B, H, W)
+    K = _rgbd_K(intrinsics, B, op)
+    init = None if init is None else _rgbd_T(init, B, "init", op)
+    lam, ddm, scale = _rgbd_params(levels, lambda_geo, depth_diff_max, rgb_scale, H, W, op)
+    damp = _tsdf_number(damp, "damp", op)
+    if not (0.0 <= damp < math.inf):
+        raise ValueError("{}: damp should be finite and not negative. Got {!r}.".format(op, damp))
+    if isinstance(numiters, int) and not isinstance(numiters, bool):
+        numiters = (numiters,) * levels
+    numiters = tuple(numiters)
+    if len(numiters) != levels or any(not isinstance(n, int) or isinstance(n, bool) or n < 0 for n in numiters):
+        raise ValueError("{}: numiters should be {} non-negative integers (finest level first). Got {!r}.".format(op, levels, numiters))
+    require_hip(td, tc, sd, sc, K, init, op=op)
+    dev = td.device
+    out_T = torch.empty((B, 4, 4), dtype=torch.float32, device=dev)
+    info = torch.empty((B, levels, 4), dtype=torch.float32, device=dev)
+    ws = workspace(ws_bytes("gs_rgbd_odometry_ws_bytes", B, H, W, levels), dev, "rgbd")
+    counts = (nv.c_i * levels)(*numiters)
+    call("gs_rgbd_odometry", ptr(td), ptr(tc), ptr(sd), ptr(sc), B, H, W, ptr(K), ptr(init), levels, counts, lam, ddm, damp, scale,
+         ptr(out_T), ptr(info), ptr(ws), ws.numel(), stream())
+    return out_T, info

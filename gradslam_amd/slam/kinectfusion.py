@@ -10,6 +10,7 @@ from ..geometry.geometryutils import compose_transformations
 from ..odometry.gradicp import GradICPOdometryProvider
 from ..odometry.icp import ICPOdometryProvider
 from ..odometry.icputils import downsample_rgbdimages
+from ..odometry.rgbd import RGBDOdometryProvider
 from ..structures.rgbdimages import RGBDImages
 from ..structures.tsdfvolume import TSDFVolume
 
@@ -28,18 +29,30 @@ class KinectFusion(nn.Module):
     `odom="gt"` the frames' poses are used.  Under autograd every piece is a node of its own: gradients reach the depths and
     colours through raycast, ICP and integrate (not the poses given, nor the intrinsics).  The volume should hold what the
     cameras see (or `dist_thresh` be set): ICP pairs every frame point with its nearest cast point, and frame points beyond the
-    volume pair with the rim of the cast surface."""
+    volume pair with the rim of the cast surface.
+
+    `odom="rgbd"` tracks frame to model with the dense photometric + depth alignment of RGBDOdometryProvider (`numiters`, `damp`,
+    `levels`, `lambda_geo`; it needs `color=True`):
+
+        target = volume.raycast(K, pose_{s-1}, H, W, step=step, min_weight=min_weight)     (the coloured image of the model)
+        pose_s = compose_transformations(odomprov.provide(target, live frame), pose_{s-1})
+
+    at full resolution (`dsratio` and `dist_thresh` are not used).  It has no reverse pass: under autograd with inputs that
+    require gradients `provide` raises NotImplementedError.  A camera that sees nothing of the volume, or a frame without valid
+    pixels, leaves the pose where it was and sets the status bit in `odomprov.last_info` (nothing synchronises the host)."""
 
     def __init__(self, *, dims, voxel_size, origin=(0.0, 0.0, 0.0), trunc=None, max_weight: float = 128.0, color: bool = True,
                  odom: str = "gradicp", dsratio: int = 4, numiters: int = 20, damp: float = 1e-8,
                  dist_thresh: Union[float, int, None] = None, lambda_max: Union[float, int] = 2.0, B: Union[float, int] = 1.0,
                  B2: Union[float, int] = 1.0, nu: Union[float, int] = 200.0, step: Optional[float] = None, min_weight: float = 1.0,
-                 device: Union[torch.device, str, None] = None):
+                 device: Union[torch.device, str, None] = None, levels: int = 3, lambda_geo: float = 0.968):
         super().__init__()
-        if odom not in ["gt", "icp", "gradicp"]:
+        if odom not in ["gt", "icp", "gradicp", "rgbd"]:
             msg = "odometry method ({}) not supported for KinectFusion. ".format(odom)
-            msg += "Currently supported odometry modules for KinectFusion are: 'gt', 'icp', 'gradicp'"
+            msg += "Currently supported odometry modules for KinectFusion are: 'gt', 'icp', 'gradicp', 'rgbd'"
             raise ValueError(msg)
+        if odom == "rgbd" and not color:
+            raise ValueError("KinectFusion: odom='rgbd' tracks against the colours of the volume and needs color=True.")
         if not isinstance(dsratio, int) or isinstance(dsratio, bool) or dsratio < 1:
             raise ValueError("KinectFusion: dsratio should be a positive integer. Got {!r}.".format(dsratio))
         odomprov = None
@@ -47,6 +60,8 @@ class KinectFusion(nn.Module):
             odomprov = ICPOdometryProvider(numiters, damp, dist_thresh)
         elif odom == "gradicp":
             odomprov = GradICPOdometryProvider(numiters, damp, dist_thresh, lambda_max, B, B2, nu)
+        elif odom == "rgbd":
+            odomprov = RGBDOdometryProvider(numiters, levels, lambda_geo, damp=damp)
         self.odom = odom
         self.odomprov = odomprov
         self.dsratio = dsratio
@@ -109,6 +124,13 @@ class KinectFusion(nn.Module):
         if live_frame.channels_first:
             live_frame = live_frame.to_channels_last()
         H, W = live_frame.shape[2:4]
+        if self.odom == "rgbd":
+            cast = volume.raycast(live_frame.intrinsics, prev_frame.poses, H, W, step=self.step_size, min_weight=self.min_weight)
+            # (both frames carry the live frame's intrinsics tensor: the cast's own is a copy of it)
+            target = RGBDImages(cast.rgb_image, cast.depth_image, live_frame.intrinsics, prev_frame.poses)
+            source = RGBDImages(live_frame.rgb_image, live_frame.depth_image, live_frame.intrinsics, prev_frame.poses)
+            transform = self.odomprov.provide(target, source)
+            return compose_transformations(transform.squeeze(1), prev_frame.poses.squeeze(1)).unsqueeze(1)
         target = volume.raycast_pointcloud(live_frame.intrinsics, prev_frame.poses, H, W, stride=self.dsratio, step=self.step_size,
                                            min_weight=self.min_weight)
         # the frame under the previous pose, as a frame of its own: the caller's keeps its poses until the step has succeeded

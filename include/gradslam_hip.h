@@ -855,6 +855,57 @@ int gs_tsdf_faces(const float *tsdf, const float *weight, int B, int nx, int ny,
                   const int32_t *edge, const int32_t *n_points, int vcap, int fcap, int32_t *faces, int32_t *n_faces,
                   void *ws, size_t ws_bytes, gs_stream_t stream);
 
+/* Dense RGB-D odometry: the transform T (B,16 row-major 4x4) that takes SOURCE-camera coordinates to TARGET-camera coordinates,
+ * by Gauss-Newton on a joint photometric + depth residual over an image pyramid, coarse to fine.  Both frames per batch element
+ * have depth (B,H,W), rgb (B,H,W,3) and the intrinsics (B,4,4) (fx = K[0], fy = K[5], cx = K[2], cy = K[6]; pixel centres at
+ * integer coordinates).  IEEE fp32 in the order written, no contraction; u is a column, v a row.
+ *   level 0    I = rgb_scale * ((0.299f R + 0.587f G) + 0.114f B);  D = depth if 0 < depth < inf, else 0 (not valid).
+ *   level l+1  floor(H_l / 2) x floor(W_l / 2) pixels; pixel (u, v) reduces the block c0 = (2u, 2v), c1 = (2u+1, 2v),
+ *              c2 = (2u, 2v+1), c3 = (2u+1, 2v+1) of level l:  I = (((I0 + I1) + I2) + I3) * 0.25f;  m = the smallest valid D of
+ *              the block; D = s / (float)n with s the sum in the order c0..c3 (from 0) and n the number of the valid D_k with
+ *              D_k - m <= depth_diff_max; 0 when n = 0.  fx, fy: * 0.5f;  cx' = (cx + 0.5f) * 0.5f - 0.5f, likewise cy.
+ *   warp       source pixel (u, v) of the level with D_s = d > 0:  px = d * (((float)u - cx) / fx), py = d * (((float)v - cy) / fy),
+ *              q_i = ((T_i0 px + T_i1 py) + T_i2 d) + T_i3;  q_z > 0;  iz = 1 / q_z;  x = (fx q_x) * iz + cx, y = (fy q_y) * iz + cy;
+ *              i = floorf(x), j = floorf(y), 0 <= i <= W_l - 2, 0 <= j <= H_l - 2; a = x - i, b = y - j; the target's four
+ *              corners c00 = (i, j), c10 = (i+1, j), c01 = (i, j+1), c11 = (i+1, j+1) all have D > 0.
+ *   sample     per channel F in (I, D):  X0 = F10 - F00, X1 = F11 - F01, top = F00 + a X0, bot = F01 + a X1;
+ *              F^ = top + b (bot - top);  F_x = X0 + b (X1 - X0);  F_y = bot - top  (the interpolant and its exact derivatives).
+ *   residuals  r_I = I^ - I_s(u, v);  r_D = D^ - q_z;  |r_D| <= depth_diff_max.  A pixel that passes every test is valid.
+ *   rows       gx = fx * iz, gy = fy * iz;  c0 = F_x gx, c1 = F_y gy, c2 = -((c0 q_x + c1 q_y) * iz), for D: ... - 1;
+ *              J = w * (c0, c1, c2, q_y c2 - q_z c1, q_z c0 - q_x c2, q_x c1 - q_y c0)   (xi = [v; omega], d q / d xi = [I | -q^]),
+ *              w_I = sqrtf(1 - lambda_geo), w_D = sqrtf(lambda_geo); the residuals are scaled by the same factors.
+ *   sums       per valid pixel the 29 terms  J_I[m] J_I[n] + J_D[m] J_D[n] (m <= n, row-major: 21) | J_I[m] r_I + J_D[m] r_D (6) |
+ *              r_I r_I + r_D r_D | 1.  Blocks of 256 consecutive pixels: six pairwise steps over a wave's 64 lanes (partners 1, 2,
+ *              4 (round the 16-lane row), 8, 16 and 32 lanes away; a lane keeps half of its sums at each step and hands over
+ *              the other half), the 4 waves added in order;
+ *              then, per batch element, a 1024-thread block: thread (g, k) adds rows g, g + 32, ... of sum k in order, and the 32
+ *              group sums are added in order.  No float atomics: the same bits from run to run.  H = the 21, g = MINUS the 6.
+ *   step       cnt < 6: status bit 1, T stays.  Else xi = (H + damp I)^-1 g (damping added in fp32, the system solved in fp64),
+ *              T <- exp(xi) T (the exponential and the product of the ICP step); xi or the product not finite: status bit 2,
+ *              T stays.
+ *   loop       from level `levels` - 1 down to 0, numiters[l] iterations at level l (a host array, finest first), from `init`
+ *              (B,16; NULL: the identity).  info (B, levels, 4) floats: cnt and err of the level's last linearisation, the status
+ *              bits of the level's iterations or-ed, the iterations run at the level (zeros for a level with none).
+ * Two launches per iteration (linearise, one source pixel per lane; step), one per frame and level for the pyramids, one to
+ * start; nothing synchronises the host, the loop state (T) lives in the workspace.  Refused before any device work: NULL
+ * pointers, B outside [1, 65535], H W > 2^24, B H W > 2^30, levels outside [1, 8] or a coarsest level smaller than 4 x 4,
+ * lambda_geo outside [0, 1], depth_diff_max not finite and positive, damp negative or not finite, rgb_scale not finite, a count
+ * outside [0, 2^20].  Workspace, every piece rounded up to 256 bytes, with P = sum_l H_l W_l:
+ *   64 B (T) | 116 B ceil(H W / 256) (partial rows) | 8 B P (target pyramid, level-major) | 8 B P (source pyramid). */
+size_t gs_rgbd_odometry_ws_bytes(int B, int H, int W, int levels);
+int gs_rgbd_odometry(const float *tgt_depth, const float *tgt_rgb, const float *src_depth, const float *src_rgb, int B, int H, int W,
+                     const float *intrinsics, const float *init, int levels, const int *numiters, float lambda_geo,
+                     float depth_diff_max, float damp, float rgb_scale, float *out_T, float *info, void *ws, size_t ws_bytes,
+                     gs_stream_t stream);
+/* One level-0 linearisation at the given T (B,16): valid (B,H,W) int32, rows (B,H,W,14) = J_I | r_I | J_D | r_D (zeros where not
+ * valid), sums (B,29) = H upper triangle | g | err | cnt.  The workspace of gs_rgbd_odometry_ws_bytes(B, H, W, 1). */
+int gs_rgbd_rows(const float *tgt_depth, const float *tgt_rgb, const float *src_depth, const float *src_rgb, int B, int H, int W,
+                 const float *intrinsics, const float *T, float lambda_geo, float depth_diff_max, float rgb_scale, int32_t *valid,
+                 float *rows, float *sums, void *ws, size_t ws_bytes, gs_stream_t stream);
+/* The pyramid of one frame alone: out holds level after level, level l as (B, H_l, W_l, 2) floats (I, D). */
+int gs_rgbd_pyramid(const float *depth, const float *rgb, int B, int H, int W, int levels, float depth_diff_max, float rgb_scale,
+                    float *out, gs_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -148,6 +148,9 @@ SIGNATURES = {
     "gs_tsdf_integrate_backward_ws_bytes": (c_sz, [c_i, c_i, c_i, c_i]),
     "gs_tsdf_integrate_backward": (c_i, [c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_f, c_p, c_f, c_f, c_p, c_p, c_p, c_p, c_p,
                                          c_p, c_p, c_p, c_sz, c_p]),
+    "gs_tsdf_integrate_backward_poses_ws_bytes": (c_sz, [c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i]),
+    "gs_tsdf_integrate_backward_poses": (c_i, [c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_f, c_p, c_f, c_f, c_p, c_p, c_p, c_p,
+                                               c_p, c_p, c_p, c_p, c_p, c_sz, c_p]),
     "gs_tsdf_extract_ws_bytes": (c_sz, [c_i, c_i, c_i, c_i]),
     "gs_tsdf_extract": (c_i, [c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_f, c_p, c_f, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_sz, c_p]),
     "gs_tsdf_extract_backward": (c_i, [c_p, c_p, c_i, c_i, c_i, c_i, c_f, c_p, c_p, c_i, c_p, c_p, c_p, c_p, c_p]),
@@ -156,6 +159,9 @@ SIGNATURES = {
     "gs_tsdf_raycast_backward_ws_bytes": (c_sz, [c_i, c_i, c_i, c_i, c_i]),
     "gs_tsdf_raycast_backward": (c_i, [c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_f, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_f, c_f, c_p, c_p, c_p,
                                        c_p, c_p, c_p, c_sz, c_p]),
+    "gs_tsdf_raycast_backward_poses_ws_bytes": (c_sz, [c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i]),
+    "gs_tsdf_raycast_backward_poses": (c_i, [c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_f, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_f, c_f, c_p, c_p,
+                                             c_p, c_p, c_p, c_p, c_p, c_sz, c_p]),
     "gs_tsdf_faces_ws_bytes": (c_sz, [c_i, c_i, c_i, c_i]),
     "gs_tsdf_faces": (c_i, [c_p, c_p, c_i, c_i, c_i, c_i, c_f, c_p, c_p, c_i, c_i, c_p, c_p, c_p, c_sz, c_p]),
     "gs_rgbd_odometry_ws_bytes": (c_sz, [c_i, c_i, c_i, c_i]),

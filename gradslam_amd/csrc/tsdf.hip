@@ -19,6 +19,10 @@
 //      gs_tsdf_raycast_backward: one thread per pixel recomputes its two samples and its hit from the tape k_end; a voxel's
 //      adjoint is a sum over many pixels: the same fold, over the voxels
 //        memset -> tsdf_raycast_bwd_k<MAX> -> tsdf_raycast_bwd_k<ACC> -> tsdf_cast_finish_k
+//   P  gs_tsdf_integrate_backward_poses / gs_tsdf_raycast_backward_poses: the same passes; the second one (POSE) also reduces a
+//      camera's pose sums (4 per frame over the voxels; 12 over the pixels) wave by wave and block by block into one row per
+//      block, which tsdf_pose_finish_k / tsdf_cast_pose_finish_k fold in a fixed order (gs_tsdf.hpp: the pose sums): plain fp32,
+//      no atomics.  Outputs nobody asks for drop their passes (FOLD = false: no maximum pass, no fold, no finish).
 // Batch elements ride in grid.y (R: frames in grid.y, batch elements in grid.z).
 #include <cmath>
 #include <stddef.h>
@@ -117,13 +121,36 @@ static inline size_t tsdf_fold_layout(int B, int L, int H, int W, void *ws, Fold
     return c.off;
 }
 
+// gs_tsdf_integrate_backward_poses: the fold | one row of 4 pose sums per (b, frame of the chunk, block of 256 voxels) | with more
+// than one chunk, the adjoints carried from chunk to chunk when the caller passes no g_tsdf_in / g_color_in to carry them in
+struct TsdfPoseWs {
+    Fold fold;
+    size_t fold_bytes;
+    float *psum, *carry_t, *carry_c;
+};
+static inline size_t tsdf_pose_fold_layout(int B, int L, int H, int W, int64_t nvox, bool has_color, void *ws, TsdfPoseWs *out) {
+    Carve c{(char *)ws};
+    TsdfPoseWs scratch, &r = out ? *out : scratch;
+    r.fold = fold_carve(c, (size_t)B * std::min(L, TSDF_CHUNK) * H * W, 4);
+    r.fold_bytes = c.off;
+    r.psum = c.take<float>(sizeof(float) * 4 * (size_t)B * std::min(L, TSDF_CHUNK) * cdiv(nvox, TSDF_T));
+    const bool carry = L > TSDF_CHUNK;
+    r.carry_t = carry ? c.take<float>(sizeof(float) * (size_t)B * nvox) : nullptr;
+    r.carry_c = carry && has_color ? c.take<float>(sizeof(float) * 3 * (size_t)B * nvox) : nullptr;
+    return c.off;
+}
+
 // grid (x: voxels, y: batch element).  ACC = false: the largest finite |term| of the chunk; ACC = true: the terms go into the
 // fold and the adjoints carried to the frames before the chunk are written (g_*_src -> g_*_dst: the same thread reads and writes
-// a voxel, so they may alias).  No thread leaves early: the camera loads are block-wide.
-template <bool ACC>
+// a voxel, so they may alias; a NULL g_*_dst is not written).  No thread leaves early: the camera loads are block-wide.
+// POSE (the second pass of gs_tsdf_integrate_backward_poses): per frame of the chunk the block's sums of gd and gd (c - t) go to
+// row ((b Lc + l) gridDim.x + blockIdx.x) of `psum` (gs_tsdf.hpp: the pose sums); FOLD = false: nothing goes into the fold.
+template <bool ACC, bool POSE = false, bool FOLD = true>
 __global__ __launch_bounds__(TSDF_T) void tsdf_bwd_k(TsdfVol vol, TsdfFrames fr, const float *__restrict__ weight_in, const float *g_tsdf_src,
-                                                     const float *g_color_src, float *g_tsdf_dst, float *g_color_dst, Fold fold, int lg) {
+                                                     const float *g_color_src, float *g_tsdf_dst, float *g_color_dst, Fold fold, int lg,
+                                                     float *__restrict__ psum = nullptr) {
     __shared__ Cam cams[TSDF_CHUNK];
+    __shared__ float red[POSE ? TSDF_CHUNK * TSDF_WAVES * 4 : 1];
     const int b = blockIdx.y;
     const int64_t nvox = tsdf_nvox(vol), j = (int64_t)blockIdx.x * TSDF_T + threadIdx.x;
     const bool live = j < nvox;
@@ -153,37 +180,56 @@ __global__ __launch_bounds__(TSDF_T) void tsdf_bwd_k(TsdfVol vol, TsdfFrames fr,
     float g = live ? g_tsdf_src[at] : 0.0f;
     f3 gc = (live && color) ? ld3(g_color_src, at) : f3{0.0f, 0.0f, 0.0f};
     const float W0 = live ? weight_in[at] : 0.0f;
-    const int E = ACC ? det_scale(*fold.maxbits, lg) : 0;
+    const int E = (ACC && FOLD) ? det_scale(*fold.maxbits, lg) : 0;
     uint32_t mx = 0;
     for (int l = fr.Lc - 1; l >= 0; --l) {
-        if (!((mask >> l) & 1u)) continue;
-        tsdf_observe(cams[l], c, fr.depth + ((int64_t)b * fr.L + fr.l0 + l) * HW, fr, vol.trunc, pix, sdf);
-        const float W = tsdf_weight_after(W0, n0 + __popc(mask & ((1u << l) - 1u)), vol.maxw);
-        const float den = W + 1.0f, keep = W / den;
-        const float gd = sdf < vol.trunc ? (g / den) / vol.trunc : 0.0f;  // t = 1 beyond trunc: no gradient
-        const f3 gr{gc.x / den, gc.y / den, gc.z / den};
-        g = g * keep;
-        gc = f3{gc.x * keep, gc.y * keep, gc.z * keep};
-        if (ACC) {
-            const int64_t p = ((int64_t)b * fr.Lc + l) * HW + pix;
-            fold_add(fold, p, 0, gd, E);
-            if (color) {
-                fold_add(fold, p, 1, gr.x, E);
-                fold_add(fold, p, 2, gr.y, E);
-                fold_add(fold, p, 3, gr.z, E);
+        const bool on = (mask >> l) & 1u;
+        if (!POSE && !on) continue;
+        float ps[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+        if (on) {
+            tsdf_observe(cams[l], c, fr.depth + ((int64_t)b * fr.L + fr.l0 + l) * HW, fr, vol.trunc, pix, sdf);
+            const float W = tsdf_weight_after(W0, n0 + __popc(mask & ((1u << l) - 1u)), vol.maxw);
+            const float den = W + 1.0f, keep = W / den;
+            const float gd = sdf < vol.trunc ? (g / den) / vol.trunc : 0.0f;  // t = 1 beyond trunc: no gradient
+            const f3 gr{gc.x / den, gc.y / den, gc.z / den};
+            g = g * keep;
+            gc = f3{gc.x * keep, gc.y * keep, gc.z * keep};
+            if (ACC && FOLD) {
+                const int64_t p = ((int64_t)b * fr.Lc + l) * HW + pix;
+                fold_add(fold, p, 0, gd, E);
+                if (color) {
+                    fold_add(fold, p, 1, gr.x, E);
+                    fold_add(fold, p, 2, gr.y, E);
+                    fold_add(fold, p, 3, gr.z, E);
+                }
+            } else if (!ACC) {
+                mx = fold_max(mx, gd);
+                if (color) mx = fold_max(fold_max(fold_max(mx, gr.x), gr.y), gr.z);
             }
-        } else {
-            mx = fold_max(mx, gd);
-            if (color) mx = fold_max(fold_max(fold_max(mx, gr.x), gr.y), gr.z);
+            if (POSE) {  // z = sum_j R[j][2] (c_j - t_j) and dL/dz = -gd: the terms of S0 and S_j
+                const float *P = fr.poses + ((int64_t)b * fr.L + fr.l0 + l) * 16;
+                ps[0] = gd;
+                ps[1] = gd * (c.x - P[3]);
+                ps[2] = gd * (c.y - P[7]);
+                ps[3] = gd * (c.z - P[11]);
+            }
         }
+        if (POSE) tsdf_pose_wave<4>(ps, on, red + l * TSDF_WAVES * 4);
     }
     if (ACC) {
         if (live) {
-            g_tsdf_dst[at] = g;
-            if (color) st3(g_color_dst, at, gc);
+            if (g_tsdf_dst) g_tsdf_dst[at] = g;
+            if (color && g_color_dst) st3(g_color_dst, at, gc);
         }
     } else {
         fold_max_commit(fold.maxbits, mx);
+    }
+    if (POSE) {
+        __syncthreads();
+        if ((int)threadIdx.x < 4 * fr.Lc) {
+            const int l = threadIdx.x >> 2, n = threadIdx.x & 3;
+            psum[(((int64_t)b * fr.Lc + l) * gridDim.x + blockIdx.x) * 4 + n] = tsdf_pose_block<4>(red + l * TSDF_WAVES * 4, n);
+        }
     }
 }
 
@@ -198,9 +244,30 @@ __global__ __launch_bounds__(TSDF_T) void tsdf_fold_finish_k(Fold fold, int lg, 
         const int64_t out = ((int64_t)b * L + l0 + l) * HW + pix;
         for (int ch = 0; ch < (g_rgb ? 4 : 1); ++ch) {
             const float r = fold_result(fold, p, ch, E);
-            if (ch == 0) g_depth[out] = r;
-            else g_rgb[3 * out + ch - 1] = r;
+            if (ch == 0) {
+                if (g_depth) g_depth[out] = r;
+            } else {
+                g_rgb[3 * out + ch - 1] = r;
+            }
         }
+    }
+}
+
+// The pose adjoint of the chunk's cameras from their blocks' rows.  grid (x: frame of the chunk, y: batch element), TSDF_POSE_T
+// threads.  With the sums S0 = sum gd, S_j = sum gd (c_j - t_j):  g_poses[b,l][j][2] = -S_j,  g_poses[b,l][j][3] = R[j][2] S0,
+// every other entry 0.
+__global__ __launch_bounds__(TSDF_POSE_T) void tsdf_pose_finish_k(const float *__restrict__ psum, int nrow, const float *__restrict__ poses,
+                                                                  int L, int l0, int Lc, float *__restrict__ g_poses) {
+    __shared__ float sm[TSDF_POSE_T + 16];
+    const int b = blockIdx.y, l = blockIdx.x;
+    tsdf_pose_rows<4>(psum + ((int64_t)b * Lc + l) * nrow * 4, nrow, sm);
+    if (threadIdx.x < 16) {
+        const int64_t cam = (int64_t)b * L + l0 + l;
+        const int i = threadIdx.x >> 2, j = threadIdx.x & 3;
+        float r = 0.0f;
+        if (i < 3 && j == 2) r = -sm[TSDF_POSE_T + 1 + i];
+        if (i < 3 && j == 3) r = poses[cam * 16 + 4 * i + 2] * sm[TSDF_POSE_T];
+        g_poses[cam * 16 + threadIdx.x] = r;
     }
 }
 
@@ -451,6 +518,16 @@ static inline size_t tsdf_cast_fold_layout(int B, int64_t nvox, int nch, void *w
     if (out) *out = f;
     return c.off;
 }
+// gs_tsdf_raycast_backward_poses: the fold | one row of 12 pose sums per (b, l, 16x16 tile)
+static inline size_t tsdf_cast_pose_layout(int B, int64_t nvox, int nch, int L, int tiles, void *ws, Fold *out, float **psum, size_t *fold_bytes) {
+    Carve c{(char *)ws};
+    const Fold f = fold_carve(c, (size_t)B * nvox, nch);
+    if (out) *out = f;
+    if (fold_bytes) *fold_bytes = c.off;
+    float *p = c.take<float>(sizeof(float) * 12 * (size_t)B * L * tiles);
+    if (psum) *psum = p;
+    return c.off;
+}
 // one term of voxel p: into the maximum, or into the sums
 template <bool ACC>
 __device__ __forceinline__ void tsdf_cast_term(const Fold &fold, int64_t p, int ch, float x, int E, uint32_t &mx) {
@@ -460,30 +537,39 @@ __device__ __forceinline__ void tsdf_cast_term(const Fold &fold, int64_t p, int 
 
 // One thread per output pixel: the two samples and the hit are recomputed from the tape k_end through the forward's bodies.
 // ACC = false: the largest finite |term|; ACC = true: the terms go into the fold.  No thread leaves before the wave's reduction.
-template <bool ACC>
+// POSE (the second pass of gs_tsdf_raycast_backward_poses): the block's 12 pose sums go to row ((b L + l) gridDim.x + blockIdx.x)
+// of `psum` (gs_tsdf.hpp: the pose sums), 3 i + j: (z0 u0 + z1 u1 + z* w)_i d_j, 9 + i: (u0 + u1 + w)_i; FOLD = false: nothing
+// goes into the fold.
+template <bool ACC, bool POSE = false, bool FOLD = true>
 __global__ __launch_bounds__(TSDF_T) void tsdf_raycast_bwd_k(TsdfVol vol, TsdfCast cast, const float *__restrict__ tsdf,
                                                              const float *__restrict__ weight, const float *__restrict__ color,
                                                              const int32_t *__restrict__ k_end, const float *__restrict__ g_depth,
-                                                             const float *__restrict__ g_rgb, Fold fold, int lg) {
+                                                             const float *__restrict__ g_rgb, Fold fold, int lg,
+                                                             float *__restrict__ psum = nullptr) {
+    __shared__ float red[POSE ? TSDF_WAVES * 12 : 1];
     int i, j;
     const bool live = tsdf_cast_pixel(cast, i, j);
     const int l = blockIdx.y, b = blockIdx.z;
     const int64_t nvox = tsdf_nvox(vol), pix = (((int64_t)b * cast.L + l) * cast.Ho + i) * cast.Wo + j;
     const float *o = vol.origin + 3 * b, *f_b = tsdf + b * nvox, *w_b = weight + b * nvox;
-    const int E = ACC ? det_scale(*fold.maxbits, lg) : 0;
+    const int E = (ACC && FOLD) ? det_scale(*fold.maxbits, lg) : 0;
     uint32_t mx = 0;
+    float ps[12] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+    bool hit = false;
     const int k = live ? k_end[pix] : 0;
     if (k >= 2 && k < TSDF_KMAX) {
         const TsdfRay ray = tsdf_ray(cast.K + 16 * b, cast.poses + ((int64_t)b * cast.L + l) * 16, i * cast.s, j * cast.s, cast.step);
         TsdfCell c0, c1, hc;
         float f0, f1, z;
+        const float z0 = tsdf_ray_z(ray, k - 1), z1 = tsdf_ray_z(ray, k);
         // (a tape that does not belong to this volume fails these tests; every gather stays behind tsdf_cell's bounds)
-        if (tsdf_sample_at(vol, o, f_b, w_b, cast.minw, tsdf_ray_at(ray, tsdf_ray_z(ray, k - 1)), c0, f0) &&
-            tsdf_sample_at(vol, o, f_b, w_b, cast.minw, tsdf_ray_at(ray, tsdf_ray_z(ray, k)), c1, f1) && f0 >= 0.0f && f1 < 0.0f &&
+        if (tsdf_sample_at(vol, o, f_b, w_b, cast.minw, tsdf_ray_at(ray, z0), c0, f0) &&
+            tsdf_sample_at(vol, o, f_b, w_b, cast.minw, tsdf_ray_at(ray, z1), c1, f1) && f0 >= 0.0f && f1 < 0.0f &&
             tsdf_hit_at(vol, o, w_b, cast.minw, ray, k, f0, f1, z, hc)) {
+            hit = true;
             float gz = g_depth ? g_depth[pix] : 0.0f;
-            const bool col = fold.nch == 4 && g_rgb != nullptr;
-            f3 gc{0.0f, 0.0f, 0.0f};
+            const bool col = color != nullptr && g_rgb != nullptr;
+            f3 gc{0.0f, 0.0f, 0.0f}, wv{0.0f, 0.0f, 0.0f};
             if (col) {
                 const float *c_b = color + 3 * b * nvox;
                 gc = ld3(g_rgb, pix);
@@ -494,26 +580,66 @@ __global__ __launch_bounds__(TSDF_T) void tsdf_raycast_bwd_k(TsdfVol vol, TsdfCa
                     tsdf_gather8c(vol, c_b, hc.j, ch, c8);
                     const f3 g = tsdf_trigrad(c8, hc);
                     gz = gz + gch[ch] * (((g.x * ray.dw.x + g.y * ray.dw.y) + g.z * ray.dw.z) / vol.v);
+                    if (POSE) wv = f3{wv.x + gch[ch] * (g.x / vol.v), wv.y + gch[ch] * (g.y / vol.v), wv.z + gch[ch] * (g.z / vol.v)};
                 }
             }
             const float den = f0 - f1, den2 = den * den, gs = gz * ray.dz;
             const float a0 = gs * ((-f1) / den2), a1 = gs * (f0 / den2);
             const int64_t at = b * nvox;
+            if (!ACC || FOLD) {
 #pragma unroll
-            for (int c = 0; c < 8; ++c) {
-                tsdf_cast_term<ACC>(fold, at + tsdf_corner(vol, c0.j, c), 0, a0 * tsdf_corner_weight(c0, c), E, mx);
-                tsdf_cast_term<ACC>(fold, at + tsdf_corner(vol, c1.j, c), 0, a1 * tsdf_corner_weight(c1, c), E, mx);
-                if (col) {
-                    const float w = tsdf_corner_weight(hc, c);
-                    const int64_t p = at + tsdf_corner(vol, hc.j, c);
-                    tsdf_cast_term<ACC>(fold, p, 1, gc.x * w, E, mx);
-                    tsdf_cast_term<ACC>(fold, p, 2, gc.y * w, E, mx);
-                    tsdf_cast_term<ACC>(fold, p, 3, gc.z * w, E, mx);
+                for (int c = 0; c < 8; ++c) {
+                    tsdf_cast_term<ACC>(fold, at + tsdf_corner(vol, c0.j, c), 0, a0 * tsdf_corner_weight(c0, c), E, mx);
+                    tsdf_cast_term<ACC>(fold, at + tsdf_corner(vol, c1.j, c), 0, a1 * tsdf_corner_weight(c1, c), E, mx);
+                    if (col && fold.nch == 4) {
+                        const float w = tsdf_corner_weight(hc, c);
+                        const int64_t p = at + tsdf_corner(vol, hc.j, c);
+                        tsdf_cast_term<ACC>(fold, p, 1, gc.x * w, E, mx);
+                        tsdf_cast_term<ACC>(fold, p, 2, gc.y * w, E, mx);
+                        tsdf_cast_term<ACC>(fold, p, 3, gc.z * w, E, mx);
+                    }
+                }
+            }
+            if (POSE) {  // p = t + z R d: u0 = a0 grad F(p0) / v, u1 = a1 grad F(p1) / v, w = sum_ch g_rgb_ch grad C_ch(p*) / v
+                float f8[8], dx, dy;
+                tsdf_gather8(vol, f_b, c0.j, f8);
+                const f3 t0 = tsdf_trigrad(f8, c0);
+                tsdf_gather8(vol, f_b, c1.j, f8);
+                const f3 t1 = tsdf_trigrad(f8, c1);
+                tsdf_ray_dir(cast.K + 16 * b, i * cast.s, j * cast.s, dx, dy);
+                const float u0[3] = {a0 * (t0.x / vol.v), a0 * (t0.y / vol.v), a0 * (t0.z / vol.v)};
+                const float u1[3] = {a1 * (t1.x / vol.v), a1 * (t1.y / vol.v), a1 * (t1.z / vol.v)};
+                const float w3[3] = {wv.x, wv.y, wv.z};
+#pragma unroll
+                for (int a = 0; a < 3; ++a) {
+                    const float q = (z0 * u0[a] + z1 * u1[a]) + z * w3[a];
+                    ps[3 * a] = q * dx;
+                    ps[3 * a + 1] = q * dy;
+                    ps[3 * a + 2] = q;
+                    ps[9 + a] = (u0[a] + u1[a]) + w3[a];
                 }
             }
         }
     }
     if (!ACC) fold_max_commit(fold.maxbits, mx);
+    if (POSE) {
+        tsdf_pose_wave<12>(ps, hit, red);
+        __syncthreads();
+        if (threadIdx.x < 12)
+            psum[((((int64_t)b * cast.L + l) * gridDim.x) + blockIdx.x) * 12 + threadIdx.x] = tsdf_pose_block<12>(red, threadIdx.x);
+    }
+}
+
+// The pose adjoint of every camera from its blocks' rows.  grid (x: frame, y: batch element), TSDF_POSE_T threads.  Sum 3 i + j
+// is entry [i][j] of the rotation, sum 9 + i entry [i][3]; row 3 is zero.
+__global__ __launch_bounds__(TSDF_POSE_T) void tsdf_cast_pose_finish_k(const float *__restrict__ psum, int nrow, float *__restrict__ g_poses) {
+    __shared__ float sm[TSDF_POSE_T + 16];
+    const int64_t cam = (int64_t)blockIdx.y * gridDim.x + blockIdx.x;
+    tsdf_pose_rows<12>(psum + cam * nrow * 12, nrow, sm);
+    if (threadIdx.x < 16) {
+        const int i = threadIdx.x >> 2, j = threadIdx.x & 3;
+        g_poses[cam * 16 + threadIdx.x] = i == 3 ? 0.0f : sm[TSDF_POSE_T + (j == 3 ? 9 + i : 3 * i + j)];
+    }
 }
 
 // every voxel: each sum rounded once to fp32.  g_color may be NULL
@@ -618,6 +744,59 @@ int gs_tsdf_integrate_backward(const float *depth, const float *intrinsics, cons
         hipLaunchKernelGGL(tsdf_fold_finish_k, dim3(std::min(cdiv((int64_t)B * fr.Lc * HW, TSDF_T), 4096)), dim3(TSDF_T), 0, st, fold, lg, B, L,
                            l0, fr.Lc, HW, g_depth, g_rgb);
         GS_LAUNCH_CHECK("gs_tsdf_integrate_backward/finish");
+    }
+    return GS_OK;
+}
+
+size_t gs_tsdf_integrate_backward_poses_ws_bytes(int B, int L, int H, int W, int nx, int ny, int nz, int has_color) {
+    if (!tsdf_vol_ok(B, nx, ny, nz) || L <= 0 || H <= 0 || W <= 0) return 0;
+    return tsdf_pose_fold_layout(B, L, H, W, (int64_t)nx * ny * nz, has_color != 0, nullptr, nullptr);
+}
+
+int gs_tsdf_integrate_backward_poses(const float *depth, const float *intrinsics, const float *poses, int B, int L, int H, int W, int nx,
+                                     int ny, int nz, float voxel_size, const float *origin, float trunc, float max_weight,
+                                     const float *weight_in, const float *g_tsdf_out, const float *g_color_out, float *g_tsdf_in,
+                                     float *g_color_in, float *g_depth, float *g_rgb, float *g_poses, void *ws, size_t ws_bytes,
+                                     gs_stream_t stream) {
+    GS_REQUIRE(depth && intrinsics && poses && origin && weight_in && g_tsdf_out && g_poses, "gs_tsdf_integrate_backward_poses: NULL argument");
+    GS_REQUIRE(g_color_out || (!g_color_in && !g_rgb), "gs_tsdf_integrate_backward_poses: g_color_in and g_rgb need g_color_out");
+    TSDF_REQUIRE_VOLUME("gs_tsdf_integrate_backward_poses");
+    TSDF_REQUIRE_FRAMES("gs_tsdf_integrate_backward_poses");
+    const size_t need = gs_tsdf_integrate_backward_poses_ws_bytes(B, L, H, W, nx, ny, nz, g_color_out != nullptr);
+    if (!ws || ws_bytes < need) {
+        set_error("gs_tsdf_integrate_backward_poses: workspace too small (%zu < %zu)", ws_bytes, need);
+        return GS_ERR_WORKSPACE_TOO_SMALL;
+    }
+    hipStream_t st = (hipStream_t)stream;
+    const TsdfVol vol{nx, ny, nz, voxel_size, trunc, max_weight, origin};
+    TsdfFrames fr = tsdf_frames(depth, nullptr, intrinsics, poses, L, H, W);
+    const int64_t nvox = tsdf_nvox(vol), HW = (int64_t)H * W;
+    TsdfPoseWs w;
+    tsdf_pose_fold_layout(B, L, H, W, nvox, g_color_out != nullptr, ws, &w);
+    const bool fold = g_depth || g_rgb, color = g_color_out && (g_color_in || g_rgb);  // what nobody asked for is not computed
+    float *dst_t = g_tsdf_in ? g_tsdf_in : w.carry_t, *dst_c = color ? (g_color_in ? g_color_in : w.carry_c) : nullptr;
+    const int lg = fold_lg(nvox);
+    const int nblk = cdiv(nvox, TSDF_T);
+    const dim3 grid(nblk, B);
+    const int last = (L - 1) / TSDF_CHUNK * TSDF_CHUNK;
+    auto second = fold ? tsdf_bwd_k<true, true, true> : tsdf_bwd_k<true, true, false>;
+    for (int l0 = last; l0 >= 0; l0 -= TSDF_CHUNK) {  // as gs_tsdf_integrate_backward, with the pose sums on the second pass
+        fr.l0 = l0;
+        fr.Lc = std::min(TSDF_CHUNK, L - l0);
+        const float *gt = l0 == last ? g_tsdf_out : dst_t, *gc = color ? (l0 == last ? g_color_out : dst_c) : nullptr;
+        if (fold) {
+            GS_HIP(hipMemsetAsync(ws, 0, w.fold_bytes, st), "gs_tsdf_integrate_backward_poses/zero");
+            hipLaunchKernelGGL(tsdf_bwd_k<false>, grid, dim3(TSDF_T), 0, st, vol, fr, weight_in, gt, gc, dst_t, dst_c, w.fold, lg);
+        }
+        hipLaunchKernelGGL(second, grid, dim3(TSDF_T), 0, st, vol, fr, weight_in, gt, gc, dst_t, dst_c, w.fold, lg, w.psum);
+        GS_LAUNCH_CHECK("gs_tsdf_integrate_backward_poses/fold");
+        if (fold) {
+            hipLaunchKernelGGL(tsdf_fold_finish_k, dim3(std::min(cdiv((int64_t)B * fr.Lc * HW, TSDF_T), 4096)), dim3(TSDF_T), 0, st, w.fold, lg,
+                               B, L, l0, fr.Lc, HW, g_depth, g_rgb);
+        }
+        hipLaunchKernelGGL(tsdf_pose_finish_k, dim3(fr.Lc, B), dim3(TSDF_POSE_T), 0, st, (const float *)w.psum, nblk, poses, L, l0, fr.Lc,
+                           g_poses);
+        GS_LAUNCH_CHECK("gs_tsdf_integrate_backward_poses/finish");
     }
     return GS_OK;
 }
@@ -737,6 +916,53 @@ int gs_tsdf_raycast_backward(const float *tsdf, const float *weight, const float
     GS_LAUNCH_CHECK("gs_tsdf_raycast_backward/fold");
     hipLaunchKernelGGL(tsdf_cast_finish_k, dim3(std::min(cdiv(total, TSDF_T), 65536)), dim3(TSDF_T), 0, st, fold, lg, total, g_tsdf, g_color);
     GS_LAUNCH_CHECK("gs_tsdf_raycast_backward/finish");
+    return GS_OK;
+}
+
+size_t gs_tsdf_raycast_backward_poses_ws_bytes(int B, int nx, int ny, int nz, int has_color, int L, int height, int width, int stride) {
+    if (!tsdf_vol_ok(B, nx, ny, nz) || L <= 0 || L > 65535 || height <= 0 || width <= 0 || stride < 1) return 0;
+    const int Ho = (int)(((int64_t)height + stride - 1) / stride), Wo = (int)(((int64_t)width + stride - 1) / stride);
+    if ((int64_t)cdiv(Ho, 16) * cdiv(Wo, 16) > TSDF_CAST_TILES) return 0;
+    return tsdf_cast_pose_layout(B, (int64_t)nx * ny * nz, has_color ? 4 : 1, L, cdiv(Ho, 16) * cdiv(Wo, 16), nullptr, nullptr, nullptr, nullptr);
+}
+
+int gs_tsdf_raycast_backward_poses(const float *tsdf, const float *weight, const float *color, int B, int nx, int ny, int nz,
+                                   float voxel_size, const float *origin, const float *intrinsics, const float *poses, int L, int height,
+                                   int width, int stride, float step, float min_weight, const int32_t *k_end, const float *g_depth,
+                                   const float *g_rgb, float *g_tsdf, float *g_color, float *g_poses, void *ws, size_t ws_bytes,
+                                   gs_stream_t stream) {
+    GS_REQUIRE(tsdf && weight && origin && intrinsics && poses && k_end && g_poses, "gs_tsdf_raycast_backward_poses: NULL argument");
+    GS_REQUIRE((!g_color || (color && g_tsdf)) && (!g_rgb || color),
+               "gs_tsdf_raycast_backward_poses: g_color needs color and g_tsdf, g_rgb needs color");
+    TSDF_REQUIRE_VOLUME("gs_tsdf_raycast_backward_poses");
+    TSDF_REQUIRE_CAST("gs_tsdf_raycast_backward_poses");
+    const size_t need = gs_tsdf_raycast_backward_poses_ws_bytes(B, nx, ny, nz, color != nullptr, L, height, width, stride);
+    if (!ws || ws_bytes < need) {
+        set_error("gs_tsdf_raycast_backward_poses: workspace too small (%zu < %zu)", ws_bytes, need);
+        return GS_ERR_WORKSPACE_TOO_SMALL;
+    }
+    hipStream_t st = (hipStream_t)stream;
+    const TsdfVol vol{nx, ny, nz, voxel_size, 0.0f, 0.0f, origin};
+    const TsdfCast cast{intrinsics, poses, L, Ho, Wo, stride, 0, step, 0.0f, 0.0f, min_weight};
+    const int tiles = cdiv(Ho, 16) * cdiv(Wo, 16);
+    Fold fold;
+    float *psum;
+    size_t fold_bytes;
+    tsdf_cast_pose_layout(B, tsdf_nvox(vol), color ? 4 : 1, L, tiles, ws, &fold, &psum, &fold_bytes);
+    const int lg = fold_lg(2 * (int64_t)L * Ho * Wo);
+    const int64_t total = (int64_t)B * tsdf_nvox(vol);
+    const dim3 grid(tiles, L, B);
+    if (g_tsdf) {  // as gs_tsdf_raycast_backward, with the pose sums on the second pass
+        GS_HIP(hipMemsetAsync(ws, 0, fold_bytes, st), "gs_tsdf_raycast_backward_poses/zero");
+        hipLaunchKernelGGL(tsdf_raycast_bwd_k<false>, grid, dim3(TSDF_T), 0, st, vol, cast, tsdf, weight, color, k_end, g_depth, g_rgb, fold, lg);
+    }
+    auto second = g_tsdf ? tsdf_raycast_bwd_k<true, true, true> : tsdf_raycast_bwd_k<true, true, false>;
+    hipLaunchKernelGGL(second, grid, dim3(TSDF_T), 0, st, vol, cast, tsdf, weight, color, k_end, g_depth, g_rgb, fold, lg, psum);
+    GS_LAUNCH_CHECK("gs_tsdf_raycast_backward_poses/fold");
+    if (g_tsdf)
+        hipLaunchKernelGGL(tsdf_cast_finish_k, dim3(std::min(cdiv(total, TSDF_T), 65536)), dim3(TSDF_T), 0, st, fold, lg, total, g_tsdf, g_color);
+    hipLaunchKernelGGL(tsdf_cast_pose_finish_k, dim3(L, B), dim3(TSDF_POSE_T), 0, st, (const float *)psum, tiles, g_poses);
+    GS_LAUNCH_CHECK("gs_tsdf_raycast_backward_poses/finish");
     return GS_OK;
 }
 

@@ -1444,9 +1444,36 @@ def tsdf_integrate_backward_raw(depth, K, poses, weight, origin, voxel_size, tru
     return o_t, o_c, g_depth, g_rgb
 
 
+def tsdf_integrate_backward_poses_raw(depth, K, poses, weight, origin, voxel_size, trunc, max_weight, g_tsdf, g_color=None,
+                                      want_state: bool = True, want_frames: bool = True):
+    """tsdf_integrate_backward_raw with the adjoint of the poses: -> (g_tsdf_in, g_color_in, g_depth, g_rgb, g_poses (B,L,4,4)).
+    The first four are tsdf_integrate_backward_raw's, bit for bit; `want_state=False` / `want_frames=False` leave (g_tsdf_in,
+    g_color_in) / (g_depth, g_rgb) out (None) and drop their share of the work.  g_poses is the adjoint of the unconstrained
+    matrix entries (render_map's convention; row 3 is zero): the update depends on a pose through the camera-frame depth of the
+    voxel centres alone, with the pixel of a voxel, the three skips, the t = 1 branch and the weight cap held constant.  Fixed
+    order fp32 sums, no atomics: the same bits from run to run.  Intrinsics, weights and origin receive no gradient."""
+    op = "tsdf_integrate_backward_poses"
+    g_t, w_in, g_c, origin, (nx, ny, nz), v = _tsdf_state(g_tsdf, weight, g_color, origin, voxel_size, op)
+    B = g_t.shape[0]
+    depth, _, K, poses, L, H, W = _tsdf_frames(depth, None, K, poses, B, False, op)
+    trunc, max_weight = _tsdf_positive(trunc, "trunc", op), _tsdf_positive(max_weight, "max_weight", op)
+    dev = g_t.device
+    o_t = torch.empty_like(g_t) if want_state else None
+    o_c = torch.empty_like(g_c) if want_state and g_c is not None else None
+    g_depth = torch.empty((B, L, H, W), dtype=torch.float32, device=dev) if want_frames else None
+    g_rgb = torch.empty((B, L, H, W, 3), dtype=torch.float32, device=dev) if want_frames and g_c is not None else None
+    g_poses = torch.empty((B, L, 4, 4), dtype=torch.float32, device=dev)
+    ws = workspace(ws_bytes("gs_tsdf_integrate_backward_poses_ws_bytes", B, L, H, W, nx, ny, nz, int(g_c is not None)), dev, "tsdf_bwd_poses")
+    call("gs_tsdf_integrate_backward_poses", ptr(depth), ptr(K), ptr(poses), B, L, H, W, nx, ny, nz, v, ptr(origin), trunc, max_weight,
+         ptr(w_in), ptr(g_t), ptr(g_c), ptr(o_t), ptr(o_c), ptr(g_depth), ptr(g_rgb), ptr(g_poses), ptr(ws), ws.numel(), stream())
+    return o_t, o_c, g_depth, g_rgb, g_poses
+
+
 class _TsdfIntegrateFn(torch.autograd.Function):
-    """(depth, rgb, tsdf, color | weight, K, poses, origin: constants) -> (tsdf', color', weight').  The pixel of a voxel, the three
-    skips, the t = 1 branch and the weight cap are constants of the graph; weight, poses and intrinsics receive None."""
+    """(depth, rgb, tsdf, color, poses | weight, K, origin: constants) -> (tsdf', color', weight').  The pixel of a voxel, the three
+    skips, the t = 1 branch and the weight cap are constants of the graph; weight, intrinsics and origin receive None.  The poses
+    receive their adjoint when they require one (tsdf_integrate_backward_poses_raw); otherwise the reverse pass is
+    tsdf_integrate_backward_raw's, as it was."""
 
     @staticmethod
     def forward(ctx, depth, rgb, tsdf, color, weight, K, poses, origin, voxel_size, trunc, max_weight):
@@ -1464,14 +1491,23 @@ class _TsdfIntegrateFn(torch.autograd.Function):
             g_t = torch.zeros_like(weight)
         if ctx.has_color and g_c is None:
             g_c = torch.zeros(tuple(weight.shape) + (3,), dtype=torch.float32, device=weight.device)
-        o_t, o_c, g_depth, g_rgb = tsdf_integrate_backward_raw(depth, K, poses, weight, origin, *ctx.cfg, g_t, g_c if ctx.has_color else None)
         need = ctx.needs_input_grad
+        g_c = g_c if ctx.has_color else None
+        g_poses = None
+        if need[6]:
+            o_t, o_c, g_depth, g_rgb, g_poses = tsdf_integrate_backward_poses_raw(
+                depth, K, poses, weight, origin, *ctx.cfg, g_t, g_c, want_state=need[2] or need[3], want_frames=need[0] or need[1])
+            g_poses = g_poses.view(poses.shape).to(poses.dtype)
+        else:
+            o_t, o_c, g_depth, g_rgb = tsdf_integrate_backward_raw(depth, K, poses, weight, origin, *ctx.cfg, g_t, g_c)
         return (g_depth.view(ctx.depth_shape) if need[0] else None, g_rgb if need[1] else None, o_t if need[2] else None,
-                o_c if need[3] else None, None, None, None, None, None, None, None)
+                o_c if need[3] else None, None, None, g_poses, None, None, None, None)
 
 
 def tsdf_integrate(depth, rgb, K, poses, tsdf, weight, color, origin, voxel_size, trunc, max_weight):
-    """Autograd-aware tsdf_integrate_raw -> (tsdf, weight, color): gradients reach the old tsdf / color, depth and rgb."""
+    """Autograd-aware tsdf_integrate_raw -> (tsdf, weight, color): gradients reach the old tsdf / color, depth, rgb and the poses
+    (the adjoint of the unconstrained matrix entries; computed only when the poses require it).  Intrinsics, weights and origin
+    are not differentiable."""
     origin = tsdf_origin(origin, tsdf.shape[0], tsdf.device, "tsdf_integrate") if torch.is_tensor(tsdf) and tsdf.ndim == 4 else origin
     t, c, w = _TsdfIntegrateFn.apply(depth, rgb, tsdf, color, weight, K, poses, origin, voxel_size, trunc, max_weight)
     return t, w, c
@@ -1665,12 +1701,9 @@ def tsdf_raycast_raw(tsdf, weight, color, origin, voxel_size, K, poses, height: 
     return depth, normal, rgb, k_end
 
 
-def tsdf_raycast_backward_raw(tsdf, weight, color, origin, voxel_size, K, poses, height: int, width: int, stride, step, min_weight,
-                              k_end, g_depth=None, g_rgb=None):
-    """Adjoint of tsdf_raycast_raw for the tape k_end (a constant): g_depth (B,L,Ho,Wo), g_rgb (B,L,Ho,Wo,3) (None: zero) ->
-    (g_tsdf, g_color or None), written in full.  Every voxel's sum over its pixels is exact and rounded once: the same bits from
-    run to run (one path, with or without torch.use_deterministic_algorithms).  Poses, intrinsics and weights get no gradient."""
-    op = "tsdf_raycast_backward"
+def _tsdf_cast_backward_args(op, tsdf, weight, color, origin, voxel_size, K, poses, height, width, stride, step, min_weight, k_end,
+                             g_depth, g_rgb):
+    """The checks the cast's two reverse passes share -> their arguments, checked and contiguous fp32."""
     t, w, c, origin, dims, v = _tsdf_state(tsdf, weight, color, origin, voxel_size, op)
     B, dev = t.shape[0], t.device
     K, poses, L, height, width, stride, step, mw = _tsdf_cast(K, poses, B, dims, v, height, width, stride, step, min_weight, op)
@@ -1684,17 +1717,53 @@ def tsdf_raycast_backward_raw(tsdf, weight, color, origin, voxel_size, K, poses,
         raise ValueError("{}: g_depth should have shape {}. Got {}.".format(op, (B, L, Ho, Wo), tuple(g_depth.shape)))
     if g_rgb is not None and (c is None or tuple(g_rgb.shape) != (B, L, Ho, Wo, 3)):
         raise ValueError("{}: g_rgb needs a volume with colours and the shape {}. Got {}.".format(op, (B, L, Ho, Wo, 3), tuple(g_rgb.shape)))
+    return t, w, c, origin, dims, v, K, poses, L, height, width, stride, step, mw, k_end.contiguous(), _f32c(g_depth), _f32c(g_rgb)
+
+
+def tsdf_raycast_backward_raw(tsdf, weight, color, origin, voxel_size, K, poses, height: int, width: int, stride, step, min_weight,
+                              k_end, g_depth=None, g_rgb=None):
+    """Adjoint of tsdf_raycast_raw for the tape k_end (a constant): g_depth (B,L,Ho,Wo), g_rgb (B,L,Ho,Wo,3) (None: zero) ->
+    (g_tsdf, g_color or None), written in full.  Every voxel's sum over its pixels is exact and rounded once: the same bits from
+    run to run (one path, with or without torch.use_deterministic_algorithms).  Poses, intrinsics and weights get no gradient."""
+    t, w, c, origin, dims, v, K, poses, L, height, width, stride, step, mw, k_end, g_depth, g_rgb = _tsdf_cast_backward_args(
+        "tsdf_raycast_backward", tsdf, weight, color, origin, voxel_size, K, poses, height, width, stride, step, min_weight, k_end, g_depth,
+        g_rgb)
+    B, dev = t.shape[0], t.device
     g_tsdf = torch.empty_like(t)
     g_color = None if c is None else torch.empty_like(c)
     ws = workspace(ws_bytes("gs_tsdf_raycast_backward_ws_bytes", B, *dims, int(c is not None)), dev, "tsdf_cast_bwd")
     call("gs_tsdf_raycast_backward", ptr(t), ptr(w), ptr(c), B, *dims, v, ptr(origin), ptr(K), ptr(poses), L, height, width, stride, step,
-         mw, ptr(k_end.contiguous()), ptr(_f32c(g_depth)), ptr(_f32c(g_rgb)), ptr(g_tsdf), ptr(g_color), ptr(ws), ws.numel(), stream())
+         mw, ptr(k_end), ptr(g_depth), ptr(g_rgb), ptr(g_tsdf), ptr(g_color), ptr(ws), ws.numel(), stream())
     return g_tsdf, g_color
 
 
+def tsdf_raycast_backward_poses_raw(tsdf, weight, color, origin, voxel_size, K, poses, height: int, width: int, stride, step, min_weight,
+                                    k_end, g_depth=None, g_rgb=None, want_volume: bool = True):
+    """tsdf_raycast_backward_raw with the adjoint of the poses: -> (g_tsdf, g_color or None, g_poses (B,L,4,4)).  The first two are
+    tsdf_raycast_backward_raw's, bit for bit; `want_volume=False` leaves them out (None) and drops their share of the work.
+    g_poses is the adjoint of the unconstrained matrix entries (render_map's convention; row 3 is zero; zeros for a camera
+    without hits), with which sample ends a ray, whether it hits and the cells of its three positions held constant.  Fixed
+    order fp32 sums, no atomics: the same bits from run to run.  Intrinsics, weights, origin and the normal image receive no
+    gradient."""
+    t, w, c, origin, dims, v, K, poses, L, height, width, stride, step, mw, k_end, g_depth, g_rgb = _tsdf_cast_backward_args(
+        "tsdf_raycast_backward_poses", tsdf, weight, color, origin, voxel_size, K, poses, height, width, stride, step, min_weight, k_end,
+        g_depth, g_rgb)
+    B, dev = t.shape[0], t.device
+    g_tsdf = torch.empty_like(t) if want_volume else None
+    g_color = torch.empty_like(c) if want_volume and c is not None else None
+    g_poses = torch.empty((B, L, 4, 4), dtype=torch.float32, device=dev)
+    ws = workspace(ws_bytes("gs_tsdf_raycast_backward_poses_ws_bytes", B, *dims, int(c is not None), L, height, width, stride), dev,
+                   "tsdf_cast_bwd_poses")
+    call("gs_tsdf_raycast_backward_poses", ptr(t), ptr(w), ptr(c), B, *dims, v, ptr(origin), ptr(K), ptr(poses), L, height, width, stride,
+         step, mw, ptr(k_end), ptr(g_depth), ptr(g_rgb), ptr(g_tsdf), ptr(g_color), ptr(g_poses), ptr(ws), ws.numel(), stream())
+    return g_tsdf, g_color, g_poses
+
+
 class _TsdfRaycastFn(torch.autograd.Function):
-    """(tsdf, color | weight, origin, K, poses: constants) -> (depth, normal, rgb, k_end).  Which sample ends a ray and whether it
-    hits are constants of the graph; normals carry no gradient; poses, intrinsics and weights receive None."""
+    """(tsdf, color, poses | weight, origin, K: constants) -> (depth, normal, rgb, k_end).  Which sample ends a ray and whether it
+    hits are constants of the graph; normals carry no gradient; intrinsics, weights and origin receive None.  The poses receive
+    their adjoint when they require one (tsdf_raycast_backward_poses_raw); otherwise the reverse pass is
+    tsdf_raycast_backward_raw's, as it was."""
 
     @staticmethod
     def forward(ctx, tsdf, color, weight, origin, voxel_size, K, poses, height, width, stride, step, near, far, min_weight):
@@ -1709,15 +1778,25 @@ class _TsdfRaycastFn(torch.autograd.Function):
     def backward(ctx, g_depth, _g_normal, g_rgb, _g_k):
         tsdf, color, weight, origin, K, poses, k_end = ctx.saved_tensors
         voxel_size, height, width, stride, step, min_weight = ctx.cfg
-        g_tsdf, g_color = tsdf_raycast_backward_raw(tsdf, weight, color, origin, voxel_size, K, poses, height, width, stride, step,
-                                                    min_weight, k_end, g_depth, g_rgb if color is not None else None)
         need = ctx.needs_input_grad
-        return (g_tsdf if need[0] else None, g_color if need[1] else None) + (None,) * 12
+        g_rgb = g_rgb if color is not None else None
+        g_poses = None
+        if need[6]:
+            g_tsdf, g_color, g_poses = tsdf_raycast_backward_poses_raw(tsdf, weight, color, origin, voxel_size, K, poses, height, width,
+                                                                       stride, step, min_weight, k_end, g_depth, g_rgb,
+                                                                       want_volume=need[0] or need[1])
+            g_poses = g_poses.view(poses.shape).to(poses.dtype)
+        else:
+            g_tsdf, g_color = tsdf_raycast_backward_raw(tsdf, weight, color, origin, voxel_size, K, poses, height, width, stride, step,
+                                                        min_weight, k_end, g_depth, g_rgb)
+        return (g_tsdf if need[0] else None, g_color if need[1] else None, None, None, None, None, g_poses) + (None,) * 7
 
 
 def tsdf_raycast(tsdf, weight, color, origin, voxel_size, K, poses, height: int, width: int, stride: int, step: float,
                  near: float = 0.0, far: float = float("inf"), min_weight: float = 1.0):
-    """Autograd-aware tsdf_raycast_raw, one node: gradients of depth and rgb reach tsdf and color."""
+    """Autograd-aware tsdf_raycast_raw, one node: gradients of depth and rgb reach tsdf, color and the poses (the adjoint of the
+    unconstrained matrix entries; computed only when the poses require it).  Intrinsics, weights, origin and the normal image are
+    not differentiable."""
     if torch.is_tensor(tsdf) and tsdf.ndim == 4:
         origin = tsdf_origin(origin, tsdf.shape[0], tsdf.device, "tsdf_raycast")
     return _TsdfRaycastFn.apply(tsdf, color, weight, origin, voxel_size, K, poses, height, width, stride, step, near, far, min_weight)

@@ -27,7 +27,11 @@ class KinectFusion(nn.Module):
 
     and the frame is integrated under pose_s.  Frame 0 takes `frames.poses[:, 0]` if given, else the identity.  With
     `odom="gt"` the frames' poses are used.  Under autograd every piece is a node of its own: gradients reach the depths and
-    colours through raycast, ICP and integrate (not the poses given, nor the intrinsics).  The volume should hold what the
+    colours through raycast, ICP and integrate (never the intrinsics).  With `pose_gradients=False` (the default) the volume
+    takes its poses as constants: raycast, raycast_pointcloud and integrate are handed detached copies, while the frames'
+    poses and the returned poses stay attached, so a gradient reaches an earlier frame through the tsdf values alone.  With
+    `pose_gradients=True` they are handed over attached and the chain pose_{s-1} -> raycast -> ICP -> pose_s -> integrate ->
+    volume -> raycast .. is whole: a gradient also flows through where each frame was put.  The volume should hold what the
     cameras see (or `dist_thresh` be set): ICP pairs every frame point with its nearest cast point, and frame points beyond the
     volume pair with the rim of the cast surface.
 
@@ -38,14 +42,15 @@ class KinectFusion(nn.Module):
         pose_s = compose_transformations(odomprov.provide(target, live frame), pose_{s-1})
 
     at full resolution (`dsratio` and `dist_thresh` are not used).  It has no reverse pass: under autograd with inputs that
-    require gradients `provide` raises NotImplementedError.  A camera that sees nothing of the volume, or a frame without valid
+    require gradients `provide` raises NotImplementedError, whatever `pose_gradients` says.  A camera that sees nothing of the volume, or a frame without valid
     pixels, leaves the pose where it was and sets the status bit in `odomprov.last_info` (nothing synchronises the host)."""
 
     def __init__(self, *, dims, voxel_size, origin=(0.0, 0.0, 0.0), trunc=None, max_weight: float = 128.0, color: bool = True,
                  odom: str = "gradicp", dsratio: int = 4, numiters: int = 20, damp: float = 1e-8,
                  dist_thresh: Union[float, int, None] = None, lambda_max: Union[float, int] = 2.0, B: Union[float, int] = 1.0,
                  B2: Union[float, int] = 1.0, nu: Union[float, int] = 200.0, step: Optional[float] = None, min_weight: float = 1.0,
-                 device: Union[torch.device, str, None] = None, levels: int = 3, lambda_geo: float = 0.968):
+                 device: Union[torch.device, str, None] = None, levels: int = 3, lambda_geo: float = 0.968,
+                 pose_gradients: bool = False):
         super().__init__()
         if odom not in ["gt", "icp", "gradicp", "rgbd"]:
             msg = "odometry method ({}) not supported for KinectFusion. ".format(odom)
@@ -55,6 +60,8 @@ class KinectFusion(nn.Module):
             raise ValueError("KinectFusion: odom='rgbd' tracks against the colours of the volume and needs color=True.")
         if not isinstance(dsratio, int) or isinstance(dsratio, bool) or dsratio < 1:
             raise ValueError("KinectFusion: dsratio should be a positive integer. Got {!r}.".format(dsratio))
+        if not isinstance(pose_gradients, bool):
+            raise TypeError("KinectFusion: pose_gradients should be a bool. Got {!r}.".format(pose_gradients))
         odomprov = None
         if odom == "icp":
             odomprov = ICPOdometryProvider(numiters, damp, dist_thresh)
@@ -67,6 +74,7 @@ class KinectFusion(nn.Module):
         self.dsratio = dsratio
         self.step_size = step
         self.min_weight = min_weight
+        self.pose_gradients = pose_gradients
         self.volume_args = dict(dims=dims, voxel_size=voxel_size, origin=origin, trunc=trunc, max_weight=max_weight, color=color)
         self.device = torch.device(device) if device is not None else torch.device("cuda")
 
@@ -102,7 +110,15 @@ class KinectFusion(nn.Module):
         if not isinstance(live_frame, RGBDImages):
             raise TypeError("Expected live_frame to be of type gradslam.RGBDImages. Got {0}.".format(type(live_frame)))
         live_frame.poses = self._localize(volume, live_frame, prev_frame, where)
-        return volume.integrate(live_frame), live_frame.poses
+        fused = live_frame
+        if not self.pose_gradients and live_frame.poses.requires_grad:  # the volume takes the pose as a constant
+            fused = RGBDImages(live_frame.rgb_image, live_frame.depth_image, live_frame.intrinsics, live_frame.poses.detach(),
+                               channels_first=live_frame.channels_first)
+        return volume.integrate(fused), live_frame.poses
+
+    def _volume_poses(self, poses):
+        """The poses as the volume's raycast receives them: attached only with pose_gradients=True."""
+        return poses if self.pose_gradients else poses.detach()
 
     def _localize(self, volume: TSDFVolume, live_frame: RGBDImages, prev_frame: Optional[RGBDImages], where: str = ""):
         if not isinstance(prev_frame, (RGBDImages, type(None))):
@@ -125,14 +141,15 @@ class KinectFusion(nn.Module):
             live_frame = live_frame.to_channels_last()
         H, W = live_frame.shape[2:4]
         if self.odom == "rgbd":
-            cast = volume.raycast(live_frame.intrinsics, prev_frame.poses, H, W, step=self.step_size, min_weight=self.min_weight)
+            cast = volume.raycast(live_frame.intrinsics, self._volume_poses(prev_frame.poses), H, W, step=self.step_size,
+                                  min_weight=self.min_weight)
             # (both frames carry the live frame's intrinsics tensor: the cast's own is a copy of it)
             target = RGBDImages(cast.rgb_image, cast.depth_image, live_frame.intrinsics, prev_frame.poses)
             source = RGBDImages(live_frame.rgb_image, live_frame.depth_image, live_frame.intrinsics, prev_frame.poses)
             transform = self.odomprov.provide(target, source)
             return compose_transformations(transform.squeeze(1), prev_frame.poses.squeeze(1)).unsqueeze(1)
-        target = volume.raycast_pointcloud(live_frame.intrinsics, prev_frame.poses, H, W, stride=self.dsratio, step=self.step_size,
-                                           min_weight=self.min_weight)
+        target = volume.raycast_pointcloud(live_frame.intrinsics, self._volume_poses(prev_frame.poses), H, W, stride=self.dsratio,
+                                           step=self.step_size, min_weight=self.min_weight)
         # the frame under the previous pose, as a frame of its own: the caller's keeps its poses until the step has succeeded
         source = downsample_rgbdimages(RGBDImages(live_frame.rgb_image, live_frame.depth_image, live_frame.intrinsics, prev_frame.poses),
                                        self.dsratio)

@@ -77,7 +77,9 @@ class TSDFVolume(object):
 
         Exactly what integrating the frames one at a time gives.  Returns a NEW TSDFVolume, or this one updated with
         `inplace=True` (when a gradient is being recorded the state is written to fresh tensors either way).  Differentiable
-        w.r.t. the depth and rgb images and the previous tsdf / color; not w.r.t. the poses and intrinsics."""
+        w.r.t. the depth and rgb images, the previous tsdf / color and the poses (through the camera-frame depth of the voxel
+        centres; the pixel a voxel falls on, the skips and the weight cap are constants of the graph; the pose adjoint is
+        computed only when `rgbdimages.poses` requires a gradient); not w.r.t. the intrinsics and the weights."""
         if not isinstance(rgbdimages, RGBDImages):
             raise TypeError("Expected rgbdimages to be of type gradslam.RGBDImages. Got {}.".format(type(rgbdimages)))
         if not rgbdimages.has_poses:
@@ -87,7 +89,8 @@ class TSDFVolume(object):
         depth, rgb = rgbdimages._cl(rgbdimages.depth_image), rgbdimages._cl(rgbdimages.rgb_image)
         args = (depth, rgb if self.has_colors else None, rgbdimages.intrinsics, rgbdimages.poses)
         cfg = (self.origin, self.voxel_size, self.trunc, self.max_weight)
-        grad = torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (depth, rgb, self.tsdf, self.color))
+        grad = torch.is_grad_enabled() and any(t is not None and t.requires_grad
+                                               for t in (depth, rgb, self.tsdf, self.color, rgbdimages.poses))
         if grad:
             tsdf, weight, color = ops.tsdf_integrate(*args, self.tsdf, self.weight, self.color, *cfg)
         else:
@@ -165,7 +168,7 @@ class TSDFVolume(object):
         far = float("inf") if far is None else far
         state = (self.tsdf, self.weight, self.color, self.origin, self.voxel_size, intrinsics, poses, height, width, stride, step, near,
                  far, min_weight)
-        if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (self.tsdf, self.color)):
+        if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (self.tsdf, self.color, poses)):
             return ops.tsdf_raycast(*state)
         return ops.tsdf_raycast_raw(*state)
 
@@ -180,8 +183,10 @@ class TSDFVolume(object):
         0 on a miss) and colour (zero for a volume without colours) with the given poses and the intrinsics of the strided grid
         (fx, fy, cx, cy divided by stride), so that its vertex maps are the hit points.  `return_normals=True` also returns the
         (B, L, Ho, Wo, 3) image of global normals (the gradient of the interpolant, pointing into free space; 0 on a miss).
-        Differentiable w.r.t. tsdf and color (which sample ends a ray is a constant of the graph; normals carry no gradient);
-        not w.r.t. the poses, the intrinsics and the weights.  No host synchronisation."""
+        Differentiable w.r.t. tsdf, color and the poses (which sample ends a ray, whether it hits and the cells of its samples
+        are constants of the graph; normals carry no gradient); not w.r.t. the intrinsics and the weights.  Poses that require
+        a gradient stay attached to the returned frames, so their global vertex map carries the pose gradient too; poses that
+        do not are detached copies, as before.  No host synchronisation."""
         depth, normal, rgb, _ = self._cast(intrinsics, poses, height, width, stride, step, near, far, min_weight)
         if rgb is None:
             rgb = torch.zeros(tuple(depth.shape) + (3,), dtype=torch.float32, device=depth.device)
@@ -190,14 +195,16 @@ class TSDFVolume(object):
         K[..., 1, 1] /= stride
         K[..., 0, 2] /= stride
         K[..., 1, 2] /= stride
-        frames = RGBDImages(rgb, depth.unsqueeze(-1), K, poses.detach().to(torch.float32))
+        attached = torch.is_grad_enabled() and poses.requires_grad
+        frames = RGBDImages(rgb, depth.unsqueeze(-1), K, (poses if attached else poses.detach()).to(torch.float32))
         return (frames, normal) if return_normals else frames
 
     def raycast_pointcloud(self, intrinsics, poses, height: int, width: int, *, stride: int = 1, step: Optional[float] = None,
                            near: float = 0.0, far: Optional[float] = None, min_weight: float = 1.0) -> Pointclouds:
         r"""The hit pixels of `raycast` from ONE camera per batch element (poses (B, 1, 4, 4)) as a Pointclouds, in pixel order:
         global points (the global vertex map of the cast image), normals and, for a volume with colours, colours.
-        Differentiable w.r.t. tsdf and color, through the depth.  One host synchronisation (the sizes)."""
+        Differentiable w.r.t. tsdf and color, through the depth, and w.r.t. poses that require a gradient, through the depth
+        and through the vertex map.  One host synchronisation (the sizes)."""
         if torch.is_tensor(poses) and poses.ndim == 4 and poses.shape[1] != 1:
             raise ValueError("TSDFVolume.raycast_pointcloud: one camera per batch element (L = 1). Got poses {}.".format(tuple(poses.shape)))
         frames, normal = self.raycast(intrinsics, poses, height, width, stride=stride, step=step, near=near, far=far,

@@ -763,6 +763,26 @@ int gs_tsdf_integrate_backward(const float *depth, const float *intrinsics, cons
                                const float *g_color_out, float *g_tsdf_in, float *g_color_in, float *g_depth,
                                float *g_rgb, void *ws, size_t ws_bytes, gs_stream_t stream);
 
+/* The same reverse pass with the adjoint of the poses.  The frame's update depends on the pose through z = sum_j R[j][2] (c_j - t_j)
+ * alone (sdf = d - z), with the same constants of the graph; with gd = (g_t / trunc iff sdf < trunc, else 0), what depth[b,l,h,w]
+ * receives from the voxel, dL/dz = -gd, and per camera, over the voxels the frame updates, S0 = sum gd, S_j = sum gd (c_j - t_j):
+ *   g_poses[b,l][j][2] = -S_j,   g_poses[b,l][j][3] = R[j][2] S0,   every other entry 0 (row 3 included)
+ * -- the adjoint of the unconstrained matrix entries, gs_render_map_backward's convention.  g_poses (B,L,4,4) is written in full.
+ * The four other outputs are gs_tsdf_integrate_backward's, bit for bit; each may be NULL (g_color_in and g_rgb need g_color_out),
+ * and what nobody asks for is not computed (without g_depth and g_rgb a chunk is two launches).  The sums are plain fp32 in one
+ * fixed order, no atomics: terms gd, gd (c_j - t_j) (a rounded difference, a rounded product); per block of 256 consecutive voxels
+ * the 64-lane butterfly (offsets 32, 16, .. 1), then the 4 waves in ascending order; the blocks' rows r, r + 64, .. in ascending
+ * order onto +0 for r = 0 .. 63, then those 64 in ascending order.  The same bits from run to run.
+ * Workspace, every piece rounded up to 256 bytes, with P = B min(L, 32) H W and N = B nx ny nz:  gs_tsdf_integrate_backward's |
+ * 16 B B min(L, 32) ceil(nx ny nz / 256) (the blocks' rows) | iff L > 32: 4 B N, and with has_color 12 B N (the adjoints carried
+ * from chunk to chunk when g_tsdf_in / g_color_in are NULL). */
+size_t gs_tsdf_integrate_backward_poses_ws_bytes(int B, int L, int H, int W, int nx, int ny, int nz, int has_color);
+int gs_tsdf_integrate_backward_poses(const float *depth, const float *intrinsics, const float *poses, int B, int L, int H,
+                                     int W, int nx, int ny, int nz, float voxel_size, const float *origin, float trunc,
+                                     float max_weight, const float *weight_in, const float *g_tsdf_out,
+                                     const float *g_color_out, float *g_tsdf_in, float *g_color_in, float *g_depth,
+                                     float *g_rgb, float *g_poses, void *ws, size_t ws_bytes, gs_stream_t stream);
+
 /* Surface extraction.  A voxel is observed iff weight >= min_weight.  Edge slot e = 3 j + a runs from voxel j to its +1
  * neighbour j+ along axis a (0: x, 1: y, 2: z) and exists iff that neighbour is inside the grid; it carries a point iff both
  * ends are observed and (f0 < 0) != (f1 < 0), f0 = tsdf[j], f1 = tsdf[j+].  Then s = f0 / (f0 - f1); the point is the centre of
@@ -834,6 +854,27 @@ int gs_tsdf_raycast_backward(const float *tsdf, const float *weight, const float
                              int height, int width, int stride, float step, float min_weight, const int32_t *k_end,
                              const float *g_depth, const float *g_rgb, float *g_tsdf, float *g_color, void *ws,
                              size_t ws_bytes, gs_stream_t stream);
+
+/* The same reverse pass with the adjoint of the poses.  Constants of the graph as above: which sample ends a ray, whether it
+ * hits, the cells of p0 = p(z_{k-1}), p1 = p(z_k) and p*; dz and z_k do not depend on the pose and p = t + z R d with
+ * d = (dx, dy, 1).  Per hit pixel, with a0 = g_z dz (-f) / (f_prev - f)^2, a1 = g_z dz f_prev / (f_prev - f)^2 and grad the
+ * gradient of the interpolant in voxel units:
+ *   u0 = a0 (grad F(p0) / v),  u1 = a1 (grad F(p1) / v),  w = sum_ch g_rgb_ch (grad C_ch(p*) / v)   (zero without colours)
+ *   g_poses[b,l][i][3] = sum_pix (u0 + u1) + w,     g_poses[b,l][i][j] = sum_pix ((z_{k-1} u0 + z_k u1) + z* w)_i d_j,   row 3 zero
+ * -- the adjoint of the unconstrained matrix entries.  g_poses (B,L,4,4) is written in full (zeros for a camera without hits).
+ * g_tsdf and g_color are gs_tsdf_raycast_backward's, bit for bit, and may be NULL (g_color needs color and g_tsdf; without
+ * g_tsdf the call is two launches).  The twelve sums are plain fp32 in one fixed order, no atomics: per block of 16 x 16 output
+ * pixels the 64-lane butterfly of each 8x8 tile (offsets 32, 16, .. 1), then the 4 waves in ascending order; the blocks' rows
+ * r, r + 64, .. in ascending order onto +0 for r = 0 .. 63, then those 64 in ascending order.  The same bits from run to run.
+ * Workspace, every piece rounded up to 256 bytes:  gs_tsdf_raycast_backward's | 48 B B L ceil(Ho / 16) ceil(Wo / 16) (the
+ * blocks' rows). */
+size_t gs_tsdf_raycast_backward_poses_ws_bytes(int B, int nx, int ny, int nz, int has_color, int L, int height, int width,
+                                               int stride);
+int gs_tsdf_raycast_backward_poses(const float *tsdf, const float *weight, const float *color, int B, int nx, int ny, int nz,
+                                   float voxel_size, const float *origin, const float *intrinsics, const float *poses, int L,
+                                   int height, int width, int stride, float step, float min_weight, const int32_t *k_end,
+                                   const float *g_depth, const float *g_rgb, float *g_tsdf, float *g_color, float *g_poses,
+                                   void *ws, size_t ws_bytes, gs_stream_t stream);
 
 /* Triangle meshes (marching cubes over the rows of gs_tsdf_extract).  A cube is the 8 voxels whose lowest corner is voxel j
  * (corner c = dx + 2 dy + 4 dz); it emits iff all 8 corners are observed (weight >= min_weight); its case has bit c set iff

@@ -139,7 +139,9 @@ int gs_project_active(const float *points, const int32_t *counts, int B, int Nma
 
 /* S: downsample_pointclouds' gather (odometry/icputils.py:600-619): for batch element b, gather
  * attribute rows `attr[b, n]` for every table row with row.b == b, order preserved, into a padded
- * (B, cap, C) output; counts[b] = rows written.  n_rows is read from d_n_rows (device). */
+ * (B, cap, C) output; counts[b] = rows written.  n_rows is read from d_n_rows (device).
+ * A batch element with more than cap rows: the first cap are written, nothing beyond, and counts[b] still states
+ * ALL its rows (it is not clamped to cap; consumers take min(counts[b], cap)). */
 size_t gs_gather_table_rows_ws_bytes(int B);
 int gs_gather_table_rows(const int64_t *rows, const int32_t *d_n_rows, int64_t max_rows,
                          const float *attr, int B, int Nmax, int C, int cap, float *out,
@@ -162,7 +164,10 @@ int gs_bucket_by_pixel(const int64_t *rows, const int32_t *d_n_rows, int64_t max
  * gs_icp_point_to_plane needs of its target -- tgt / tgt_normals (B,cap,3) and counts (B) in the reference's
  * order, plus the search hints.  tgt_index (B,cap; optional, NULL to skip) receives the map index n of every
  * target slot (what the reverse pass scatters the target adjoints back with), tgt_pix (B,cap; optional) its
- * ds-grid pixel (gs_icp_hints.tgt_pix). */
+ * ds-grid pixel (gs_icp_hints.tgt_pix).
+ * A batch element with more than cap rows (both entry points): slots below cap are written, nothing at or beyond cap;
+ * counts[b] and pix_start still state ALL its rows (neither is clamped to cap), and scan_orig below cap may then name
+ * a rank >= cap. */
 size_t gs_build_icp_target_ws_bytes(int B, int H, int W, int ds);
 int gs_build_icp_target(const int64_t *rows, const int32_t *d_n_rows, int64_t max_rows, int B, int H,
                         int W, int ds, const float *map_points, const float *map_normals, int Nmax,

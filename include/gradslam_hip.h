@@ -80,7 +80,12 @@ int gs_get_alpha_backward(const float *points, int64_t n, float sigma, float eps
  * What the reference's dataset loaders do per frame on the host (datasets/tum.py:346, :455-499; icl.py:387;
  * scannet.py:189), done on the device from the raw integer frames so that 5 instead of 16 bytes per pixel
  * cross PCIe: depth (B,Hd,Wd) = uint16 (B,Hs,Ws) / depth_scale, nearest-neighbour resize; rgb (B,Hd,Wd,3) =
- * uint8 (B,Hs,Ws,3), bilinear resize (pixel centres at +0.5), optionally / 255.  Either input may be NULL. */
+ * uint8 (B,Hs,Ws,3), bilinear resize (pixel centres at +0.5), optionally / 255.  Either input may be NULL.
+ * The arithmetic is float64, rounded once: depth is float32(float64(u16) / depth_scale) at source pixel
+ * floor(y * (Hs / Hd)), clamped; colour is the float32 nearest the float64 bilinear value, and a same-size frame keeps
+ * its values exactly (before the optional / 255).  depth_scale is taken as `float`: a scale that float32 cannot represent is rounded before the division
+ * (5000, 1000 and 1 are exact).  B == 0, depth_scale <= 0 with depth given, an input whose output is NULL and two NULL
+ * inputs are GS_ERR_INVALID_ARG. */
 int gs_frames_from_raw(const uint16_t *depth_raw, const uint8_t *rgb_raw, int B, int Hs, int Ws, int Hd,
                        int Wd, float depth_scale, int normalise_color, float *depth, float *rgb,
                        gs_stream_t stream);
@@ -95,7 +100,9 @@ int gs_compact_rows(const float *src, const uint8_t *mask, int64_t n_rows, int r
 
 /* Same, for up to 4 row arrays sharing one mask and one scan (h_src / h_row_floats / h_out are HOST
  * arrays of n_arrays device pointers / widths): the append of fuse_with_map compacts vertex, normal,
- * colour and alpha rows of the new pixels in one go (slam/fusionutils.py:710-713). */
+ * colour and alpha rows of the new pixels in one go (slam/fusionutils.py:710-713).  Rows are moved as 32-bit
+ * words (any bit pattern survives); rows of h_out[a] at and beyond *out_count are not written.  n_arrays outside
+ * 1..4 or a NULL member is GS_ERR_INVALID_ARG; n_rows == 0 gives *out_count = 0. */
 int gs_compact_multi(int n_arrays, const float *const *h_src, const int *h_row_floats,
                      float *const *h_out, const uint8_t *mask, int64_t n_rows, int32_t *out_count,
                      void *ws, size_t ws_bytes, gs_stream_t stream);
@@ -108,7 +115,9 @@ int gs_append_rows(int n_arrays, const float *const *h_src, const int *h_row_flo
                    const uint8_t *mask, int64_t n_rows, int32_t *d_count, int cap, int32_t *d_appended,
                    int32_t *d_overflow, void *ws, size_t ws_bytes, gs_stream_t stream);
 /* Adjoint of gs_compact_multi (what autograd does for x[mask] in the reference): h_out[a] (n_rows, w_a)
- * receives the compacted adjoint row of every selected row and zeros everywhere else. */
+ * receives the compacted adjoint row of every selected row and zeros everywhere else: every one of the n_rows rows is
+ * WRITTEN (the caller need not clear h_out), rejected rows with the word +0.0.  With an empty selection h_grad[a] is
+ * never read, but must still be non-NULL. */
 int gs_expand_multi(int n_arrays, const float *const *h_grad, const int *h_row_floats,
                     float *const *h_out, const uint8_t *mask, int64_t n_rows, void *ws, size_t ws_bytes,
                     gs_stream_t stream);
@@ -117,7 +126,10 @@ int gs_expand_multi(int n_arrays, const float *const *h_grad, const int *h_row_f
  * downsample_rgbdimages (odometry/icputils.py:651-669): [::ds, ::ds] sub-grid of the global
  * vertex / normal maps and the rgb image of ONE frame per batch element (L == 1), valid-depth
  * pixels only, row-major order.  Outputs are padded (B, cap, 3) with cap >= ceil(H/ds)*ceil(W/ds);
- * counts[b] receives the number of rows written for batch b.  Any of the three outputs may be NULL. */
+ * counts[b] receives the number of rows written for batch b.  Any of the three outputs may be NULL.
+ * A pixel is valid iff depth > 0 (strict; NaN is rejected, +inf and subnormals are kept); H and W need not be multiples
+ * of ds.  Rows at and beyond counts[b] are not written; an output requested without its source map, or cap below the
+ * grid size, is GS_ERR_INVALID_ARG. */
 size_t gs_downsample_frame_ws_bytes(int H, int W, int ds);
 int gs_downsample_frame(const float *depth, const float *gvertex, const float *gnormal,
                         const float *rgb, int B, int H, int W, int ds, int cap, float *out_points,
@@ -193,7 +205,9 @@ int gs_knn1(const float *src, const int32_t *d_ns, int max_ns, const float *tgt,
             gs_stream_t stream);
 int gs_knn1_bruteforce(const float *src, const int32_t *d_ns, int max_ns, const float *tgt,
                        const int32_t *d_nt, int max_nt, uint64_t *best, gs_stream_t stream);
-/* unpack to the reference's output types: dist2 fp32 (ns), idx int64 (ns) */
+/* unpack to the reference's output types: dist2 fp32 (ns), idx int64 (ns): the key's upper word reinterpreted and its
+ * lower word zero-extended (a row without a target, key ~0, gives a NaN and 0xffffffff).  Either output may be NULL;
+ * rows at and beyond *d_ns are neither read nor written. */
 int gs_knn1_unpack(const uint64_t *best, const int32_t *d_ns, int max_ns, float *dist2,
                    int64_t *idx, gs_stream_t stream);
 
@@ -205,20 +219,27 @@ int gs_knn1_unpack(const uint64_t *best, const int32_t *d_ns, int max_ns, float 
  * a = [n ; s x n], b = n.(d - s), over rows with dist2 < dist_thresh (dist_thresh < 0: all rows;
  * NB the reference compares the threshold with the SQUARED distance).
  * out: 44 floats = H (36, row-major) | g (6) | e | cnt (as float).  Deterministic (fixed-order
- * two-level reduction, no float atomics). */
+ * two-level reduction, no float atomics).
+ * Contract of this entry point, gs_icp_rows and both backward forms: the threshold is the STRICT d2 < dist_thresh on the
+ * squared distance the key carries (a row exactly on it is rejected; dist_thresh == 0 keeps nothing); a row whose key
+ * is ~0 (no target: what gs_knn1 writes for an empty target) is invalid; rows at and beyond *d_ns (<= max_ns) are
+ * neither read nor written.  max_ns == 0 is accepted: 44 zeros here, nothing written by the other three. */
 size_t gs_icp_linearize_ws_bytes(int max_ns);
 int gs_icp_linearize(const float *src, const int32_t *d_ns, int max_ns, const float *tgt,
                      const float *tgt_normals, const uint64_t *best, float dist_thresh,
                      float *out44, void *ws, size_t ws_bytes, gs_stream_t stream);
 
 /* Rows form of the same algebra for API parity with gauss_newton_solve: A (ns,6), b (ns), and a
- * keep mask (ns) u8; callers compact with gs_compact_rows. */
+ * keep mask (ns) u8; callers compact with gs_compact_rows.  Rejected rows below *d_ns get keep = 0 and +0.0 in A and
+ * b; kept rows are float32 elementwise arithmetic (each product and difference rounded on its own). */
 int gs_icp_rows(const float *src, const int32_t *d_ns, int max_ns, const float *tgt,
                 const float *tgt_normals, const uint64_t *best, float dist_thresh, float *A,
                 float *b, uint8_t *keep, gs_stream_t stream);
 
 /* Adjoint of gs_icp_linearize: given d/dH (36), d/dg (6), d/de (1) in g_out43, accumulate
- * d/dsrc (ns,3) (plain stores) and d/dtgt, d/dnormals (nt,3) (atomic scatter-add; zero-init). */
+ * d/dsrc (ns,3) (plain stores) and d/dtgt, d/dnormals (nt,3) (atomic scatter-add; zero-init).
+ * g_src rows below *d_ns are WRITTEN (zeros for rejected rows and rows without a target); g_tgt and g_normals are
+ * ACCUMULATED into, so the caller zeroes them; targets no kept row points to are left as they were. */
 int gs_icp_linearize_backward(const float *src, const int32_t *d_ns, int max_ns, const float *tgt,
                               const float *tgt_normals, const uint64_t *best, float dist_thresh,
                               const float *g_out43, float *g_src, float *g_tgt, float *g_normals,

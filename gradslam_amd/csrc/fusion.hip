@@ -242,17 +242,24 @@ __global__ void fuse_bwd_matched_k(const unsigned int *__restrict__ t_pix_n, con
     }
 }
 // appended rows: row base + k of the arena is the k-th unmatched valid pixel in row-major order -- the adjoint of the
-// append is the same compaction run backwards (the writer reads where AppendWriter wrote)
+// append is the same compaction run backwards (the writer reads where AppendWriter wrote).  A pixel whose row the
+// clamped forward dropped (AppendWriter's at >= cap) has no row to read: its adjoints are zero.
 struct AppendBwdWriter {
     const float *G[4];
     float *out[4];
     int words[4];
     const int32_t *base;
+    int cap;
     __device__ void operator()(int64_t i, int64_t pos) const {
         const int64_t at = (int64_t)(*base) + pos;
+        const bool kept = at < cap;
 #pragma unroll
         for (int a = 0; a < 4; ++a)
-            for (int w = 0; w < words[a]; ++w) out[a][(int64_t)words[a] * i + w] = G[a][(int64_t)words[a] * at + w];
+            for (int w = 0; w < words[a]; ++w) {
+                float g = 0.0f;
+                if (kept) g = G[a][(int64_t)words[a] * at + w];
+                out[a][(int64_t)words[a] * i + w] = g;
+            }
     }
 };
 
@@ -719,7 +726,7 @@ int fusion_tape_appended(void *tape, int B, int H, int W, const int32_t *appende
     return GS_OK;
 }
 // reverse of merge + append for one frame (see fuse_bwd_matched_k): frame adjoints fully written, G pulled back in
-// place, arena rows and counts restored to the previous frame's
+// place, the matched arena rows and the counts restored to the previous frame's (unmatched rows keep the merge's re-rounding)
 int fusion_update_reverse(const void *tape, int B, int H, int W, int Nmax, const float *depth, const float *gvertex,
                           const float *gnormal, const float *rgb, const float *alpha, float *points, float *normals, float *colors,
                           float *ccounts, int32_t *counts, float *Gp, float *Gn, float *Gc, float *Gcc, float *g_gvertex,
@@ -734,7 +741,7 @@ int fusion_update_reverse(const void *tape, int B, int H, int W, int Nmax, const
         float *out[4] = {g_gvertex + b * HW * 3, g_gnormal + b * HW * 3, g_rgb + b * HW * 3, g_alpha + b * HW};
         const int words[4] = {3, 3, 3, 1};
         for (int a = 0; a < 4; ++a) { wr.G[a] = G[a]; wr.out[a] = out[a]; wr.words[a] = words[a]; }
-        wr.base = t.n_before + b;
+        wr.base = t.n_before + b; wr.cap = Nmax;
         int *total = (int *)((char *)cws + compact_ws_bytes(HW));
         AppendPredPix pred{depth + b * HW, t.pix_n + b * HW};
         const int rc = compact_launch(HW, pred, wr, total, cws, st, name);

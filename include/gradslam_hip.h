@@ -368,9 +368,16 @@ int gs_pointfusion_update(const float *depth, const float *rgb, const float *int
  * the adjoint of the map AFTER this frame on entry and of the map BEFORE it on return): pulls G back through the merge
  * at the matched rows only (an unmatched point passes its adjoint through: x' = (c x + 0)/c), reads the appended rows'
  * adjoints out behind the previous count, writes the frame's adjoints g_vertex (local vertex map, through alpha),
- * g_gvertex, g_gnormal, g_rgb (B,H,W,3 each, fully written) and RESTORES map_* / map_counts to the previous frame's,
- * so that the localisation's reverse pass of the same frame finds the map it ran against.  O(pixels) per frame,
- * no host synchronisation. */
+ * g_gvertex, g_gnormal, g_rgb (B,H,W,3 each, fully written: a pixel whose row a clamped forward dropped, row >= Nmax,
+ * receives zeros like an invalid one) and walks the arena one frame back: the MATCHED rows get the bits they held
+ * before this frame and map_counts the previous counts, so that the localisation's reverse pass of the same frame
+ * finds the positions and normals it ran against up to the merge's re-rounding -- an unmatched live row keeps the
+ * forward's re-rounded (c x + 0) * (1 / c), map rows behind the previous count keep what the forward appended, and the
+ * G_* rows behind the previous count are left as they were.  O(pixels) per frame, no host synchronisation.
+ * The pair assumes that every live row has a confidence count > 0, which holds for every row these updates append
+ * (alpha >= 1e-7).  On an unmatched row with count 0 in a frame that has any correspondence the forward follows the
+ * reference and writes zeros (c2 == 0: inv = 1); the reference's adjoint of that row is 0 for the three attributes,
+ * whereas the backward, which does not visit unmatched rows, leaves the row's G_* and its zeros in place. */
 size_t gs_pointfusion_update_tape_bytes(int B, int H, int W);
 int gs_pointfusion_update_taped(const float *depth, const float *rgb, const float *intrinsics, const float *poses,
                                 int B, int H, int W, float *map_points, float *map_normals, float *map_colors,

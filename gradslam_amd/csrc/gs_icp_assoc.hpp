@@ -26,6 +26,7 @@
 #include <type_traits>
 
 #include "gs_common.hpp"
+#include "gs_lanewin.hpp"
 
 namespace gs {
 
@@ -139,7 +140,8 @@ struct KnnShared {
     int cnt;
     float tbox[6];             // the source tile's AABB (lo.xyz, hi.xyz)
     // grid search (knn1_loop_k<true>)
-    int win[WROWS][64];        // per lane: the packed window rows (LaneWin), from the staging waves
+    int win[WROWS][64];        // per lane: the COVERED chunks of its window rows, packed (LaneWin), from the staging waves
+    int2 wrow[WROWS][64];      // per lane: the EXAMINED slots of its window rows: (LaneWin::base, length)
     int wflag[64];             // per lane: rel | full << 2 | window radius << 3
     int centre[64];            // per lane: the window's centre pixel
     CamK cam;                  // the bucketing camera (copied once per block: the proof reads it at LDS, not scalar-cache, latency)
@@ -292,14 +294,29 @@ __device__ __forceinline__ void tile_box(KnnShared &sh, const f3 s, const bool a
     }
 }
 
-// Per-lane examined slot ranges of the grid search (three window rows, chunk aligned: a chunk whose first slot
-// lies in a range lies in it entirely).
+// Per-lane window rows of the grid search, in two descriptions (written by wave 2 of knn1_loop_k<true>):
+//   examined (sh.wrow): the EXACT slot range [lo, hi) of the row's three pixels, pix_start[g - 1] .. pix_start[g + 2) -- what the
+//                       window scan looks at;
+//   covered  (sh.win):  the chunks that lie WHOLLY inside that range (lanewin::covered_chunks) -- what the fallback searches
+//                       skip for this lane (covers), chunk-granular because they deal in chunk boxes.
+// INVARIANT: examined set >= the slots of the lane's 3x3 window pixels (the proof's premise), and covered set <= examined set
+// (a chunk is skipped for a lane only if that lane really looked at all of it).  A chunk examined in part is examined again by
+// the fallback: harmless, the key is a minimum.
 struct LaneWin {
-    // per window row: first chunk << 9 | number of chunks (<= POOL / CHUNK < 512); 0 = empty
-    __device__ __forceinline__ static int pack(int lo, int n) { return n > 0 ? ((lo / CHUNK) << 9) | ((n + CHUNK - 1) / CHUNK) : 0; }
-    __device__ __forceinline__ static int lo(int r) { return (r >> 9) * CHUNK; }
-    __device__ __forceinline__ static int len(int r, int nt) { return min((r & 511) * CHUNK, nt - lo(r)); }  // slots
-    // does the window of point `who` (rows in sh.win) contain the chunk that starts at `slot`?
+    static_assert(lanewin::kChunk == CHUNK, "gs_lanewin.hpp states the chunk size for host programs");
+    // covered, per window row: first chunk << 9 | number of chunks; 0 = none.  (Nine bits: a longer run is cut to 511 chunks --
+    // a subset of the examined set still.)
+    __device__ __forceinline__ static int pack(int lo, int hi, int nt) {
+        const lanewin::Covered c = lanewin::covered_chunks(lo, hi, nt);
+        return c.count > 0 ? (c.first << 9) | min(c.count, 511) : 0;
+    }
+    // examined, per window row: where its first slot is read from -- its element of the LDS pool (>= 0), or, when the row's band
+    // is not in the pool and the candidates come from memory, its slot with the top bit set (< 0)
+    __device__ __forceinline__ static int base(int lo, int band_lo, int pool_off /* INT_MAX: not in the pool */) {
+        return pool_off != 0x7fffffff ? pool_off + (lo - band_lo) : (int)((unsigned)lo | 0x80000000u);
+    }
+    __device__ __forceinline__ static int mem_slot(int element) { return element & 0x7fffffff; }  // of an element < 0
+    // do the covered chunks of point `who` (sh.win) include the chunk that starts at `slot`?
     __device__ __forceinline__ static bool covers(const KnnShared &sh, int who, int slot) {
         const int c = slot / CHUNK;
         // (the empty asm ties the LDS reads to this call: hoisted out of the search loops the rows would cost the

@@ -22,7 +22,7 @@ namespace gs {
 // GRID (all search hints given): the association is a GRID SEARCH WITH A GEOMETRIC PROOF.
 //   window : the target is bucketed by ds-grid pixel of the camera it was selected with (scan order, hints.pix_start).
 //            Every lane examines ALL targets of the 3 x 3 pixels around the pixel its point projects to (three
-//            contiguous slot ranges, widened to whole chunks), staged through LDS by coalesced loads issued before the
+//            contiguous slot ranges, exact: LaneWin), staged through LDS by coalesced loads issued before the
 //            folded step, so they cost no time.  The lanes of a tile move together, so their windows lie in at most
 //            four row bands, each one contiguous slot range (row-major pixels), which share a pool of POOL staged points.
 //   proof  : every target OUTSIDE the window projects at least 2 ds - 0.5 image pixels from the window's centre pixel,
@@ -425,32 +425,42 @@ __global__ __launch_bounds__(NW * 64, 2 * NW / 4) void knn1_loop_k(const LoopCon
             }
         }
         if (wave == 2) {
+            // (seeds and camera first: their nine registers are free again while the rows are worked out -- the sixteen-wave
+            // form has 64 and must not spill)
+            *reinterpret_cast<float4 *>(sh.seed[0][lane]) = sd[0];
+            *reinterpret_cast<float4 *>(sh.seed[1][lane]) = sd[1];
+            if (lane < (int)(sizeof(CamK) / 4)) reinterpret_cast<int *>(&sh.cam)[lane] = e_cam;
             const int rel = sh.wflag[lane];  // (the planner's; its centre is this wave's own c: same arithmetic on the same words)
             const bool in = rel <= 1;
             bool full = in;
 #pragma unroll
             for (int r = 0; r < WROWS; ++r) {
                 int packed = 0;
+                int2 ex = make_int2(0, 0);
                 const int g = c + (r - R) * Wd;
                 if (in && r <= 2 * R && g + R >= 0 && g - R <= nc - 1) {
-                    const int lo = min(max(row_lo[r], 0), nt) & ~(CHUNK - 1);
-                    const int hi = min((min(max(row_hi[r], 0), nt) + CHUNK - 1) & ~(CHUNK - 1), nt);
+                    // the row's EXACT slots: the scan examines these and no others (the bands stay chunk aligned; a row is
+                    // not widened to them -- LaneWin)
+                    const int lo = min(max(row_lo[r], 0), nt), hi = min(max(row_hi[r], 0), nt);
                     if (hi > lo) {
-                        int bb = bbase[0], bn = bcnt[0];
-#pragma unroll
-                        for (int q = 1; q < WBANDS; ++q) { bb = (rel + r) == q ? bbase[q] : bb; bn = (rel + r) == q ? bcnt[q] : bn; }
-                        // inside the staged band, or not examined (then the lane has no certificate: `full`)
-                        // (LaneWin packs the chunk count in 9 bits: a staged band is at most POOL / CHUNK = 256 chunks, but a
-                        // band read from memory has no such bound -- a longer row stays unpacked and the lane uncertified)
-                        if (lo >= bb && hi <= bb + bn && (hi - lo + CHUNK - 1) / CHUNK <= 511) packed = LaneWin::pack(lo, hi - lo); else full = false;
+                        // the row's band, from the plan in LDS (three reads behind the staging loads, which take far longer:
+                        // selecting it from bbase / pstart / bcnt would keep those twelve registers alive across them)
+                        const int kk = min(rel + r, WBANDS - 1);
+                        const int bb = sh.band[kk], bp = sh.plan[kk], bn = sh.plan[WBANDS + kk];
+                        // inside the tile's band (staged, or read from memory), or not examined (then the lane has no
+                        // certificate: `full`)
+                        if (lo >= bb && hi <= bb + bn) {
+                            ex = make_int2(LaneWin::base(lo, bb, bp), hi - lo);
+                            packed = LaneWin::pack(lo, hi, nt);
+                        } else {
+                            full = false;
+                        }
                     }
                 }
                 sh.win[r][lane] = packed;
+                sh.wrow[r][lane] = ex;
             }
             sh.wflag[lane] = min(rel, 2) | (full ? 4 : 0) | (R << 3);
-            if (lane < (int)(sizeof(CamK) / 4)) reinterpret_cast<int *>(&sh.cam)[lane] = e_cam;
-            *reinterpret_cast<float4 *>(sh.seed[0][lane]) = sd[0];
-            *reinterpret_cast<float4 *>(sh.seed[1][lane]) = sd[1];
         }
 #pragma unroll
         for (int r = 0; r < NR; ++r) {
@@ -501,32 +511,67 @@ __global__ __launch_bounds__(NW * 64, 2 * NW / 4) void knn1_loop_k(const LoopCon
             }
             atomicMin(&sh.key[lane], k0);
         }
-        {   // window: every wave takes every NW-th slot of the lane's row ranges
+#ifdef GS_DIAG_STAMPS
+        unsigned long long scan_diag = 0;  // this wave's trips through the scan loop << 8 | the tile's longest sequence << 32
+#endif
+        {   // Window: the lane's three rows are ONE sequence of n0 + n1 + n2 exact slots (LaneWin: no widening to chunks), and
+            // every wave takes every NW-th of them, two per trip so that both candidate reads are in flight before either is
+            // used.  The phase is a chain of dependent LDS round trips, not instruction bound: what counts is
+            // their number.  The three (base, length) pairs come in one batch; where a candidate is read from follows from two
+            // compares (lanewin::element).  Any order of examination gives the same key: a minimum over (distance, index).
+            // RESULTS are what the chunk-widened scan gave.  A slot outside the lane's 3x3 pixels holds a target at distance^2
+            // >= bound2 (cam_bound2), so: if the in-window best satisfies the proof below it is below every such target and
+            // was the best of the widened scan too; if it does not, no such target could have satisfied it either.  The proven
+            // lanes, need_mask and every path taken are the same; an unproven lane may enter the exact search with a looser
+            // seed and leaves it with the same key.
             float bd = INFINITY;
             int bi = 0x7fffffff;
-#pragma unroll
-            for (int r = 0; r < WROWS; ++r) {
-                const int wr = sh.win[r][lane];
-                const int kk = (rel & 3) + r, wn = LaneWin::len(wr, nt);
-                const int po = sh.band[WBANDS + min(kk, WBANDS - 1)];
-                const float *row = sh.u.stage + 4 * (max(po, 0) + LaneWin::lo(wr) - sh.band[min(kk, WBANDS - 1)]);
-                for (int p = wave; p < wn; p += NW) {
+            const int2 w0 = sh.wrow[0][lane], w1 = sh.wrow[1][lane], w2 = sh.wrow[2][lane];
+            static_assert(WROWS == 3, "the flattened scan names its three rows");
+            const int total = w0.y + w1.y + w2.y;
+            auto element = [&](const int p) { return lanewin::element(p, w0.y, w1.y, w0.x, w1.x, w2.x); };
+            auto take = [&](const float4 q) {
+                const float d = dist2(s, q.x, q.y, q.z);
+                const int jj = __float_as_int(q.w);
+                const bool better = (d < bd) | ((d == bd) & (jj < bi));
+                bd = better ? d : bd;
+                bi = better ? jj : bi;
+            };
+#ifdef GS_DIAG_STAMPS
+            unsigned int n_iter = 0;
+#endif
+            const float4 *pool = reinterpret_cast<const float4 *>(sh.u.stage);
+            if (!__any((w0.x | w1.x | w2.x) < 0)) {  // (an empty row's base is 0)
+                for (int p = wave; p < total; p += 2 * NW) {
+                    const int ea = element(p), eb = element(min(p + NW, total - 1));  // (past the end: the last one again, harmless)
+                    const float4 qa = pool[ea], qb = pool[eb];
+                    take(qa);
+                    take(qb);
+#ifdef GS_DIAG_STAMPS
+                    ++n_iter;
+#endif
+                }
+            } else {  // some band of the tile is not in the pool: its rows come straight from memory (rare: one at a time)
+                for (int p = wave; p < total; p += NW) {
+                    const int e = element(p);
                     float4 q;
-                    if (po >= 0) {
-                        q = *reinterpret_cast<const float4 *>(row + 4 * p);
-                    } else {  // band not staged: straight from memory
-                        const int slot = LaneWin::lo(wr) + p;
+                    if (e >= 0) {
+                        q = pool[e];
+                    } else {
+                        const int slot = LaneWin::mem_slot(e);
                         const f3 g3 = ld3(C->hints.scan_points, slot);
                         q = make_float4(g3.x, g3.y, g3.z, __int_as_float(C->hints.scan_orig[slot]));
                     }
-                    const float d = dist2(s, q.x, q.y, q.z);
-                    const int jj = __float_as_int(q.w);
-                    const bool better = (d < bd) | ((d == bd) & (jj < bi));
-                    bd = better ? d : bd;
-                    bi = better ? jj : bi;
+                    take(q);
+#ifdef GS_DIAG_STAMPS
+                    ++n_iter;
+#endif
                 }
             }
             if (ok && bd < INFINITY) atomicMin(&sh.key[lane], pack_key(bd, bi));
+#ifdef GS_DIAG_STAMPS
+            scan_diag = ((unsigned long long)n_iter << 8) | ((unsigned long long)(unsigned)wave_max_i(total) << 32);
+#endif
         }
         __syncthreads();
         GS_STAMP(1);
@@ -539,7 +584,11 @@ __global__ __launch_bounds__(NW * 64, 2 * NW / 4) void knn1_loop_k(const LoopCon
         const bool proven = !C->cert_off & ((rel & 4) != 0) & (bd * 1.0001f < bound2);
         need = ok & !proven;
         const unsigned long long need_mask = __ballot(need);  // the same 64 lanes in every wave: block-uniform
-        GS_COUNT(12, (unsigned long long)__popcll(need_mask));
+        // diagnostic build: lanes in need | scan trips << 8 | longest sequence << 32 (each its own count, one slot: all
+        // sixteen are taken)
+#ifdef GS_DIAG_STAMPS
+        GS_COUNT(12, (unsigned long long)__popcll(need_mask) | scan_diag);
+#endif
         bool tile_search = __popcll(need_mask) > 6;
         if (!tile_search && need_mask) {
             tile_search = !knn_point_search<NW>(sh, s, need_mask, C->hints.scan_points, C->hints.scan_orig, C->boxes, C->sboxes, nt);  // ends with a barrier

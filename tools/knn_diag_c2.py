@@ -37,7 +37,7 @@ for k in range(0, 6):
     live_b = a[..., 3].max(1) > 0
     a = a[live_b]
     t0, t1, t2, t3, t6, t7 = a[..., 0], a[..., 1], a[..., 2], a[..., 3], a[..., 6], a[..., 7]
-    need = a[:, 0, 12]
+    need = (raw[live_b][:, 0, 12] & 0xff).astype(np.float64)  # (the slot's upper bits: the window scan's counts, knn_diag_long.py)
     p = lambda x: np.percentile(x, 50)
     print("association %d of the loop (live frame %d): prologue %.2f | seed+window %.2f | verify %.2f | block total p50 %.2f max %.2f | span %.1f us | "
           "lanes needing exact search per tile mean %.1f, tiles with none %d/%d | coarse %.2f fine %.2f barrier %.2f (p50 per wave, where run) scanned/tile %.1f" % (

@@ -8,6 +8,7 @@ Stamp slots per wave (16 x 8 bytes per wave, GS_STAMP / GS_COUNT in csrc/gs_icp_
   wave 1 (planner): 13 window centres + majority displacement known | 14 plan published | 15 its share staged
   waves 2.. : 14 plan seen | 15 staged (wave 2, the lanes' wave: rows packed)
   0 / 1 / 2 / 3 search start / window scan done / proof + fallbacks done / end ; 5 (wave 0) HW_ID | XCC_ID: which CU
+  12 lanes in need of the exact search | the wave's trips through the window scan's loop << 8 | the tile's longest candidate sequence << 32
 Every stamp costs ~0.1 us: compare runs of the same build, not absolute values with the product's timings.
 Printed: the phases' percentiles, the same split by how many blocks share a CU, per role, and the old chunk-box figures."""
 import ctypes, os, sys
@@ -72,7 +73,11 @@ print("barrier wait us(per wave)  p50 %.2f p99 %.2f" % pc((t3 - t2) * tick, [50,
 print("block total us             p50 %.2f p99 %.2f max %.2f" % pc((t3.max(1) - t6.min(1)) * tick, [50, 99, 100]))
 print("kernel entry spread us p50 %.2f p99 %.2f" % pc((t6.min(1) - t6.min()) * tick, [50, 99]))
 print("kernel span us %.1f" % ((t3.max() - t6.min()) * tick))
-need = a[:, 0, 12]
+w12 = raw[live][..., 12]  # lanes in need | this wave's trips through the window scan's loop << 8 | the tile's longest sequence << 32
+need = (w12[:, 0] & 0xff).astype(np.float64)
+trips, longest = (w12 >> 8) & 0xffffff, (w12[:, 0] >> 32) & 0xffffffff
+print("window scan: trips through the loop per wave p50 %d p99 %d max %d ; longest candidate sequence of a tile (slots) p50 %d p99 %d max %d" % (
+    *pc(trips, [50, 99, 100]), *pc(longest, [50, 99, 100])))
 print("grid search: lanes needing the exact search per tile: mean %.2f, tiles with none %d of %d, max %d" % (need.mean(), int((need == 0).sum()), need.shape[0], int(need.max())))
 why = raw[live][:, 0, 13]
 rad = raw[live][:, 0, 14]

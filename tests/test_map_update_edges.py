@@ -365,8 +365,7 @@ NAMES = ("points", "normals", "colors", "feats")
 
 
 def _check_fusion(variant, got, counts, stats, nmax, clamped=()):
-    """The updated arena against the oracle.  Decisions and every value that does not pass through alpha: exact.  Values
-    that carry alpha: rel_err against the float64 oracle, bounded by 4 x the float32 oracle's own (floor 2^-22)."""
+    """The updated arena against the oracle: the stats words here, the map's values in _check_fusion_values."""
     c, o32, o64 = _case(variant), _oracle(variant, torch.float32), _oracle(variant, torch.float64)
     want_counts = [min(n, nmax) for n in o32["out"].counts]
     assert counts == want_counts
@@ -375,15 +374,25 @@ def _check_fusion(variant, got, counts, stats, nmax, clamped=()):
     assert stats[2] == (1 if clamped else 0)
     assert stats[3] == int(_bits(torch.tensor([o32["max_dot"]], dtype=torch.float32))) and o32["max_dot"] > 1.0
     assert stats[4:] == [want_counts[b] - COUNTS[b] for b in range(B)]
+    _check_fusion_values(variant, c["feats"], o32["unique"], o32["out"], o64["out"], got, counts, nmax)
+
+
+def _check_fusion_values(label, feats_in, unique, out32, out64, got, counts, nmax):
+    """An updated map (four padded arrays `got`, per-element `counts`) against the oracle's (out32, out64: the float32 and
+    float64 Clouds after fuse_with_map with the table `unique` on a map whose confidence counts were feats_in).  Decisions and
+    every value that does not pass through alpha: exact.  Values that carry alpha: rel_err against the float64 oracle,
+    bounded by 4 x the float32 oracle's own (floor 2^-22).  Shared with tests/test_fusion_stages_edges.py."""
+    want_counts = [min(n, nmax) for n in out32.counts]
+    assert counts == want_counts
     alpha_gpu, alpha_32, alpha_64 = ({n: [] for n in NAMES} for _ in range(3))
-    for b in range(B):
-        n_in, n_out = COUNTS[b], want_counts[b]
+    for b in range(len(feats_in)):
+        n_in, n_out = feats_in[b].shape[0], want_counts[b]
         matched = torch.zeros(n_in, dtype=torch.bool)
-        matched[[int(r[1]) for r in o32["unique"] if int(r[0]) == b]] = True
+        matched[[int(r[1]) for r in unique if int(r[0]) == b]] = True
         # the matched rows are the rows whose confidence count moved (alpha >= exp(-8.5 / 4.5) here, counts <= 3)
-        assert torch.equal(got[3][b, :n_in, 0] != c["feats"][b][:, 0], matched), "set of matched rows, b = %d" % b
+        assert torch.equal(got[3][b, :n_in, 0] != feats_in[b][:, 0], matched), "set of matched rows, b = %d" % b
         for i, name in enumerate(NAMES):
-            g, w32, w64 = got[i][b], getattr(o32["out"], name)[b], getattr(o64["out"], name)[b]
+            g, w32, w64 = got[i][b], getattr(out32, name)[b], getattr(out64, name)[b]
             assert _same_bits(g[:n_in][~matched], w32[:n_in][~matched]), (name, b, "unmatched live rows")
             if name != "feats":  # row-major order over the unmatched valid pixels, bit for bit
                 assert _same_bits(g[n_in:n_out], w32[n_in:n_out]), (name, b, "appended rows")
@@ -398,7 +407,7 @@ def _check_fusion(variant, got, counts, stats, nmax, clamped=()):
         own = rel_err(torch.cat(alpha_32[name]), ref)
         err = rel_err(torch.cat(alpha_gpu[name]), ref)
         bound = max(4.0 * own, 2.0 ** -22)
-        print("%s/%s: alpha-path rel_err GPU %.3e, float32 oracle %.3e, bound %.3e" % (variant, name, err, own, bound))
+        print("%s/%s: alpha-path rel_err GPU %.3e, float32 oracle %.3e, bound %.3e" % (label, name, err, own, bound))
         # Measured on an MI355X, GPU / float32 oracle / bound -- variant main: points 5.760e-8 / 5.760e-8 / 2.384e-7 (floor),
         # normals 5.619e-8 / 5.619e-8 / 2.384e-7 (floor), colours 1.132e-7 / 1.132e-7 / 4.529e-7, counts 4.354e-8 / 4.354e-8 /
         # 2.384e-7 (floor); variant none (appended counts only): 1.415e-7 / 1.415e-7 / 5.659e-7; variant b1_only: points

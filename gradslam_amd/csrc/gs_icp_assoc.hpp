@@ -164,6 +164,24 @@ struct KnnShared {
 // search overflowed its pair list and fell back to the tile-level search}.  One atomic per loop from icp_prepare_k (and
 // one per overflowing tile: a rare path); tests read them to make sure a run really exercised those paths.
 __device__ unsigned int g_loop_counts[4];
+// Counters (gs_window_counts) of the grid search's second, re-centred window (knn_second_window): {blocks that took it, lanes it
+// proved, lanes it handed on to the exact search, blocks the cap refused}.  Counted by one thread of a block on that path only,
+// as the block's last instructions: an atomic to memory takes microseconds to be acknowledged, and the wave's next wait for a
+// load waits for it too -- counted where the decision is taken, with every block of a launch on the path and all of them adding
+// to one line, the counters cost a launch 15 to 20 us.  Hence also the stripes: a block adds to the stripe of its index
+// (one 64-byte line each), the host sums them.
+constexpr int WCOUNT_STRIPES = 64;
+__device__ unsigned int g_window_counts[WCOUNT_STRIPES][16];
+__device__ __forceinline__ void window_count(const unsigned int word /* still in need | took << 8 | refused << 9 | .. | proven << 16 */) {
+    unsigned int *c = g_window_counts[blockIdx.x % WCOUNT_STRIPES];
+    if (word & 0x100u) {
+        atomicAdd(&c[0], 1u);
+        atomicAdd(&c[1], (word >> 16) & 0xffu);
+        atomicAdd(&c[2], word & 0xffu);
+    } else {
+        atomicAdd(&c[3], 1u);
+    }
+}
 
 #ifdef GS_DIAG_STAMPS
 // Diagnostic build only (libgradslam_hip_diag.so, never loaded by the product): per-wave phase stamps.  A block owns

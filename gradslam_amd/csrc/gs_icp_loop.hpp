@@ -101,6 +101,149 @@ __device__ __forceinline__ float cam_bound2(const CamK &k, const f3 s, const int
     return L > 0.0f ? L * L : 0.0f;  // (NaN compares false: no proof)
 }
 
+// SECOND WINDOW of the grid search, for the lanes whose first window carried no proof (`need`), in tiles with more than six of
+// them -- the tiles that would take the tile-level search.
+// The first window is centred on the pixel the point projected to in the PREVIOUS launch.  After the loop's large early steps
+// most points sit in another cell, and in the strip the camera's motion uncovered the nearest target is two or three cells
+// away: the proof fails although the neighbour is close by, and the lane would pay for the chunk-box search (a tile with more
+// than six such lanes: the tile-level search, twice a proven tile's time).  So, first: a window centred on the cell the point
+// projects to NOW, c' = cam_cell(cam, s), with the smallest radius R' in 1 .. 3 whose bound cam_bound2(cam, s, c', R') exceeds
+// the lane's current best -- if the best IS the neighbour, that window proves it; a lane without a best, or with none inside
+// radius 3, has no second window.  Its 2 R' + 1 rows are exact slot ranges from pix_start (lanewin::recentred_row: clamped as
+// the planner clamps), read from the staged pool where a row lies wholly inside a staged band and from memory otherwise; the
+// NW waves share every lane's sequence as in the main scan (every NW-th slot, all reads of a wave in one batch) and publish by atomicMin.
+// After one barrier the proof is evaluated for (c', R'): the window was examined completely, whatever it was read from.
+// Results cannot change: the key is a minimum over (distance, index) whoever finds it, the proof is cam_bound2 for a window
+// examined completely, and a lane it does not prove enters the exact search with a seed at least as good as before.  (The
+// covered chunks of the fallback searches stay the first window's: a subset of what was examined.)
+// Block-uniform decisions: taken at all only if the tile's longest first-window sequence is at most WIN2_CAP slots (a dense
+// target is refused before any request is made: a re-centred window of radius 1 holds about as many) and, with the rows'
+// lengths known, if the longest re-centred sequence is (the refusals happen before / after the first of the two barriers, for
+// the whole block alike).  Returns the lanes still in need; `word` receives took << 8 | refused << 9 |
+// lanes proven << 16 for the counters, which the kernel adds up at its very end (window_count).  Barriers: one before the scan (the rows' ends are in LDS, and every wave has
+// read the keys its first proof -- and with it this decision -- rests on), one after it.
+constexpr int WIN2_CAP = 64;  // slots: 49 pixels of a radius-3 window at one target per pixel, with some room
+
+template <int NW>
+__device__ __forceinline__ bool knn_second_window(KnnShared &sh, const f3 s, const bool need, const float bd0, const int nt,
+                                                  const int32_t *__restrict__ pix_start, const float *__restrict__ scan,
+                                                  const int32_t *__restrict__ scan_orig, unsigned int &word) {
+    using namespace lanewin;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    // the rows of the second window live in the last kRows2 x 64 int2 of the pool (its tail: the staged bands fill it from the
+    // front, the searches' list and the epilogue's rows lie in front too) -- a tile whose bands reach that far is refused
+    constexpr int W2_ELEMS = kRows2 * 64 * (int)sizeof(int2) / (int)sizeof(float4);  // pool elements the rows take
+    int2 *const wrow2 = reinterpret_cast<int2 *>(sh.u.stage + 4 * (POOL - W2_ELEMS));
+    const int first_len = sh.wrow[0][lane].y + sh.wrow[1][lane].y + sh.wrow[2][lane].y;
+    if (wave_max_i(first_len) > WIN2_CAP || sh.band[2 * WBANDS] > POOL - W2_ELEMS) {
+        word |= 0x200u;
+        return need;
+    }
+    int c2 = 0, R2 = 0;
+    float bound_new = 0.0f;
+    if (need && bd0 < INFINITY) {
+        c2 = cam_cell(sh.cam, s);
+#pragma unroll
+        for (int r = 3; r >= 1; --r) {
+            const float b = cam_bound2(sh.cam, s, c2, r);
+            if (bd0 * 1.0001f < b) { R2 = r; bound_new = b; }
+        }
+    }
+    if (!__any(R2 > 0)) return need;
+    // Row k's ends are requested by wave k alone, for every lane, and handed to the others through LDS: requested by every wave,
+    // the fourteen loads of a lane were 8 x 14 vector-memory instructions per block, and those -- not the trips -- are what a
+    // block on this path waits for (one address unit per CU).  (A lane without a second window asks for pixel 0.)  The barrier
+    // is the one the scan needs anyway: behind it every wave has read the keys its first proof rests on.
+    const int Wd = sh.cam.Wd, nc = sh.cam.Wd * sh.cam.Hd;
+    static_assert(NW >= kRows2, "one wave per row of the re-centred window");
+    if (wave < kRows2) {
+        const PixRow pr = recentred_row(c2, wave, R2, Wd, nc);
+        const bool have = pr.first <= pr.last;
+        const int lo_raw = pix_start[have ? pr.first : 0], hi_raw = pix_start[have ? pr.last + 1 : 0];
+        const int lo = min(max(lo_raw, 0), nt), hi = min(max(hi_raw, 0), nt);
+        wrow2[wave * 64 + lane] = make_int2(lo, (have && hi > lo) ? hi - lo : 0);
+    }
+    __syncthreads();
+    // the staged bands (the plan is the prologue's: first slot | pool offset or INT_MAX | length); a row wholly inside one is
+    // read from the pool
+    const int pl = sh.band[min(lane, 2 * WBANDS)], ps = sh.plan[min(lane, 2 * WBANDS - 1)];
+    auto where = [pl, ps](const int lo, const int hi) {
+        int base = LaneWin::base(lo, 0, 0x7fffffff);
+#pragma unroll
+        for (int q = 0; q < WBANDS; ++q) {
+            const int bb = __builtin_amdgcn_readlane(pl, q), bp = __builtin_amdgcn_readlane(ps, q), bn = __builtin_amdgcn_readlane(ps, WBANDS + q);
+            if (bp != 0x7fffffff && lo >= bb && hi <= bb + bn) base = LaneWin::base(lo, bb, bp);
+        }
+        return base;
+    };
+#define GS_W2_ROW(k)                                \
+    const int2 w##k = wrow2[k * 64 + lane];         \
+    const int n##k = w##k.y;                        \
+    const int b##k = where(w##k.x, w##k.x + w##k.y);
+    GS_W2_ROW(0) GS_W2_ROW(1) GS_W2_ROW(2) GS_W2_ROW(3) GS_W2_ROW(4) GS_W2_ROW(5) GS_W2_ROW(6)
+#undef GS_W2_ROW
+    const int p1 = n0, p2 = p1 + n1, p3 = p2 + n2, p4 = p3 + n3, p5 = p4 + n4, p6 = p5 + n5, total = p6 + n6;
+    const int a0 = b0, a1 = seq_adj(b1, p1), a2 = seq_adj(b2, p2), a3 = seq_adj(b3, p3), a4 = seq_adj(b4, p4), a5 = seq_adj(b5, p5),
+              a6 = seq_adj(b6, p6);
+    if (wave_max_i(total) > WIN2_CAP) {
+        word |= 0x200u;
+        return need;
+    }
+    {
+        float bd = INFINITY;
+        int bi = 0x7fffffff;
+        // Every wave takes every NW-th candidate of every lane's sequence: at most NE = WIN2_CAP / NW each.  All of them are
+        // requested in ONE batch: a trip to memory for data another kernel of the step wrote costs a microsecond or more, and a
+        // loop of dependent trips (measured: two reads in flight per trip, four trips for a radius-3 window) cost the block
+        // 15 us -- more than the tile-level search it was meant to spare.  The branches are wave-uniform and around requests
+        // only (nothing is waited for inside): a turn no lane of the wave has a candidate for, or none from memory, issues
+        // nothing.  Candidates in the pool are read from LDS behind the requests.
+        constexpr int NE = WIN2_CAP / NW;
+        static_assert(NE * NW == WIN2_CAP, "the cap is a whole number of candidates per wave");
+        const float4 *pool = reinterpret_cast<const float4 *>(sh.u.stage);
+        int e[NE];
+        f3 g3[NE];
+        int gj[NE];
+#pragma unroll
+        for (int u = 0; u < NE; ++u) {
+            const int p = wave + u * NW;
+            e[u] = p < total ? element7(p, p1, p2, p3, p4, p5, p6, a0, a1, a2, a3, a4, a5, a6) : 0;  // (0: pool element 0, dropped)
+            g3[u] = f3{0.0f, 0.0f, 0.0f};
+            gj[u] = 0;
+        }
+#pragma unroll
+        for (int u = 0; u < NE; ++u) {
+            if (__any(e[u] < 0)) {
+                const int slot = e[u] < 0 ? LaneWin::mem_slot(e[u]) : 0;
+                g3[u] = ld3(scan, slot);
+                gj[u] = scan_orig[slot];
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < NE; ++u) {
+            const bool has = wave + u * NW < total;
+            if (!__any(has)) continue;
+            const float4 ql = pool[max(e[u], 0)];
+            const bool mem = e[u] < 0;
+            const float4 q = make_float4(mem ? g3[u].x : ql.x, mem ? g3[u].y : ql.y, mem ? g3[u].z : ql.z, mem ? __int_as_float(gj[u]) : ql.w);
+            const float d = has ? dist2(s, q.x, q.y, q.z) : INFINITY;
+            const int jj = __float_as_int(q.w);
+            const bool better = (d < bd) | ((d == bd) & (jj < bi));
+            bd = better ? d : bd;
+            bi = better ? jj : bi;
+        }
+        if (bd < INFINITY) atomicMin(&sh.key[lane], pack_key(bd, bi));
+    }
+    __syncthreads();
+    float bd;
+    int bi;
+    key_unpack(sh.key[lane], bd, bi);
+    const bool still = need & !((R2 > 0) & (bd * 1.0001f < bound_new));
+    const unsigned long long before = __ballot(need), after = __ballot(still);
+    word |= 0x100u | ((unsigned)(__popcll(before) - __popcll(after)) << 16);
+    return still;
+}
+
 template <bool GRID, int NL, int NW>
 // (NW: waves per block, 16 or 8 -- chosen by the host, loop_waves; every result is the same bit for bit: the neighbour is a
 // minimum over packed keys whoever finds it, and the row sums keep their groups and their order)
@@ -497,6 +640,8 @@ __global__ __launch_bounds__(NW * 64, 2 * NW / 4) void knn1_loop_k(const LoopCon
     }
     unsigned long long key;
     bool need = false;
+    unsigned int win2_word = 0;  // second window: lanes still in need | took it << 8 | refused << 9 | lanes proven << 16 (window_count);
+                                 // | tile-level search ran << 10: read by the diagnostic build only (slot 15)
     int rel = 2;  // grid search: the lane's centre row relative to the tile's first (0 / 1), | 4 = window fully staged
     if (grid) {
         GS_STAMP(0);
@@ -583,12 +728,24 @@ __global__ __launch_bounds__(NW * 64, 2 * NW / 4) void knn1_loop_k(const LoopCon
         const float bound2 = (ok && C->cam_ok) ? cam_bound2(sh.cam, s, sh.centre[lane], rel >> 3) : 0.0f;
         const bool proven = !C->cert_off & ((rel & 4) != 0) & (bd * 1.0001f < bound2);
         need = ok & !proven;
-        const unsigned long long need_mask = __ballot(need);  // the same 64 lanes in every wave: block-uniform
+        unsigned long long need_mask = __ballot(need);  // the same 64 lanes in every wave: block-uniform
         // diagnostic build: lanes in need | scan trips << 8 | longest sequence << 32 (each its own count, one slot: all
-        // sixteen are taken)
+        // sixteen are taken -- the second window's word below shares slot 15 with the staging waves' stamp, which is safe only
+        // because wave 0, the one that writes the word, runs the step and never stages)
 #ifdef GS_DIAG_STAMPS
         GS_COUNT(12, (unsigned long long)__popcll(need_mask) | scan_diag);
 #endif
+        // The second window, for tiles with more than six lanes in need -- the tiles the tile-level search would take: 8 us on
+        // a one-frame map where the second window is 3.7; for one to six lanes the point-serial search is 1.7 (measured,
+        // DESIGN section 3).  A proven tile pays the branch and nothing else.  The sixteen-wave form -- the one dense targets
+        // run -- never takes it: the window would be refused there anyway (ten targets per pixel: ~90 slots at radius 1), and
+        // with the path compiled in its registers cost the 200-frame figures 1 to 2 % (profiles/r10f_full_ab.txt).
+        if constexpr (NW == 8) {
+            if (__popcll(need_mask) > 6 && C->cam_ok && !C->cert_off) {
+                need = knn_second_window<NW>(sh, s, need, bd, nt, C->hints.pix_start, C->hints.scan_points, C->hints.scan_orig, win2_word);
+                need_mask = __ballot(need);
+            }
+        }
         bool tile_search = __popcll(need_mask) > 6;
         if (!tile_search && need_mask) {
             tile_search = !knn_point_search<NW>(sh, s, need_mask, C->hints.scan_points, C->hints.scan_orig, C->boxes, C->sboxes, nt);  // ends with a barrier
@@ -598,6 +755,11 @@ __global__ __launch_bounds__(NW * 64, 2 * NW / 4) void knn1_loop_k(const LoopCon
             __syncthreads();
             knn_prune_search<true, NW>(sh, s, ok, need, C->hints.scan_points, C->hints.scan_orig, C->boxes, C->sboxes, nt);  // ends with a barrier
         }
+        if constexpr (NW == 8) win2_word |= (unsigned)__popcll(need_mask) | (tile_search ? 0x400u : 0u);
+#ifdef GS_DIAG_STAMPS
+        if (wave == 0) GS_COUNT(15, (unsigned long long)win2_word);  // (every block: the buffer keeps the earlier launches' words)
+#endif
+
         GS_STAMP(2);
         key = ok ? sh.key[lane] : KEY_NONE;
         GS_STAMP(3);
@@ -649,6 +811,9 @@ __global__ __launch_bounds__(NW * 64, 2 * NW / 4) void knn1_loop_k(const LoopCon
 #pragma unroll
         for (int q = 0; q < 16; ++q) v += sh.u.a.part[threadIdx.x][q];
         partials[blockIdx.x * NACC + threadIdx.x] = v;
+    }
+    if constexpr (GRID && NW == 8) {
+        if (threadIdx.x == 0 && (win2_word & 0x300u)) window_count(win2_word);  // (behind the block's last store: nothing waits for it)
     }
 }
 

@@ -602,6 +602,22 @@ int gs_loop_counts(unsigned int *out4, int reset) {
     return GS_OK;
 }
 
+int gs_window_counts(unsigned int *out4, int reset) {
+    GS_REQUIRE(out4, "gs_window_counts: NULL argument");
+    unsigned int stripes[WCOUNT_STRIPES][16];  // (4 KiB, local: the entry point holds no state of its own)
+    GS_HIP(hipMemcpyFromSymbol(stripes, HIP_SYMBOL(g_window_counts), sizeof(stripes)), "gs_window_counts");  // synchronises with the device
+    for (int k = 0; k < 4; ++k) {
+        out4[k] = 0;
+        for (int q = 0; q < WCOUNT_STRIPES; ++q) out4[k] += stripes[q][k];
+    }
+    if (reset) {
+        for (int q = 0; q < WCOUNT_STRIPES; ++q)
+            for (int k = 0; k < 16; ++k) stripes[q][k] = 0;
+        GS_HIP(hipMemcpyToSymbol(HIP_SYMBOL(g_window_counts), stripes, sizeof(stripes)), "gs_window_counts/reset");
+    }
+    return GS_OK;
+}
+
 void gs_profile_enable(int on) {
     g_prof.on = on != 0;
     for (int t = 0; t < 2; ++t) { g_prof.used[t] = 0; g_prof.total_ms[t] = 0.0; g_prof.count[t] = 0; }

@@ -508,6 +508,13 @@ int gs_icp_launch_geometry(int max_ns, int have_hints, int *blocks, int *tile_po
  * redone by the tile-level search}.  Synchronises with the device; reset != 0 zeroes the counters afterwards.  Replaces
  * nothing in the reference; lets a test assert which paths a run really exercised. */
 int gs_loop_counts(unsigned int *out4, int reset);
+/* Counters kept on the DEVICE for the second, re-centred window of the grid search (a lane whose first window -- centred on
+ * the pixel its point projected to in the previous launch -- carried no proof looks at the 3x3 to 7x7 pixels around the pixel
+ * it projects to now, before it takes the exact chunk-box search): out4 = {blocks that took the second window, lanes it
+ * proved, lanes it handed on to the exact search, blocks the cap on the window's length refused (dense targets)}.
+ * Synchronises with the device; reset != 0 zeroes the counters afterwards.  Replaces nothing in the reference; lets a test
+ * assert which paths a run really exercised. */
+int gs_window_counts(unsigned int *out4, int reset);
 
 /* ---------------------------------------------------------------- C+U: fusion correspondences
  * find_similar_map_points (slam/fusionutils.py:381-401): keep[i] = |Vg(b,h,w) - p(b,n)| < dist_th

@@ -4,9 +4,13 @@ PyTorch is used only as plumbing: it owns the HBM allocations (`tensor.data_ptr(
 stream (`torch.cuda.current_stream().cuda_stream`); every kernel on the hot path lives in the
 shared library.  There is NO CPU fallback: if the library is missing, or a tensor is not on a HIP
 device, the call raises.
+
+SIGNATURES, the (restype, argtypes) every symbol is given when the library loads, is read from include/gradslam_hip.h at
+import -- the header of this tree, the one the in-tree build compiles from -- so the two cannot disagree: see read_signatures.
 """
 import ctypes
 import os
+import re
 import subprocess
 
 import torch
@@ -17,159 +21,36 @@ CSRC = os.path.join(_HERE, "csrc")
 
 c_i, c_i64, c_f, c_p, c_sz = ctypes.c_int, ctypes.c_int64, ctypes.c_float, ctypes.c_void_p, ctypes.c_size_t
 
-# name -> (restype, [argtypes]); mirrors include/gradslam_hip.h one to one
-SIGNATURES = {
-    "gs_abi_version": (c_i, []),
-    "gs_last_error": (ctypes.c_char_p, []),
-    "gs_vertex_normal_maps": (c_i, [c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_p]),
-    "gs_vertex_normal_maps_backward_ws_bytes": (c_sz, [c_i, c_i, c_i, c_i]),
-    "gs_vertex_normal_maps_backward": (c_i, [c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_p,
-                                             c_p, c_sz, c_p]),
-    "gs_vertex_normal_maps_backward_det_ws_bytes": (c_sz, [c_i, c_i, c_i, c_i]),
-    "gs_vertex_normal_maps_backward_det": (c_i, [c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_p,
-                                                 c_p, c_sz, c_p]),
-    "gs_get_alpha": (c_i, [c_p, c_i64, c_f, c_f, c_p, c_p]),
-    "gs_get_alpha_backward": (c_i, [c_p, c_i64, c_f, c_f, c_p, c_p, c_p]),
-    "gs_frames_from_raw": (c_i, [c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_f, c_i, c_p, c_p, c_p]),
-    "gs_compact_ws_bytes": (c_sz, [c_i64]),
-    "gs_compact_rows": (c_i, [c_p, c_p, c_i64, c_i, c_p, c_p, c_p, c_sz, c_p]),
-    "gs_compact_multi": (c_i, [c_i, c_p, c_p, c_p, c_p, c_i64, c_p, c_p, c_sz, c_p]),
-    "gs_expand_multi": (c_i, [c_i, c_p, c_p, c_p, c_p, c_i64, c_p, c_sz, c_p]),
-    "gs_append_rows_ws_bytes": (c_sz, [c_i64]),
-    "gs_append_rows": (c_i, [c_i, c_p, c_p, c_p, c_p, c_i64, c_p, c_i, c_p, c_p, c_p, c_sz, c_p]),
-    "gs_fusion_merge_inplace_ws_bytes": (c_sz, [c_i, c_i]),
-    "gs_fusion_merge_inplace": (c_i, [c_p, c_p, c_i64, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_p,
-                                      c_sz, c_p]),
-    "gs_aggregate_update_ws_bytes": (c_sz, [c_i, c_i, c_i]),
-    "gs_aggregate_update": (c_i, [c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_i, c_p, c_p, c_sz, c_p]),
-    "gs_pointfusion_update_ws_bytes": (c_sz, [c_i, c_i, c_i, c_i]),
-    "gs_pointfusion_update": (c_i, [c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_i, c_f, c_f, c_f, c_p, c_p,
-                                    c_sz, c_p]),
-    "gs_downsample_frame_ws_bytes": (c_sz, [c_i, c_i, c_i]),
-    "gs_downsample_frame": (c_i, [c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_sz, c_p]),
-    "gs_build_icp_target_ws_bytes": (c_sz, [c_i, c_i, c_i, c_i]),
-    "gs_build_icp_target": (c_i, [c_p, c_p, c_i64, c_i, c_i, c_i, c_i, c_p, c_p, c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_p,
-                                  c_p, c_p, c_sz, c_p]),
-    "gs_bucket_by_pixel_ws_bytes": (c_sz, [c_i, c_i, c_i, c_i]),
-    "gs_bucket_by_pixel": (c_i, [c_p, c_p, c_i64, c_i, c_i, c_i, c_i, c_p, c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_sz, c_p]),
-    "gs_project_active_ws_bytes": (c_sz, [c_i, c_i]),
-    "gs_project_active": (c_i, [c_p, c_p, c_i, c_i, c_p, c_p, c_i, c_i, c_i, c_p, c_p, c_p, c_sz, c_p]),
-    "gs_gather_table_rows_ws_bytes": (c_sz, [c_i]),
-    "gs_gather_table_rows": (c_i, [c_p, c_p, c_i64, c_p, c_i, c_i, c_i, c_i, c_p, c_p, c_p, c_sz, c_p]),
-    "gs_table_ds_mask": (c_i, [c_p, c_i64, c_i, c_p, c_p]),
-    "gs_knn1_ws_bytes": (c_sz, [c_i]),
-    "gs_knn1": (c_i, [c_p, c_p, c_i, c_p, c_p, c_i, c_p, c_p, c_sz, c_p]),
-    "gs_knn1_bruteforce": (c_i, [c_p, c_p, c_i, c_p, c_p, c_i, c_p, c_p]),
-    "gs_knn1_unpack": (c_i, [c_p, c_p, c_i, c_p, c_p, c_p]),
-    "gs_icp_linearize_ws_bytes": (c_sz, [c_i]),
-    "gs_icp_linearize": (c_i, [c_p, c_p, c_i, c_p, c_p, c_p, c_f, c_p, c_p, c_sz, c_p]),
-    "gs_icp_rows": (c_i, [c_p, c_p, c_i, c_p, c_p, c_p, c_f, c_p, c_p, c_p, c_p]),
-    "gs_icp_linearize_backward": (c_i, [c_p, c_p, c_i, c_p, c_p, c_p, c_f, c_p, c_p, c_p, c_p, c_p]),
-    "gs_icp_linearize_backward_det_ws_bytes": (c_sz, [c_i, c_i]),
-    "gs_icp_linearize_backward_det": (c_i, [c_p, c_p, c_i, c_p, c_p, c_p, c_i, c_p, c_f, c_p, c_p, c_p, c_p, c_p, c_sz, c_p]),
-    "gs_transform_points": (c_i, [c_p, c_p, c_i, c_p, c_p, c_p]),
-    "gs_icp_ws_bytes": (c_sz, [c_i, c_i]),
-    "gs_icp_point_to_plane": (c_i, [c_p, c_p, c_i, c_p, c_p, c_p, c_i, c_p, c_i, c_f, c_f, c_p, c_p, c_p, c_p, c_p, c_sz,
-                                    c_p]),
-    "gs_icp_point_to_plane_grad": (c_i, [c_p, c_p, c_i, c_p, c_p, c_p, c_i, c_p, c_i, c_f, c_f, c_f, c_f, c_f, c_f,
-                                         c_p, c_p, c_p, c_p, c_p, c_sz, c_p]),
-    "gs_icp_tape_bytes": (c_sz, [c_i, c_i, c_i]),
-    "gs_icp_point_to_plane_taped": (c_i, [c_p, c_p, c_i, c_p, c_p, c_p, c_i, c_p, c_i, c_f, c_f, c_i, c_f, c_f, c_f, c_f,
-                                          c_p, c_p, c_p, c_p, c_sz, c_p, c_sz, c_p]),
-    "gs_icp_backward_ws_bytes": (c_sz, [c_i]),
-    "gs_icp_point_to_plane_backward": (c_i, [c_p, c_p, c_i, c_p, c_p, c_p, c_i, c_p, c_i, c_f, c_i, c_f, c_f, c_f, c_f, c_p, c_sz,
-                                             c_p, c_p, c_p, c_p, c_p, c_p, c_sz, c_p]),
-    "gs_icp_backward_det_ws_bytes": (c_sz, [c_i, c_i, c_i, c_i]),
-    "gs_icp_point_to_plane_backward_det": (c_i, [c_p, c_p, c_i, c_p, c_p, c_p, c_i, c_p, c_i, c_f, c_i, c_f, c_f, c_f, c_f, c_p,
-                                                 c_sz, c_p, c_p, c_p, c_p, c_p, c_p, c_sz, c_p]),
-    "gs_slam_localize_tape_bytes": (c_sz, [c_i, c_i, c_i, c_i, c_i, c_i, c_i]),
-    "gs_slam_localize_taped": (c_i, [c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_p, c_p, c_p, c_i, c_i, c_i, c_f, c_f, c_f, c_f,
-                                     c_f, c_f, c_p, c_p, c_sz, c_p, c_sz, c_p]),
-    "gs_slam_localize_backward_ws_bytes": (c_sz, [c_i, c_i, c_i, c_i, c_i]),
-    "gs_slam_localize_backward": (c_i, [c_p, c_i, c_i, c_i, c_i, c_p, c_p, c_i, c_i, c_i, c_f, c_f, c_f, c_f, c_f, c_p, c_sz,
-                                        c_p, c_p, c_p, c_p, c_p, c_i, c_p, c_sz, c_p]),
-    "gs_slam_localize_backward_det_ws_bytes": (c_sz, [c_i, c_i, c_i, c_i, c_i, c_i, c_i]),
-    "gs_slam_localize_backward_det": (c_i, [c_p, c_i, c_i, c_i, c_i, c_p, c_p, c_i, c_i, c_i, c_f, c_f, c_f, c_f, c_f, c_p, c_sz,
-                                            c_p, c_p, c_p, c_p, c_p, c_i, c_p, c_sz, c_p]),
-    "gs_pointfusion_update_tape_bytes": (c_sz, [c_i, c_i, c_i]),
-    "gs_pointfusion_update_taped": (c_i, [c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_i, c_f, c_f, c_f, c_p, c_p,
-                                          c_sz, c_p, c_sz, c_p]),
-    "gs_pointfusion_update_backward_ws_bytes": (c_sz, [c_i, c_i, c_i]),
-    "gs_pointfusion_update_backward": (c_i, [c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_i, c_f, c_p, c_sz,
-                                             c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_sz, c_p]),
-    "gs_compose_poses": (c_i, [c_p, c_p, c_i, c_p, c_p]),
-    "gs_set_graph_mode": (None, [c_i]),
-    "gs_graph_stats": (c_i, [ctypes.POINTER(ctypes.c_double)]),
-    "gs_slam_localize_ws_bytes": (c_sz, [c_i, c_i, c_i, c_i, c_i]),
-    "gs_slam_localize": (c_i, [c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_p, c_p, c_p, c_i, c_i, c_i, c_f, c_f, c_f, c_f, c_f,
-                               c_f, c_p, c_p, c_p, c_p, c_p, c_p, c_sz, c_p]),
-    "gs_set_grid_search": (None, [c_i]),
-    "gs_set_fused_setup": (None, [c_i]),
-    "gs_set_tile_points": (None, [c_i]),
-    "gs_set_loop_waves": (c_i, [c_i]),
-    "gs_icp_launch_geometry": (c_i, [c_i, c_i, ctypes.POINTER(c_i), ctypes.POINTER(c_i), ctypes.POINTER(c_i)]),
-    "gs_loop_counts": (c_i, [ctypes.POINTER(ctypes.c_uint), c_i]),
-    "gs_window_counts": (c_i, [ctypes.POINTER(ctypes.c_uint), c_i]),
-    "gs_profile_enable": (None, [c_i]),
-    "gs_profile_read": (c_i, [c_i, ctypes.POINTER(ctypes.c_long), ctypes.POINTER(ctypes.c_double)]),
-    "gs_fusion_similar": (c_i, [c_p, c_p, c_i64, c_p, c_p, c_i, c_i, c_p, c_p, c_i, c_f, c_f, c_p, c_p, c_p]),
-    "gs_fusion_unique_ws_bytes": (c_sz, [c_i, c_i, c_i]),
-    "gs_fusion_unique": (c_i, [c_p, c_p, c_p, c_i64, c_p, c_i, c_i, c_i, c_p, c_p, c_i, c_p, c_p, c_p, c_sz, c_p]),
-    "gs_fusion_merge_ws_bytes": (c_sz, [c_i, c_i]),
-    "gs_fusion_merge": (c_i, [c_p, c_p, c_i64, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_p,
-                              c_p, c_p, c_p, c_p, c_sz, c_p]),
-    "gs_fusion_merge_backward": (c_i, [c_p, c_p, c_i64, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_p, c_p, c_p, c_p,
-                                       c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_sz,
-                                       c_p]),
-    "gs_fusion_new_mask": (c_i, [c_p, c_p, c_p, c_i64, c_i, c_i, c_i, c_p, c_p]),
-    "gs_render_map_ws_bytes": (c_sz, [c_i, c_i, c_i]),
-    "gs_render_map": (c_i, [c_p, c_p, c_p, c_p, c_i, c_i, c_p, c_p, c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_sz, c_p]),
-    "gs_render_map_backward_ws_bytes": (c_sz, [c_i, c_i, c_i]),
-    "gs_render_map_backward": (c_i, [c_p, c_p, c_i, c_i, c_p, c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_sz,
-                                     c_p]),
-    "gs_chamfer_ws_bytes": (c_sz, [c_i, c_i, c_i]),
-    "gs_chamfer": (c_i, [c_p, c_p, c_i, c_p, c_p, c_i, c_i, c_f, c_i, c_p, c_p, c_p, c_p, c_sz, c_p]),
-    "gs_chamfer_backward_ws_bytes": (c_sz, [c_i, c_i, c_i]),
-    "gs_chamfer_backward": (c_i, [c_p, c_p, c_i, c_p, c_p, c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_sz, c_p]),
-    "gs_chamfer_backward_det_ws_bytes": (c_sz, [c_i, c_i, c_i]),
-    "gs_chamfer_backward_det": (c_i, [c_p, c_p, c_i, c_p, c_p, c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_sz, c_p]),
-    "gs_voxel_assign_ws_bytes": (c_sz, [c_i, c_i]),
-    "gs_voxel_assign": (c_i, [c_p, c_p, c_i, c_i, c_f, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_sz, c_p]),
-    "gs_voxel_reduce_ws_bytes": (c_sz, [c_i, c_i, c_i]),
-    "gs_voxel_reduce": (c_i, [c_p, c_p, c_i, c_i, c_i, c_p, c_p, c_p, c_i, c_i, c_p, c_p, c_sz, c_p]),
-    "gs_voxel_reduce_backward": (c_i, [c_p, c_p, c_i, c_i, c_i, c_p, c_p, c_i, c_i, c_p, c_p]),
-    "gs_set_knn_grid": (None, [c_i]),
-    "gs_knn_ws_bytes": (c_sz, [c_i, c_i, c_i, c_i]),
-    "gs_knn": (c_i, [c_p, c_p, c_i, c_p, c_p, c_i, c_i, c_i, c_p, c_p, c_sz, c_p]),
-    "gs_knn_backward_ws_bytes": (c_sz, [c_i, c_i, c_i, c_i]),
-    "gs_knn_backward": (c_i, [c_p, c_p, c_i, c_p, c_p, c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_sz, c_p]),
-    "gs_knn_normals": (c_i, [c_p, c_p, c_i, c_p, c_p, c_i, c_i, c_i, c_p, c_i, c_p, c_p, c_p, c_p]),
-    "gs_tsdf_integrate": (c_i, [c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_f, c_p, c_f, c_f, c_p, c_p, c_p, c_p, c_p, c_p,
-                                c_p]),
-    "gs_tsdf_integrate_backward_ws_bytes": (c_sz, [c_i, c_i, c_i, c_i]),
-    "gs_tsdf_integrate_backward": (c_i, [c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_f, c_p, c_f, c_f, c_p, c_p, c_p, c_p, c_p,
-                                         c_p, c_p, c_p, c_sz, c_p]),
-    "gs_tsdf_integrate_backward_poses_ws_bytes": (c_sz, [c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i]),
-    "gs_tsdf_integrate_backward_poses": (c_i, [c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_f, c_p, c_f, c_f, c_p, c_p, c_p, c_p,
-                                               c_p, c_p, c_p, c_p, c_p, c_sz, c_p]),
-    "gs_tsdf_extract_ws_bytes": (c_sz, [c_i, c_i, c_i, c_i]),
-    "gs_tsdf_extract": (c_i, [c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_f, c_p, c_f, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_sz, c_p]),
-    "gs_tsdf_extract_backward": (c_i, [c_p, c_p, c_i, c_i, c_i, c_i, c_f, c_p, c_p, c_i, c_p, c_p, c_p, c_p, c_p]),
-    "gs_tsdf_raycast": (c_i, [c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_f, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_f, c_f, c_f, c_f, c_p, c_p, c_p,
-                              c_p, c_p]),
-    "gs_tsdf_raycast_backward_ws_bytes": (c_sz, [c_i, c_i, c_i, c_i, c_i]),
-    "gs_tsdf_raycast_backward": (c_i, [c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_f, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_f, c_f, c_p, c_p, c_p,
-                                       c_p, c_p, c_p, c_sz, c_p]),
-    "gs_tsdf_raycast_backward_poses_ws_bytes": (c_sz, [c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i]),
-    "gs_tsdf_raycast_backward_poses": (c_i, [c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_f, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_f, c_f, c_p, c_p,
-                                             c_p, c_p, c_p, c_p, c_p, c_sz, c_p]),
-    "gs_tsdf_faces_ws_bytes": (c_sz, [c_i, c_i, c_i, c_i]),
-    "gs_tsdf_faces": (c_i, [c_p, c_p, c_i, c_i, c_i, c_i, c_f, c_p, c_p, c_i, c_i, c_p, c_p, c_p, c_sz, c_p]),
-    "gs_rgbd_odometry_ws_bytes": (c_sz, [c_i, c_i, c_i, c_i]),
-    "gs_rgbd_odometry": (c_i, [c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_p, c_p, c_i, c_p, c_f, c_f, c_f, c_f, c_p, c_p, c_p, c_sz, c_p]),
-    "gs_rgbd_rows": (c_i, [c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_p, c_p, c_f, c_f, c_f, c_p, c_p, c_p, c_p, c_sz, c_p]),
-    "gs_rgbd_pyramid": (c_i, [c_p, c_p, c_i, c_i, c_i, c_i, c_f, c_f, c_p, c_p]),
-}
+_SCALARS = {"int": c_i, "int64_t": c_i64, "float": c_f, "size_t": c_sz, "gs_stream_t": c_p, "void": None}
+
+
+def _ctype(words, decl):
+    """ctypes type of one type spelling (a list of words, `*` its own word): any pointer is c_void_p, a scalar is one of the
+    six spellings the header uses; anything else is an error that names the declaration -- never a guess."""
+    words = [w for w in words if w != "const"]
+    if "*" in words:
+        return c_p
+    if len(words) != 1 or words[0] not in _SCALARS:
+        raise ValueError("gradslam_hip.h: unknown type '{}' in: {}".format(" ".join(words), decl))
+    return _SCALARS[words[0]]
+
+
+def read_signatures(header_text: str) -> dict:
+    """name -> (restype, [argtypes]) of every `ret gs_name(args);` of the header, in header order.  A reader for this header
+    (plain C by contract, one form of declaration), not a C parser."""
+    text = re.sub(r"/\*.*?\*/|//[^\n]*|^[ \t]*#[^\n]*", "", header_text, flags=re.S | re.M)
+    split = lambda spelling: spelling.replace("*", " * ").split()
+    sigs = {}
+    for ret, name, params in re.findall(r"([\w \t*]+?)\s*\b(gs_\w+)\s*\(([^()]*)\)\s*;", text):
+        decl = "{} {}({})".format(ret.strip(), name, " ".join(params.split()))
+        res = ctypes.c_char_p if split(ret) == ["const", "char", "*"] else _ctype(split(ret), decl)
+        args = [split(p) for p in params.split(",") if split(p) not in ([], ["void"])]
+        sigs[name] = (res, [_ctype(a if "*" in a else a[:-1], decl) for a in args])  # (a scalar's last word is its name)
+    return sigs
+
+
+with open(os.path.join(os.path.dirname(_HERE), "include", "gradslam_hip.h")) as _f:
+    SIGNATURES = read_signatures(_f.read())
 
 _lib = None
 

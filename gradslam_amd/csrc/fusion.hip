@@ -298,25 +298,34 @@ int gs_fusion_similar(const int64_t *rows, const int32_t *d_n_rows, int64_t max_
     return GS_OK;
 }
 
-size_t gs_fusion_unique_ws_bytes(int B, int H, int W) {
+// per-pixel keys | per-pixel winners | the compaction's scratch
+struct UniqueWs {
+    unsigned long long *pix_key;
+    unsigned int *pix_n;
+    void *cws;
+};
+static size_t unique_layout(int B, int H, int W, void *ws, UniqueWs *out) {
     const size_t npix = (size_t)B * H * W;
-    return align_up(npix * 8, 256) + align_up(npix * 4, 256) + compact_ws_bytes((int64_t)npix);
+    Carve c{(char *)ws};
+    UniqueWs scratch, &w = out ? *out : scratch;
+    w.pix_key = c.take<unsigned long long>(npix * 8);
+    w.pix_n = c.take<unsigned int>(npix * 4);
+    w.cws = c.take(compact_ws_bytes((int64_t)npix));
+    return c.off;
 }
+size_t gs_fusion_unique_ws_bytes(int B, int H, int W) { return unique_layout(B, H, W, nullptr, nullptr); }
 
 int gs_fusion_unique(const int64_t *rows, const uint8_t *keep, const int32_t *d_n_rows, int64_t max_rows,
                      const float *gvertex, int B, int H, int W, const float *map_points, const float *map_ccounts,
                      int Nmax, int64_t *out_rows, int32_t *out_count, void *ws, size_t ws_bytes, gs_stream_t stream) {
     GS_REQUIRE(rows && d_n_rows && gvertex && map_points && map_ccounts && out_rows && out_count, "gs_fusion_unique: NULL argument");
     GS_REQUIRE(B > 0 && H > 0 && W > 0 && Nmax > 0 && max_rows >= 0, "gs_fusion_unique: bad shape");
-    if (!ws || ws_bytes < gs_fusion_unique_ws_bytes(B, H, W)) {
-        set_error("gs_fusion_unique: workspace too small (%zu < %zu)", ws_bytes, gs_fusion_unique_ws_bytes(B, H, W));
-        return GS_ERR_WORKSPACE_TOO_SMALL;
-    }
+    UniqueWs w;
+    GS_REQUIRE_WS("gs_fusion_unique", ws, ws_bytes, unique_layout(B, H, W, ws, &w));
     hipStream_t st = (hipStream_t)stream;
     const size_t npix = (size_t)B * H * W;
-    unsigned long long *pix_key = (unsigned long long *)ws;
-    unsigned int *pix_n = (unsigned int *)((char *)ws + align_up(npix * 8, 256));
-    void *cws = (char *)pix_n + align_up(npix * 4, 256);
+    unsigned long long *pix_key = w.pix_key;
+    unsigned int *pix_n = w.pix_n;
     GS_HIP(hipMemsetAsync(pix_key, 0xff, npix * 8, st), "gs_fusion_unique/memset");
     GS_HIP(hipMemsetAsync(pix_n, 0xff, npix * 4, st), "gs_fusion_unique/memset");
     if (max_rows > 0) {
@@ -329,17 +338,14 @@ int gs_fusion_unique(const int64_t *rows, const uint8_t *keep, const int32_t *d_
     }
     PixPred pred{pix_n};
     PixWriter wr{pix_n, out_rows, H, W};
-    return compact_launch((int64_t)npix, pred, wr, out_count, cws, st, "gs_fusion_unique/compact");
+    return compact_launch((int64_t)npix, pred, wr, out_count, w.cws, st, "gs_fusion_unique/compact");
 }
 
-size_t gs_fusion_merge_ws_bytes(int B, int Nmax) { return align_up((size_t)B * Nmax * 4, 256); }
+size_t gs_fusion_merge_ws_bytes(int B, int Nmax) { return one_piece_bytes((size_t)B * Nmax * 4); }
 
 static int build_match(const int64_t *rows, const int32_t *d_n_rows, int64_t max_rows, int B, int H, int W, int Nmax,
                        void *ws, size_t ws_bytes, hipStream_t st, const char *name) {
-    if (!ws || ws_bytes < gs_fusion_merge_ws_bytes(B, Nmax)) {
-        set_error("%s: workspace too small", name);
-        return GS_ERR_WORKSPACE_TOO_SMALL;
-    }
+    GS_REQUIRE_WS(name, ws, ws_bytes, gs_fusion_merge_ws_bytes(B, Nmax));
     hipLaunchKernelGGL(fill_i32_k, dim3(grid1d((int64_t)B * Nmax)), dim3(256), 0, st, (int *)ws, (int64_t)B * Nmax, -1);
     GS_LAUNCH_CHECK(name);
     if (max_rows > 0) {
@@ -742,7 +748,7 @@ int fusion_update_reverse(const void *tape, int B, int H, int W, int Nmax, const
         const int words[4] = {3, 3, 3, 1};
         for (int a = 0; a < 4; ++a) { wr.G[a] = G[a]; wr.out[a] = out[a]; wr.words[a] = words[a]; }
         wr.base = t.n_before + b; wr.cap = Nmax;
-        int *total = (int *)((char *)cws + compact_ws_bytes(HW));
+        int *total = compact_ws(HW, true, cws).total;
         AppendPredPix pred{depth + b * HW, t.pix_n + b * HW};
         const int rc = compact_launch(HW, pred, wr, total, cws, st, name);
         if (rc) return rc;
@@ -754,12 +760,13 @@ int fusion_update_reverse(const void *tape, int B, int H, int W, int Nmax, const
     GS_HIP(hipMemcpyAsync(counts, t.n_before, (size_t)B * 4, hipMemcpyDeviceToDevice, st), name);
     return GS_OK;
 }
+size_t append_scratch_bytes(int64_t HW) { return compact_layout(HW, true, nullptr, nullptr); }
 // valid pixels of batch element b (n_arrays row arrays) appended behind the rows its arena already holds
 int append_valid_pixels(int n_arrays, const float *depth_b, int64_t HW, const float *const *h_src, const int *h_row_floats,
                         float *const *h_dst, int32_t *d_count, int cap, int32_t *d_appended, int32_t *d_overflow, void *cws,
                         hipStream_t st) {
     const AppendWriter wr = append_writer(n_arrays, h_src, h_row_floats, h_dst, d_count, cap);
-    int *total = (int *)((char *)cws + compact_ws_bytes(HW));
+    int *total = compact_ws(HW, true, cws).total;
     ValidDepthPred pred{depth_b};
     const int rc = compact_launch(HW, pred, wr, total, cws, st, "gs_aggregate_update/append");
     if (rc) return rc;

@@ -26,6 +26,20 @@ void set_error(const char *fmt, ...);
         }                                  \
     } while (0)
 
+// A caller's buffer must be there and hold `need` bytes (evaluated once): "<name>: workspace too small (<have> < <need>)" and
+// GS_ERR_WORKSPACE_TOO_SMALL otherwise.  GS_REQUIRE_TAPE words it for an autograd tape and takes the code to return: the ICP
+// loop (icp_run) answers a short tape with GS_ERR_WORKSPACE_TOO_SMALL, every other entry with GS_ERR_INVALID_ARG (codes are ABI).
+#define GS_REQUIRE_BYTES_(what, code, name, ptr, have, need)                                                         \
+    do {                                                                                                             \
+        const size_t have__ = (have), need__ = (need);                                                               \
+        if (!(ptr) || have__ < need__) {                                                                             \
+            gs::set_error("%s: " what " too small (%zu < %zu)", (const char *)(name), have__, need__);               \
+            return code;                                                                                             \
+        }                                                                                                            \
+    } while (0)
+#define GS_REQUIRE_WS(name, ptr, have, need) GS_REQUIRE_BYTES_("workspace", GS_ERR_WORKSPACE_TOO_SMALL, name, ptr, have, need)
+#define GS_REQUIRE_TAPE(name, ptr, have, need, code) GS_REQUIRE_BYTES_("tape", code, name, ptr, have, need)
+
 #define GS_LAUNCH_CHECK(name)                                                    \
     do {                                                                         \
         hipError_t e__ = hipGetLastError();                                      \
@@ -55,6 +69,8 @@ struct Carve {
     template <class T = void>
     T *take(size_t bytes) { const size_t o = off; off += align_up(bytes, 256); return (T *)(base ? base + o : nullptr); }
 };
+// the size of a workspace that is one piece (its pointer is the workspace itself)
+static inline size_t one_piece_bytes(size_t bytes) { return align_up(bytes, 256); }
 
 // ------------------------------------------------------------------ device helpers
 struct f3 {

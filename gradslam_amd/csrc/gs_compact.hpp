@@ -49,8 +49,26 @@ constexpr int kCI = 4;                 // consecutive items per thread
 constexpr int kCB = kCT * kCI;         // items per block
 
 static inline int compact_blocks(int64_t n) { return n > 0 ? cdiv(n, kCB) : 1; }
-// workspace: block_counts[nb] + block_offsets[nb]
-static inline size_t compact_ws_bytes(int64_t n) { return align_up(2 * sizeof(int) * (size_t)compact_blocks(n), 256); }
+// The compaction's scratch: block_counts[nb] | block_offsets[nb] as ONE piece (the offsets follow the counts directly, not
+// 256-aligned) and, with_total, a slot behind it for callers that keep the compaction's total on the device.
+struct CompactWs {
+    int *counts, *offsets, *total;
+};
+static inline size_t compact_layout(int64_t n, bool with_total, void *ws, CompactWs *out) {
+    const int nb = compact_blocks(n);
+    Carve c{(char *)ws};
+    CompactWs scratch, &w = out ? *out : scratch;
+    w.counts = c.take<int>(2 * sizeof(int) * (size_t)nb);
+    w.offsets = w.counts ? w.counts + nb : nullptr;
+    w.total = with_total ? c.take<int>(sizeof(int)) : nullptr;
+    return c.off;
+}
+static inline size_t compact_ws_bytes(int64_t n) { return compact_layout(n, false, nullptr, nullptr); }
+static inline CompactWs compact_ws(int64_t n, bool with_total, void *ws) {
+    CompactWs w;
+    compact_layout(n, with_total, ws, &w);
+    return w;
+}
 
 // `flags` (optional, one byte per thread = its kCI verdicts): the write pass then reads the verdicts instead of evaluating the
 // predicate again -- for predicates that cost more to evaluate than a byte costs to move (the projection: two IEEE
@@ -265,14 +283,14 @@ __global__ __launch_bounds__(kCT) void compact_write2_k(int64_t nA, PA pa, WA wa
 // Enqueue the launches.  ws must hold compact_ws_bytes(n).
 // (A one-block, one-launch variant for small inputs was measured and rejected: 19 200 candidates on a single CU
 // take ~60 us of dependent gathers -- two launches spread over 19 blocks take ~9.)
-static inline size_t compact_flags_bytes(int64_t n) { return align_up((size_t)compact_blocks(n) * kCT, 256); }  // optional verdict bytes
+static inline size_t compact_flags_bytes(int64_t n) { return (size_t)compact_blocks(n) * kCT; }  // optional verdict bytes
 
 template <class Pred, class Writer>
 static inline int compact_launch(int64_t n, Pred pred, Writer writer, int *d_out_count, void *ws,
                                  hipStream_t st, const char *name, unsigned char *flags = nullptr /* compact_flags_bytes(n), or NULL */) {
     const int nb = compact_blocks(n);
-    int *counts = (int *)ws;
-    int *offsets = counts + nb;
+    const CompactWs w = compact_ws(n, false, ws);
+    int *counts = w.counts, *offsets = w.offsets;
     hipLaunchKernelGGL((compact_count_k<Pred>), dim3(nb), dim3(kCT), 0, st, n, pred, counts, flags);
     GS_LAUNCH_CHECK(name);
     if (nb <= kSelfScanBlocks) {
@@ -299,7 +317,8 @@ static inline int compact_launch2(int64_t nA, PA pa, WA wa, int *d_countA, void 
         set_error("%s: second compaction too large for the fused form", name);
         return GS_ERR_INVALID_ARG;
     }
-    int *countsA = (int *)wsA, *offsetsA = countsA + nbA, *countsB = (int *)wsB;
+    const CompactWs a = compact_ws(nA, false, wsA);
+    int *countsA = a.counts, *offsetsA = a.offsets, *countsB = compact_ws(nB, false, wsB).counts;
     hipLaunchKernelGGL((compact_count2_k<PA, PB>), dim3(nbA + nbB), dim3(kCT), 0, st, nA, pa, countsA, flagsA, nbA, nB, pb, countsB, nbB);
     GS_LAUNCH_CHECK(name);
     if (nbA <= kSelfScanBlocks) {

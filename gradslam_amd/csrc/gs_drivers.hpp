@@ -43,6 +43,7 @@ int fusion_append_corr(void *state, int B, int H, int W, int Nmax, int b, const 
                        hipStream_t st);
 int fusion_finish(void *state, int B, int H, int W, int Nmax, int32_t *ctr, int32_t *counts, const int *totals, int cap, int32_t *appended,
                   int32_t *stats, hipStream_t st);
+size_t append_scratch_bytes(int64_t HW);  // the `cws` of the append passes below: one frame's compaction scratch with its total
 size_t fusion_tape_bytes(int B, int H, int W);
 int fusion_tape_record(const void *state, void *tape, int B, int H, int W, int Nmax, const int32_t *counts, const float *points,
                        const float *normals, const float *colors, const float *ccounts, hipStream_t st);

@@ -409,14 +409,12 @@ struct BwdWs {
     float *gP, *partials[2];
 };
 static inline size_t bwd_ws_layout(int max_ns, void *ws, BwdWs *out) {
-    const size_t sS = align_up(sizeof(BwdState), 256), sG = align_up((size_t)max_ns * 12, 256), sP = align_up((size_t)BWD_MAXB * 12 * 4, 256);
-    if (ws && out) {
-        char *p = (char *)ws;
-        out->S[0] = (BwdState *)p; out->S[1] = (BwdState *)(p + sS);
-        out->gP = (float *)(p + 2 * sS);
-        out->partials[0] = (float *)(p + 2 * sS + sG); out->partials[1] = (float *)(p + 2 * sS + sG + sP);
-    }
-    return 2 * sS + sG + 2 * sP;
+    Carve c{(char *)ws};
+    BwdWs scratch, &w = out ? *out : scratch;
+    w.S[0] = c.take<BwdState>(sizeof(BwdState)); w.S[1] = c.take<BwdState>(sizeof(BwdState));
+    w.gP = c.take<float>((size_t)max_ns * 12);
+    w.partials[0] = c.take<float>((size_t)BWD_MAXB * 12 * 4); w.partials[1] = c.take<float>((size_t)BWD_MAXB * 12 * 4);
+    return c.off;
 }
 
 __global__ void zero_rows_k(float *__restrict__ a, float *__restrict__ b, const int32_t *__restrict__ d_n, int cap) {

@@ -225,7 +225,7 @@ static inline int lin_blocks(int max_ns) {
     if (nb < 1) nb = 1;
     return nb;
 }
-static inline size_t boxes_bytes(int max_nt) { return align_up((size_t)cdiv(max_nt > 0 ? max_nt : 1, CHUNK) * 6 * 4, 256); }
+static inline size_t boxes_bytes(int max_nt) { return (size_t)cdiv(max_nt > 0 ? max_nt : 1, CHUNK) * 6 * 4; }
 
 // ------------------------------------------------------------------ optional per-kernel timing
 // bench.py asks for the average duration of the two hot kernels of the loop, measured with HIP events
@@ -298,29 +298,28 @@ struct IcpWs {
     LoopConst *lc;       // the loop's constants (knn1_loop_k reads them from here, not from its arguments)
     int32_t *cells;      // grid search: (2, max_ns) ds-grid pixel of every point an association wrote, by launch parity
 };
+// n equal pieces in a row, as LoopBufs wants its slots: the first one's address, *stride = a piece's size in elements
+template <class T>
+static inline T *take_slots(Carve &c, int n, size_t bytes, int64_t *stride) {
+    const size_t o = c.off;
+    T *first = c.take<T>(bytes);
+    *stride = (int64_t)((c.off - o) / sizeof(T));
+    for (int k = 1; k < n; ++k) c.take(bytes);
+    return first;
+}
 static inline size_t icp_ws_layout(int max_ns, int max_nt, void *ws, IcpWs *out) {
-    size_t off = 0;
-    auto take = [&](size_t bytes) { size_t o = off; off += align_up(bytes, 256); return o; };
-    const size_t oS = take(sizeof(IcpState)), oS1 = take(sizeof(IcpState));
-    const size_t oP0 = take((size_t)max_ns * 12), oP1 = take((size_t)max_ns * 12);
-    const size_t oB0 = take((size_t)max_ns * 8), oB1 = take((size_t)max_ns * 8);
-    const size_t oPart = take((size_t)partial_rows_alloc(max_ns) * NACC * 4), oPart1 = take((size_t)partial_rows_alloc(max_ns) * NACC * 4);
-    const size_t oBox = take(boxes_bytes(max_nt)), oSBox = take((size_t)cdiv(max_nt > 0 ? max_nt : 1, 1024) * 6 * 4);
-    const size_t oLc = take(sizeof(LoopConst)), oCells = take((size_t)max_ns * 12);  // cells by launch parity (2 planes) | the loop's copy of hints.src_pix
-    if (ws && out) {
-        char *p = (char *)ws;
-        out->S[0] = (IcpState *)(p + oS); out->S[1] = (IcpState *)(p + oS1);
-        out->B.pts = (float *)(p + oP0);
-        out->B.pts_stride = (int64_t)(oP1 - oP0) / 4;
-        out->B.best = (unsigned long long *)(p + oB0);
-        out->B.best_stride = (int64_t)(oB1 - oB0) / 8;
-        out->partials[0] = (float *)(p + oPart); out->partials[1] = (float *)(p + oPart1);
-        out->boxes = (float *)(p + oBox);
-        out->sboxes = (float *)(p + oSBox);
-        out->lc = (LoopConst *)(p + oLc);
-        out->cells = (int32_t *)(p + oCells);
-    }
-    return off;
+    Carve c{(char *)ws};
+    IcpWs scratch, &w = out ? *out : scratch;
+    const size_t part_b = (size_t)partial_rows_alloc(max_ns) * NACC * 4;
+    w.S[0] = c.take<IcpState>(sizeof(IcpState)); w.S[1] = c.take<IcpState>(sizeof(IcpState));
+    w.B.pts = take_slots<float>(c, 2, (size_t)max_ns * 12, &w.B.pts_stride);
+    w.B.best = take_slots<unsigned long long>(c, 2, (size_t)max_ns * 8, &w.B.best_stride);
+    w.partials[0] = c.take<float>(part_b); w.partials[1] = c.take<float>(part_b);
+    w.boxes = c.take<float>(boxes_bytes(max_nt));
+    w.sboxes = c.take<float>((size_t)cdiv(max_nt > 0 ? max_nt : 1, 1024) * 6 * 4);
+    w.lc = c.take<LoopConst>(sizeof(LoopConst));
+    w.cells = c.take<int32_t>((size_t)max_ns * 12);  // cells by launch parity (2 planes) | the loop's copy of hints.src_pix
+    return c.off;
 }
 
 // ------------------------------------------------------------------ tape (autograd)
@@ -333,19 +332,13 @@ struct Tape {
 };
 static inline int tape_launches(bool grad, int numiters) { return grad ? 2 * numiters : numiters + 1; }
 static inline size_t tape_layout(bool grad, int max_ns, int numiters, void *tape, Tape *out) {
-    const int n = tape_launches(grad, numiters > 0 ? numiters : 1);
-    const size_t rec_b = align_up((size_t)(n + 1) * REC_WORDS * 4, 256);
-    const size_t pts_b = align_up((size_t)max_ns * 12, 256), best_b = align_up((size_t)max_ns * 8, 256);
-    if (tape && out) {
-        char *p = (char *)tape;
-        out->rec = (float *)p;
-        out->B.pts = (float *)(p + rec_b);
-        out->B.pts_stride = (int64_t)pts_b / 4;
-        out->B.best = (unsigned long long *)(p + rec_b + (size_t)n * pts_b);
-        out->B.best_stride = (int64_t)best_b / 8;
-        out->nslots = n;
-    }
-    return rec_b + (size_t)n * (pts_b + best_b);
+    Carve c{(char *)tape};
+    Tape scratch, &t = out ? *out : scratch;
+    t.nslots = tape_launches(grad, numiters > 0 ? numiters : 1);
+    t.rec = c.take<float>((size_t)(t.nslots + 1) * REC_WORDS * 4);
+    t.B.pts = take_slots<float>(c, t.nslots, (size_t)max_ns * 12, &t.B.pts_stride);
+    t.B.best = take_slots<unsigned long long>(c, t.nslots, (size_t)max_ns * 8, &t.B.best_stride);
+    return c.off;
 }
 
 // GradParams of a gradLM loop from the caller's lambda_max / B / B2 / nu, and what the plain LM loops pass in their place
@@ -365,28 +358,20 @@ static int icp_run(bool grad, const float *src, const int32_t *d_ns, int max_ns,
     GS_REQUIRE(!hints.scan_points || hints.scan_orig, "%s: hints.scan_points needs hints.scan_orig", name);
     GS_REQUIRE(src && d_ns && tgt && nrm && d_nt && out_T, "%s: NULL argument", name);  // init_T NULL = identity
     GS_REQUIRE(max_ns > 0 && max_nt > 0 && numiters >= 0, "%s: bad sizes max_ns=%d max_nt=%d numiters=%d", name, max_ns, max_nt, numiters);
-    if (!ws || ws_bytes < icp_ws_layout(max_ns, max_nt, nullptr, nullptr)) {
-        set_error("%s: workspace too small (%zu < %zu)", name, ws_bytes, icp_ws_layout(max_ns, max_nt, nullptr, nullptr));
-        return GS_ERR_WORKSPACE_TOO_SMALL;
-    }
+    IcpWs w;
+    GS_REQUIRE_WS(name, ws, ws_bytes, icp_ws_layout(max_ns, max_nt, ws, &w));
     if (numiters == 0) {
         if (init_T) {
             GS_HIP(hipMemcpyAsync(out_T, init_T, 64, hipMemcpyDeviceToDevice, st), name);
         } else {
-            hipLaunchKernelGGL(icp_init_state_k, dim3(1), dim3(64), 0, st, (IcpState *)ws, init_T, damp);
-            GS_HIP(hipMemcpyAsync(out_T, ws, 64, hipMemcpyDeviceToDevice, st), name);  // IcpState starts with T
+            hipLaunchKernelGGL(icp_init_state_k, dim3(1), dim3(64), 0, st, w.S[0], init_T, damp);
+            GS_HIP(hipMemcpyAsync(out_T, w.S[0], 64, hipMemcpyDeviceToDevice, st), name);  // IcpState starts with T
         }
         return GS_OK;
     }
-    IcpWs w;
-    icp_ws_layout(max_ns, max_nt, ws, &w);
     Tape tp{nullptr, {}, 0};
     if (tape) {
-        if (tape_bytes < tape_layout(grad, max_ns, numiters, nullptr, nullptr)) {
-            set_error("%s: tape too small (%zu < %zu)", name, tape_bytes, tape_layout(grad, max_ns, numiters, nullptr, nullptr));
-            return GS_ERR_WORKSPACE_TOO_SMALL;
-        }
-        tape_layout(grad, max_ns, numiters, tape, &tp);
+        GS_REQUIRE_TAPE(name, tape, tape_bytes, tape_layout(grad, max_ns, numiters, tape, &tp), GS_ERR_WORKSPACE_TOO_SMALL);
         w.B = tp.B;  // the tape is the loop's working storage
     }
     int n_assoc = 0, n_step = 0;
@@ -493,9 +478,21 @@ static int icp_run(bool grad, const float *src, const int32_t *d_ns, int max_ns,
 // det: the target / normal adjoints by the deterministic fold (gs_detfold.hpp) -- reverse launch q (q = numiters - 1 - k for LM;
 // 2 (numiters - 1 - k) and + 1 for gradLM's look / lin pair) stores its contributions in its own rows, the fold adds them up
 static inline int bwd_launches(bool grad, int numiters) { return grad ? 2 * numiters : numiters; }
-static inline size_t bwd_det_ws_bytes(bool grad, int max_ns, int max_nt, int numiters) {
-    return align_up(bwd_ws_layout(max_ns, nullptr, nullptr), 256) +
-           det_ws_layout(bwd_launches(grad, numiters > 0 ? numiters : 1), max_ns, max_nt, nullptr, nullptr);
+// the reverse pass's workspace and, behind it in det mode, the fold's: each taken as one piece and handed to its own layout
+struct BwdDetWs {
+    BwdWs bwd;
+    DetWs det;
+};
+static inline size_t bwd_det_layout(bool det, bool grad, int max_ns, int max_nt, int numiters, void *ws, BwdDetWs *out) {
+    Carve c{(char *)ws};
+    BwdDetWs scratch, &w = out ? *out : scratch;
+    bwd_ws_layout(max_ns, c.take(bwd_ws_layout(max_ns, nullptr, nullptr)), &w.bwd);
+    w.det = DetWs{};
+    if (det) {
+        const int Q = bwd_launches(grad, numiters > 0 ? numiters : 1);
+        det_ws_layout(Q, max_ns, max_nt, c.take(det_ws_layout(Q, max_ns, max_nt, nullptr, nullptr)), &w.det);
+    }
+    return c.off;
 }
 
 static int icp_backward_run(bool grad, const float *src, const int32_t *d_ns, int max_ns, const float *tgt, const float *nrm,
@@ -506,18 +503,13 @@ static int icp_backward_run(bool grad, const float *src, const int32_t *d_ns, in
     GS_REQUIRE(src && d_ns && tgt && nrm && d_nt && init_T && tape && grad_T && g_src && g_init_T, "%s: NULL argument", name);
     GS_REQUIRE(max_ns > 0 && max_nt > 0 && numiters >= 0, "%s: bad sizes", name);
     GS_REQUIRE(!det || bwd_launches(grad, numiters) <= 65535, "%s: too many iterations for the deterministic fold", name);
-    if (!ws || ws_bytes < (det ? bwd_det_ws_bytes(grad, max_ns, max_nt, numiters) : bwd_ws_layout(max_ns, nullptr, nullptr))) {
-        set_error("%s: workspace too small", name);
-        return GS_ERR_WORKSPACE_TOO_SMALL;
-    }
-    GS_REQUIRE(tape_bytes >= tape_layout(grad, max_ns, numiters, nullptr, nullptr), "%s: tape too small", name);
+    BwdDetWs both;
+    GS_REQUIRE_WS(name, ws, ws_bytes, bwd_det_layout(det, grad, max_ns, max_nt, numiters, ws, &both));
     Tape tp;
-    tape_layout(grad, max_ns, numiters, (void *)tape, &tp);
-    BwdWs w;
-    bwd_ws_layout(max_ns, ws, &w);
-    DetWs dw{};
+    GS_REQUIRE_TAPE(name, tape, tape_bytes, tape_layout(grad, max_ns, numiters, (void *)tape, &tp), GS_ERR_INVALID_ARG);
+    const BwdWs &w = both.bwd;
+    const DetWs &dw = both.det;
     const bool fold = det && (g_tgt || g_nrm);
-    if (fold) det_ws_layout(bwd_launches(grad, numiters), max_ns, max_nt, (char *)ws + align_up(bwd_ws_layout(max_ns, nullptr, nullptr), 256), &dw);
     // what the walk's kernels scatter into: the outputs (float atomics) or, DET, launch q's contribution rows
     auto rows_of = [&](int q) { return fold ? dw.rows + (size_t)q * max_ns * DET_ROW : nullptr; };
     float *walk_nrm = det ? nullptr : g_nrm;
@@ -642,7 +634,7 @@ int gs_profile_read(int tag, long *launches, double *total_ms) {
     return GS_OK;
 }
 
-size_t gs_knn1_ws_bytes(int max_nt) { return boxes_bytes(max_nt); }
+size_t gs_knn1_ws_bytes(int max_nt) { return one_piece_bytes(boxes_bytes(max_nt)); }
 
 int gs_knn1(const float *src, const int32_t *d_ns, int max_ns, const float *tgt, const int32_t *d_nt, int max_nt,
             uint64_t *best, void *ws, size_t ws_bytes, gs_stream_t stream) {
@@ -655,10 +647,7 @@ int gs_knn1(const float *src, const int32_t *d_ns, int max_ns, const float *tgt,
         GS_LAUNCH_CHECK("gs_knn1/fill");
         return GS_OK;
     }
-    if (!ws || ws_bytes < boxes_bytes(max_nt)) {
-        set_error("gs_knn1: workspace too small (%zu < %zu)", ws_bytes, boxes_bytes(max_nt));
-        return GS_ERR_WORKSPACE_TOO_SMALL;
-    }
+    GS_REQUIRE_WS("gs_knn1", ws, ws_bytes, gs_knn1_ws_bytes(max_nt));
     hipLaunchKernelGGL(tgt_boxes_k, dim3(cdiv(max_nt, 64)), dim3(64), 0, st, tgt, d_nt, (float *)ws);
     GS_LAUNCH_CHECK("gs_knn1/boxes");
     hipLaunchKernelGGL(knn1_box_k, dim3(cdiv(max_ns, 64)), dim3(KNN_BT), 0, st, src, d_ns, tgt, (const float *)ws, d_nt,
@@ -692,17 +681,14 @@ int gs_knn1_unpack(const uint64_t *best, const int32_t *d_ns, int max_ns, float 
     return GS_OK;
 }
 
-size_t gs_icp_linearize_ws_bytes(int max_ns) { (void)max_ns; return align_up((size_t)LIN_MAXB * NACC * 4, 256); }
+size_t gs_icp_linearize_ws_bytes(int max_ns) { (void)max_ns; return one_piece_bytes((size_t)LIN_MAXB * NACC * 4); }
 
 int gs_icp_linearize(const float *src, const int32_t *d_ns, int max_ns, const float *tgt, const float *tgt_normals,
                      const uint64_t *best, float dist_thresh, float *out44, void *ws, size_t ws_bytes,
                      gs_stream_t stream) {
     GS_REQUIRE(src && d_ns && tgt && tgt_normals && best && out44, "gs_icp_linearize: NULL argument");
     GS_REQUIRE(max_ns >= 0, "gs_icp_linearize: negative size");
-    if (!ws || ws_bytes < gs_icp_linearize_ws_bytes(max_ns)) {
-        set_error("gs_icp_linearize: workspace too small");
-        return GS_ERR_WORKSPACE_TOO_SMALL;
-    }
+    GS_REQUIRE_WS("gs_icp_linearize", ws, ws_bytes, gs_icp_linearize_ws_bytes(max_ns));
     hipStream_t st = (hipStream_t)stream;
     const int nb = lin_blocks(max_ns);  // capped at LIN_MAXB: large clouds grid-stride
     hipLaunchKernelGGL(linearize_k, dim3(nb), dim3(LIN_T), 0, st, src, d_ns, tgt, tgt_normals,
@@ -745,13 +731,9 @@ int gs_icp_linearize_backward_det(const float *src, const int32_t *d_ns, int max
     GS_REQUIRE(src && d_ns && tgt && tgt_normals && d_nt && best && g_out43, "%s: NULL argument", name);
     if (max_ns <= 0) return GS_OK;
     GS_REQUIRE(max_nt > 0, "%s: bad sizes", name);
-    if (!ws || ws_bytes < gs_icp_linearize_backward_det_ws_bytes(max_ns, max_nt)) {
-        set_error("%s: workspace too small", name);
-        return GS_ERR_WORKSPACE_TOO_SMALL;
-    }
-    hipStream_t st = (hipStream_t)stream;
     DetWs dw;
-    det_ws_layout(1, max_ns, max_nt, ws, &dw);
+    GS_REQUIRE_WS(name, ws, ws_bytes, det_ws_layout(1, max_ns, max_nt, ws, &dw));
+    hipStream_t st = (hipStream_t)stream;
     const bool fold = g_tgt || g_normals;
     hipLaunchKernelGGL(linearize_bwd_k<true>, dim3(min(cdiv(max_ns, 256), 2048)), dim3(256), 0, st, src, d_ns, tgt, tgt_normals,
                        (const unsigned long long *)best, dist_thresh, g_out43, g_src, fold ? dw.rows : nullptr, nullptr);
@@ -806,10 +788,10 @@ int gs_icp_point_to_plane_taped(const float *src, const int32_t *d_ns, int max_n
                    best_last, nullptr, ws, ws_bytes, (hipStream_t)stream, "gs_icp_point_to_plane_taped", tape, tape_bytes);
 }
 
-size_t gs_icp_backward_ws_bytes(int max_ns) { return bwd_ws_layout(max_ns > 0 ? max_ns : 1, nullptr, nullptr); }
+size_t gs_icp_backward_ws_bytes(int max_ns) { return bwd_det_layout(false, false, max_ns > 0 ? max_ns : 1, 1, 1, nullptr, nullptr); }
 
 size_t gs_icp_backward_det_ws_bytes(int max_ns, int max_nt, int numiters, int grad_lm) {
-    return bwd_det_ws_bytes(grad_lm != 0, max_ns > 0 ? max_ns : 1, max_nt > 0 ? max_nt : 1, numiters);
+    return bwd_det_layout(true, grad_lm != 0, max_ns > 0 ? max_ns : 1, max_nt > 0 ? max_nt : 1, numiters, nullptr, nullptr);
 }
 
 static int icp_backward_entry(bool det, const float *src, const int32_t *d_ns, int max_ns, const float *tgt, const float *tgt_normals,

@@ -418,14 +418,23 @@ int vertex_normal_maps_cam(const float *depth, const float *intrinsics, const fl
 
 extern "C" {
 
-size_t gs_vertex_normal_maps_backward_ws_bytes(int B, int L, int H, int W) {
-    return align_up((size_t)B * L * H * W * 3 * sizeof(float), 256) * 2 +
-           align_up((size_t)B * L * cdiv((int64_t)H * W, 256) * VN_PART * sizeof(float), 256);
+// the reverse pass of the maps: two (B,L,H,W,3) maps, pass 1's results for pass 2 | the partial sums of every block | det
+// only: the K terms of every (b,l)
+struct VnBwdWs {
+    float *dhb, *dvb, *part, *terms;
+};
+static size_t vn_bwd_layout(bool det, int B, int L, int H, int W, void *ws, VnBwdWs *out) {
+    Carve c{(char *)ws};
+    VnBwdWs scratch, &w = out ? *out : scratch;
+    w.dhb = c.take<float>((size_t)B * L * H * W * 3 * sizeof(float)); w.dvb = c.take<float>((size_t)B * L * H * W * 3 * sizeof(float));
+    w.part = c.take<float>((size_t)B * L * cdiv((int64_t)H * W, 256) * VN_PART * sizeof(float));
+    w.terms = det ? c.take<float>((size_t)B * L * 4 * sizeof(float)) : nullptr;
+    return c.off;
 }
 
-size_t gs_vertex_normal_maps_backward_det_ws_bytes(int B, int L, int H, int W) {
-    return gs_vertex_normal_maps_backward_ws_bytes(B, L, H, W) + align_up((size_t)B * L * 4 * sizeof(float), 256);
-}
+size_t gs_vertex_normal_maps_backward_ws_bytes(int B, int L, int H, int W) { return vn_bwd_layout(false, B, L, H, W, nullptr, nullptr); }
+
+size_t gs_vertex_normal_maps_backward_det_ws_bytes(int B, int L, int H, int W) { return vn_bwd_layout(true, B, L, H, W, nullptr, nullptr); }
 
 static int maps_backward(bool det, const float *depth, const float *intrinsics, const float *poses, int B, int L, int H,
                          int W, const float *g_vertex, const float *g_normal, const float *g_gvertex,
@@ -433,24 +442,15 @@ static int maps_backward(bool det, const float *depth, const float *intrinsics, 
                          void *ws, size_t ws_bytes, gs_stream_t stream) {
     GS_REQUIRE(depth && intrinsics, "gs_vertex_normal_maps_backward: depth/intrinsics must not be NULL");
     GS_REQUIRE(B > 0 && L > 0 && H >= 2 && W >= 2 && (int64_t)B * L <= 65535, "gs_vertex_normal_maps_backward: bad shape");
-    if (det && (ws_bytes < gs_vertex_normal_maps_backward_det_ws_bytes(B, L, H, W) || !ws)) {
-        set_error("gs_vertex_normal_maps_backward_det: workspace too small");
-        return GS_ERR_WORKSPACE_TOO_SMALL;
-    }
+    VnBwdWs w;
+    GS_REQUIRE_WS(det ? "gs_vertex_normal_maps_backward_det" : "gs_vertex_normal_maps_backward", ws, ws_bytes,
+                  vn_bwd_layout(det, B, L, H, W, ws, &w));
     const bool need_n = g_normal || g_gnormal;
-    float *dhb = nullptr, *dvb = nullptr;
+    float *dhb = need_n ? w.dhb : nullptr, *dvb = need_n ? w.dvb : nullptr, *part = w.part;
     hipStream_t st = (hipStream_t)stream;
     const int64_t HW = (int64_t)H * W;
     dim3 grid(cdiv(HW, 256), B * L);
-    if (ws_bytes < gs_vertex_normal_maps_backward_ws_bytes(B, L, H, W) || !ws) {
-        set_error("gs_vertex_normal_maps_backward: workspace too small");
-        return GS_ERR_WORKSPACE_TOO_SMALL;
-    }
-    const size_t map_b = align_up((size_t)B * L * HW * 3 * sizeof(float), 256);
-    float *part = (float *)((char *)ws + 2 * map_b);
     if (need_n) {
-        dhb = (float *)ws;
-        dvb = (float *)((char *)ws + map_b);
         hipLaunchKernelGGL(vn_bwd_pass1_k, grid, dim3(256), 0, st, depth, intrinsics, poses, L, H, W, g_normal,
                            g_gnormal, dhb, dvb, part);
         GS_LAUNCH_CHECK("gs_vertex_normal_maps_backward/1");
@@ -458,7 +458,7 @@ static int maps_backward(bool det, const float *depth, const float *intrinsics, 
     hipLaunchKernelGGL(vn_bwd_pass2_k, grid, dim3(256), 0, st, depth, intrinsics, poses, L, H, W, g_vertex, g_gvertex,
                        dhb, dvb, g_depth, part);
     if (det) {  // the K terms of every (b,l) to the workspace's tail, then added in increasing l
-        float *terms = (float *)((char *)ws + gs_vertex_normal_maps_backward_ws_bytes(B, L, H, W));
+        float *terms = w.terms;
         if (g_intrinsics || (g_poses && poses))
             hipLaunchKernelGGL(vn_bwd_final_k<true>, dim3(B * L), dim3(1024), 0, st, part, (int)grid.x, need_n ? 1 : 0, intrinsics, poses, L,
                                g_intrinsics ? terms : nullptr, g_poses);
@@ -513,10 +513,7 @@ int gs_compact_rows(const float *src, const uint8_t *mask, int64_t n_rows, int r
                     int32_t *out_count, void *ws, size_t ws_bytes, gs_stream_t stream) {
     GS_REQUIRE(mask && out_count && n_rows >= 0 && row_floats >= 0, "gs_compact_rows: bad arguments");
     GS_REQUIRE(row_floats == 0 || (src && out), "gs_compact_rows: src/out must not be NULL when row_floats > 0");
-    if (ws_bytes < compact_ws_bytes(n_rows) || !ws) {
-        set_error("gs_compact_rows: workspace too small (%zu < %zu)", ws_bytes, compact_ws_bytes(n_rows));
-        return GS_ERR_WORKSPACE_TOO_SMALL;
-    }
+    GS_REQUIRE_WS("gs_compact_rows", ws, ws_bytes, compact_ws_bytes(n_rows));
     MaskPred pred{mask};
     RowWriter wr{(const uint32_t *)src, (uint32_t *)out, row_floats};
     return compact_launch(n_rows, pred, wr, out_count, ws, (hipStream_t)stream, "gs_compact_rows");
@@ -527,10 +524,7 @@ int gs_compact_multi(int n_arrays, const float *const *h_src, const int *h_row_f
                      gs_stream_t stream) {
     GS_REQUIRE(n_arrays >= 1 && n_arrays <= 4 && h_src && h_row_floats && h_out && mask && out_count && n_rows >= 0,
                "gs_compact_multi: bad arguments (1..4 arrays)");
-    if (ws_bytes < compact_ws_bytes(n_rows) || !ws) {
-        set_error("gs_compact_multi: workspace too small (%zu < %zu)", ws_bytes, compact_ws_bytes(n_rows));
-        return GS_ERR_WORKSPACE_TOO_SMALL;
-    }
+    GS_REQUIRE_WS("gs_compact_multi", ws, ws_bytes, compact_ws_bytes(n_rows));
     MultiWriter wr;
     wr.n_arrays = n_arrays;
     for (int a = 0; a < 4; ++a) {
@@ -547,10 +541,7 @@ int gs_expand_multi(int n_arrays, const float *const *h_grad, const int *h_row_f
                     const uint8_t *mask, int64_t n_rows, void *ws, size_t ws_bytes, gs_stream_t stream) {
     GS_REQUIRE(n_arrays >= 1 && n_arrays <= 4 && h_grad && h_row_floats && h_out && mask && n_rows >= 0,
                "gs_expand_multi: bad arguments (1..4 arrays)");
-    if (ws_bytes < compact_ws_bytes(n_rows) || !ws) {
-        set_error("gs_expand_multi: workspace too small (%zu < %zu)", ws_bytes, compact_ws_bytes(n_rows));
-        return GS_ERR_WORKSPACE_TOO_SMALL;
-    }
+    GS_REQUIRE_WS("gs_expand_multi", ws, ws_bytes, compact_ws_bytes(n_rows));
     ExpandWriter wr;
     wr.n_arrays = n_arrays;
     for (int a = 0; a < 4; ++a) {
@@ -574,17 +565,14 @@ int gs_frames_from_raw(const uint16_t *depth_raw, const uint8_t *rgb_raw, int B,
     return GS_OK;
 }
 
-size_t gs_append_rows_ws_bytes(int64_t n_rows) { return compact_ws_bytes(n_rows) + 256; }
+size_t gs_append_rows_ws_bytes(int64_t n_rows) { return compact_layout(n_rows, true, nullptr, nullptr); }
 
 int gs_append_rows(int n_arrays, const float *const *h_src, const int *h_row_floats, float *const *h_dst, const uint8_t *mask,
                    int64_t n_rows, int32_t *d_count, int cap, int32_t *d_appended, int32_t *d_overflow, void *ws,
                    size_t ws_bytes, gs_stream_t stream) {
     GS_REQUIRE(n_arrays >= 1 && n_arrays <= 4 && h_src && h_row_floats && h_dst && mask && d_count && n_rows >= 0 && cap >= 0,
                "gs_append_rows: bad arguments (1..4 arrays)");
-    if (ws_bytes < gs_append_rows_ws_bytes(n_rows) || !ws) {
-        set_error("gs_append_rows: workspace too small (%zu < %zu)", ws_bytes, gs_append_rows_ws_bytes(n_rows));
-        return GS_ERR_WORKSPACE_TOO_SMALL;
-    }
+    GS_REQUIRE_WS("gs_append_rows", ws, ws_bytes, gs_append_rows_ws_bytes(n_rows));
     AppendWriter wr;
     wr.n_arrays = n_arrays;
     wr.base = d_count;
@@ -595,7 +583,7 @@ int gs_append_rows(int n_arrays, const float *const *h_src, const int *h_row_flo
         wr.words[a] = a < n_arrays ? h_row_floats[a] : 0;
         GS_REQUIRE(a >= n_arrays || (h_src[a] && h_dst[a] && h_row_floats[a] > 0), "gs_append_rows: NULL array %d", a);
     }
-    int *total = (int *)((char *)ws + compact_ws_bytes(n_rows));
+    int *total = compact_ws(n_rows, true, ws).total;
     MaskPred pred{mask};
     const int rc = compact_launch(n_rows, pred, wr, total, ws, (hipStream_t)stream, "gs_append_rows");
     if (rc) return rc;
@@ -616,10 +604,7 @@ int gs_downsample_frame(const float *depth, const float *gvertex, const float *g
     GS_REQUIRE(cap >= Hd * Wd, "gs_downsample_frame: cap (%d) < ceil(H/ds)*ceil(W/ds) (%d)", cap, Hd * Wd);
     GS_REQUIRE((!out_points || gvertex) && (!out_normals || gnormal) && (!out_colors || rgb),
                "gs_downsample_frame: an output was requested without its source map");
-    if (ws_bytes < gs_downsample_frame_ws_bytes(H, W, ds) || !ws) {
-        set_error("gs_downsample_frame: workspace too small");
-        return GS_ERR_WORKSPACE_TOO_SMALL;
-    }
+    GS_REQUIRE_WS("gs_downsample_frame", ws, ws_bytes, gs_downsample_frame_ws_bytes(H, W, ds));
     const int64_t HW = (int64_t)H * W;
     for (int b = 0; b < B; ++b) {
         DsPred pred{depth + b * HW, W, Wd, ds};

@@ -305,10 +305,7 @@ int gs_chamfer(const float *a, const int32_t *a_counts, int Na_max, const float 
                gs_stream_t stream) {
     GS_REQUIRE(a && a_counts && b && b_counts && stats && keys_ab && keys_ba, "gs_chamfer: NULL argument");
     GS_REQUIRE(cham_shape_ok(B, Na_max, Nb_max), "gs_chamfer: bad shape B=%d Na_max=%d Nb_max=%d", B, Na_max, Nb_max);
-    if (!ws || ws_bytes < gs_chamfer_ws_bytes(B, Na_max, Nb_max)) {
-        set_error("gs_chamfer: workspace too small (%zu < %zu)", ws_bytes, gs_chamfer_ws_bytes(B, Na_max, Nb_max));
-        return GS_ERR_WORKSPACE_TOO_SMALL;
-    }
+    GS_REQUIRE_WS("gs_chamfer", ws, ws_bytes, gs_chamfer_ws_bytes(B, Na_max, Nb_max));
     hipStream_t st = (hipStream_t)stream;
     ChamWs w;
     cham_layout(B, Na_max, Nb_max, ws, &w);
@@ -344,10 +341,7 @@ static int chamfer_backward_entry(const char *name, bool det, const float *a, co
                                   gs_stream_t stream) {
     GS_REQUIRE(a && a_counts && b && b_counts && keys_ab && keys_ba && g2 && g1 && g_a && g_b, "%s: NULL argument", name);
     GS_REQUIRE(cham_shape_ok(B, Na_max, Nb_max), "%s: bad shape B=%d Na_max=%d Nb_max=%d", name, B, Na_max, Nb_max);
-    if (det && (!ws || ws_bytes < gs_chamfer_backward_det_ws_bytes(B, Na_max, Nb_max))) {
-        set_error("%s: workspace too small (%zu < %zu)", name, ws_bytes, gs_chamfer_backward_det_ws_bytes(B, Na_max, Nb_max));
-        return GS_ERR_WORKSPACE_TOO_SMALL;
-    }
+    if (det) GS_REQUIRE_WS(name, ws, ws_bytes, gs_chamfer_backward_det_ws_bytes(B, Na_max, Nb_max));
     hipStream_t st = (hipStream_t)stream;
     const ChamIn in{{a, b}, {a_counts, b_counts}, {Na_max, Nb_max}};
     const unsigned long long *kab = (const unsigned long long *)keys_ab, *kba = (const unsigned long long *)keys_ba;

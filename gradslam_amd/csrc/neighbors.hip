@@ -513,10 +513,7 @@ int gs_knn(const float *src, const int32_t *src_counts, int Ns_max, const float 
            int K, uint64_t *keys, void *ws, size_t ws_bytes, gs_stream_t stream) {
     GS_REQUIRE(src && src_counts && tgt && tgt_counts && keys, "gs_knn: NULL argument");
     GS_REQUIRE(nb_shape_ok(B, Ns_max, Nt_max, K), "gs_knn: bad shape B=%d Ns_max=%d Nt_max=%d K=%d (1 <= K <= 32)", B, Ns_max, Nt_max, K);
-    if (!ws || ws_bytes < gs_knn_ws_bytes(B, Ns_max, Nt_max, K)) {
-        set_error("gs_knn: workspace too small (%zu < %zu)", ws_bytes, gs_knn_ws_bytes(B, Ns_max, Nt_max, K));
-        return GS_ERR_WORKSPACE_TOO_SMALL;
-    }
+    GS_REQUIRE_WS("gs_knn", ws, ws_bytes, gs_knn_ws_bytes(B, Ns_max, Nt_max, K));
     hipStream_t st = (hipStream_t)stream;
     NbWs w;
     nb_layout(B, Ns_max, Nt_max, K, ws, &w);
@@ -552,10 +549,7 @@ int gs_knn_backward(const float *src, const int32_t *src_counts, int Ns_max, con
     GS_REQUIRE(nb_shape_ok(B, Ns_max, Nt_max, K), "gs_knn_backward: bad shape B=%d Ns_max=%d Nt_max=%d K=%d (1 <= K <= 32)", B, Ns_max,
                Nt_max, K);
     GS_REQUIRE(g_src != g_tgt, "gs_knn_backward: g_src and g_tgt must be distinct buffers");
-    if (!ws || ws_bytes < gs_knn_backward_ws_bytes(B, Ns_max, Nt_max, K)) {
-        set_error("gs_knn_backward: workspace too small (%zu < %zu)", ws_bytes, gs_knn_backward_ws_bytes(B, Ns_max, Nt_max, K));
-        return GS_ERR_WORKSPACE_TOO_SMALL;
-    }
+    GS_REQUIRE_WS("gs_knn_backward", ws, ws_bytes, gs_knn_backward_ws_bytes(B, Ns_max, Nt_max, K));
     hipStream_t st = (hipStream_t)stream;
     NbBwd a;
     const size_t bytes = nb_bwd_layout(B, Nt_max, ws, &a);

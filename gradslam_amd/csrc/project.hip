@@ -336,49 +336,86 @@ __global__ void tgt_scatter_gather1_k(const int64_t *__restrict__ rows, const in
     }
 }
 
+// ---------------------------------------------------------------- workspace layouts
+// gs_project_active: the cameras of more than kCamB sequences (room for one at least) | the compaction's scratch
+struct ActiveWs {
+    Cam *cams;
+    void *cws;
+};
+static size_t active_layout(int B, int Nmax, void *ws, ActiveWs *out) {
+    Carve c{(char *)ws};
+    ActiveWs scratch, &w = out ? *out : scratch;
+    w.cams = c.take<Cam>(sizeof(Cam) * (size_t)(B > 0 ? B : 1));
+    w.cws = c.take(compact_ws_bytes((int64_t)B * Nmax));
+    return c.off;
+}
+
+// The front end of gs_slam_localize for one sequence: project_target1 and project_front1 share this layout, order included.
+struct FrontWs {
+    int *cnt, *fill;       // per ds-grid pixel: rows counted, slots handed out
+    void *map_cws;         // the projection's compaction scratch (Nmax rows) ...
+    unsigned char *flags;  // ... and its count pass's verdicts for the write pass
+    void *frame_cws;       // the frame's ds-grid compaction scratch (its block counts)
+};
+static size_t front_layout(int H, int W, int ds, int Nmax, void *ws, FrontWs *out) {
+    const size_t npix = (size_t)cdiv(H, ds) * cdiv(W, ds);
+    Carve c{(char *)ws};
+    FrontWs scratch, &w = out ? *out : scratch;
+    w.cnt = c.take<int>(npix * 4); w.fill = c.take<int>(npix * 4);
+    w.map_cws = c.take(compact_ws_bytes(Nmax));
+    w.flags = c.take<unsigned char>(compact_flags_bytes(Nmax));
+    w.frame_cws = c.take(compact_ws_bytes((int64_t)npix));
+    return c.off;
+}
+
+// gs_bucket_by_pixel and gs_build_icp_target: each sequence's first row (B + 1) | per-pixel counts | per-pixel fill (B x npix)
+struct BucketWs {
+    int32_t *starts;
+    int *cnt, *fill;
+};
+static size_t bucket_layout(int B, int H, int W, int ds, void *ws, BucketWs *out) {
+    const size_t npix = (size_t)cdiv(H, ds) * cdiv(W, ds);
+    Carve c{(char *)ws};
+    BucketWs scratch, &w = out ? *out : scratch;
+    w.starts = c.take<int32_t>(sizeof(int32_t) * (size_t)(B + 1));
+    w.cnt = c.take<int>((size_t)B * npix * 4); w.fill = c.take<int>((size_t)B * npix * 4);
+    return c.off;
+}
+
 }  // namespace gs
 
 using namespace gs;
 
 extern "C" {
 
-size_t gs_project_active_ws_bytes(int B, int Nmax) {
-    return align_up(sizeof(Cam) * (size_t)(B > 0 ? B : 1), 256) + compact_ws_bytes((int64_t)B * Nmax);
-}
+size_t gs_project_active_ws_bytes(int B, int Nmax) { return active_layout(B, Nmax, nullptr, nullptr); }
 
 int gs_project_active(const float *points, const int32_t *counts, int B, int Nmax, const float *poses,
                       const float *intrinsics, int H, int W, int ds, int64_t *out_rows, int32_t *out_count, void *ws,
                       size_t ws_bytes, gs_stream_t stream) {
     GS_REQUIRE(points && counts && poses && intrinsics && out_rows && out_count, "gs_project_active: NULL argument");
     GS_REQUIRE(B > 0 && Nmax > 0 && H > 0 && W > 0, "gs_project_active: bad shape B=%d Nmax=%d H=%d W=%d", B, Nmax, H, W);
-    if (!ws || ws_bytes < gs_project_active_ws_bytes(B, Nmax)) {
-        set_error("gs_project_active: workspace too small (%zu < %zu)", ws_bytes, gs_project_active_ws_bytes(B, Nmax));
-        return GS_ERR_WORKSPACE_TOO_SMALL;
-    }
+    ActiveWs w;
+    GS_REQUIRE_WS("gs_project_active", ws, ws_bytes, active_layout(B, Nmax, ws, &w));
     hipStream_t st = (hipStream_t)stream;
-    Cam *cams = (Cam *)ws;
-    void *cws = (char *)ws + align_up(sizeof(Cam) * (size_t)B, 256);
     const float umax = (float)((double)W - 0.999), vmax = (float)((double)H - 0.999);
     if (B <= kCamB) {  // cameras built per block in LDS: no preparation launch
         ActivePredL pred{points, counts, poses, intrinsics, B, Nmax, H, W, ds, umax, vmax};
         ActiveWriterL wr{points, out_rows, Nmax, H, W, umax, vmax};
-        return compact_launch((int64_t)B * Nmax, pred, wr, out_count, cws, st, "gs_project_active");
+        return compact_launch((int64_t)B * Nmax, pred, wr, out_count, w.cws, st, "gs_project_active");
     }
-    hipLaunchKernelGGL(build_cams_k, dim3(cdiv(B, 64)), dim3(64), 0, st, poses, intrinsics, B, cams);
+    hipLaunchKernelGGL(build_cams_k, dim3(cdiv(B, 64)), dim3(64), 0, st, poses, intrinsics, B, w.cams);
     GS_LAUNCH_CHECK("gs_project_active/cams");
-    ActivePred pred{points, counts, cams, Nmax, H, W, ds, umax, vmax};
-    ActiveWriter wr{points, cams, out_rows, Nmax, H, W, umax, vmax};
-    return compact_launch((int64_t)B * Nmax, pred, wr, out_count, cws, st, "gs_project_active");
+    ActivePred pred{points, counts, w.cams, Nmax, H, W, ds, umax, vmax};
+    ActiveWriter wr{points, w.cams, out_rows, Nmax, H, W, umax, vmax};
+    return compact_launch((int64_t)B * Nmax, pred, wr, out_count, w.cws, st, "gs_project_active");
 }
 
 }  // extern "C"
 
 namespace gs {
 // gs_project_active (ds-grid) + gs_build_icp_target for one sequence in 4 launches instead of 6 (see ActivePredH)
-size_t project_target1_ws_bytes(int H, int W, int ds, int Nmax) {
-    const size_t npix = (size_t)cdiv(H, ds) * cdiv(W, ds);
-    return compact_ws_bytes(Nmax) + 2 * align_up(npix * 4, 256) + compact_flags_bytes(Nmax) + compact_ws_bytes((int64_t)npix);
-}
+size_t project_target1_ws_bytes(int H, int W, int ds, int Nmax) { return front_layout(H, W, ds, Nmax, nullptr, nullptr); }
 // `frame` (optional): the ds-grid source cloud of the live frame (gs_downsample_frame for one sequence) rides on the same two
 // launches -- its inputs (the maps kernel's output) are ready when the projection's are
 int project_target1(const float *points, const int32_t *counts, int Nmax, const float *poses, const float *intrinsics, int H,
@@ -386,15 +423,12 @@ int project_target1(const float *points, const int32_t *counts, int Nmax, const 
                     int32_t *nt, float *scan_points, int32_t *scan_orig, int32_t *pix_start, int32_t *tgt_index, int32_t *tgt_pix,
                     void *ws, size_t ws_bytes, hipStream_t st, const DsJob *frame) {
     const char *name = "gs_slam_localize/target";
-    if (!ws || ws_bytes < project_target1_ws_bytes(H, W, ds, Nmax)) {
-        set_error("%s: workspace too small", name);
-        return GS_ERR_WORKSPACE_TOO_SMALL;
-    }
+    FrontWs w;
+    GS_REQUIRE_WS(name, ws, ws_bytes, front_layout(H, W, ds, Nmax, ws, &w));
     const int Wd = cdiv(W, ds), npix = cdiv(H, ds) * Wd;
-    char *p = (char *)ws;
-    void *cws = p; p += compact_ws_bytes(Nmax);
-    int *cnt = (int *)p, *fill = (int *)(p + align_up((size_t)npix * 4, 256));
-    unsigned char *flags = (unsigned char *)(p + 2 * align_up((size_t)npix * 4, 256));  // the count pass's verdicts for the write pass
+    int *cnt = w.cnt, *fill = w.fill;
+    void *cws = w.map_cws, *dws = w.frame_cws;
+    unsigned char *flags = w.flags;
     const float umax = (float)((double)W - 0.999), vmax = (float)((double)H - 0.999);
     ActivePredH pred{points, counts, poses, intrinsics, Nmax, H, W, ds, umax, vmax, cnt, fill, npix};
     ActiveWriterH wr{points, rows, H, W, ds, Wd, umax, vmax, cnt};
@@ -403,7 +437,6 @@ int project_target1(const float *points, const int32_t *counts, int Nmax, const 
         const int Hd = cdiv(H, ds);
         DsPred dp{frame->depth, W, Wd, ds};
         DsWriter dw{frame->gvertex, nullptr, nullptr, frame->out_points, nullptr, nullptr, frame->out_pix, W, Wd, ds};
-        void *dws = (char *)flags + compact_flags_bytes(Nmax);  // (the frame's block counts: behind everything the projection uses)
         if (compact_blocks((int64_t)Hd * Wd) <= kSelfScanBlocks) {
             rc = compact_launch2((int64_t)Nmax, pred, wr, nrows, cws, flags, (int64_t)Hd * Wd, dp, dw, frame->count, dws, st, name);
         } else {  // a ds-grid of more than a million pixels: its write pass needs the scan launch, so it goes by itself
@@ -502,26 +535,23 @@ int project_front1(const float *depth, const float *points, const int32_t *count
                    float *cam_out, int32_t *row_pix, float *tgt, float *tnrm, int32_t *nt, int32_t *tgt_index, float *scan_points,
                    int32_t *scan_orig, int32_t *pix_start, const DsJob &frame, void *ws, size_t ws_bytes, hipStream_t st) {
     const char *name = "gs_slam_localize/front";
-    if (!ws || ws_bytes < project_target1_ws_bytes(H, W, ds, Nmax)) {  // (the same pieces in another order)
-        set_error("%s: workspace too small", name);
-        return GS_ERR_WORKSPACE_TOO_SMALL;
-    }
+    FrontWs w;
+    GS_REQUIRE_WS(name, ws, ws_bytes, front_layout(H, W, ds, Nmax, ws, &w));
     const int Wd = cdiv(W, ds), Hd = cdiv(H, ds), npix = Hd * Wd;
     if (npix > kBucketPixMax) {
         set_error("%s: ds-grid too large for the fused form", name);
         return GS_ERR_INVALID_ARG;
     }
-    int *cnt = (int *)ws, *fill = (int *)((char *)ws + align_up((size_t)npix * 4, 256));
-    char *p = (char *)ws + 2 * align_up((size_t)npix * 4, 256);
-    int *countsA = (int *)p; p += compact_ws_bytes(Nmax);
-    unsigned char *flags = (unsigned char *)p; p += compact_flags_bytes(Nmax);
-    int *countsB = (int *)p;
+    int *cnt = w.cnt, *fill = w.fill;
+    unsigned char *flags = w.flags;
     const float umax = (float)((double)W - 0.999), vmax = (float)((double)H - 0.999);
     ActivePredH pa{points, counts, poses, intrinsics, Nmax, H, W, ds, umax, vmax, cnt, fill, npix};
     ActiveWriterT wa{points, map_normals, H, W, ds, Wd, umax, vmax, cnt, cap, tgt, tnrm, tgt_index, row_pix};
     DsPred pb{frame.depth, W, Wd, ds};
     DsWriter wb{frame.gvertex, nullptr, nullptr, frame.out_points, nullptr, nullptr, frame.out_pix, W, Wd, ds};
     const int64_t nA = Nmax, nB = (int64_t)npix;
+    const CompactWs cA = compact_ws(nA, false, w.map_cws);
+    int *countsA = cA.counts, *countsB = compact_ws(nB, false, w.frame_cws).counts;
     const int nbA = compact_blocks(nA), nbB = compact_blocks(nB), gx = cdiv(W, TW), nbV = depth ? gx * cdiv(H, TH) : 0;  // (depth NULL: no maps)
     if (nbB > kSelfScanBlocks) {
         set_error("%s: ds-grid too large for the fused form", name);
@@ -535,7 +565,7 @@ int project_front1(const float *depth, const float *points, const int32_t *count
         hipLaunchKernelGGL((compact_write2_k<ActivePredH, ActiveWriterT, true, DsPred, DsWriter>), dim3(nbA + nbB), dim3(kCT), 0, st, nA, pa, wa,
                            (const int *)countsA, nt, (const unsigned char *)flags, nbA, nB, pb, wb, (const int *)countsB, frame.count, nbB);
     } else {  // a map of more than a million points: its write pass needs the scan launch
-        int *offsetsA = countsA + nbA;
+        int *offsetsA = cA.offsets;
         hipLaunchKernelGGL(compact_scan_k, dim3(1), dim3(1024), 0, st, countsA, nbA, offsetsA, nt);
         GS_LAUNCH_CHECK(name);
         hipLaunchKernelGGL((compact_write2_k<ActivePredH, ActiveWriterT, false, DsPred, DsWriter>), dim3(nbA + nbB), dim3(kCT), 0, st, nA, pa, wa,
@@ -552,17 +582,14 @@ int project_front1(const float *depth, const float *points, const int32_t *count
 
 extern "C" {
 
-size_t gs_gather_table_rows_ws_bytes(int B) { return align_up(sizeof(int32_t) * (size_t)(B + 1), 256); }
+size_t gs_gather_table_rows_ws_bytes(int B) { return one_piece_bytes(sizeof(int32_t) * (size_t)(B + 1)); }
 
 int gs_gather_table_rows(const int64_t *rows, const int32_t *d_n_rows, int64_t max_rows, const float *attr, int B,
                          int Nmax, int C, int cap, float *out, int32_t *counts, void *ws, size_t ws_bytes,
                          gs_stream_t stream) {
     GS_REQUIRE(rows && d_n_rows && attr && out, "gs_gather_table_rows: NULL argument");
     GS_REQUIRE(B > 0 && B <= 256 && Nmax > 0 && C > 0 && cap >= 0 && max_rows >= 0, "gs_gather_table_rows: bad shape (B <= 256)");
-    if (!ws || ws_bytes < gs_gather_table_rows_ws_bytes(B)) {
-        set_error("gs_gather_table_rows: workspace too small");
-        return GS_ERR_WORKSPACE_TOO_SMALL;
-    }
+    GS_REQUIRE_WS("gs_gather_table_rows", ws, ws_bytes, gs_gather_table_rows_ws_bytes(B));
     hipStream_t st = (hipStream_t)stream;
     int32_t *starts = (int32_t *)ws;
     hipLaunchKernelGGL(table_starts_k, dim3(cdiv(B + 1, 64)), dim3(64), 0, st, rows, d_n_rows, B, starts);
@@ -574,26 +601,19 @@ int gs_gather_table_rows(const int64_t *rows, const int32_t *d_n_rows, int64_t m
     return GS_OK;
 }
 
-size_t gs_bucket_by_pixel_ws_bytes(int B, int H, int W, int ds) {
-    const size_t npix = (size_t)cdiv(H, ds) * cdiv(W, ds);
-    return align_up(sizeof(int32_t) * (size_t)(B + 1), 256) + 2 * align_up((size_t)B * npix * 4, 256);
-}
+size_t gs_bucket_by_pixel_ws_bytes(int B, int H, int W, int ds) { return bucket_layout(B, H, W, ds, nullptr, nullptr); }
 
 int gs_bucket_by_pixel(const int64_t *rows, const int32_t *d_n_rows, int64_t max_rows, int B, int H, int W, int ds,
                        const float *map_points, int Nmax, int cap, float *scan_points, int32_t *scan_orig,
                        int32_t *pix_start, int32_t *tgt_pix, void *ws, size_t ws_bytes, gs_stream_t stream) {
     GS_REQUIRE(rows && d_n_rows && map_points && scan_points && scan_orig && pix_start, "gs_bucket_by_pixel: NULL argument");
     GS_REQUIRE(B > 0 && B <= 256 && H > 0 && W > 0 && ds > 0 && Nmax > 0 && cap > 0 && max_rows >= 0, "gs_bucket_by_pixel: bad shape");
-    if (!ws || ws_bytes < gs_bucket_by_pixel_ws_bytes(B, H, W, ds)) {
-        set_error("gs_bucket_by_pixel: workspace too small");
-        return GS_ERR_WORKSPACE_TOO_SMALL;
-    }
+    BucketWs w;
+    GS_REQUIRE_WS("gs_bucket_by_pixel", ws, ws_bytes, bucket_layout(B, H, W, ds, ws, &w));
     hipStream_t st = (hipStream_t)stream;
     const int Wd = cdiv(W, ds), npix = cdiv(H, ds) * Wd;
-    char *p = (char *)ws;
-    int32_t *starts = (int32_t *)p; p += align_up(sizeof(int32_t) * (size_t)(B + 1), 256);
-    const size_t seg = align_up((size_t)B * npix * 4, 256);
-    int *cnt = (int *)p, *fill = (int *)(p + seg);
+    int32_t *starts = w.starts;
+    int *cnt = w.cnt, *fill = w.fill;
     const int64_t nbins = (int64_t)B * npix;
     hipLaunchKernelGGL(tgt_init_k, dim3(min(cdiv(nbins, 256), 1024)), dim3(256), 0, st, cnt, fill, nbins, rows, d_n_rows, B, starts);
     const int nb = max_rows > 0 ? min(cdiv(max_rows, 256), 1024) : 1;
@@ -614,16 +634,12 @@ int gs_build_icp_target(const int64_t *rows, const int32_t *d_n_rows, int64_t ma
     GS_REQUIRE(rows && d_n_rows && map_points && map_normals && tgt && tgt_normals && counts && scan_points && scan_orig && pix_start,
                "gs_build_icp_target: NULL argument");
     GS_REQUIRE(B > 0 && B <= 256 && H > 0 && W > 0 && ds > 0 && Nmax > 0 && cap > 0 && max_rows >= 0, "gs_build_icp_target: bad shape");
-    if (!ws || ws_bytes < gs_build_icp_target_ws_bytes(B, H, W, ds)) {
-        set_error("gs_build_icp_target: workspace too small");
-        return GS_ERR_WORKSPACE_TOO_SMALL;
-    }
+    BucketWs w;
+    GS_REQUIRE_WS("gs_build_icp_target", ws, ws_bytes, bucket_layout(B, H, W, ds, ws, &w));
     hipStream_t st = (hipStream_t)stream;
     const int Wd = cdiv(W, ds), npix = cdiv(H, ds) * Wd;
-    char *p = (char *)ws;
-    int32_t *starts = (int32_t *)p; p += align_up(sizeof(int32_t) * (size_t)(B + 1), 256);
-    const size_t seg = align_up((size_t)B * npix * 4, 256);
-    int *cnt = (int *)p, *fill = (int *)(p + seg);
+    int32_t *starts = w.starts;
+    int *cnt = w.cnt, *fill = w.fill;
     const int64_t nbins = (int64_t)B * npix;
     hipLaunchKernelGGL(tgt_init_k, dim3(min(cdiv(nbins, 256), 1024)), dim3(256), 0, st, cnt, fill, nbins, rows, d_n_rows, B, starts);
     const int nb = max_rows > 0 ? min(cdiv(max_rows, 256), 1024) : 1;

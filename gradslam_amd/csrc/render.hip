@@ -224,10 +224,7 @@ int gs_render_map(const float *points, const float *normals, const float *colors
                   float *out_normals, float *out_colors, void *ws, size_t ws_bytes, gs_stream_t stream) {
     GS_REQUIRE(points && counts && poses && intrinsics && out_index && out_depth, "gs_render_map: NULL argument");
     GS_REQUIRE(render_shape_ok(B, Nmax, H, W), "gs_render_map: bad shape B=%d Nmax=%d H=%d W=%d", B, Nmax, H, W);
-    if (!ws || ws_bytes < gs_render_map_ws_bytes(B, H, W)) {
-        set_error("gs_render_map: workspace too small (%zu < %zu)", ws_bytes, gs_render_map_ws_bytes(B, H, W));
-        return GS_ERR_WORKSPACE_TOO_SMALL;
-    }
+    GS_REQUIRE_WS("gs_render_map", ws, ws_bytes, gs_render_map_ws_bytes(B, H, W));
     hipStream_t st = (hipStream_t)stream;
     RenderWs r;
     render_layout(B, H, W, ws, &r);
@@ -256,10 +253,7 @@ int gs_render_map_backward(const float *points, const int32_t *counts, int B, in
                            size_t ws_bytes, gs_stream_t stream) {
     GS_REQUIRE(points && counts && poses && index, "gs_render_map_backward: NULL argument");
     GS_REQUIRE(render_shape_ok(B, Nmax, H, W), "gs_render_map_backward: bad shape B=%d Nmax=%d H=%d W=%d", B, Nmax, H, W);
-    if (!ws || ws_bytes < gs_render_map_backward_ws_bytes(B, H, W)) {
-        set_error("gs_render_map_backward: workspace too small (%zu < %zu)", ws_bytes, gs_render_map_backward_ws_bytes(B, H, W));
-        return GS_ERR_WORKSPACE_TOO_SMALL;
-    }
+    GS_REQUIRE_WS("gs_render_map_backward", ws, ws_bytes, gs_render_map_backward_ws_bytes(B, H, W));
     hipStream_t st = (hipStream_t)stream;
     RenderBwdWs r;
     render_bwd_layout(B, H, W, ws, &r);

@@ -360,10 +360,7 @@ int gs_rgbd_rows(const float *tgt_depth, const float *tgt_rgb, const float *src_
     RGBD_REQUIRE_LAMBDA("gs_rgbd_rows");
     RGBD_REQUIRE_PARAMS("gs_rgbd_rows");
     const size_t need = gs_rgbd_odometry_ws_bytes(B, H, W, levels);
-    if (!ws || ws_bytes < need) {
-        set_error("gs_rgbd_rows: workspace too small (%zu < %zu)", ws_bytes, need);
-        return GS_ERR_WORKSPACE_TOO_SMALL;
-    }
+    GS_REQUIRE_WS("gs_rgbd_rows", ws, ws_bytes, need);
     hipStream_t st = (hipStream_t)stream;
     RgbdWs w;
     rgbd_layout(B, H, W, levels, ws, &w);
@@ -393,10 +390,7 @@ int gs_rgbd_odometry(const float *tgt_depth, const float *tgt_rgb, const float *
     for (int l = 0; l < levels; ++l)
         GS_REQUIRE(numiters[l] >= 0 && numiters[l] <= (1 << 20), "gs_rgbd_odometry: numiters[%d] must be in [0, 2^20], got %d", l, numiters[l]);
     const size_t need = gs_rgbd_odometry_ws_bytes(B, H, W, levels);
-    if (!ws || ws_bytes < need) {
-        set_error("gs_rgbd_odometry: workspace too small (%zu < %zu)", ws_bytes, need);
-        return GS_ERR_WORKSPACE_TOO_SMALL;
-    }
+    GS_REQUIRE_WS("gs_rgbd_odometry", ws, ws_bytes, need);
     hipStream_t st = (hipStream_t)stream;
     RgbdWs w;
     rgbd_layout(B, H, W, levels, ws, &w);

@@ -249,11 +249,6 @@ struct FuseWs {
     void *sub;
     size_t sub_bytes;
 };
-// the compaction's scratch for one H x W frame and, behind it, the room for its total: fusion.hip's append passes keep the
-// total at cws + compact_ws_bytes(HW)
-constexpr size_t kCompactTotalBytes = 256;
-static inline size_t compact_total_ws_bytes(int H, int W) { return gs_compact_ws_bytes((int64_t)H * W) + kCompactTotalBytes; }
-
 constexpr int kCtrWords = 64;  // counter block (zeroed by the maps kernel): ctr[0..], appended at +64, totals at +128
 static size_t fuse_layout(int B, int H, int W, int Nmax, void *ws, FuseWs *out) {
     const size_t npix = (size_t)B * H * W;
@@ -263,7 +258,7 @@ static size_t fuse_layout(int B, int H, int W, int Nmax, void *ws, FuseWs *out) 
     w.state = c.take(fusion_corr_state_bytes(B, H, W, Nmax));
     w.ctr = c.take<int32_t>((size_t)(kCtrWords + 2 * 64) * 4);
     w.appended = w.ctr + kCtrWords; w.totals = (int *)(w.ctr + kCtrWords + 64);
-    w.sub_bytes = compact_total_ws_bytes(H, W);
+    w.sub_bytes = append_scratch_bytes((int64_t)H * W);
     w.sub = c.take(w.sub_bytes);
     return c.off;
 }
@@ -279,7 +274,7 @@ static size_t fuse_bwd_layout(int B, int H, int W, void *ws, FuseBwdWs *out) {
     FuseBwdWs scratch, &w = out ? *out : scratch;
     w.V = c.take<float>(npix * 12); w.N = c.take<float>(npix * 12); w.gV = c.take<float>(npix * 12); w.gN = c.take<float>(npix * 12);
     w.alpha = c.take<float>(npix * 4); w.g_alpha = c.take<float>(npix * 4);
-    w.cws = c.take(compact_total_ws_bytes(H, W));
+    w.cws = c.take(append_scratch_bytes((int64_t)H * W));
     c.take(256);  // spare: nothing lives here, the size has always carried it
     return c.off;
 }
@@ -300,7 +295,7 @@ static size_t agg_layout(int B, int H, int W, void *ws, AggWs *out) {
     const size_t counters = c.off;
     w.overflow = c.take<int32_t>(4); w.appended = c.take<int32_t>((size_t)B * 4);
     w.counter_bytes = c.off - counters;
-    w.cws = c.take(compact_total_ws_bytes(H, W));
+    w.cws = c.take(append_scratch_bytes((int64_t)H * W));
     return c.off;
 }
 
@@ -448,10 +443,7 @@ int gs_slam_localize(const float *depth, const float *intrinsics, const float *p
     GS_REQUIRE(depth && intrinsics && prev_poses && map_points && map_normals && map_counts && gvertex && out_poses,
                "gs_slam_localize: NULL argument (gvertex is required, the other maps are optional)");
     GS_REQUIRE(B > 0 && H >= 2 && W >= 2 && ds > 0 && Nmax > 0 && numiters >= 0, "gs_slam_localize: bad shape");
-    if (!ws || ws_bytes < gs_slam_localize_ws_bytes(B, H, W, ds, Nmax)) {
-        set_error("gs_slam_localize: workspace too small (%zu < %zu)", ws_bytes, gs_slam_localize_ws_bytes(B, H, W, ds, Nmax));
-        return GS_ERR_WORKSPACE_TOO_SMALL;
-    }
+    GS_REQUIRE_WS("gs_slam_localize", ws, ws_bytes, gs_slam_localize_ws_bytes(B, H, W, ds, Nmax));
     hipStream_t st = (hipStream_t)stream;
     LocWs w;
     loc_layout(B, H, W, ds, Nmax, ws, &w);
@@ -499,10 +491,7 @@ static int pointfusion_update_impl(const float *depth, const float *rgb, const f
     GS_REQUIRE(depth && rgb && intrinsics && poses && map_points && map_normals && map_colors && map_ccounts && map_counts,
                "%s: NULL argument", name);
     GS_REQUIRE(B > 0 && B <= 60 && H >= 2 && W >= 2 && Nmax > 0, "%s: bad shape", name);
-    if (!ws || ws_bytes < gs_pointfusion_update_ws_bytes(B, H, W, Nmax)) {
-        set_error("%s: workspace too small (%zu < %zu)", name, ws_bytes, gs_pointfusion_update_ws_bytes(B, H, W, Nmax));
-        return GS_ERR_WORKSPACE_TOO_SMALL;
-    }
+    GS_REQUIRE_WS(name, ws, ws_bytes, gs_pointfusion_update_ws_bytes(B, H, W, Nmax));
     hipStream_t st = (hipStream_t)stream;
     FuseWs w;
     fuse_layout(B, H, W, Nmax, ws, &w);
@@ -554,7 +543,7 @@ int gs_pointfusion_update_taped(const float *depth, const float *rgb, const floa
                                 float *map_points, float *map_normals, float *map_colors, float *map_ccounts, int32_t *map_counts,
                                 int Nmax, float dist_th, float dot_th, float sigma, int32_t *stats, void *tape, size_t tape_bytes,
                                 void *ws, size_t ws_bytes, gs_stream_t stream) {
-    GS_REQUIRE(tape && tape_bytes >= gs_pointfusion_update_tape_bytes(B, H, W), "gs_pointfusion_update_taped: tape missing or too small");
+    GS_REQUIRE_TAPE("gs_pointfusion_update_taped", tape, tape_bytes, gs_pointfusion_update_tape_bytes(B, H, W), GS_ERR_INVALID_ARG);
     return pointfusion_update_impl(depth, rgb, intrinsics, poses, B, H, W, map_points, map_normals, map_colors, map_ccounts, map_counts,
                                    Nmax, dist_th, dot_th, sigma, stats, ws, ws_bytes, stream, tape, "gs_pointfusion_update_taped");
 }
@@ -573,11 +562,8 @@ int gs_pointfusion_update_backward(const float *depth, const float *rgb, const f
     GS_REQUIRE(depth && rgb && intrinsics && poses && map_points && map_normals && map_colors && map_ccounts && map_counts && tape &&
                    G_points && G_normals && G_colors && G_ccounts && g_vertex && g_gvertex && g_gnormal && g_rgb, "%s: NULL argument", name);
     GS_REQUIRE(B > 0 && B <= 60 && H >= 2 && W >= 2 && Nmax > 0, "%s: bad shape", name);
-    GS_REQUIRE(tape_bytes >= gs_pointfusion_update_tape_bytes(B, H, W), "%s: tape too small", name);
-    if (!ws || ws_bytes < gs_pointfusion_update_backward_ws_bytes(B, H, W)) {
-        set_error("%s: workspace too small (%zu < %zu)", name, ws_bytes, gs_pointfusion_update_backward_ws_bytes(B, H, W));
-        return GS_ERR_WORKSPACE_TOO_SMALL;
-    }
+    GS_REQUIRE_TAPE(name, tape, tape_bytes, gs_pointfusion_update_tape_bytes(B, H, W), GS_ERR_INVALID_ARG);
+    GS_REQUIRE_WS(name, ws, ws_bytes, gs_pointfusion_update_backward_ws_bytes(B, H, W));
     hipStream_t st = (hipStream_t)stream;
     const size_t npix = (size_t)B * H * W;
     FuseBwdWs w;
@@ -606,10 +592,7 @@ int gs_aggregate_update(const float *depth, const float *rgb, const float *intri
     const char *name = "gs_aggregate_update";
     GS_REQUIRE(depth && rgb && intrinsics && poses && map_points && map_normals && map_colors && map_counts, "%s: NULL argument", name);
     GS_REQUIRE(B > 0 && B <= 60 && H >= 2 && W >= 2 && Nmax > 0, "%s: bad shape", name);
-    if (!ws || ws_bytes < gs_aggregate_update_ws_bytes(B, H, W)) {
-        set_error("%s: workspace too small (%zu < %zu)", name, ws_bytes, gs_aggregate_update_ws_bytes(B, H, W));
-        return GS_ERR_WORKSPACE_TOO_SMALL;
-    }
+    GS_REQUIRE_WS(name, ws, ws_bytes, gs_aggregate_update_ws_bytes(B, H, W));
     hipStream_t st = (hipStream_t)stream;
     AggWs w;
     agg_layout(B, H, W, ws, &w);
@@ -645,12 +628,9 @@ int gs_slam_localize_taped(const float *depth, const float *gvertex, const float
     GS_REQUIRE(depth && gvertex && intrinsics && prev_poses && map_points && map_normals && map_counts && out_poses && tape,
                "gs_slam_localize_taped: NULL argument");
     GS_REQUIRE(B > 0 && H >= 2 && W >= 2 && ds > 0 && Nmax > 0 && numiters >= 0, "gs_slam_localize_taped: bad shape");
-    if (!ws || ws_bytes < gs_slam_localize_ws_bytes(B, H, W, ds, Nmax)) {
-        set_error("gs_slam_localize_taped: workspace too small (%zu < %zu)", ws_bytes, gs_slam_localize_ws_bytes(B, H, W, ds, Nmax));
-        return GS_ERR_WORKSPACE_TOO_SMALL;
-    }
-    GS_REQUIRE(tape_bytes >= gs_slam_localize_tape_bytes(B, H, W, ds, Nmax, numiters, use_grad_lm),
-               "gs_slam_localize_taped: tape too small");
+    GS_REQUIRE_WS("gs_slam_localize_taped", ws, ws_bytes, gs_slam_localize_ws_bytes(B, H, W, ds, Nmax));
+    GS_REQUIRE_TAPE("gs_slam_localize_taped", tape, tape_bytes, gs_slam_localize_tape_bytes(B, H, W, ds, Nmax, numiters, use_grad_lm),
+                    GS_ERR_INVALID_ARG);
     hipStream_t st = (hipStream_t)stream;
     LocWs w;
     loc_layout(B, H, W, ds, Nmax, ws, &w);
@@ -692,11 +672,8 @@ static int localize_backward(bool det, const float *prev_poses, int B, int H, in
     GS_REQUIRE(prev_poses && map_points && map_normals && tape && grad_out_poses && grad_gvertex && grad_prev_poses,
                "%s: NULL argument", name);
     GS_REQUIRE(B > 0 && H >= 2 && W >= 2 && ds > 0 && Nmax > 0 && numiters >= 0, "%s: bad shape", name);
-    if (!ws || ws_bytes < loc_bwd_layout(det, B, H, W, ds, Nmax, numiters, use_grad_lm, nullptr, nullptr)) {
-        set_error("%s: workspace too small", name);
-        return GS_ERR_WORKSPACE_TOO_SMALL;
-    }
-    GS_REQUIRE(tape_bytes >= gs_slam_localize_tape_bytes(B, H, W, ds, Nmax, numiters, use_grad_lm), "%s: tape too small", name);
+    GS_REQUIRE_WS(name, ws, ws_bytes, loc_bwd_layout(det, B, H, W, ds, Nmax, numiters, use_grad_lm, nullptr, nullptr));
+    GS_REQUIRE_TAPE(name, tape, tape_bytes, gs_slam_localize_tape_bytes(B, H, W, ds, Nmax, numiters, use_grad_lm), GS_ERR_INVALID_ARG);
     hipStream_t st = (hipStream_t)stream;
     LocTape tp;
     loc_tape_layout(B, H, W, ds, Nmax, numiters, use_grad_lm, (void *)tape, &tp);

@@ -720,10 +720,7 @@ int gs_tsdf_integrate_backward(const float *depth, const float *intrinsics, cons
     TSDF_REQUIRE_VOLUME("gs_tsdf_integrate_backward");
     TSDF_REQUIRE_FRAMES("gs_tsdf_integrate_backward");
     const size_t need = gs_tsdf_integrate_backward_ws_bytes(B, L, H, W);
-    if (!ws || ws_bytes < need) {
-        set_error("gs_tsdf_integrate_backward: workspace too small (%zu < %zu)", ws_bytes, need);
-        return GS_ERR_WORKSPACE_TOO_SMALL;
-    }
+    GS_REQUIRE_WS("gs_tsdf_integrate_backward", ws, ws_bytes, need);
     hipStream_t st = (hipStream_t)stream;
     const TsdfVol vol{nx, ny, nz, voxel_size, trunc, max_weight, origin};
     TsdfFrames fr = tsdf_frames(depth, nullptr, intrinsics, poses, L, H, W);
@@ -763,10 +760,7 @@ int gs_tsdf_integrate_backward_poses(const float *depth, const float *intrinsics
     TSDF_REQUIRE_VOLUME("gs_tsdf_integrate_backward_poses");
     TSDF_REQUIRE_FRAMES("gs_tsdf_integrate_backward_poses");
     const size_t need = gs_tsdf_integrate_backward_poses_ws_bytes(B, L, H, W, nx, ny, nz, g_color_out != nullptr);
-    if (!ws || ws_bytes < need) {
-        set_error("gs_tsdf_integrate_backward_poses: workspace too small (%zu < %zu)", ws_bytes, need);
-        return GS_ERR_WORKSPACE_TOO_SMALL;
-    }
+    GS_REQUIRE_WS("gs_tsdf_integrate_backward_poses", ws, ws_bytes, need);
     hipStream_t st = (hipStream_t)stream;
     const TsdfVol vol{nx, ny, nz, voxel_size, trunc, max_weight, origin};
     TsdfFrames fr = tsdf_frames(depth, nullptr, intrinsics, poses, L, H, W);
@@ -814,10 +808,7 @@ int gs_tsdf_extract(const float *tsdf, const float *weight, const float *color, 
     TSDF_REQUIRE_VOLUME("gs_tsdf_extract");
     GS_REQUIRE(min_weight == min_weight, "gs_tsdf_extract: min_weight must be a number");
     const size_t need = gs_tsdf_extract_ws_bytes(B, nx, ny, nz);
-    if (!ws || ws_bytes < need) {
-        set_error("gs_tsdf_extract: workspace too small (%zu < %zu)", ws_bytes, need);
-        return GS_ERR_WORKSPACE_TOO_SMALL;
-    }
+    GS_REQUIRE_WS("gs_tsdf_extract", ws, ws_bytes, need);
     hipStream_t st = (hipStream_t)stream;
     const TsdfVol vol{nx, ny, nz, voxel_size, 0.0f, 0.0f, origin};
     TsdfExtractWs w;
@@ -898,10 +889,7 @@ int gs_tsdf_raycast_backward(const float *tsdf, const float *weight, const float
     TSDF_REQUIRE_VOLUME("gs_tsdf_raycast_backward");
     TSDF_REQUIRE_CAST("gs_tsdf_raycast_backward");
     const size_t need = gs_tsdf_raycast_backward_ws_bytes(B, nx, ny, nz, color != nullptr);
-    if (!ws || ws_bytes < need) {
-        set_error("gs_tsdf_raycast_backward: workspace too small (%zu < %zu)", ws_bytes, need);
-        return GS_ERR_WORKSPACE_TOO_SMALL;
-    }
+    GS_REQUIRE_WS("gs_tsdf_raycast_backward", ws, ws_bytes, need);
     hipStream_t st = (hipStream_t)stream;
     const TsdfVol vol{nx, ny, nz, voxel_size, 0.0f, 0.0f, origin};
     const TsdfCast cast{intrinsics, poses, L, Ho, Wo, stride, 0, step, 0.0f, 0.0f, min_weight};
@@ -937,10 +925,7 @@ int gs_tsdf_raycast_backward_poses(const float *tsdf, const float *weight, const
     TSDF_REQUIRE_VOLUME("gs_tsdf_raycast_backward_poses");
     TSDF_REQUIRE_CAST("gs_tsdf_raycast_backward_poses");
     const size_t need = gs_tsdf_raycast_backward_poses_ws_bytes(B, nx, ny, nz, color != nullptr, L, height, width, stride);
-    if (!ws || ws_bytes < need) {
-        set_error("gs_tsdf_raycast_backward_poses: workspace too small (%zu < %zu)", ws_bytes, need);
-        return GS_ERR_WORKSPACE_TOO_SMALL;
-    }
+    GS_REQUIRE_WS("gs_tsdf_raycast_backward_poses", ws, ws_bytes, need);
     hipStream_t st = (hipStream_t)stream;
     const TsdfVol vol{nx, ny, nz, voxel_size, 0.0f, 0.0f, origin};
     const TsdfCast cast{intrinsics, poses, L, Ho, Wo, stride, 0, step, 0.0f, 0.0f, min_weight};

@@ -317,10 +317,7 @@ int gs_voxel_assign(const float *points, const int32_t *counts, int N_max, int B
     GS_REQUIRE(voxel_size > 0.0f && voxel_size < INFINITY, "gs_voxel_assign: voxel_size must be finite and positive, got %g",
                (double)voxel_size);
     GS_REQUIRE(std::isfinite(origin[0]) && std::isfinite(origin[1]) && std::isfinite(origin[2]), "gs_voxel_assign: origin must be finite");
-    if (!ws || ws_bytes < gs_voxel_assign_ws_bytes(B, N_max)) {
-        set_error("gs_voxel_assign: workspace too small (%zu < %zu)", ws_bytes, gs_voxel_assign_ws_bytes(B, N_max));
-        return GS_ERR_WORKSPACE_TOO_SMALL;
-    }
+    GS_REQUIRE_WS("gs_voxel_assign", ws, ws_bytes, gs_voxel_assign_ws_bytes(B, N_max));
     hipStream_t st = (hipStream_t)stream;
     VoxWs w;
     vox_assign_layout(B, N_max, ws, &w);
@@ -353,10 +350,7 @@ int gs_voxel_reduce(const float *x, const int32_t *counts, int N_max, int C, int
     GS_REQUIRE(vred_shape_ok(B, N_max, C, M_max), "gs_voxel_reduce: bad shape B=%d N_max=%d C=%d M_max=%d (1 <= C <= 64, M_max <= N_max)",
                B, N_max, C, M_max);
     GS_REQUIRE(mode >= 0 && mode <= 3, "gs_voxel_reduce: bad mode %d", mode);
-    if (!ws || ws_bytes < gs_voxel_reduce_ws_bytes(B, M_max, C)) {
-        set_error("gs_voxel_reduce: workspace too small (%zu < %zu)", ws_bytes, gs_voxel_reduce_ws_bytes(B, M_max, C));
-        return GS_ERR_WORKSPACE_TOO_SMALL;
-    }
+    GS_REQUIRE_WS("gs_voxel_reduce", ws, ws_bytes, gs_voxel_reduce_ws_bytes(B, M_max, C));
     hipStream_t st = (hipStream_t)stream;
     Fold w;
     const size_t bytes = vox_reduce_layout(B, M_max, C, ws, &w);

@@ -32,6 +32,32 @@ def test_library_exports_every_declared_symbol():
     assert lib.gs_abi_version() == 3
 
 
+def test_signatures_carry_the_header_types():
+    """_native.SIGNATURES is read from the header: one entry per class of type, spelled out here by hand from the
+    declarations (any pointer is c_void_p; gs_last_error's string is the one c_char_p)."""
+    from ctypes import c_char_p, c_float as f, c_int as i, c_int64 as i64, c_size_t as sz, c_void_p as p
+
+    expected = {
+        "gs_get_alpha": (i, [p, i64, f, f, p, p]),
+        "gs_knn1_ws_bytes": (sz, [i]),
+        "gs_last_error": (c_char_p, []),
+        "gs_set_grid_search": (None, [i]),
+        "gs_graph_stats": (i, [p]),
+        "gs_icp_point_to_plane_taped": (i, [p, p, i, p, p, p, i, p, i, f, f, i, f, f, f, f, p, p, p, p, sz, p, sz, p]),
+    }
+    for name, sig in expected.items():
+        assert _native.SIGNATURES[name] == sig, name
+
+
+def test_signature_reader_refuses_an_unknown_type():
+    """A spelling outside the six scalars is an error that names the declaration, never a guess."""
+    ok = _native.read_signatures("/* c */ int gs_a(const float *x, int64_t n);  // d\n#define Z 1\nvoid gs_b(void);\nsize_t gs_c();")
+    assert ok == {"gs_a": (_native.c_i, [_native.c_p, _native.c_i64]), "gs_b": (None, []), "gs_c": (_native.c_sz, [])}
+    for text in ("int gs_f(int n, double x);", "double gs_f(int n);", "int gs_f(unsigned int n);", "int gs_f(int);"):
+        with pytest.raises(ValueError, match="gs_f"):
+            _native.read_signatures(text)
+
+
 def test_icp_launch_geometry_fits_the_workspace():
     """The loops' association launch (host-side rule, no device work): 64-point tiles unless a test forces another size;
     the workspace holds a partial row for every block under every tile-size setting."""

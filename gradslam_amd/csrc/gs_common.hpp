@@ -9,6 +9,9 @@
 #include <stdint.h>
 #include <stdio.h>
 
+#include <algorithm>
+#include <type_traits>
+
 #include "../../include/gradslam_hip.h"
 
 namespace gs {
@@ -60,6 +63,10 @@ void set_error(const char *fmt, ...);
 
 static inline int cdiv(int64_t a, int64_t b) { return (int)((a + b - 1) / b); }
 static inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
+// blocks of `threads` for a grid-stride loop over `items`: at least one, at most `cap`
+static inline int rows_grid(int64_t items, int threads, int cap) {
+    return (int)std::min<int64_t>(std::max<int64_t>((items + threads - 1) / threads, 1), cap);
+}
 
 // Carves a workspace into 256-byte aligned pieces, in order; with a NULL base it only adds up the size.  A *_layout function
 // runs it once for both questions, so a workspace's size and its pointers cannot drift apart.
@@ -136,6 +143,32 @@ __device__ __forceinline__ int wave_sum_i(int v) {
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, kWave);
     return v;
+}
+// wave-uniform broadcast of lane l's value (v_readlane_b32: no memory round trip)
+__device__ __forceinline__ float rlane(float v, int l) {
+    return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), l));
+}
+// Minimum / maximum over the wave's 64 lanes, uniform result.  Inside each row of 16 lanes by DPP (quad_perm [1,0,3,2],
+// [2,3,0,1], row_half_mirror, row_mirror: eight VALU instructions, no LDS), across the four rows through scalars.  The
+// __shfl_xor butterfly these replace is six DEPENDENT ds_bpermute round trips (~0.3 us per reduction on the planner's path).
+template <int CTRL>
+__device__ __forceinline__ int dpp_i(int v) {
+    return __builtin_amdgcn_update_dpp(v, v, CTRL, 0xf, 0xf, false);
+}
+template <class Op>
+__device__ __forceinline__ float wave_reduce_f(float v, Op op) {
+    auto d = [](float x, auto tag) { return __int_as_float(dpp_i<decltype(tag)::value>(__float_as_int(x))); };
+    v = op(v, d(v, std::integral_constant<int, 0xB1>{}));
+    v = op(v, d(v, std::integral_constant<int, 0x4E>{}));
+    v = op(v, d(v, std::integral_constant<int, 0x141>{}));
+    v = op(v, d(v, std::integral_constant<int, 0x140>{}));
+    return op(op(rlane(v, 0), rlane(v, 16)), op(rlane(v, 32), rlane(v, 48)));
+}
+__device__ __forceinline__ float wave_min_f(float v) {
+    return wave_reduce_f(v, [](float a, float b) { return fminf(a, b); });
+}
+__device__ __forceinline__ float wave_max_f(float v) {
+    return wave_reduce_f(v, [](float a, float b) { return fmaxf(a, b); });
 }
 
 // exclusive prefix sum of one int per thread over a block of NT threads (NT multiple of 64,

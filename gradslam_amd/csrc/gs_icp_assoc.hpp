@@ -206,17 +206,7 @@ __device__ unsigned long long *g_diag = nullptr;
 #define GS_ACCUM(acc, t0)
 #endif
 
-// wave-uniform broadcast of lane l's value (v_readlane_b32: no memory round trip)
-__device__ __forceinline__ float rlane(float v, int l) {
-    return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), l));
-}
-// Minimum / maximum over the wave's 64 lanes, uniform result.  Inside each row of 16 lanes by DPP (quad_perm [1,0,3,2],
-// [2,3,0,1], row_half_mirror, row_mirror: eight VALU instructions, no LDS), across the four rows through scalars.  The
-// __shfl_xor butterfly these replace is six DEPENDENT ds_bpermute round trips (~0.3 us per reduction on the planner's path).
-template <int CTRL>
-__device__ __forceinline__ int dpp_i(int v) {
-    return __builtin_amdgcn_update_dpp(v, v, CTRL, 0xf, 0xf, false);
-}
+// (rlane, dpp_i and the float reductions wave_min_f / wave_max_f: gs_common.hpp)
 template <class Op>
 __device__ __forceinline__ int wave_reduce_i(int v, Op op) {
     v = op(v, dpp_i<0xB1>(v));
@@ -225,21 +215,6 @@ __device__ __forceinline__ int wave_reduce_i(int v, Op op) {
     v = op(v, dpp_i<0x140>(v));
     return op(op(__builtin_amdgcn_readlane(v, 0), __builtin_amdgcn_readlane(v, 16)),
               op(__builtin_amdgcn_readlane(v, 32), __builtin_amdgcn_readlane(v, 48)));
-}
-template <class Op>
-__device__ __forceinline__ float wave_reduce_f(float v, Op op) {
-    auto d = [](float x, auto tag) { return __int_as_float(dpp_i<decltype(tag)::value>(__float_as_int(x))); };
-    v = op(v, d(v, std::integral_constant<int, 0xB1>{}));
-    v = op(v, d(v, std::integral_constant<int, 0x4E>{}));
-    v = op(v, d(v, std::integral_constant<int, 0x141>{}));
-    v = op(v, d(v, std::integral_constant<int, 0x140>{}));
-    return op(op(rlane(v, 0), rlane(v, 16)), op(rlane(v, 32), rlane(v, 48)));
-}
-__device__ __forceinline__ float wave_min_f(float v) {
-    return wave_reduce_f(v, [](float a, float b) { return fminf(a, b); });
-}
-__device__ __forceinline__ float wave_max_f(float v) {
-    return wave_reduce_f(v, [](float a, float b) { return fmaxf(a, b); });
 }
 
 // Test the n (<= 64) target points held one per lane in (px,py,pz) with target index pj against the

@@ -37,8 +37,6 @@ __device__ __forceinline__ bool cham_contrib(const ChamIn &in, const unsigned lo
     return true;
 }
 
-static inline int cham_rows_grid(int cap0, int cap1) { return std::min(cdiv(std::max(std::max(cap0, cap1), 1), 256), 2048); }
-
 // the deterministic scatter (gs_metrics_det.hpp): -v of every source folded into its target's row of g_pts[1 - d] in exact
 // fixed point (gs_detfold.hpp); rows below the target's count are overwritten, the others untouched
 size_t chamfer_det_ws_bytes(int B, int cap0, int cap1);

@@ -45,7 +45,7 @@ int chamfer_det_scatter(const ChamIn &in, int B, const unsigned long long *keys_
                         const float *g1, float *g_a, float *g_b, void *ws, hipStream_t st, const char *name) {
     ChamDetWs w;
     cham_det_layout(B, in.cap[0], in.cap[1], ws, &w);
-    hipLaunchKernelGGL(cham_bwd_rows_k, dim3(cham_rows_grid(in.cap[0], in.cap[1]), B, 2), dim3(256), 0, st, in, keys_ab, keys_ba, g2, g1,
+    hipLaunchKernelGGL(cham_bwd_rows_k, dim3(rows_grid(std::max(in.cap[0], in.cap[1]), 256, 2048), B, 2), dim3(256), 0, st, in, keys_ab, keys_ba, g2, g1,
                        w.rows[0], w.rows[1]);
     GS_LAUNCH_CHECK(name);
     float *g_pts[2] = {g_a, g_b};

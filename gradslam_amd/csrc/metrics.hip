@@ -89,22 +89,7 @@ static size_t cham_layout(int B, int cap0, int cap1, void *ws, ChamWs *out) {
 __global__ __launch_bounds__(CHAM_T) void cham_bbox_k(ChamIn in, uint32_t *__restrict__ bacc) {
     const int s = blockIdx.z, b = blockIdx.y, n = cham_count(in, s, b);
     if ((int)(blockIdx.x * CHAM_T) >= n) return;
-    const float *pts = in.pts[s] + (int64_t)b * in.cap[s] * 3;
-    float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
-    for (int i = blockIdx.x * CHAM_T + threadIdx.x; i < n; i += gridDim.x * CHAM_T) {
-        const f3 p = ld3(pts, i);
-        lo[0] = fminf(lo[0], p.x); lo[1] = fminf(lo[1], p.y); lo[2] = fminf(lo[2], p.z);
-        hi[0] = fmaxf(hi[0], p.x); hi[1] = fmaxf(hi[1], p.y); hi[2] = fmaxf(hi[2], p.z);
-    }
-    uint32_t *acc = bacc + ((int64_t)s * gridDim.y + b) * 8;
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-        const float l = wave_min_f(lo[a]), h = wave_max_f(hi[a]);
-        if ((threadIdx.x & 63) == 0 && l <= h) {  // (a wave without rows: +inf > -inf)
-            atomicMax(acc + a, ord_bits(h));
-            atomicMax(acc + 3 + a, ~ord_bits(l));
-        }
-    }
+    cell_bbox(in.pts[s] + (int64_t)b * in.cap[s] * 3, n, [&] { return bacc + ((int64_t)s * gridDim.y + b) * 8; }, CHAM_T);
 }
 
 __global__ __launch_bounds__(CHAM_T) void cham_hist_k(ChamIn in, ChamWs w) {
@@ -127,28 +112,7 @@ __global__ __launch_bounds__(1024) void cham_scan_k(ChamIn in, ChamWs w) {
     const int s = blockIdx.y, b = blockIdx.x, n = cham_count(in, s, b);
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int ncells = min(cham_grid(w.bacc + ((int64_t)s * gridDim.x + b) * 8, n).ncells, w.hist_stride[s] - 1);
-    int32_t *hist = w.hist[s] + (int64_t)b * w.hist_stride[s];
-    const int seg = ((ncells + 15) / 16 + 63) & ~63;
-    const int c0 = min(wave * seg, ncells), c1 = min(c0 + seg, ncells);
-    int run = 0;
-    for (int c = c0; c < c1; c += 64) {
-        const int idx = c + lane;
-        const int v = idx < c1 ? hist[idx] : 0;
-        int inc = v;
-#pragma unroll
-        for (int off = 1; off < 64; off <<= 1) {
-            const int t = __shfl_up(inc, off, kWave);
-            if (lane >= off) inc += t;
-        }
-        if (idx < c1) hist[idx] = run + inc - v;
-        run += __shfl(inc, 63, kWave);
-    }
-    if (lane == 0) wtot[wave] = run;
-    __syncthreads();
-    int base = 0;
-    for (int k = 0; k < wave; ++k) base += wtot[k];
-    if (base)
-        for (int c = c0 + lane; c < c1; c += 64) hist[c] += base;
+    cell_hist_scan(w.hist[s] + (int64_t)b * w.hist_stride[s], ncells, wtot, lane, wave);
 }
 
 __global__ __launch_bounds__(CHAM_T) void cham_scatter_k(ChamIn in, ChamWs w) {
@@ -345,7 +309,7 @@ static int chamfer_backward_entry(const char *name, bool det, const float *a, co
     hipStream_t st = (hipStream_t)stream;
     const ChamIn in{{a, b}, {a_counts, b_counts}, {Na_max, Nb_max}};
     const unsigned long long *kab = (const unsigned long long *)keys_ab, *kba = (const unsigned long long *)keys_ba;
-    const dim3 grid(cham_rows_grid(Na_max, Nb_max), B, 2);
+    const dim3 grid(rows_grid(std::max(Na_max, Nb_max), CHAM_T, 2048), B, 2);
     if (det) {  // the fold overwrites the rows below the counts with the scattered part; the direct part is added to it
         const int rc = chamfer_det_scatter(in, B, kab, kba, g2, g1, g_a, g_b, ws, st, name);
         if (rc != GS_OK) return rc;

@@ -102,22 +102,7 @@ static size_t nb_layout(int B, int cap0, int cap1, int K, void *ws, NbWs *out) {
 __global__ __launch_bounds__(NB_T) void nb_bbox_k(NbIn in, uint32_t *__restrict__ bacc) {
     const int b = blockIdx.y, n = nb_count(in, 1, b);
     if ((int)(blockIdx.x * NB_T) >= n) return;
-    const float *pts = in.pts[1] + (int64_t)b * in.cap[1] * 3;
-    float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
-    for (int i = blockIdx.x * NB_T + threadIdx.x; i < n; i += gridDim.x * NB_T) {
-        const f3 p = ld3(pts, i);
-        lo[0] = fminf(lo[0], p.x); lo[1] = fminf(lo[1], p.y); lo[2] = fminf(lo[2], p.z);
-        hi[0] = fmaxf(hi[0], p.x); hi[1] = fmaxf(hi[1], p.y); hi[2] = fmaxf(hi[2], p.z);
-    }
-    uint32_t *acc = bacc + (int64_t)b * 8;
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-        const float l = wave_min_f(lo[a]), h = wave_max_f(hi[a]);
-        if ((threadIdx.x & 63) == 0 && l <= h) {  // (a wave without rows: +inf > -inf)
-            atomicMax(acc + a, ord_bits(h));
-            atomicMax(acc + 3 + a, ~ord_bits(l));
-        }
-    }
+    cell_bbox(in.pts[1] + (int64_t)b * in.cap[1] * 3, n, [&] { return bacc + (int64_t)b * 8; }, NB_T);
 }
 
 // an integer atomic maximum that most callers skip: the plain read may be stale, which only costs an atomic
@@ -175,28 +160,7 @@ __global__ __launch_bounds__(1024) void nb_scan_k(NbIn in, NbWs w) {
         }
     }
     const int ncells = min(G.ncells, w.hist_stride);
-    int32_t *hist = w.hist[s] + (int64_t)b * w.hist_stride;
-    const int seg = ((ncells + 15) / 16 + 63) & ~63;
-    const int c0 = min(wave * seg, ncells), c1 = min(c0 + seg, ncells);
-    int run = 0;
-    for (int c = c0; c < c1; c += 64) {
-        const int idx = c + lane;
-        const int v = idx < c1 ? hist[idx] : 0;
-        int inc = v;
-#pragma unroll
-        for (int off = 1; off < 64; off <<= 1) {
-            const int t = __shfl_up(inc, off, kWave);
-            if (lane >= off) inc += t;
-        }
-        if (idx < c1) hist[idx] = run + inc - v;
-        run += __shfl(inc, 63, kWave);
-    }
-    if (lane == 0) wtot[wave] = run;
-    __syncthreads();
-    int base = 0;
-    for (int k = 0; k < wave; ++k) base += wtot[k];
-    if (base)
-        for (int c = c0 + lane; c < c1; c += 64) hist[c] += base;
+    cell_hist_scan(w.hist[s] + (int64_t)b * w.hist_stride, ncells, wtot, lane, wave);
 }
 
 // grid (x: rows, y: batch element, z: side).  Every cell's cursor starts at the cell's first slot and ends at its end, which
@@ -494,7 +458,6 @@ __global__ __launch_bounds__(NB_T) void nb_normals_k(NbIn in, const unsigned lon
 static inline bool nb_shape_ok(int B, int cap0, int cap1, int K) {
     return B > 0 && B <= 65535 && cap0 > 0 && cap1 > 0 && K >= 1 && K <= NB_KMAX;
 }
-static inline int nb_rows_grid(int64_t items) { return (int)std::min<int64_t>(std::max<int64_t>((items + NB_T - 1) / NB_T, 1), 4096); }
 
 }  // namespace gs
 
@@ -560,10 +523,10 @@ int gs_knn_backward(const float *src, const int32_t *src_counts, int Ns_max, con
     a.g_tgt = g_tgt;
     a.lg = fold_lg((int64_t)Ns_max * K);  // no target row receives more terms
     GS_HIP(hipMemsetAsync(ws, 0, bytes, st), "gs_knn_backward/zero");
-    hipLaunchKernelGGL(nb_bwd_src_k, dim3(nb_rows_grid(Ns_max), B), dim3(NB_T), 0, st, a);
-    hipLaunchKernelGGL(nb_bwd_acc_k, dim3(nb_rows_grid((int64_t)Ns_max * K), B), dim3(NB_T), 0, st, a);
+    hipLaunchKernelGGL(nb_bwd_src_k, dim3(rows_grid(Ns_max, NB_T, 4096), B), dim3(NB_T), 0, st, a);
+    hipLaunchKernelGGL(nb_bwd_acc_k, dim3(rows_grid((int64_t)Ns_max * K, NB_T, 4096), B), dim3(NB_T), 0, st, a);
     GS_LAUNCH_CHECK("gs_knn_backward/fold");
-    hipLaunchKernelGGL(nb_bwd_finish_k, dim3(nb_rows_grid((int64_t)Nt_max * 3), B), dim3(NB_T), 0, st, a);
+    hipLaunchKernelGGL(nb_bwd_finish_k, dim3(rows_grid((int64_t)Nt_max * 3, NB_T, 4096), B), dim3(NB_T), 0, st, a);
     GS_LAUNCH_CHECK("gs_knn_backward/finish");
     return GS_OK;
 }
@@ -577,7 +540,7 @@ int gs_knn_normals(const float *src, const int32_t *src_counts, int Ns_max, cons
     GS_REQUIRE(mode >= 0 && mode <= 2, "gs_knn_normals: bad orientation mode %d", mode);
     GS_REQUIRE(mode == 0 || orient, "gs_knn_normals: orientation mode %d needs its viewpoint / reference normals", mode);
     const NbIn in{{src, tgt}, {src_counts, tgt_counts}, {Ns_max, Nt_max}, K, 0};
-    hipLaunchKernelGGL(nb_normals_k, dim3(nb_rows_grid(Ns_max), B), dim3(NB_T), 0, (hipStream_t)stream, in,
+    hipLaunchKernelGGL(nb_normals_k, dim3(rows_grid(Ns_max, NB_T, 4096), B), dim3(NB_T), 0, (hipStream_t)stream, in,
                        (const unsigned long long *)keys, mode, orient, normals, variation);
     GS_LAUNCH_CHECK("gs_knn_normals");
     return GS_OK;

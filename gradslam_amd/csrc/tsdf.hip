@@ -19,7 +19,8 @@
 //      gs_tsdf_raycast_backward: one thread per pixel recomputes its two samples and its hit from the tape k_end; a voxel's
 //      adjoint is a sum over many pixels: the same fold, over the voxels
 //        memset -> tsdf_raycast_bwd_k<MAX> -> tsdf_raycast_bwd_k<ACC> -> tsdf_cast_finish_k
-//   P  gs_tsdf_integrate_backward_poses / gs_tsdf_raycast_backward_poses: the same passes; the second one (POSE) also reduces a
+//   P  gs_tsdf_integrate_backward_poses / gs_tsdf_raycast_backward_poses: the same passes from the same host drivers
+//      (tsdf_integrate_backward_run, tsdf_raycast_backward_run); with g_poses the second one (POSE) also reduces a
 //      camera's pose sums (4 per frame over the voxels; 12 over the pixels) wave by wave and block by block into one row per
 //      block, which tsdf_pose_finish_k / tsdf_cast_pose_finish_k fold in a fixed order (gs_tsdf.hpp: the pose sums): plain fp32,
 //      no atomics.  Outputs nobody asks for drop their passes (FOLD = false: no maximum pass, no fold, no finish).
@@ -113,28 +114,22 @@ __global__ __launch_bounds__(TSDF_T) void tsdf_integrate_k(TsdfVol vol, TsdfFram
 }
 
 // ------------------------------------------------------------------ reverse pass of the integration
-// the fold of one chunk: per pixel (b, l, h, w) of the chunk 4 sums (depth, r, g, b)
-static inline size_t tsdf_fold_layout(int B, int L, int H, int W, void *ws, Fold *out) {
-    Carve c{(char *)ws};
-    const Fold f = fold_carve(c, (size_t)B * std::min(L, TSDF_CHUNK) * H * W, 4);
-    if (out) *out = f;
-    return c.off;
-}
-
-// gs_tsdf_integrate_backward_poses: the fold | one row of 4 pose sums per (b, frame of the chunk, block of 256 voxels) | with more
-// than one chunk, the adjoints carried from chunk to chunk when the caller passes no g_tsdf_in / g_color_in to carry them in
-struct TsdfPoseWs {
+// The fold of one chunk: per pixel (b, l, h, w) of the chunk 4 sums (depth, r, g, b).  With `poses` (the workspace of
+// gs_tsdf_integrate_backward_poses; nvox and has_color count for it alone) behind it: one row of 4 pose sums per (b, frame of the
+// chunk, block of 256 voxels) | with more than one chunk, the adjoints carried from chunk to chunk when the caller passes no
+// g_tsdf_in / g_color_in to carry them in
+struct TsdfBwdWs {
     Fold fold;
     size_t fold_bytes;
     float *psum, *carry_t, *carry_c;
 };
-static inline size_t tsdf_pose_fold_layout(int B, int L, int H, int W, int64_t nvox, bool has_color, void *ws, TsdfPoseWs *out) {
+static inline size_t tsdf_bwd_layout(int B, int L, int H, int W, bool poses, int64_t nvox, bool has_color, void *ws, TsdfBwdWs *out) {
     Carve c{(char *)ws};
-    TsdfPoseWs scratch, &r = out ? *out : scratch;
+    TsdfBwdWs scratch, &r = out ? *out : scratch;
     r.fold = fold_carve(c, (size_t)B * std::min(L, TSDF_CHUNK) * H * W, 4);
     r.fold_bytes = c.off;
-    r.psum = c.take<float>(sizeof(float) * 4 * (size_t)B * std::min(L, TSDF_CHUNK) * cdiv(nvox, TSDF_T));
-    const bool carry = L > TSDF_CHUNK;
+    const bool carry = poses && L > TSDF_CHUNK;
+    r.psum = poses ? c.take<float>(sizeof(float) * 4 * (size_t)B * std::min(L, TSDF_CHUNK) * cdiv(nvox, TSDF_T)) : nullptr;
     r.carry_t = carry ? c.take<float>(sizeof(float) * (size_t)B * nvox) : nullptr;
     r.carry_c = carry && has_color ? c.take<float>(sizeof(float) * 3 * (size_t)B * nvox) : nullptr;
     return c.off;
@@ -511,21 +506,19 @@ __global__ __launch_bounds__(TSDF_T) void tsdf_raycast_k(TsdfVol vol, TsdfCast c
     k_end[pix] = kend;
 }
 
-// the fold of the reverse pass: per voxel (b, j) nch sums (tsdf; r, g, b)
-static inline size_t tsdf_cast_fold_layout(int B, int64_t nvox, int nch, void *ws, Fold *out) {
+// The fold of the reverse pass: per voxel (b, j) nch sums (tsdf; r, g, b).  With `poses` (the workspace of
+// gs_tsdf_raycast_backward_poses; L and tiles count for it alone) behind it: one row of 12 pose sums per (b, l, 16x16 tile)
+struct TsdfCastBwdWs {
+    Fold fold;
+    size_t fold_bytes;
+    float *psum;
+};
+static inline size_t tsdf_cast_bwd_layout(int B, int64_t nvox, int nch, bool poses, int L, int tiles, void *ws, TsdfCastBwdWs *out) {
     Carve c{(char *)ws};
-    const Fold f = fold_carve(c, (size_t)B * nvox, nch);
-    if (out) *out = f;
-    return c.off;
-}
-// gs_tsdf_raycast_backward_poses: the fold | one row of 12 pose sums per (b, l, 16x16 tile)
-static inline size_t tsdf_cast_pose_layout(int B, int64_t nvox, int nch, int L, int tiles, void *ws, Fold *out, float **psum, size_t *fold_bytes) {
-    Carve c{(char *)ws};
-    const Fold f = fold_carve(c, (size_t)B * nvox, nch);
-    if (out) *out = f;
-    if (fold_bytes) *fold_bytes = c.off;
-    float *p = c.take<float>(sizeof(float) * 12 * (size_t)B * L * tiles);
-    if (psum) *psum = p;
+    TsdfCastBwdWs scratch, &r = out ? *out : scratch;
+    r.fold = fold_carve(c, (size_t)B * nvox, nch);
+    r.fold_bytes = c.off;
+    r.psum = poses ? c.take<float>(sizeof(float) * 12 * (size_t)B * L * tiles) : nullptr;
     return c.off;
 }
 // one term of voxel p: into the maximum, or into the sums
@@ -668,13 +661,19 @@ static inline TsdfFrames tsdf_frames(const float *depth, const float *rgb, const
 
 using namespace gs;
 
-#define TSDF_REQUIRE_VOLUME(name)                                                                                                       \
-    GS_REQUIRE(tsdf_vol_ok(B, nx, ny, nz), name ": bad volume B=%d dims=(%d, %d, %d) (1 <= B <= 65535, nx ny nz <= 2^29)", B, nx, ny, nz); \
-    GS_REQUIRE(tsdf_pos(voxel_size), name ": voxel_size must be finite and positive, got %g", (double)voxel_size)
-#define TSDF_REQUIRE_FRAMES(name)                                                                                        \
-    GS_REQUIRE(L > 0 && H > 0 && W > 0 && (int64_t)H * W <= INT32_MAX, name ": bad frames L=%d H=%d W=%d", L, H, W);      \
-    GS_REQUIRE(tsdf_pos(trunc) && tsdf_pos(max_weight), name ": trunc and max_weight must be finite and positive, got %g and %g", \
+// (name: a const char *, so that the drivers two entries share can pass their caller's on)
+#define TSDF_REQUIRE_VOLUME(name)                                                                                                          \
+    GS_REQUIRE(tsdf_vol_ok(B, nx, ny, nz), "%s: bad volume B=%d dims=(%d, %d, %d) (1 <= B <= 65535, nx ny nz <= 2^29)", name, B, nx, ny, nz); \
+    GS_REQUIRE(tsdf_pos(voxel_size), "%s: voxel_size must be finite and positive, got %g", name, (double)voxel_size)
+#define TSDF_REQUIRE_FRAMES(name)                                                                                           \
+    GS_REQUIRE(L > 0 && H > 0 && W > 0 && (int64_t)H * W <= INT32_MAX, "%s: bad frames L=%d H=%d W=%d", name, L, H, W);      \
+    GS_REQUIRE(tsdf_pos(trunc) && tsdf_pos(max_weight), "%s: trunc and max_weight must be finite and positive, got %g and %g", name, \
                (double)trunc, (double)max_weight)
+// "<name>/<stage>": what GS_HIP and GS_LAUNCH_CHECK report from a shared driver (built only when they report)
+struct TsdfStage {
+    char text[64];
+    TsdfStage(const char *name, const char *stage) { snprintf(text, sizeof text, "%s/%s", name, stage); }
+};
 
 extern "C" {
 
@@ -704,9 +703,55 @@ int gs_tsdf_integrate(const float *depth, const float *rgb, const float *intrins
     return GS_OK;
 }
 
+// The reverse pass of the integration behind both entries (their NULL rules come first).  g_poses == NULL: the second pass is
+// tsdf_bwd_k<ACC>, without the pose sums and their finish.  What nobody asked for is not computed; adjoints the caller gives no
+// g_tsdf_in / g_color_in for are carried from chunk to chunk in the workspace.
+static int tsdf_integrate_backward_run(const char *name, const float *depth, const float *intrinsics, const float *poses, int B, int L, int H,
+                                       int W, int nx, int ny, int nz, float voxel_size, const float *origin, float trunc, float max_weight,
+                                       const float *weight_in, const float *g_tsdf_out, const float *g_color_out, float *g_tsdf_in,
+                                       float *g_color_in, float *g_depth, float *g_rgb, float *g_poses /* may be NULL */, void *ws,
+                                       size_t ws_bytes, size_t need /* the entry's own size query */, gs_stream_t stream) {
+    TSDF_REQUIRE_VOLUME(name);
+    TSDF_REQUIRE_FRAMES(name);
+    GS_REQUIRE_WS(name, ws, ws_bytes, need);
+    hipStream_t st = (hipStream_t)stream;
+    const bool pose = g_poses != nullptr;
+    const TsdfVol vol{nx, ny, nz, voxel_size, trunc, max_weight, origin};
+    const int64_t nvox = tsdf_nvox(vol), HW = (int64_t)H * W;
+    TsdfFrames fr = tsdf_frames(depth, nullptr, intrinsics, poses, L, H, W);
+    TsdfBwdWs w;
+    tsdf_bwd_layout(B, L, H, W, pose, nvox, g_color_out != nullptr, ws, &w);
+    const bool fold = g_depth || g_rgb, color = g_color_out && (g_color_in || g_rgb);
+    float *dst_t = g_tsdf_in ? g_tsdf_in : w.carry_t, *dst_c = color ? (g_color_in ? g_color_in : w.carry_c) : nullptr;
+    const int lg = fold_lg(nvox);  // a pixel receives at most one term per voxel
+    const int nblk = cdiv(nvox, TSDF_T);
+    const dim3 grid(nblk, B);
+    const int last = (L - 1) / TSDF_CHUNK * TSDF_CHUNK;
+    auto second = !pose ? tsdf_bwd_k<true> : (fold ? tsdf_bwd_k<true, true, true> : tsdf_bwd_k<true, true, false>);
+    for (int l0 = last; l0 >= 0; l0 -= TSDF_CHUNK) {  // the last chunk starts from the upstream adjoints, the others from the carried ones
+        fr.l0 = l0;
+        fr.Lc = std::min(TSDF_CHUNK, L - l0);
+        const float *gt = l0 == last ? g_tsdf_out : dst_t, *gc = color ? (l0 == last ? g_color_out : dst_c) : nullptr;
+        if (fold) {
+            GS_HIP(hipMemsetAsync(ws, 0, w.fold_bytes, st), TsdfStage(name, "zero").text);
+            hipLaunchKernelGGL(tsdf_bwd_k<false>, grid, dim3(TSDF_T), 0, st, vol, fr, weight_in, gt, gc, dst_t, dst_c, w.fold, lg);
+        }
+        hipLaunchKernelGGL(second, grid, dim3(TSDF_T), 0, st, vol, fr, weight_in, gt, gc, dst_t, dst_c, w.fold, lg, w.psum);
+        GS_LAUNCH_CHECK(TsdfStage(name, "fold").text);
+        if (fold)
+            hipLaunchKernelGGL(tsdf_fold_finish_k, dim3(std::min(cdiv((int64_t)B * fr.Lc * HW, TSDF_T), 4096)), dim3(TSDF_T), 0, st, w.fold, lg,
+                               B, L, l0, fr.Lc, HW, g_depth, g_rgb);
+        if (pose)
+            hipLaunchKernelGGL(tsdf_pose_finish_k, dim3(fr.Lc, B), dim3(TSDF_POSE_T), 0, st, (const float *)w.psum, nblk, poses, L, l0, fr.Lc,
+                               g_poses);
+        GS_LAUNCH_CHECK(TsdfStage(name, "finish").text);
+    }
+    return GS_OK;
+}
+
 size_t gs_tsdf_integrate_backward_ws_bytes(int B, int L, int H, int W) {
     if (B <= 0 || B > 65535 || L <= 0 || H <= 0 || W <= 0) return 0;
-    return tsdf_fold_layout(B, L, H, W, nullptr, nullptr);
+    return tsdf_bwd_layout(B, L, H, W, false, 0, false, nullptr, nullptr);
 }
 
 int gs_tsdf_integrate_backward(const float *depth, const float *intrinsics, const float *poses, int B, int L, int H, int W, int nx, int ny,
@@ -717,37 +762,14 @@ int gs_tsdf_integrate_backward(const float *depth, const float *intrinsics, cons
                "gs_tsdf_integrate_backward: NULL argument");
     GS_REQUIRE((g_color_out != nullptr) == (g_color_in != nullptr) && (g_color_out != nullptr) == (g_rgb != nullptr),
                "gs_tsdf_integrate_backward: g_color_out, g_color_in and g_rgb go together");
-    TSDF_REQUIRE_VOLUME("gs_tsdf_integrate_backward");
-    TSDF_REQUIRE_FRAMES("gs_tsdf_integrate_backward");
-    const size_t need = gs_tsdf_integrate_backward_ws_bytes(B, L, H, W);
-    GS_REQUIRE_WS("gs_tsdf_integrate_backward", ws, ws_bytes, need);
-    hipStream_t st = (hipStream_t)stream;
-    const TsdfVol vol{nx, ny, nz, voxel_size, trunc, max_weight, origin};
-    TsdfFrames fr = tsdf_frames(depth, nullptr, intrinsics, poses, L, H, W);
-    Fold fold;
-    tsdf_fold_layout(B, L, H, W, ws, &fold);
-    const int64_t nvox = tsdf_nvox(vol), HW = (int64_t)H * W;
-    const int lg = fold_lg(nvox);  // a pixel receives at most one term per voxel
-    const dim3 grid(cdiv(nvox, TSDF_T), B);
-    const int last = (L - 1) / TSDF_CHUNK * TSDF_CHUNK;
-    for (int l0 = last; l0 >= 0; l0 -= TSDF_CHUNK) {  // the last chunk starts from the upstream adjoints, the others from the carried ones
-        fr.l0 = l0;
-        fr.Lc = std::min(TSDF_CHUNK, L - l0);
-        const float *gt = l0 == last ? g_tsdf_out : g_tsdf_in, *gc = l0 == last ? g_color_out : g_color_in;
-        GS_HIP(hipMemsetAsync(ws, 0, need, st), "gs_tsdf_integrate_backward/zero");
-        hipLaunchKernelGGL(tsdf_bwd_k<false>, grid, dim3(TSDF_T), 0, st, vol, fr, weight_in, gt, gc, g_tsdf_in, g_color_in, fold, lg);
-        hipLaunchKernelGGL(tsdf_bwd_k<true>, grid, dim3(TSDF_T), 0, st, vol, fr, weight_in, gt, gc, g_tsdf_in, g_color_in, fold, lg);
-        GS_LAUNCH_CHECK("gs_tsdf_integrate_backward/fold");
-        hipLaunchKernelGGL(tsdf_fold_finish_k, dim3(std::min(cdiv((int64_t)B * fr.Lc * HW, TSDF_T), 4096)), dim3(TSDF_T), 0, st, fold, lg, B, L,
-                           l0, fr.Lc, HW, g_depth, g_rgb);
-        GS_LAUNCH_CHECK("gs_tsdf_integrate_backward/finish");
-    }
-    return GS_OK;
+    return tsdf_integrate_backward_run("gs_tsdf_integrate_backward", depth, intrinsics, poses, B, L, H, W, nx, ny, nz, voxel_size, origin,
+                                       trunc, max_weight, weight_in, g_tsdf_out, g_color_out, g_tsdf_in, g_color_in, g_depth, g_rgb, nullptr,
+                                       ws, ws_bytes, gs_tsdf_integrate_backward_ws_bytes(B, L, H, W), stream);
 }
 
 size_t gs_tsdf_integrate_backward_poses_ws_bytes(int B, int L, int H, int W, int nx, int ny, int nz, int has_color) {
     if (!tsdf_vol_ok(B, nx, ny, nz) || L <= 0 || H <= 0 || W <= 0) return 0;
-    return tsdf_pose_fold_layout(B, L, H, W, (int64_t)nx * ny * nz, has_color != 0, nullptr, nullptr);
+    return tsdf_bwd_layout(B, L, H, W, true, (int64_t)nx * ny * nz, has_color != 0, nullptr, nullptr);
 }
 
 int gs_tsdf_integrate_backward_poses(const float *depth, const float *intrinsics, const float *poses, int B, int L, int H, int W, int nx,
@@ -757,42 +779,10 @@ int gs_tsdf_integrate_backward_poses(const float *depth, const float *intrinsics
                                      gs_stream_t stream) {
     GS_REQUIRE(depth && intrinsics && poses && origin && weight_in && g_tsdf_out && g_poses, "gs_tsdf_integrate_backward_poses: NULL argument");
     GS_REQUIRE(g_color_out || (!g_color_in && !g_rgb), "gs_tsdf_integrate_backward_poses: g_color_in and g_rgb need g_color_out");
-    TSDF_REQUIRE_VOLUME("gs_tsdf_integrate_backward_poses");
-    TSDF_REQUIRE_FRAMES("gs_tsdf_integrate_backward_poses");
-    const size_t need = gs_tsdf_integrate_backward_poses_ws_bytes(B, L, H, W, nx, ny, nz, g_color_out != nullptr);
-    GS_REQUIRE_WS("gs_tsdf_integrate_backward_poses", ws, ws_bytes, need);
-    hipStream_t st = (hipStream_t)stream;
-    const TsdfVol vol{nx, ny, nz, voxel_size, trunc, max_weight, origin};
-    TsdfFrames fr = tsdf_frames(depth, nullptr, intrinsics, poses, L, H, W);
-    const int64_t nvox = tsdf_nvox(vol), HW = (int64_t)H * W;
-    TsdfPoseWs w;
-    tsdf_pose_fold_layout(B, L, H, W, nvox, g_color_out != nullptr, ws, &w);
-    const bool fold = g_depth || g_rgb, color = g_color_out && (g_color_in || g_rgb);  // what nobody asked for is not computed
-    float *dst_t = g_tsdf_in ? g_tsdf_in : w.carry_t, *dst_c = color ? (g_color_in ? g_color_in : w.carry_c) : nullptr;
-    const int lg = fold_lg(nvox);
-    const int nblk = cdiv(nvox, TSDF_T);
-    const dim3 grid(nblk, B);
-    const int last = (L - 1) / TSDF_CHUNK * TSDF_CHUNK;
-    auto second = fold ? tsdf_bwd_k<true, true, true> : tsdf_bwd_k<true, true, false>;
-    for (int l0 = last; l0 >= 0; l0 -= TSDF_CHUNK) {  // as gs_tsdf_integrate_backward, with the pose sums on the second pass
-        fr.l0 = l0;
-        fr.Lc = std::min(TSDF_CHUNK, L - l0);
-        const float *gt = l0 == last ? g_tsdf_out : dst_t, *gc = color ? (l0 == last ? g_color_out : dst_c) : nullptr;
-        if (fold) {
-            GS_HIP(hipMemsetAsync(ws, 0, w.fold_bytes, st), "gs_tsdf_integrate_backward_poses/zero");
-            hipLaunchKernelGGL(tsdf_bwd_k<false>, grid, dim3(TSDF_T), 0, st, vol, fr, weight_in, gt, gc, dst_t, dst_c, w.fold, lg);
-        }
-        hipLaunchKernelGGL(second, grid, dim3(TSDF_T), 0, st, vol, fr, weight_in, gt, gc, dst_t, dst_c, w.fold, lg, w.psum);
-        GS_LAUNCH_CHECK("gs_tsdf_integrate_backward_poses/fold");
-        if (fold) {
-            hipLaunchKernelGGL(tsdf_fold_finish_k, dim3(std::min(cdiv((int64_t)B * fr.Lc * HW, TSDF_T), 4096)), dim3(TSDF_T), 0, st, w.fold, lg,
-                               B, L, l0, fr.Lc, HW, g_depth, g_rgb);
-        }
-        hipLaunchKernelGGL(tsdf_pose_finish_k, dim3(fr.Lc, B), dim3(TSDF_POSE_T), 0, st, (const float *)w.psum, nblk, poses, L, l0, fr.Lc,
-                           g_poses);
-        GS_LAUNCH_CHECK("gs_tsdf_integrate_backward_poses/finish");
-    }
-    return GS_OK;
+    return tsdf_integrate_backward_run("gs_tsdf_integrate_backward_poses", depth, intrinsics, poses, B, L, H, W, nx, ny, nz, voxel_size,
+                                       origin, trunc, max_weight, weight_in, g_tsdf_out, g_color_out, g_tsdf_in, g_color_in, g_depth, g_rgb,
+                                       g_poses, ws, ws_bytes,
+                                       gs_tsdf_integrate_backward_poses_ws_bytes(B, L, H, W, nx, ny, nz, g_color_out != nullptr), stream);
 }
 
 size_t gs_tsdf_extract_ws_bytes(int B, int nx, int ny, int nz) {
@@ -845,17 +835,17 @@ int gs_tsdf_extract_backward(const float *tsdf, const float *color, int B, int n
 }
 
 // the arguments a cast and its reverse pass share; kmax: the bound of a thread's loop
-#define TSDF_REQUIRE_CAST(name)                                                                                                             \
-    GS_REQUIRE(L > 0 && L <= 65535 && height > 0 && width > 0 && (int64_t)height * width <= INT32_MAX, name ": bad frames L=%d H=%d W=%d", L, \
-               height, width);                                                                                                              \
-    GS_REQUIRE(stride >= 1, name ": stride must be at least 1, got %d", stride);                                                            \
-    const int Ho = (int)(((int64_t)height + stride - 1) / stride), Wo = (int)(((int64_t)width + stride - 1) / stride);                      \
-    GS_REQUIRE((int64_t)cdiv(Ho, 16) * cdiv(Wo, 16) <= TSDF_CAST_TILES, name ": %d x %d output pixels need more than 2^22 tiles of 16 x 16", \
-               Ho, Wo);                                                                                                                     \
-    GS_REQUIRE(tsdf_pos(step), name ": step must be finite and positive, got %g", (double)step);                                            \
-    GS_REQUIRE(min_weight == min_weight, name ": min_weight must be a number");                                                             \
-    const double span = ((double)nx + ny + nz) * (double)voxel_size / (double)step;                                                         \
-    GS_REQUIRE(span <= 1048576.0, name ": (nx + ny + nz) voxel_size / step = %g exceeds 2^20 samples per ray", span)
+#define TSDF_REQUIRE_CAST(name)                                                                                                                \
+    GS_REQUIRE(L > 0 && L <= 65535 && height > 0 && width > 0 && (int64_t)height * width <= INT32_MAX, "%s: bad frames L=%d H=%d W=%d", name, L, \
+               height, width);                                                                                                                 \
+    GS_REQUIRE(stride >= 1, "%s: stride must be at least 1, got %d", name, stride);                                                            \
+    const int Ho = (int)(((int64_t)height + stride - 1) / stride), Wo = (int)(((int64_t)width + stride - 1) / stride);                         \
+    GS_REQUIRE((int64_t)cdiv(Ho, 16) * cdiv(Wo, 16) <= TSDF_CAST_TILES, "%s: %d x %d output pixels need more than 2^22 tiles of 16 x 16", name, \
+               Ho, Wo);                                                                                                                        \
+    GS_REQUIRE(tsdf_pos(step), "%s: step must be finite and positive, got %g", name, (double)step);                                            \
+    GS_REQUIRE(min_weight == min_weight, "%s: min_weight must be a number", name);                                                             \
+    const double span = ((double)nx + ny + nz) * (double)voxel_size / (double)step;                                                            \
+    GS_REQUIRE(span <= 1048576.0, "%s: (nx + ny + nz) voxel_size / step = %g exceeds 2^20 samples per ray", name, span)
 
 int gs_tsdf_raycast(const float *tsdf, const float *weight, const float *color, int B, int nx, int ny, int nz, float voxel_size,
                     const float *origin, const float *intrinsics, const float *poses, int L, int height, int width, int stride, float step,
@@ -875,9 +865,43 @@ int gs_tsdf_raycast(const float *tsdf, const float *weight, const float *color, 
     return GS_OK;
 }
 
+// The reverse pass of a cast behind both entries (their NULL rules come first).  g_poses == NULL: the second pass is
+// tsdf_raycast_bwd_k<ACC>, without the pose sums and their finish; g_tsdf == NULL (the pose entry allows it): no fold.
+static int tsdf_raycast_backward_run(const char *name, const float *tsdf, const float *weight, const float *color, int B, int nx, int ny,
+                                     int nz, float voxel_size, const float *origin, const float *intrinsics, const float *poses, int L,
+                                     int height, int width, int stride, float step, float min_weight, const int32_t *k_end,
+                                     const float *g_depth, const float *g_rgb, float *g_tsdf /* may be NULL */, float *g_color,
+                                     float *g_poses /* may be NULL */, void *ws, size_t ws_bytes, size_t need /* the entry's own size query */,
+                                     gs_stream_t stream) {
+    TSDF_REQUIRE_VOLUME(name);
+    TSDF_REQUIRE_CAST(name);
+    GS_REQUIRE_WS(name, ws, ws_bytes, need);
+    hipStream_t st = (hipStream_t)stream;
+    const TsdfVol vol{nx, ny, nz, voxel_size, 0.0f, 0.0f, origin};
+    const TsdfCast cast{intrinsics, poses, L, Ho, Wo, stride, 0, step, 0.0f, 0.0f, min_weight};
+    const int tiles = cdiv(Ho, 16) * cdiv(Wo, 16);
+    TsdfCastBwdWs w;
+    tsdf_cast_bwd_layout(B, tsdf_nvox(vol), color ? 4 : 1, g_poses != nullptr, L, tiles, ws, &w);
+    const int lg = fold_lg(2 * (int64_t)L * Ho * Wo);  // a voxel receives at most two terms per pixel of its batch element
+    const int64_t total = (int64_t)B * tsdf_nvox(vol);
+    const dim3 grid(tiles, L, B);
+    if (g_tsdf) {
+        GS_HIP(hipMemsetAsync(ws, 0, w.fold_bytes, st), TsdfStage(name, "zero").text);
+        hipLaunchKernelGGL(tsdf_raycast_bwd_k<false>, grid, dim3(TSDF_T), 0, st, vol, cast, tsdf, weight, color, k_end, g_depth, g_rgb, w.fold, lg);
+    }
+    auto second = !g_poses ? tsdf_raycast_bwd_k<true> : (g_tsdf ? tsdf_raycast_bwd_k<true, true, true> : tsdf_raycast_bwd_k<true, true, false>);
+    hipLaunchKernelGGL(second, grid, dim3(TSDF_T), 0, st, vol, cast, tsdf, weight, color, k_end, g_depth, g_rgb, w.fold, lg, w.psum);
+    GS_LAUNCH_CHECK(TsdfStage(name, "fold").text);
+    if (g_tsdf)
+        hipLaunchKernelGGL(tsdf_cast_finish_k, dim3(std::min(cdiv(total, TSDF_T), 65536)), dim3(TSDF_T), 0, st, w.fold, lg, total, g_tsdf, g_color);
+    if (g_poses) hipLaunchKernelGGL(tsdf_cast_pose_finish_k, dim3(L, B), dim3(TSDF_POSE_T), 0, st, (const float *)w.psum, tiles, g_poses);
+    GS_LAUNCH_CHECK(TsdfStage(name, "finish").text);
+    return GS_OK;
+}
+
 size_t gs_tsdf_raycast_backward_ws_bytes(int B, int nx, int ny, int nz, int has_color) {
     if (!tsdf_vol_ok(B, nx, ny, nz)) return 0;
-    return tsdf_cast_fold_layout(B, (int64_t)nx * ny * nz, has_color ? 4 : 1, nullptr, nullptr);
+    return tsdf_cast_bwd_layout(B, (int64_t)nx * ny * nz, has_color ? 4 : 1, false, 0, 0, nullptr, nullptr);
 }
 
 int gs_tsdf_raycast_backward(const float *tsdf, const float *weight, const float *color, int B, int nx, int ny, int nz, float voxel_size,
@@ -886,32 +910,16 @@ int gs_tsdf_raycast_backward(const float *tsdf, const float *weight, const float
                              float *g_color, void *ws, size_t ws_bytes, gs_stream_t stream) {
     GS_REQUIRE(tsdf && weight && origin && intrinsics && poses && k_end && g_tsdf, "gs_tsdf_raycast_backward: NULL argument");
     GS_REQUIRE((color != nullptr) == (g_color != nullptr) && (!g_rgb || color), "gs_tsdf_raycast_backward: color and g_color go together, g_rgb needs them");
-    TSDF_REQUIRE_VOLUME("gs_tsdf_raycast_backward");
-    TSDF_REQUIRE_CAST("gs_tsdf_raycast_backward");
-    const size_t need = gs_tsdf_raycast_backward_ws_bytes(B, nx, ny, nz, color != nullptr);
-    GS_REQUIRE_WS("gs_tsdf_raycast_backward", ws, ws_bytes, need);
-    hipStream_t st = (hipStream_t)stream;
-    const TsdfVol vol{nx, ny, nz, voxel_size, 0.0f, 0.0f, origin};
-    const TsdfCast cast{intrinsics, poses, L, Ho, Wo, stride, 0, step, 0.0f, 0.0f, min_weight};
-    Fold fold;
-    tsdf_cast_fold_layout(B, tsdf_nvox(vol), color ? 4 : 1, ws, &fold);
-    const int lg = fold_lg(2 * (int64_t)L * Ho * Wo);  // a voxel receives at most two terms per pixel of its batch element
-    const int64_t total = (int64_t)B * tsdf_nvox(vol);
-    const dim3 grid(cdiv(Ho, 16) * cdiv(Wo, 16), L, B);
-    GS_HIP(hipMemsetAsync(ws, 0, need, st), "gs_tsdf_raycast_backward/zero");
-    hipLaunchKernelGGL(tsdf_raycast_bwd_k<false>, grid, dim3(TSDF_T), 0, st, vol, cast, tsdf, weight, color, k_end, g_depth, g_rgb, fold, lg);
-    hipLaunchKernelGGL(tsdf_raycast_bwd_k<true>, grid, dim3(TSDF_T), 0, st, vol, cast, tsdf, weight, color, k_end, g_depth, g_rgb, fold, lg);
-    GS_LAUNCH_CHECK("gs_tsdf_raycast_backward/fold");
-    hipLaunchKernelGGL(tsdf_cast_finish_k, dim3(std::min(cdiv(total, TSDF_T), 65536)), dim3(TSDF_T), 0, st, fold, lg, total, g_tsdf, g_color);
-    GS_LAUNCH_CHECK("gs_tsdf_raycast_backward/finish");
-    return GS_OK;
+    return tsdf_raycast_backward_run("gs_tsdf_raycast_backward", tsdf, weight, color, B, nx, ny, nz, voxel_size, origin, intrinsics, poses, L,
+                                     height, width, stride, step, min_weight, k_end, g_depth, g_rgb, g_tsdf, g_color, nullptr, ws, ws_bytes,
+                                     gs_tsdf_raycast_backward_ws_bytes(B, nx, ny, nz, color != nullptr), stream);
 }
 
 size_t gs_tsdf_raycast_backward_poses_ws_bytes(int B, int nx, int ny, int nz, int has_color, int L, int height, int width, int stride) {
     if (!tsdf_vol_ok(B, nx, ny, nz) || L <= 0 || L > 65535 || height <= 0 || width <= 0 || stride < 1) return 0;
     const int Ho = (int)(((int64_t)height + stride - 1) / stride), Wo = (int)(((int64_t)width + stride - 1) / stride);
     if ((int64_t)cdiv(Ho, 16) * cdiv(Wo, 16) > TSDF_CAST_TILES) return 0;
-    return tsdf_cast_pose_layout(B, (int64_t)nx * ny * nz, has_color ? 4 : 1, L, cdiv(Ho, 16) * cdiv(Wo, 16), nullptr, nullptr, nullptr, nullptr);
+    return tsdf_cast_bwd_layout(B, (int64_t)nx * ny * nz, has_color ? 4 : 1, true, L, cdiv(Ho, 16) * cdiv(Wo, 16), nullptr, nullptr);
 }
 
 int gs_tsdf_raycast_backward_poses(const float *tsdf, const float *weight, const float *color, int B, int nx, int ny, int nz,
@@ -922,33 +930,10 @@ int gs_tsdf_raycast_backward_poses(const float *tsdf, const float *weight, const
     GS_REQUIRE(tsdf && weight && origin && intrinsics && poses && k_end && g_poses, "gs_tsdf_raycast_backward_poses: NULL argument");
     GS_REQUIRE((!g_color || (color && g_tsdf)) && (!g_rgb || color),
                "gs_tsdf_raycast_backward_poses: g_color needs color and g_tsdf, g_rgb needs color");
-    TSDF_REQUIRE_VOLUME("gs_tsdf_raycast_backward_poses");
-    TSDF_REQUIRE_CAST("gs_tsdf_raycast_backward_poses");
-    const size_t need = gs_tsdf_raycast_backward_poses_ws_bytes(B, nx, ny, nz, color != nullptr, L, height, width, stride);
-    GS_REQUIRE_WS("gs_tsdf_raycast_backward_poses", ws, ws_bytes, need);
-    hipStream_t st = (hipStream_t)stream;
-    const TsdfVol vol{nx, ny, nz, voxel_size, 0.0f, 0.0f, origin};
-    const TsdfCast cast{intrinsics, poses, L, Ho, Wo, stride, 0, step, 0.0f, 0.0f, min_weight};
-    const int tiles = cdiv(Ho, 16) * cdiv(Wo, 16);
-    Fold fold;
-    float *psum;
-    size_t fold_bytes;
-    tsdf_cast_pose_layout(B, tsdf_nvox(vol), color ? 4 : 1, L, tiles, ws, &fold, &psum, &fold_bytes);
-    const int lg = fold_lg(2 * (int64_t)L * Ho * Wo);
-    const int64_t total = (int64_t)B * tsdf_nvox(vol);
-    const dim3 grid(tiles, L, B);
-    if (g_tsdf) {  // as gs_tsdf_raycast_backward, with the pose sums on the second pass
-        GS_HIP(hipMemsetAsync(ws, 0, fold_bytes, st), "gs_tsdf_raycast_backward_poses/zero");
-        hipLaunchKernelGGL(tsdf_raycast_bwd_k<false>, grid, dim3(TSDF_T), 0, st, vol, cast, tsdf, weight, color, k_end, g_depth, g_rgb, fold, lg);
-    }
-    auto second = g_tsdf ? tsdf_raycast_bwd_k<true, true, true> : tsdf_raycast_bwd_k<true, true, false>;
-    hipLaunchKernelGGL(second, grid, dim3(TSDF_T), 0, st, vol, cast, tsdf, weight, color, k_end, g_depth, g_rgb, fold, lg, psum);
-    GS_LAUNCH_CHECK("gs_tsdf_raycast_backward_poses/fold");
-    if (g_tsdf)
-        hipLaunchKernelGGL(tsdf_cast_finish_k, dim3(std::min(cdiv(total, TSDF_T), 65536)), dim3(TSDF_T), 0, st, fold, lg, total, g_tsdf, g_color);
-    hipLaunchKernelGGL(tsdf_cast_pose_finish_k, dim3(L, B), dim3(TSDF_POSE_T), 0, st, (const float *)psum, tiles, g_poses);
-    GS_LAUNCH_CHECK("gs_tsdf_raycast_backward_poses/finish");
-    return GS_OK;
+    return tsdf_raycast_backward_run("gs_tsdf_raycast_backward_poses", tsdf, weight, color, B, nx, ny, nz, voxel_size, origin, intrinsics,
+                                     poses, L, height, width, stride, step, min_weight, k_end, g_depth, g_rgb, g_tsdf, g_color, g_poses, ws,
+                                     ws_bytes, gs_tsdf_raycast_backward_poses_ws_bytes(B, nx, ny, nz, color != nullptr, L, height, width, stride),
+                                     stream);
 }
 
 }  // extern "C"

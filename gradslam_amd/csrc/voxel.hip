@@ -291,7 +291,6 @@ __global__ __launch_bounds__(VOX_T) void vred_bwd_k(const float *__restrict__ g_
     }
 }
 
-static inline int vox_grid(int64_t items) { return (int)std::min<int64_t>(std::max<int64_t>((items + VOX_T - 1) / VOX_T, 1), 4096); }
 static inline bool vox_shape_ok(int B, int N_max) { return B > 0 && B <= 65535 && N_max > 0 && N_max <= VOX_NMAX; }
 static inline bool vred_shape_ok(int B, int N_max, int C, int M_max) {
     return vox_shape_ok(B, N_max) && C >= 1 && C <= VOX_CMAX && M_max > 0 && M_max <= N_max;
@@ -322,8 +321,8 @@ int gs_voxel_assign(const float *points, const int32_t *counts, int N_max, int B
     VoxWs w;
     vox_assign_layout(B, N_max, ws, &w);
     const VoxIn in{points, counts, N_max, voxel_size, f3{origin[0], origin[1], origin[2]}};
-    const dim3 rows(vox_grid(N_max), B);
-    hipLaunchKernelGGL(vox_init_k, dim3(vox_grid(w.S), B), dim3(VOX_T), 0, st, w, N_max, n_voxels, n_dropped, voxel_count, voxel_first);
+    const dim3 rows(rows_grid(N_max, VOX_T, 4096), B);
+    hipLaunchKernelGGL(vox_init_k, dim3(rows_grid(w.S, VOX_T, 4096), B), dim3(VOX_T), 0, st, w, N_max, n_voxels, n_dropped, voxel_count, voxel_first);
     hipLaunchKernelGGL(vox_insert_k, rows, dim3(VOX_T), 0, st, in, w, n_dropped);
     GS_LAUNCH_CHECK("gs_voxel_assign/insert");
     hipLaunchKernelGGL(vox_count_k, dim3(w.nb, B), dim3(kCT), 0, st, w, N_max);
@@ -357,12 +356,12 @@ int gs_voxel_reduce(const float *x, const int32_t *counts, int N_max, int C, int
     const VredIn in{x, counts, voxel_of, n_voxels, voxel_count, N_max, C, M_max};
     const int lg = fold_lg(N_max);  // no voxel has more members
     GS_HIP(hipMemsetAsync(ws, 0, bytes, st), "gs_voxel_reduce/zero");
-    hipLaunchKernelGGL(vred_max_k, dim3(vox_grid((int64_t)N_max * C), B), dim3(VOX_T), 0, st, in, w);
-    const dim3 rows(vox_grid(N_max), B);
+    hipLaunchKernelGGL(vred_max_k, dim3(rows_grid((int64_t)N_max * C, VOX_T, 4096), B), dim3(VOX_T), 0, st, in, w);
+    const dim3 rows(rows_grid(N_max, VOX_T, 4096), B);
     if (mode & GS_VOXEL_NO_PREAGG) hipLaunchKernelGGL(vred_acc_k<false>, rows, dim3(VOX_T), 0, st, in, w, lg);
     else hipLaunchKernelGGL(vred_acc_k<true>, rows, dim3(VOX_T), 0, st, in, w, lg);
     GS_LAUNCH_CHECK("gs_voxel_reduce/fold");
-    hipLaunchKernelGGL(vred_finish_k, dim3(vox_grid((int64_t)M_max * C), B), dim3(VOX_T), 0, st, in, w, lg, mode & GS_VOXEL_MEAN, out);
+    hipLaunchKernelGGL(vred_finish_k, dim3(rows_grid((int64_t)M_max * C, VOX_T, 4096), B), dim3(VOX_T), 0, st, in, w, lg, mode & GS_VOXEL_MEAN, out);
     GS_LAUNCH_CHECK("gs_voxel_reduce/finish");
     return GS_OK;
 }
@@ -374,7 +373,7 @@ int gs_voxel_reduce_backward(const float *g_out, const int32_t *counts, int N_ma
                "gs_voxel_reduce_backward: bad shape B=%d N_max=%d C=%d M_max=%d (1 <= C <= 64, M_max <= N_max)", B, N_max, C, M_max);
     GS_REQUIRE(mode >= 0 && mode <= 3, "gs_voxel_reduce_backward: bad mode %d", mode);
     const VredIn in{nullptr, counts, voxel_of, nullptr, voxel_count, N_max, C, M_max};
-    hipLaunchKernelGGL(vred_bwd_k, dim3(vox_grid((int64_t)N_max * C), B), dim3(VOX_T), 0, (hipStream_t)stream, g_out, in,
+    hipLaunchKernelGGL(vred_bwd_k, dim3(rows_grid((int64_t)N_max * C, VOX_T, 4096), B), dim3(VOX_T), 0, (hipStream_t)stream, g_out, in,
                        mode & GS_VOXEL_MEAN, g_x);
     GS_LAUNCH_CHECK("gs_voxel_reduce_backward");
     return GS_OK;

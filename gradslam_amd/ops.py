@@ -890,6 +890,51 @@ def fusion_new_mask_raw(depth, rows, n_rows_dev, max_rows):
     return mask
 
 
+# ---------------------------------------------------------------------------------------------- argument checkers the modules share
+def _as_float(value) -> float:
+    try:
+        return float(value)
+    except (TypeError, ValueError):
+        return float("nan")
+
+
+def _number(value, name, op):
+    x = _as_float(value)
+    if math.isnan(x):
+        raise ValueError("{}: {} should be a number. Got {!r}.".format(op, name, value))
+    return x
+
+
+def _positive(value, name, op):
+    x = _as_float(value)
+    x32 = float(torch.tensor(x, dtype=torch.float32)) if math.isfinite(x) else x  # what the kernels compute with
+    if not (math.isfinite(x32) and x32 > 0.0):
+        raise ValueError("{}: {} should be a finite positive number. Got {!r}.".format(op, name, value))
+    return x
+
+
+def _counts(c, B, name, op):
+    if c.dtype != torch.int32 or c.numel() != B:
+        raise ValueError("{}: {} should be {} int32 values. Got {} of {}.".format(op, name, B, c.numel(), c.dtype))
+    return c.contiguous()
+
+
+def _padded_pair(x, y, x_counts, y_counts, names, op):
+    """Two padded clouds (B, N, 3) with int32 device counts, called names[0] / names[1] in the messages -> (x, y, counts of x,
+    counts of y), contiguous (fp32 for the clouds); `x is y` stays so."""
+    require_hip(x, y, x_counts, y_counts, op=op)
+    same = x is y
+    x = _f32c(x)
+    y = x if same else _f32c(y)
+    for name, t in zip(names, (x, y)):
+        if t.ndim != 3 or t.shape[-1] != 3 or t.shape[1] == 0:
+            raise ValueError("{}: {} should have shape (B, N, 3) with N > 0. Got {}.".format(op, name, tuple(t.shape)))
+    B = x.shape[0]
+    if y.shape[0] != B or B == 0:
+        raise ValueError("{}: {} and {} should share a batch size B > 0. Got {} and {}.".format(op, *names, x.shape[0], y.shape[0]))
+    return x, y, _counts(x_counts, B, names[0] + "_counts", op), _counts(y_counts, B, names[1] + "_counts", op)
+
+
 # ---------------------------------------------------------------------------------------------- R
 def _render_args(points_padded, normals_padded, colors_padded, counts_i32, poses_b44, K_b44, H, W, op):
     require_hip(points_padded, normals_padded, colors_padded, counts_i32, poses_b44, K_b44, op=op)
@@ -904,12 +949,11 @@ def _render_args(points_padded, normals_padded, colors_padded, counts_i32, poses
     for name, x in (("poses", poses), ("intrinsics", K)):
         if x.numel() != 16 * B or x.shape[-2:] != (4, 4):
             raise ValueError("{}: {} should hold one 4x4 matrix per batch element (B = {}). Got {}.".format(op, name, B, tuple(x.shape)))
-    if counts_i32.dtype != torch.int32 or counts_i32.numel() != B:
-        raise ValueError("{}: counts should be {} int32 values. Got {} of {}.".format(op, B, counts_i32.numel(), counts_i32.dtype))
+    counts = _counts(counts_i32, B, "counts", op)
     if int(H) <= 0 or int(W) <= 0 or pts.shape[1] == 0:
         raise ValueError("{}: needs a non-empty map array and a positive image size. Got N = {}, H = {}, W = {}.".format(
             op, pts.shape[1], H, W))
-    return pts, nrm, col, counts_i32.contiguous(), poses, K
+    return pts, nrm, col, counts, poses, K
 
 
 def render_map_raw(points_padded, normals_padded, colors_padded, counts_i32, poses_b44, K_b44, H: int, W: int):
@@ -981,28 +1025,13 @@ def render_map(points_padded, normals_padded, colors_padded, counts_i32, poses_b
 KEY_NONE = -1  # a packed key without a neighbour (all ones), as int64
 
 
-def _chamfer_args(a, b, a_counts, b_counts, op):
-    require_hip(a, b, a_counts, b_counts, op=op)
-    a, b = _f32c(a), _f32c(b)
-    for name, x in (("a", a), ("b", b)):
-        if x.ndim != 3 or x.shape[-1] != 3 or x.shape[1] == 0:
-            raise ValueError("{}: {} should have shape (B, N, 3) with N > 0. Got {}.".format(op, name, tuple(x.shape)))
-    B = a.shape[0]
-    if b.shape[0] != B or B == 0:
-        raise ValueError("{}: a and b should share a batch size B > 0. Got {} and {}.".format(op, a.shape[0], b.shape[0]))
-    for name, c in (("a_counts", a_counts), ("b_counts", b_counts)):
-        if c.dtype != torch.int32 or c.numel() != B:
-            raise ValueError("{}: {} should be {} int32 values. Got {} of {}.".format(op, name, B, c.numel(), c.dtype))
-    return a, b, a_counts.contiguous(), b_counts.contiguous()
-
-
 def chamfer_raw(a, b, a_counts, b_counts, tau2: float = float("inf"), reorder: bool = True, out=None):
     """Two-sided exact nearest neighbours of padded clouds a (B,Na,3), b (B,Nb,3) with int32 device counts ->
     (stats (B,2,4) float64, keys_ab (B,Na) int64, keys_ba (B,Nb) int64).  stats[b, d] = [sum d2, sum d, #(d2 < tau2), max d2]
     of direction d (0: a -> b, 1: b -> a); keys are dist2_bits << 32 | index, KEY_NONE beyond the counts and where the other
     cloud is empty.  reorder scans each target in cell-grid order (same bits, another cost).  `out`: (keys_ab, keys_ba)
     buffers to write into (rows beyond the counts are left as they are)."""
-    a, b, ca, cb = _chamfer_args(a, b, a_counts, b_counts, "chamfer")
+    a, b, ca, cb = _padded_pair(a, b, a_counts, b_counts, ("a", "b"), "chamfer")
     B, Na, Nb = a.shape[0], a.shape[1], b.shape[1]
     dev = a.device
     stats = torch.empty((B, 2, 4), dtype=torch.float64, device=dev)
@@ -1021,7 +1050,7 @@ def chamfer_backward_raw(a, b, a_counts, b_counts, keys_ab, keys_ba, g2, g1, out
     """Adjoint of chamfer_raw's sum d2 / sum d w.r.t. both clouds: g2, g1 (B,2) -> (g_a (B,Na,3), g_b (B,Nb,3)); the keys are
     constants.  The deterministic fold under torch.use_deterministic_algorithms, float atomics otherwise.  `out`: (g_a, g_b)
     buffers to write into (rows beyond the counts are left as they are; fresh buffers hold zeros there)."""
-    a, b, ca, cb = _chamfer_args(a, b, a_counts, b_counts, "chamfer_backward")
+    a, b, ca, cb = _padded_pair(a, b, a_counts, b_counts, ("a", "b"), "chamfer_backward")
     require_hip(keys_ab, keys_ba, g2, g1, op="chamfer_backward")
     B, Na, Nb = a.shape[0], a.shape[1], b.shape[1]
     dev = a.device
@@ -1062,17 +1091,6 @@ def chamfer(a, b, a_counts, b_counts, tau2: float = float("inf"), reorder: bool 
 
 
 # ---------------------------------------------------------------------------------------------- V
-def _voxel_size(voxel_size, op):
-    try:
-        v = float(voxel_size)
-    except (TypeError, ValueError):
-        v = float("nan")
-    v32 = float(torch.tensor(v, dtype=torch.float32)) if math.isfinite(v) else v  # what the kernels divide by
-    if not (math.isfinite(v32) and v32 > 0.0):
-        raise ValueError("{}: voxel_size should be a finite positive number. Got {!r}.".format(op, voxel_size))
-    return v
-
-
 def _voxel_origin(origin, op):
     vals = [0.0, 0.0, 0.0] if origin is None else [float(t) for t in (origin.tolist() if torch.is_tensor(origin) else origin)]
     if len(vals) != 3 or not all(math.isfinite(t) for t in vals):
@@ -1085,9 +1103,7 @@ def _voxel_rows(x, counts, op):
     x = _f32c(x)
     if x.ndim != 3 or x.shape[0] == 0 or x.shape[1] == 0:
         raise ValueError("{}: expected a padded (B, N, C) tensor with B > 0 and N > 0. Got {}.".format(op, tuple(x.shape)))
-    if counts.dtype != torch.int32 or counts.numel() != x.shape[0]:
-        raise ValueError("{}: counts should be {} int32 values. Got {} of {}.".format(op, x.shape[0], counts.numel(), counts.dtype))
-    return x, counts.contiguous()
+    return x, _counts(counts, x.shape[0], "counts", op)
 
 
 def voxel_assign(points_padded, counts_i32, voxel_size, origin=None):
@@ -1096,7 +1112,7 @@ def voxel_assign(points_padded, counts_i32, voxel_size, origin=None):
     voxel_count (B,N), voxel_first (B,N)), all int32: voxels are numbered in order of first appearance; voxel_of is -1 for
     padding rows and for dropped ones (non-finite, or |k| >= 2^20: counted in n_dropped); voxel_count / voxel_first hold 0 / -1
     beyond n_voxels.  No gradient: the assignment is a constant of the graph.  Nothing synchronises the host."""
-    v, o = _voxel_size(voxel_size, "voxel_assign"), _voxel_origin(origin, "voxel_assign")
+    v, o = _positive(voxel_size, "voxel_size", "voxel_assign"), _voxel_origin(origin, "voxel_assign")
     with torch.no_grad():
         pts, counts = _voxel_rows(points_padded.detach(), counts_i32, "voxel_assign")
         if pts.shape[-1] != 3:
@@ -1135,11 +1151,10 @@ def voxel_reduce_raw(x, counts_i32, voxel_of, n_voxels, voxel_count, M_max, mode
     voxel_of, voxel_count = _voxel_index_args(x, voxel_of, voxel_count, M_max, "voxel_reduce")
     require_hip(n_voxels, op="voxel_reduce")
     B, N, C = x.shape
-    if n_voxels.dtype != torch.int32 or n_voxels.numel() != B:
-        raise ValueError("voxel_reduce: n_voxels should be {} int32 values. Got {} of {}.".format(B, n_voxels.numel(), n_voxels.dtype))
+    n_voxels = _counts(n_voxels, B, "n_voxels", "voxel_reduce")
     out = torch.empty((B, int(M_max), C), dtype=torch.float32, device=x.device)
     ws = workspace(ws_bytes("gs_voxel_reduce_ws_bytes", B, int(M_max), C), x.device, "voxel_reduce")
-    call("gs_voxel_reduce", ptr(x), ptr(counts), N, C, B, ptr(voxel_of), ptr(n_voxels.contiguous()), ptr(voxel_count), int(M_max),
+    call("gs_voxel_reduce", ptr(x), ptr(counts), N, C, B, ptr(voxel_of), ptr(n_voxels), ptr(voxel_count), int(M_max),
          int(mode), ptr(out), ptr(ws), ws.numel(), stream())
     return out
 
@@ -1183,22 +1198,10 @@ KNN_KMAX = 32
 
 
 def _knn_args(src, tgt, src_counts, tgt_counts, K, op):
-    require_hip(src, tgt, src_counts, tgt_counts, op=op)
-    same = src is tgt
-    src = _f32c(src)
-    tgt = src if same else _f32c(tgt)
-    for name, x in (("src", src), ("tgt", tgt)):
-        if x.ndim != 3 or x.shape[-1] != 3 or x.shape[1] == 0:
-            raise ValueError("{}: {} should have shape (B, N, 3) with N > 0. Got {}.".format(op, name, tuple(x.shape)))
-    B = src.shape[0]
-    if tgt.shape[0] != B or B == 0:
-        raise ValueError("{}: src and tgt should share a batch size B > 0. Got {} and {}.".format(op, src.shape[0], tgt.shape[0]))
-    for name, c in (("src_counts", src_counts), ("tgt_counts", tgt_counts)):
-        if c.dtype != torch.int32 or c.numel() != B:
-            raise ValueError("{}: {} should be {} int32 values. Got {} of {}.".format(op, name, B, c.numel(), c.dtype))
+    checked = _padded_pair(src, tgt, src_counts, tgt_counts, ("src", "tgt"), op)
     if isinstance(K, bool) or not isinstance(K, int) or not 1 <= K <= KNN_KMAX:
         raise ValueError("{}: K should be an int in [1, {}]. Got {!r}.".format(op, KNN_KMAX, K))
-    return src, tgt, src_counts.contiguous(), tgt_counts.contiguous()
+    return checked
 
 
 def knn_raw(src, tgt, src_counts, tgt_counts, K: int, out=None) -> torch.Tensor:
@@ -1318,17 +1321,6 @@ def _tsdf_on_device(op, *tensors):
     require_hip(*tensors, op=op)
 
 
-def _tsdf_positive(value, name, op):
-    try:
-        x = float(value)
-    except (TypeError, ValueError):
-        x = float("nan")
-    x32 = float(torch.tensor(x, dtype=torch.float32)) if math.isfinite(x) else x  # what the kernels compute with
-    if not (math.isfinite(x32) and x32 > 0.0):
-        raise ValueError("{}: {} should be a finite positive number. Got {!r}.".format(op, name, value))
-    return x
-
-
 def _tsdf_dims(dims, op):
     try:
         d = tuple(dims)
@@ -1364,18 +1356,25 @@ def tsdf_origin(origin, B: int, device, op: str = "tsdf_origin") -> torch.Tensor
     return o.contiguous().to(device)
 
 
-def _tsdf_state(tsdf, weight, color, origin, voxel_size, op):
-    """Checks one volume's tensors -> (tsdf, weight, color, origin (B,3), (nx, ny, nz), voxel_size)."""
-    _tsdf_on_device(op, tsdf, weight, color)
+def _tsdf_volume(tsdf, weight, op):
+    """Checks the shapes of a volume's tsdf and weight (device tensors) -> (B, (nx, ny, nz))."""
     if tsdf.ndim != 4 or tsdf.shape[0] == 0 or tsdf.shape[0] > 65535:
         raise ValueError("{}: tsdf should have shape (B, nz, ny, nx) with 1 <= B <= 65535. Got {}.".format(op, tuple(tsdf.shape)))
     B, nz, ny, nx = (int(n) for n in tsdf.shape)
     dims = _tsdf_dims((nx, ny, nz), op)
     if weight.shape != tsdf.shape:
         raise ValueError("{}: weight should have the shape of tsdf {}. Got {}.".format(op, tuple(tsdf.shape), tuple(weight.shape)))
+    return B, dims
+
+
+def _tsdf_state(tsdf, weight, color, origin, voxel_size, op):
+    """Checks one volume's tensors -> (tsdf, weight, color, origin (B,3), (nx, ny, nz), voxel_size)."""
+    _tsdf_on_device(op, tsdf, weight, color)
+    B, dims = _tsdf_volume(tsdf, weight, op)
+    nx, ny, nz = dims
     if color is not None and tuple(color.shape) != (B, nz, ny, nx, 3):
         raise ValueError("{}: color should have shape {}. Got {}.".format(op, (B, nz, ny, nx, 3), tuple(color.shape)))
-    v = _tsdf_positive(voxel_size, "voxel_size", op)
+    v = _positive(voxel_size, "voxel_size", op)
     origin = tsdf_origin(origin, B, tsdf.device, op)
     _tsdf_on_device(op, origin)
     return _f32c(tsdf), _f32c(weight), _f32c(color), origin, dims, v
@@ -1411,7 +1410,7 @@ def tsdf_integrate_raw(depth, rgb, K, poses, tsdf, weight, color, origin, voxel_
     t_in, w_in, c_in, origin, (nx, ny, nz), v = _tsdf_state(tsdf, weight, color, origin, voxel_size, op)
     B = t_in.shape[0]
     depth, rgb, K, poses, L, H, W = _tsdf_frames(depth, rgb, K, poses, B, c_in is not None, op)
-    trunc, max_weight = _tsdf_positive(trunc, "trunc", op), _tsdf_positive(max_weight, "max_weight", op)
+    trunc, max_weight = _positive(trunc, "trunc", op), _positive(max_weight, "max_weight", op)
     if inplace:
         if any(a is not b for a, b in ((t_in, tsdf), (w_in, weight), (c_in, color))):
             raise ValueError("{}: inplace needs contiguous float32 state tensors.".format(op))
@@ -1424,24 +1423,33 @@ def tsdf_integrate_raw(depth, rgb, K, poses, tsdf, weight, color, origin, voxel_
     return t_out, w_out, c_out
 
 
+def _tsdf_integrate_backward(op, with_poses, want_state, want_frames, depth, K, poses, weight, origin, voxel_size, trunc, max_weight,
+                             g_tsdf, g_color):
+    """The body of tsdf_integrate_backward_raw (op "tsdf_integrate_backward": gs_<op> with its own size query and workspace) and
+    of tsdf_integrate_backward_poses_raw -> (g_tsdf_in, g_color_in, g_depth, g_rgb, g_poses or None)."""
+    g_t, w_in, g_c, origin, (nx, ny, nz), v = _tsdf_state(g_tsdf, weight, g_color, origin, voxel_size, op)
+    B = g_t.shape[0]
+    depth, _, K, poses, L, H, W = _tsdf_frames(depth, None, K, poses, B, False, op)
+    trunc, max_weight = _positive(trunc, "trunc", op), _positive(max_weight, "max_weight", op)
+    dev = g_t.device
+    o_t = torch.empty_like(g_t) if want_state else None
+    o_c = torch.empty_like(g_c) if want_state and g_c is not None else None
+    g_depth = torch.empty((B, L, H, W), dtype=torch.float32, device=dev) if want_frames else None
+    g_rgb = torch.empty((B, L, H, W, 3), dtype=torch.float32, device=dev) if want_frames and g_c is not None else None
+    g_poses = torch.empty((B, L, 4, 4), dtype=torch.float32, device=dev) if with_poses else None
+    size_args = (B, L, H, W, nx, ny, nz, int(g_c is not None)) if with_poses else (B, L, H, W)
+    ws = workspace(ws_bytes("gs_{}_ws_bytes".format(op), *size_args), dev, "tsdf_bwd_poses" if with_poses else "tsdf_bwd")
+    call("gs_" + op, ptr(depth), ptr(K), ptr(poses), B, L, H, W, nx, ny, nz, v, ptr(origin), trunc, max_weight, ptr(w_in), ptr(g_t),
+         ptr(g_c), ptr(o_t), ptr(o_c), ptr(g_depth), ptr(g_rgb), *((ptr(g_poses),) if with_poses else ()), ptr(ws), ws.numel(), stream())
+    return o_t, o_c, g_depth, g_rgb, g_poses
+
+
 def tsdf_integrate_backward_raw(depth, K, poses, weight, origin, voxel_size, trunc, max_weight, g_tsdf, g_color=None):
     """Adjoint of tsdf_integrate_raw: the adjoints g_tsdf (B,nz,ny,nx) / g_color (B,nz,ny,nx,3 or None) of the new state ->
     (g_tsdf_in, g_color_in, g_depth (B,L,H,W), g_rgb (B,L,H,W,3)); `weight` is the weight BEFORE the integration.  The pixel sums
     are exact and rounded once: the same bits from run to run (one path, with or without torch.use_deterministic_algorithms)."""
-    op = "tsdf_integrate_backward"
-    g_t, w_in, g_c, origin, (nx, ny, nz), v = _tsdf_state(g_tsdf, weight, g_color, origin, voxel_size, op)
-    B = g_t.shape[0]
-    depth, _, K, poses, L, H, W = _tsdf_frames(depth, None, K, poses, B, False, op)
-    trunc, max_weight = _tsdf_positive(trunc, "trunc", op), _tsdf_positive(max_weight, "max_weight", op)
-    dev = g_t.device
-    o_t = torch.empty_like(g_t)
-    o_c = None if g_c is None else torch.empty_like(g_c)
-    g_depth = torch.empty((B, L, H, W), dtype=torch.float32, device=dev)
-    g_rgb = None if g_c is None else torch.empty((B, L, H, W, 3), dtype=torch.float32, device=dev)
-    ws = workspace(ws_bytes("gs_tsdf_integrate_backward_ws_bytes", B, L, H, W), dev, "tsdf_bwd")
-    call("gs_tsdf_integrate_backward", ptr(depth), ptr(K), ptr(poses), B, L, H, W, nx, ny, nz, v, ptr(origin), trunc, max_weight,
-         ptr(w_in), ptr(g_t), ptr(g_c), ptr(o_t), ptr(o_c), ptr(g_depth), ptr(g_rgb), ptr(ws), ws.numel(), stream())
-    return o_t, o_c, g_depth, g_rgb
+    return _tsdf_integrate_backward("tsdf_integrate_backward", False, True, True, depth, K, poses, weight, origin, voxel_size, trunc,
+                                    max_weight, g_tsdf, g_color)[:4]
 
 
 def tsdf_integrate_backward_poses_raw(depth, K, poses, weight, origin, voxel_size, trunc, max_weight, g_tsdf, g_color=None,
@@ -1452,21 +1460,8 @@ def tsdf_integrate_backward_poses_raw(depth, K, poses, weight, origin, voxel_siz
     matrix entries (render_map's convention; row 3 is zero): the update depends on a pose through the camera-frame depth of the
     voxel centres alone, with the pixel of a voxel, the three skips, the t = 1 branch and the weight cap held constant.  Fixed
     order fp32 sums, no atomics: the same bits from run to run.  Intrinsics, weights and origin receive no gradient."""
-    op = "tsdf_integrate_backward_poses"
-    g_t, w_in, g_c, origin, (nx, ny, nz), v = _tsdf_state(g_tsdf, weight, g_color, origin, voxel_size, op)
-    B = g_t.shape[0]
-    depth, _, K, poses, L, H, W = _tsdf_frames(depth, None, K, poses, B, False, op)
-    trunc, max_weight = _tsdf_positive(trunc, "trunc", op), _tsdf_positive(max_weight, "max_weight", op)
-    dev = g_t.device
-    o_t = torch.empty_like(g_t) if want_state else None
-    o_c = torch.empty_like(g_c) if want_state and g_c is not None else None
-    g_depth = torch.empty((B, L, H, W), dtype=torch.float32, device=dev) if want_frames else None
-    g_rgb = torch.empty((B, L, H, W, 3), dtype=torch.float32, device=dev) if want_frames and g_c is not None else None
-    g_poses = torch.empty((B, L, 4, 4), dtype=torch.float32, device=dev)
-    ws = workspace(ws_bytes("gs_tsdf_integrate_backward_poses_ws_bytes", B, L, H, W, nx, ny, nz, int(g_c is not None)), dev, "tsdf_bwd_poses")
-    call("gs_tsdf_integrate_backward_poses", ptr(depth), ptr(K), ptr(poses), B, L, H, W, nx, ny, nz, v, ptr(origin), trunc, max_weight,
-         ptr(w_in), ptr(g_t), ptr(g_c), ptr(o_t), ptr(o_c), ptr(g_depth), ptr(g_rgb), ptr(g_poses), ptr(ws), ws.numel(), stream())
-    return o_t, o_c, g_depth, g_rgb, g_poses
+    return _tsdf_integrate_backward("tsdf_integrate_backward_poses", True, want_state, want_frames, depth, K, poses, weight, origin,
+                                    voxel_size, trunc, max_weight, g_tsdf, g_color)
 
 
 class _TsdfIntegrateFn(torch.autograd.Function):
@@ -1520,12 +1515,7 @@ def tsdf_extract_raw(tsdf, weight, color, origin, voxel_size, min_weight: float 
     cap = 0 only counts (the arrays are None): size with it first.  colors is None for a volume without colours."""
     op = "tsdf_extract"
     t, w, c, origin, (nx, ny, nz), v = _tsdf_state(tsdf, weight, color, origin, voxel_size, op)
-    try:
-        mw = float(min_weight)
-    except (TypeError, ValueError):
-        mw = float("nan")
-    if math.isnan(mw):
-        raise ValueError("{}: min_weight should be a number. Got {!r}.".format(op, min_weight))
+    mw = _number(min_weight, "min_weight", op)
     cap = int(cap)
     if cap < 0 or cap > 3 * TSDF_NMAX:
         raise ValueError("{}: cap should lie in 0 .. 3 * 2^29. Got {}.".format(op, cap))
@@ -1549,19 +1539,18 @@ def tsdf_extract_backward_raw(tsdf, color, voxel_size, edge, n_points, g_points=
         raise ValueError("{}: tsdf should have shape (B, nz, ny, nx). Got {}.".format(op, tuple(tsdf.shape)))
     B, nz, ny, nx = (int(n) for n in tsdf.shape)
     _tsdf_dims((nx, ny, nz), op)
-    v = _tsdf_positive(voxel_size, "voxel_size", op)
+    v = _positive(voxel_size, "voxel_size", op)
     if edge.dtype != torch.int32 or edge.ndim != 2 or edge.shape[0] != B or edge.shape[1] == 0:
         raise ValueError("{}: edge should be int32 of shape ({}, cap) with cap > 0. Got {} of {}.".format(op, B, tuple(edge.shape), edge.dtype))
     cap = int(edge.shape[1])
-    if n_points.dtype != torch.int32 or n_points.numel() != B:
-        raise ValueError("{}: n_points should be {} int32 values. Got {} of {}.".format(op, B, n_points.numel(), n_points.dtype))
+    n_points = _counts(n_points, B, "n_points", op)
     for name, g in (("g_points", g_points), ("g_colors", g_colors)):
         if g is not None and tuple(g.shape) != (B, cap, 3):
             raise ValueError("{}: {} should have shape {}. Got {}.".format(op, name, (B, cap, 3), tuple(g.shape)))
     t, c = _f32c(tsdf), _f32c(color)
     g_tsdf = torch.empty_like(t)
     g_color = None if c is None else torch.empty_like(c)
-    call("gs_tsdf_extract_backward", ptr(t), ptr(c), B, nx, ny, nz, v, ptr(edge.contiguous()), ptr(n_points.contiguous()), cap,
+    call("gs_tsdf_extract_backward", ptr(t), ptr(c), B, nx, ny, nz, v, ptr(edge.contiguous()), ptr(n_points), cap,
          ptr(_f32c(g_points)), ptr(_f32c(g_colors)), ptr(g_tsdf), ptr(g_color), stream())
     return g_tsdf, g_color
 
@@ -1608,16 +1597,11 @@ def tsdf_faces_raw(tsdf, weight, min_weight, edge, n_points, fcap: int = 0, poin
     vcap from them, passes points_fit=True.  Integers only: no autograd node."""
     op = "tsdf_faces"
     _tsdf_on_device(op, tsdf, weight, edge, n_points)
-    if tsdf.ndim != 4 or tsdf.shape[0] == 0 or tsdf.shape[0] > 65535:
-        raise ValueError("{}: tsdf should have shape (B, nz, ny, nx) with 1 <= B <= 65535. Got {}.".format(op, tuple(tsdf.shape)))
-    B, nz, ny, nx = (int(n) for n in tsdf.shape)
-    _tsdf_dims((nx, ny, nz), op)
+    B, (nx, ny, nz) = _tsdf_volume(tsdf, weight, op)
     if nx * ny * nz > MESH_NMAX:
         raise ValueError("{}: at most 2^28 voxels per batch element can be meshed. Got dims {} = {} voxels.".format(
             op, (nx, ny, nz), nx * ny * nz))
-    if weight.shape != tsdf.shape:
-        raise ValueError("{}: weight should have the shape of tsdf {}. Got {}.".format(op, tuple(tsdf.shape), tuple(weight.shape)))
-    mw = _tsdf_number(min_weight, "min_weight", op)
+    mw = _number(min_weight, "min_weight", op)
     fcap = int(fcap)
     if fcap < 0 or fcap > 5 * MESH_NMAX:
         raise ValueError("{}: fcap should lie in 0 .. 5 * 2^28. Got {}.".format(op, fcap))
@@ -1627,13 +1611,12 @@ def tsdf_faces_raw(tsdf, weight, min_weight, edge, n_points, fcap: int = 0, poin
             raise ValueError("{}: fcap = {} rows need the edge list and n_points of tsdf_extract_raw.".format(op, fcap))
         if edge.dtype != torch.int32 or edge.ndim != 2 or edge.shape[0] != B:
             raise ValueError("{}: edge should be int32 of shape ({}, vcap). Got {} of {}.".format(op, B, tuple(edge.shape), edge.dtype))
-        if n_points.dtype != torch.int32 or n_points.numel() != B:
-            raise ValueError("{}: n_points should be {} int32 values. Got {} of {}.".format(op, B, n_points.numel(), n_points.dtype))
+        n_points = _counts(n_points, B, "n_points", op)
         vcap = int(edge.shape[1])
         if not points_fit and int(n_points.max()) > vcap:
             raise ValueError("{}: the edge list is truncated: it holds {} rows per batch element, n_points is up to {}.".format(
                 op, vcap, int(n_points.max())))
-        edge, n_points = edge.contiguous(), n_points.contiguous()
+        edge = edge.contiguous()
     t, w = _f32c(tsdf.detach()), _f32c(weight.detach())
     dev = t.device
     n_faces = torch.empty((B,), dtype=torch.int32, device=dev)
@@ -1642,16 +1625,6 @@ def tsdf_faces_raw(tsdf, weight, min_weight, edge, n_points, fcap: int = 0, poin
     call("gs_tsdf_faces", ptr(t), ptr(w), B, nx, ny, nz, mw, ptr(edge) if (fcap and vcap) else None, ptr(n_points) if fcap else None, vcap,
          fcap, ptr(faces), ptr(n_faces), ptr(ws), ws.numel(), stream())
     return faces, n_faces
-
-
-def _tsdf_number(value, name, op):
-    try:
-        x = float(value)
-    except (TypeError, ValueError):
-        x = float("nan")
-    if math.isnan(x):
-        raise ValueError("{}: {} should be a number. Got {!r}.".format(op, name, value))
-    return x
 
 
 def _tsdf_cast(K, poses, B, dims, v, height, width, stride, step, min_weight, op):
@@ -1671,11 +1644,11 @@ def _tsdf_cast(K, poses, B, dims, v, height, width, stride, step, min_weight, op
     if -(-height // (16 * stride)) * -(-width // (16 * stride)) > 2 ** 22:
         raise ValueError("{}: at most 2^22 tiles of 16 x 16 output pixels per image are supported. Got {} x {} at stride {}.".format(
             op, height, width, stride))
-    step = _tsdf_positive(step, "step", op)
+    step = _positive(step, "step", op)
     if sum(dims) * v / step > 2 ** 20:
         raise ValueError("{}: (nx + ny + nz) voxel_size / step should be at most 2^20 samples per ray. Got {:g}.".format(
             op, sum(dims) * v / step))
-    return _f32c(K), _f32c(poses), int(poses.shape[1]), height, width, stride, step, _tsdf_number(min_weight, "min_weight", op)
+    return _f32c(K), _f32c(poses), int(poses.shape[1]), height, width, stride, step, _number(min_weight, "min_weight", op)
 
 
 def tsdf_raycast_raw(tsdf, weight, color, origin, voxel_size, K, poses, height: int, width: int, stride: int, step: float,
@@ -1688,7 +1661,7 @@ def tsdf_raycast_raw(tsdf, weight, color, origin, voxel_size, K, poses, height: 
     t, w, c, origin, dims, v = _tsdf_state(tsdf, weight, color, origin, voxel_size, op)
     B, dev = t.shape[0], t.device
     K, poses, L, height, width, stride, step, mw = _tsdf_cast(K, poses, B, dims, v, height, width, stride, step, min_weight, op)
-    near, far = _tsdf_number(near, "near", op), _tsdf_number(far, "far", op)
+    near, far = _number(near, "near", op), _number(far, "far", op)
     if near < 0.0:
         raise ValueError("{}: near should not be negative. Got {!r}.".format(op, near))
     Ho, Wo = -(-height // stride), -(-width // stride)
@@ -1701,9 +1674,10 @@ def tsdf_raycast_raw(tsdf, weight, color, origin, voxel_size, K, poses, height: 
     return depth, normal, rgb, k_end
 
 
-def _tsdf_cast_backward_args(op, tsdf, weight, color, origin, voxel_size, K, poses, height, width, stride, step, min_weight, k_end,
-                             g_depth, g_rgb):
-    """The checks the cast's two reverse passes share -> their arguments, checked and contiguous fp32."""
+def _tsdf_raycast_backward(op, with_poses, want_volume, tsdf, weight, color, origin, voxel_size, K, poses, height, width, stride, step,
+                           min_weight, k_end, g_depth, g_rgb):
+    """The body of tsdf_raycast_backward_raw (op "tsdf_raycast_backward": gs_<op> with its own size query and workspace) and of
+    tsdf_raycast_backward_poses_raw -> (g_tsdf, g_color, g_poses or None)."""
     t, w, c, origin, dims, v = _tsdf_state(tsdf, weight, color, origin, voxel_size, op)
     B, dev = t.shape[0], t.device
     K, poses, L, height, width, stride, step, mw = _tsdf_cast(K, poses, B, dims, v, height, width, stride, step, min_weight, op)
@@ -1717,7 +1691,15 @@ def _tsdf_cast_backward_args(op, tsdf, weight, color, origin, voxel_size, K, pos
         raise ValueError("{}: g_depth should have shape {}. Got {}.".format(op, (B, L, Ho, Wo), tuple(g_depth.shape)))
     if g_rgb is not None and (c is None or tuple(g_rgb.shape) != (B, L, Ho, Wo, 3)):
         raise ValueError("{}: g_rgb needs a volume with colours and the shape {}. Got {}.".format(op, (B, L, Ho, Wo, 3), tuple(g_rgb.shape)))
-    return t, w, c, origin, dims, v, K, poses, L, height, width, stride, step, mw, k_end.contiguous(), _f32c(g_depth), _f32c(g_rgb)
+    k_end, g_depth, g_rgb = k_end.contiguous(), _f32c(g_depth), _f32c(g_rgb)
+    g_tsdf = torch.empty_like(t) if want_volume else None
+    g_color = torch.empty_like(c) if want_volume and c is not None else None
+    g_poses = torch.empty((B, L, 4, 4), dtype=torch.float32, device=dev) if with_poses else None
+    size_args = (B, *dims, int(c is not None)) + ((L, height, width, stride) if with_poses else ())
+    ws = workspace(ws_bytes("gs_{}_ws_bytes".format(op), *size_args), dev, "tsdf_cast_bwd_poses" if with_poses else "tsdf_cast_bwd")
+    call("gs_" + op, ptr(t), ptr(w), ptr(c), B, *dims, v, ptr(origin), ptr(K), ptr(poses), L, height, width, stride, step, mw, ptr(k_end),
+         ptr(g_depth), ptr(g_rgb), ptr(g_tsdf), ptr(g_color), *((ptr(g_poses),) if with_poses else ()), ptr(ws), ws.numel(), stream())
+    return g_tsdf, g_color, g_poses
 
 
 def tsdf_raycast_backward_raw(tsdf, weight, color, origin, voxel_size, K, poses, height: int, width: int, stride, step, min_weight,
@@ -1725,16 +1707,8 @@ def tsdf_raycast_backward_raw(tsdf, weight, color, origin, voxel_size, K, poses,
     """Adjoint of tsdf_raycast_raw for the tape k_end (a constant): g_depth (B,L,Ho,Wo), g_rgb (B,L,Ho,Wo,3) (None: zero) ->
     (g_tsdf, g_color or None), written in full.  Every voxel's sum over its pixels is exact and rounded once: the same bits from
     run to run (one path, with or without torch.use_deterministic_algorithms).  Poses, intrinsics and weights get no gradient."""
-    t, w, c, origin, dims, v, K, poses, L, height, width, stride, step, mw, k_end, g_depth, g_rgb = _tsdf_cast_backward_args(
-        "tsdf_raycast_backward", tsdf, weight, color, origin, voxel_size, K, poses, height, width, stride, step, min_weight, k_end, g_depth,
-        g_rgb)
-    B, dev = t.shape[0], t.device
-    g_tsdf = torch.empty_like(t)
-    g_color = None if c is None else torch.empty_like(c)
-    ws = workspace(ws_bytes("gs_tsdf_raycast_backward_ws_bytes", B, *dims, int(c is not None)), dev, "tsdf_cast_bwd")
-    call("gs_tsdf_raycast_backward", ptr(t), ptr(w), ptr(c), B, *dims, v, ptr(origin), ptr(K), ptr(poses), L, height, width, stride, step,
-         mw, ptr(k_end), ptr(g_depth), ptr(g_rgb), ptr(g_tsdf), ptr(g_color), ptr(ws), ws.numel(), stream())
-    return g_tsdf, g_color
+    return _tsdf_raycast_backward("tsdf_raycast_backward", False, True, tsdf, weight, color, origin, voxel_size, K, poses, height, width,
+                                  stride, step, min_weight, k_end, g_depth, g_rgb)[:2]
 
 
 def tsdf_raycast_backward_poses_raw(tsdf, weight, color, origin, voxel_size, K, poses, height: int, width: int, stride, step, min_weight,
@@ -1745,18 +1719,8 @@ def tsdf_raycast_backward_poses_raw(tsdf, weight, color, origin, voxel_size, K, 
     without hits), with which sample ends a ray, whether it hits and the cells of its three positions held constant.  Fixed
     order fp32 sums, no atomics: the same bits from run to run.  Intrinsics, weights, origin and the normal image receive no
     gradient."""
-    t, w, c, origin, dims, v, K, poses, L, height, width, stride, step, mw, k_end, g_depth, g_rgb = _tsdf_cast_backward_args(
-        "tsdf_raycast_backward_poses", tsdf, weight, color, origin, voxel_size, K, poses, height, width, stride, step, min_weight, k_end,
-        g_depth, g_rgb)
-    B, dev = t.shape[0], t.device
-    g_tsdf = torch.empty_like(t) if want_volume else None
-    g_color = torch.empty_like(c) if want_volume and c is not None else None
-    g_poses = torch.empty((B, L, 4, 4), dtype=torch.float32, device=dev)
-    ws = workspace(ws_bytes("gs_tsdf_raycast_backward_poses_ws_bytes", B, *dims, int(c is not None), L, height, width, stride), dev,
-                   "tsdf_cast_bwd_poses")
-    call("gs_tsdf_raycast_backward_poses", ptr(t), ptr(w), ptr(c), B, *dims, v, ptr(origin), ptr(K), ptr(poses), L, height, width, stride,
-         step, mw, ptr(k_end), ptr(g_depth), ptr(g_rgb), ptr(g_tsdf), ptr(g_color), ptr(g_poses), ptr(ws), ws.numel(), stream())
-    return g_tsdf, g_color, g_poses
+    return _tsdf_raycast_backward("tsdf_raycast_backward_poses", True, want_volume, tsdf, weight, color, origin, voxel_size, K, poses,
+                                  height, width, stride, step, min_weight, k_end, g_depth, g_rgb)
 
 
 class _TsdfRaycastFn(torch.autograd.Function):
@@ -1841,7 +1805,7 @@ def _rgbd_params(levels, lambda_geo, depth_diff_max, rgb_scale, H, W, op):
         raise ValueError("{}: levels should be an integer in [1, 8]. Got {!r}.".format(op, levels))
     if (H >> (levels - 1)) < 4 or (W >> (levels - 1)) < 4:
         raise ValueError("{}: the coarsest of {} levels of a {} x {} image would be smaller than 4 x 4.".format(op, levels, H, W))
-    lam, ddm, scale = (_tsdf_number(x, n, op) for x, n in ((lambda_geo, "lambda_geo"), (depth_diff_max, "depth_diff_max"),
+    lam, ddm, scale = (_number(x, n, op) for x, n in ((lambda_geo, "lambda_geo"), (depth_diff_max, "depth_diff_max"),
                                                            (rgb_scale, "rgb_scale")))
     if not 0.0 <= lam <= 1.0:
         raise ValueError("{}: lambda_geo should be in [0, 1]. Got {!r}.".format(op, lambda_geo))
@@ -1909,7 +1873,7 @@ def rgbd_odometry(tgt_depth, tgt_rgb, src_depth, src_rgb, intrinsics, init=None,
     K = _rgbd_K(intrinsics, B, op)
     init = None if init is None else _rgbd_T(init, B, "init", op)
     lam, ddm, scale = _rgbd_params(levels, lambda_geo, depth_diff_max, rgb_scale, H, W, op)
-    damp = _tsdf_number(damp, "damp", op)
+    damp = _number(damp, "damp", op)
     if not (0.0 <= damp < math.inf):
         raise ValueError("{}: damp should be finite and not negative. Got {!r}.".format(op, damp))
     if isinstance(numiters, int) and not isinstance(numiters, bool):

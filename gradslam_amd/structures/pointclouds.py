@@ -516,7 +516,7 @@ class Pointclouds(object):
         its lowest member row (-1 beyond)."""
         from .. import ops
 
-        voxel_size = ops._voxel_size(voxel_size, "voxel_downsample")
+        voxel_size = ops._positive(voxel_size, "voxel_size", "voxel_downsample")
         if feature_reduction not in ("mean", "sum"):
             raise ValueError('feature_reduction should be "mean" or "sum". Got {!r}.'.format(feature_reduction))
         if not self.has_points or self._B == 0:

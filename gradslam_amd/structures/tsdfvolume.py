@@ -28,9 +28,9 @@ class TSDFVolume(object):
                  color: bool = True, device="cuda"):
         op = "TSDFVolume"
         self.dims = ops._tsdf_dims(dims, op)
-        self.voxel_size = ops._tsdf_positive(voxel_size, "voxel_size", op)
-        self.trunc = ops._tsdf_positive(4.0 * self.voxel_size if trunc is None else trunc, "trunc", op)
-        self.max_weight = ops._tsdf_positive(max_weight, "max_weight", op)
+        self.voxel_size = ops._positive(voxel_size, "voxel_size", op)
+        self.trunc = ops._positive(4.0 * self.voxel_size if trunc is None else trunc, "trunc", op)
+        self.max_weight = ops._positive(max_weight, "max_weight", op)
         self.device = torch.device(device)
         if self.device.type != "cuda":
             raise ValueError("{}: device is {}; TSDF volumes only live on a HIP device (no CPU fallback is provided).".format(op, self.device))

@@ -1,5 +1,6 @@
 // rgbd.hip -- dense RGB-D odometry: joint photometric + depth alignment of two frames over an image pyramid, coarse to fine
-// (gs_rgbd_odometry, gs_rgbd_rows, gs_rgbd_pyramid).  The rule -- every fp32 operation in order -- is stated in
+// (gs_rgbd_odometry, gs_rgbd_rows, gs_rgbd_pyramid) and its reverse pass (gs_rgbd_odometry_taped, gs_rgbd_odometry_bwd,
+// gs_rgbd_rows_bwd: Xb, Lb, Pb further down).  The rule -- every fp32 operation in order -- is stated in
 // include/gradslam_hip.h above the entry points; this file follows it line by line (the library is built without contraction).
 //
 // P  pyramid: level 0 is (intensity, depth or 0) per pixel as ONE float2, so that a bilinear corner is one 8-byte load; every
@@ -20,6 +21,8 @@
 #define icp_step_k icp_step_k_in_rgbd_unit
 #include "gs_icp_step.hpp"
 #undef icp_step_k
+#include "gs_fixed128.hpp"
+#include "gs_se3_bwd.hpp"
 
 namespace gs {
 
@@ -214,9 +217,13 @@ __global__ __launch_bounds__(RGBD_T) void rgbd_linearize_k(const float2 *__restr
 // grid B, 1024 threads.  Reduces batch element b's `nblocks` partial rows; `sums` (B, 29: H upper | g = -sum | err | cnt)
 // is written when given; with `apply`, lane 0 solves and composes T[b] <- exp(xi) T[b], and writes out_T[b] and the level's
 // info row (cnt, err, status bits of the level so far, iterations run at the level).
+// TAPE: the iteration's tape row of batch element b (RGBD_TAPE_WORDS floats at tape + RGBD_TAPE_WORDS b): T before the step (16),
+// the 29 sums as reduced (g not yet negated), xi (6), 1 if the step was applied else 0 -- what the reverse pass replays.
+constexpr int RGBD_TAPE_WORDS = 64, RGBD_TAPE_SUMS = 16, RGBD_TAPE_XI = 45, RGBD_TAPE_APPLIED = 51;
+template <bool TAPE>
 __global__ __launch_bounds__(1024) void rgbd_step_k(float *__restrict__ Tall, const float *__restrict__ partials, int nblocks, int prow,
                                                    float damp, int level, int levels, int it, int apply, float *__restrict__ out_T,
-                                                   float *__restrict__ info, float *__restrict__ sums) {
+                                                   float *__restrict__ info, float *__restrict__ sums, float *__restrict__ tape) {
     __shared__ float acc[NACC];
     __shared__ double lu_sm[42];
     const int b = blockIdx.x;
@@ -230,6 +237,13 @@ __global__ __launch_bounds__(1024) void rgbd_step_k(float *__restrict__ Tall, co
     float *row = info + ((int64_t)b * levels + level) * 4;
     int status = it == 0 ? 0 : (int)row[2];
     const float cnt = acc[28];
+    float *rec = TAPE ? tape + RGBD_TAPE_WORDS * b : nullptr;
+    if constexpr (TAPE) {
+        for (int k = 0; k < 16; ++k) rec[k] = T[k];
+        for (int k = 0; k < NACC; ++k) rec[RGBD_TAPE_SUMS + k] = acc[k];
+        for (int k = 0; k < 6; ++k) rec[RGBD_TAPE_XI + k] = 0.0f;
+        rec[RGBD_TAPE_APPLIED] = 0.0f;
+    }
     if (cnt < 6.0f) {
         status |= RGBD_STATUS_FEW;
     } else {
@@ -245,6 +259,10 @@ __global__ __launch_bounds__(1024) void rgbd_step_k(float *__restrict__ Tall, co
             for (int k = 0; k < 12; ++k) fin = fin && fabsf(Tn[k]) < INFINITY;
         }
         if (fin) {
+            if constexpr (TAPE) {
+                for (int k = 0; k < 6; ++k) rec[RGBD_TAPE_XI + k] = xi[k];
+                rec[RGBD_TAPE_APPLIED] = 1.0f;
+            }
             for (int k = 0; k < 16; ++k) T[k] = Tn[k];
         } else {
             status |= RGBD_STATUS_SOLVE;
@@ -267,6 +285,292 @@ __global__ __launch_bounds__(256) void rgbd_init_k(const float *__restrict__ ini
         out_T[i] = v;
     }
     if (i < n_info) info[i] = 0.0f;
+}
+
+// ------------------------------------------------------------------ the reverse pass (the rule: include/gradslam_hip.h)
+// Per iteration, last to first:
+// Xb step reverse, one 256-thread block per batch element: the pixel pass before left 12-sum rows -- the adjoint of T_{k+1}
+//    through ITS linearisation -- which are folded (reduce12) into the carried adjoint; then, one lane, fp64 where the forward's
+//    fp32 value would lose the gradient: dT-bar = T-bar_{k+1} T_k^T, T-bar_k = dT^T T-bar_{k+1}, the exponential's and the
+//    solve's adjoints -> the adjoints of the iteration's 29 sums.  A step that was not applied is the identity.
+// Lb pixel reverse, the forward's geometry: the pixel's forward values again from the taped T_k (the same operations: the
+//    same decisions), the adjoints of its two rows and residuals from those of the sums, pulled back to q, the eight corner
+//    values, the source pixel and T.  <MAX> does all of it but the corner sums, of which it takes the largest magnitude;
+//    <ACC> only adds the corner terms into the level's exact fold (gs_fixed128.hpp).  One fold and one finish per level.
+// Pb the pyramids' adjoints, coarsest to finest, after all levels: a gather per fine pixel, then level 0 into the images.
+constexpr int RGBD_ADJ_WORDS = 32;  // adjoints of the 28 sums AS REDUCED (the six of g: of the sum, not of minus it; cnt has none)
+constexpr int RGBD_ADJ_LIVE = 28;   // 1: the pixel pass applies them; 0: a step that was not applied -- nothing, not even 0 x inf
+enum { RGBD_BWD_MAX = 0, RGBD_BWD_ACC = 1 };
+
+// out[b] (stride floats, 12 or 16: the bottom row is zero) = gT_in[b] rows 0..2 (NULL: zero) + the sum of b's 12-wide rows
+__global__ __launch_bounds__(BWD_T) void rgbd_gT_k(const float *__restrict__ gT_in, const float *__restrict__ partials12, int nblocks,
+                                                  int prow, float *__restrict__ out, int stride) {
+    __shared__ float sums[12];
+    const int b = blockIdx.x;
+    reduce12(partials12 + (int64_t)b * prow * 12, nblocks, sums);
+    if ((int)threadIdx.x < stride)
+        out[stride * b + threadIdx.x] = threadIdx.x < 12 ? (gT_in ? gT_in[16 * b + threadIdx.x] : 0.0f) + sums[threadIdx.x] : 0.0f;
+}
+
+// gs_rgbd_rows_bwd: the adjoints of the sums as gs_rgbd_rows returns them (g = MINUS the sum) -> of the sums as reduced; the
+// adjoint of cnt is ignored
+__global__ __launch_bounds__(256) void rgbd_sums_adj_k(const float *__restrict__ g_sums, int B, float *__restrict__ adj) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= B * RGBD_ADJ_WORDS) return;
+    const int b = i / RGBD_ADJ_WORDS, k = i - b * RGBD_ADJ_WORDS;
+    const float g = k < 28 ? g_sums[NACC * b + k] : 0.0f;
+    adj[i] = k == RGBD_ADJ_LIVE ? 1.0f : ((k >= 21 && k < 27) ? -g : g);
+}
+
+// grid B.  gT (B,16): the carried adjoint of T (rows 0..2), updated in place; rec: this iteration's tape rows; adj: its (B, 32)
+__global__ __launch_bounds__(BWD_T) void rgbd_step_bwd_k(float *__restrict__ gTall, const float *__restrict__ partials12, int nblocks,
+                                                        int prow, const float *__restrict__ rec_all, float damp,
+                                                        float *__restrict__ adj_all) {
+    __shared__ float sums[12];
+    __shared__ double lu_sm[42];
+    __shared__ float g[16], xi[6], dT[16], hg[44], gx[6], y[6];
+    __shared__ double gdT[12], gxi[6];
+    const int b = blockIdx.x;
+    reduce12(partials12 + (int64_t)b * prow * 12, nblocks, sums);
+    if (threadIdx.x != 0) return;
+    const float *rec = rec_all + RGBD_TAPE_WORDS * b;
+    float *gT = gTall + 16 * b, *A = adj_all + RGBD_ADJ_WORDS * b;
+    for (int k = 0; k < 16; ++k) g[k] = k < 12 ? gT[k] + sums[k] : 0.0f;
+    for (int k = 0; k < RGBD_ADJ_WORDS; ++k) A[k] = 0.0f;
+    if (rec[RGBD_TAPE_APPLIED] != 0.0f) {
+        for (int k = 0; k < 6; ++k) xi[k] = rec[RGBD_TAPE_XI + k];
+        se3_exp_dev(xi, dT);  // the forward's dT, bit for bit
+        top3_times_Tt(g, rec, gdT);
+        pull_gT(g, dT);
+        se3_exp_bwd(xi, gdT, gxi);
+        // xi = M^-1 g', M = H + damp I symmetric, g' = MINUS the six sums:  y = M^-1 xi-bar;  H-bar = -y xi^T, g'-bar = y
+        expand44(rec + RGBD_TAPE_SUMS, hg);
+        for (int k = 0; k < 6; ++k) gx[k] = (float)gxi[k];
+        solve6(hg, gx, damp, y, lu_sm);
+        int q = 0;
+        for (int u = 0; u < 6; ++u)
+            for (int v = u; v < 6; ++v) A[q++] = u == v ? -(y[u] * xi[u]) : -(y[u] * xi[v] + y[v] * xi[u]);
+        for (int u = 0; u < 6; ++u) A[21 + u] = -y[u];
+        A[RGBD_ADJ_LIVE] = 1.0f;
+    }
+    for (int k = 0; k < 12; ++k) gT[k] = g[k];
+}
+
+// One source pixel's forward values, by rgbd_linearize_k's operations in its order (the same bits, so the same decisions).
+struct RgbdPix {
+    float px, py, d, ux, vy;  // the back-projection: px = d ux, py = d vy
+    float qx, qy, qz, iz, a, bb;
+    int corner;               // c00's index in the level's image
+    float2 c00, c10, c01, c11;
+    float Is;
+};
+__device__ __forceinline__ bool rgbd_pixel_fwd(const float2 *__restrict__ timg, const float2 s, int u, int v, int Hl, int Wl,
+                                               const RgbdCam cam, const float *__restrict__ T, float ddm, RgbdPix &P) {
+    if (!(s.y > 0.0f)) return false;
+    const float d = s.y;
+    P.ux = ((float)u - cam.cx) / cam.fx;
+    P.vy = ((float)v - cam.cy) / cam.fy;
+    const float px = d * P.ux, py = d * P.vy;
+    const float qx = ((T[0] * px + T[1] * py) + T[2] * d) + T[3];
+    const float qy = ((T[4] * px + T[5] * py) + T[6] * d) + T[7];
+    const float qz = ((T[8] * px + T[9] * py) + T[10] * d) + T[11];
+    bool ok = qz > 0.0f;
+    const float iz = 1.0f / qz;
+    const float x = (cam.fx * qx) * iz + cam.cx, y = (cam.fy * qy) * iz + cam.cy;
+    const float xf = floorf(x), yf = floorf(y);
+    ok = ok && xf >= 0.0f && xf <= (float)(Wl - 2) && yf >= 0.0f && yf <= (float)(Hl - 2);
+    if (!ok) return false;
+    const int i = (int)xf, j = (int)yf;
+    P.corner = j * Wl + i;
+    const float2 *c = timg + P.corner;
+    P.c00 = c[0]; P.c10 = c[1]; P.c01 = c[Wl]; P.c11 = c[Wl + 1];
+    if (!(P.c00.y > 0.0f && P.c10.y > 0.0f && P.c01.y > 0.0f && P.c11.y > 0.0f)) return false;
+    P.a = x - xf; P.bb = y - yf;
+    const float dX0 = P.c10.y - P.c00.y, dX1 = P.c11.y - P.c01.y;
+    const float dTop = P.c00.y + P.a * dX0, dBot = P.c01.y + P.a * dX1;
+    const float Dh = dTop + P.bb * (dBot - dTop);
+    if (!(fabsf(Dh - qz) <= ddm)) return false;
+    P.px = px; P.py = py; P.d = d; P.qx = qx; P.qy = qy; P.qz = qz; P.iz = iz; P.Is = s.x;
+    return true;
+}
+
+// One channel F (I or D) of a valid pixel: its row J (6) and residual r again, their adjoints from those of the sums (M: the
+// symmetric 6 x 6 that J-bar = M J + g r needs, g: the adjoints of the six sums J r, e2 = twice err's), pulled back to the
+// four corners cb (00, 10, 01, 11), to q, iz, gx, gy and to the cell coordinates a, b.  `minus`: the other term of the residual
+// (I_s or q_z); returns its adjoint.
+__device__ __forceinline__ float rgbd_chan_bwd(float F00, float F10, float F01, float F11, float minus, float cz, float w, const RgbdPix &P,
+                                               float gx, float gy, const float *__restrict__ M, const float *__restrict__ g, float e2,
+                                               float (&cb)[4], float &qxb, float &qyb, float &qzb, float &izb, float &gxb, float &gyb,
+                                               float &ab, float &bbb) {
+    const float qx = P.qx, qy = P.qy, qz = P.qz, iz = P.iz, a = P.a, bb = P.bb;
+    const float X0 = F10 - F00, X1 = F11 - F01;
+    const float top = F00 + a * X0, bot = F01 + a * X1;
+    const float Fh = top + bb * (bot - top), Fx = X0 + bb * (X1 - X0), Fy = bot - top;
+    const float c0 = Fx * gx, c1 = Fy * gy, t = c0 * qx + c1 * qy, c2 = -(t * iz) - cz;
+    float J[6] = {w * c0, w * c1, w * c2, w * (qy * c2 - qz * c1), w * (qz * c0 - qx * c2), w * (qx * c1 - qy * c0)};
+    const float r = w * (Fh - minus);
+    float Jb[6], rb = e2 * r;
+#pragma unroll
+    for (int u = 0; u < 6; ++u) {
+        float v = g[u] * r;
+#pragma unroll
+        for (int k = 0; k < 6; ++k) v += M[6 * u + k] * J[k];
+        Jb[u] = v;
+        rb += g[u] * J[u];
+    }
+    float c0b = w * ((Jb[0] + qz * Jb[4]) - qy * Jb[5]);
+    float c1b = w * ((Jb[1] - qz * Jb[3]) + qx * Jb[5]);
+    const float c2b = w * ((Jb[2] + qy * Jb[3]) - qx * Jb[4]);
+    qxb += w * (c1 * Jb[5] - c2 * Jb[4]);
+    qyb += w * (c2 * Jb[3] - c0 * Jb[5]);
+    qzb += w * (c0 * Jb[4] - c1 * Jb[3]);
+    const float tb = -(c2b * iz);
+    izb -= c2b * t;
+    c0b += tb * qx; c1b += tb * qy;
+    qxb += tb * c0; qyb += tb * c1;
+    const float Fxb = c0b * gx, Fyb = c1b * gy, Fhb = w * rb;
+    gxb += c0b * Fx; gyb += c1b * Fy;
+    const float topb = Fhb * (1.0f - bb) - Fyb, botb = Fhb * bb + Fyb;
+    bbb += Fhb * (bot - top) + Fxb * (X1 - X0);  // F_x's b-derivative = F_y's a-derivative: the one second derivative of the cell
+    const float X0b = Fxb * (1.0f - bb) + topb * a, X1b = Fxb * bb + botb * a;
+    ab += topb * X0 + botb * X1;
+    cb[0] = topb - X0b; cb[1] = X0b; cb[2] = botb - X1b; cb[3] = X1b;
+    return -Fhb;
+}
+
+// grid (blocks of RGBD_T source pixels, B), rgbd_linearize_k's.  T: batch element b's transform at T + tstride b; adj (B, 32).
+// MAX: gsrc[pixel] += the source pixel's (I, D) adjoint (its owner lane, in launch order); the block's 12 sums of T's adjoint
+// -> partials12 row blockIdx.x; the largest corner term -> the fold.  ACC: the eight corner terms -> the fold's sums (row =
+// the target pixel, channel I or D), scaled for at most 2^lg terms per sum.
+template <int MODE>
+__global__ __launch_bounds__(RGBD_T) void rgbd_pixel_bwd_k(const float2 *__restrict__ tgt, const float2 *__restrict__ src, int Hl, int Wl,
+                                                          int level, const float *__restrict__ K, const float *__restrict__ Tall,
+                                                          int tstride, const float *__restrict__ adj, float wI, float wD, float ddm,
+                                                          Fold fold, int lg, float2 *__restrict__ gsrc, float *__restrict__ partials12,
+                                                          int prow) {
+    __shared__ float M[36], g[6], e2s;
+    const int b = blockIdx.y, npix = Hl * Wl;
+    const int p = blockIdx.x * RGBD_T + threadIdx.x;
+    const float *__restrict__ A = adj + RGBD_ADJ_WORDS * b;
+    if (threadIdx.x < 36) {
+        int u = threadIdx.x / 6, v = threadIdx.x % 6;
+        const bool diag = u == v;
+        if (u > v) { const int t = u; u = v; v = t; }
+        const float s = A[u * 6 - (u * (u - 1)) / 2 + (v - u)];
+        M[threadIdx.x] = diag ? 2.0f * s : s;
+    } else if (threadIdx.x < 42) {
+        g[threadIdx.x - 36] = A[21 + (threadIdx.x - 36)];
+    } else if (threadIdx.x == 42) {
+        e2s = 2.0f * A[27];
+    }
+    __syncthreads();
+    const RgbdCam cam = rgbd_cam(K + 16 * b, level);
+    const float *__restrict__ T = Tall + (int64_t)tstride * b;
+    const float2 *__restrict__ timg = tgt + (int64_t)b * npix;
+    RgbdPix P;
+    bool ok = false;
+    if (p < npix && A[RGBD_ADJ_LIVE] != 0.0f) {
+        const int v = p / Wl, u = p - v * Wl;
+        ok = rgbd_pixel_fwd(timg, src[(int64_t)b * npix + p], u, v, Hl, Wl, cam, T, ddm, P);
+    }
+    float acc[12];
+#pragma unroll
+    for (int k = 0; k < 12; ++k) acc[k] = 0.0f;
+    uint32_t mx = 0;
+    const int E = MODE == RGBD_BWD_ACC ? det_scale(*fold.maxbits, lg) : 0;
+    if (ok) {
+        const float gx = cam.fx * P.iz, gy = cam.fy * P.iz;
+        float cI[4], cD[4], qxb = 0.0f, qyb = 0.0f, qzb = 0.0f, izb = 0.0f, gxb = 0.0f, gyb = 0.0f, ab = 0.0f, bbb = 0.0f;
+        const float Isb = rgbd_chan_bwd(P.c00.x, P.c10.x, P.c01.x, P.c11.x, P.Is, 0.0f, wI, P, gx, gy, M, g, e2s, cI, qxb, qyb, qzb, izb, gxb,
+                                        gyb, ab, bbb);
+        const float qzr = rgbd_chan_bwd(P.c00.y, P.c10.y, P.c01.y, P.c11.y, P.qz, 1.0f, wD, P, gx, gy, M, g, e2s, cD, qxb, qyb, qzb, izb, gxb,
+                                        gyb, ab, bbb);
+        qzb += qzr;  // r_D = w_D (D^ - q_z)
+        if (MODE == RGBD_BWD_ACC) {
+            const int64_t row = (int64_t)b * npix + P.corner;
+            const int64_t rows[4] = {row, row + 1, row + Wl, row + Wl + 1};
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                fold_add(fold, rows[k], 0, cI[k], E);
+                fold_add(fold, rows[k], 1, cD[k], E);
+            }
+        } else {
+#pragma unroll
+            for (int k = 0; k < 4; ++k) mx = fold_max(fold_max(mx, cI[k]), cD[k]);
+            // x = (fx q_x) iz + cx, y likewise; gx = fx iz, gy = fy iz; iz = 1 / q_z
+            izb += cam.fx * gxb + cam.fy * gyb;
+            qxb += ab * gx; izb += ab * (cam.fx * P.qx);
+            qyb += bbb * gy; izb += bbb * (cam.fy * P.qy);
+            qzb -= (izb * P.iz) * P.iz;
+            // q = T (px, py, d, 1)
+            acc[0] = qxb * P.px; acc[1] = qxb * P.py; acc[2] = qxb * P.d; acc[3] = qxb;
+            acc[4] = qyb * P.px; acc[5] = qyb * P.py; acc[6] = qyb * P.d; acc[7] = qyb;
+            acc[8] = qzb * P.px; acc[9] = qzb * P.py; acc[10] = qzb * P.d; acc[11] = qzb;
+            const float pxb = (T[0] * qxb + T[4] * qyb) + T[8] * qzb, pyb = (T[1] * qxb + T[5] * qyb) + T[9] * qzb;
+            const float db = (((T[2] * qxb + T[6] * qyb) + T[10] * qzb) + pxb * P.ux) + pyb * P.vy;
+            float2 *o = gsrc + (int64_t)b * npix + p;
+            const float2 old = *o;
+            *o = make_float2(old.x + Isb, old.y + db);
+        }
+    }
+    if (MODE == RGBD_BWD_MAX) {
+        // The fold's maximum only grows, so a term no larger than a value it has held needs no atomic: after the first blocks
+        // almost none is issued (thousands of waves, one address).  The maximum is the same whichever are skipped.
+        if (mx <= __hip_atomic_load(fold.maxbits, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) mx = 0;
+        fold_max_commit(fold.maxbits, mx);
+        block_store12(acc, partials12 + (int64_t)b * prow * 12);
+    }
+}
+
+// the level's target adjoint from its fold: n = B npix rows, two channels
+__global__ __launch_bounds__(256) void rgbd_fold_finish_k(Fold fold, int lg, int64_t n, float2 *__restrict__ gtgt) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const int E = det_scale(*fold.maxbits, lg);
+    gtgt[i] = make_float2(fold_result(fold, i, 0, E), fold_result(fold, i, 1, E));
+}
+
+// rgbd_down_k's adjoint as a gather: fine pixel p of (B, Hp, Wp) belongs to one coarse pixel (none in an odd last row or column);
+// gin[p] += (0.25 I-bar, D-bar / n where the fine depth was taken).  grid (blocks of 256 fine pixels, B)
+__global__ __launch_bounds__(256) void rgbd_down_bwd_k(const float2 *__restrict__ in, int Hp, int Wp, int Hl, int Wl, float ddm,
+                                                      const float2 *__restrict__ gout, float2 *__restrict__ gin) {
+    const int p = blockIdx.x * 256 + threadIdx.x;
+    if (p >= Hp * Wp) return;
+    const int v = p / Wp, u = p - v * Wp, cv = v >> 1, cu = u >> 1;
+    if (cv >= Hl || cu >= Wl) return;
+    const float2 *src = in + (int64_t)blockIdx.y * Hp * Wp + (int64_t)(2 * cv) * Wp + 2 * cu;
+    const float2 c[4] = {src[0], src[1], src[Wp], src[Wp + 1]};
+    float dmin = INFINITY;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) dmin = (c[k].y > 0.0f && c[k].y < dmin) ? c[k].y : dmin;
+    int n = 0;
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+        if (c[k].y > 0.0f && c[k].y - dmin <= ddm) ++n;
+    const float mine = (v & 1) ? ((u & 1) ? c[3].y : c[2].y) : ((u & 1) ? c[1].y : c[0].y);
+    const float2 go = gout[(int64_t)blockIdx.y * Hl * Wl + (int64_t)cv * Wl + cu];
+    const bool taken = mine > 0.0f && mine - dmin <= ddm;
+    float2 *o = gin + (int64_t)blockIdx.y * Hp * Wp + p;
+    const float2 old = *o;
+    *o = make_float2(old.x + 0.25f * go.x, old.y + (taken ? go.y / (float)n : 0.0f));
+}
+
+// rgbd_level0_k's adjoint: the luma weights times rgb_scale into rgb, the depth's where the depth was kept; either may be NULL
+__global__ __launch_bounds__(256) void rgbd_level0_bwd_k(const float *__restrict__ depth, const float2 *__restrict__ g, int64_t n,
+                                                        float rgb_scale, float *__restrict__ g_depth, float *__restrict__ g_rgb) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const float2 gi = g[i];
+    if (g_rgb) {
+        const float s = rgb_scale * gi.x;
+        g_rgb[3 * i] = 0.299f * s;
+        g_rgb[3 * i + 1] = 0.587f * s;
+        g_rgb[3 * i + 2] = 0.114f * s;
+    }
+    if (g_depth) {
+        const float d = depth[i];
+        g_depth[i] = (d > 0.0f && d < INFINITY) ? gi.y : 0.0f;
+    }
 }
 
 // ------------------------------------------------------------------ host
@@ -330,6 +634,42 @@ static int rgbd_build_pyramid(const char *name, const float *depth, const float 
     return 0;
 }
 
+
+// the reverse pass's workspace: the forward's pyramids again (f: its sizes and offsets; f.T and f.partials are not carved)
+struct RgbdBwdWs {
+    RgbdWs f;
+    float *gT;          // B x 16: the carried adjoint of T
+    float *adj;         // max(iterations, 1) x B x RGBD_ADJ_WORDS, in the order the iterations ran
+    float *partials12;  // B x prow x 12
+    float2 *gtgt, *gsrc;  // the pyramids' adjoints, the forward's layout, one piece (adj_pyr_bytes)
+    size_t adj_pyr_bytes;
+    Fold fold;          // B H W rows x 2 channels; a coarser level uses its first rows
+    void *fold_base;
+    size_t fold_bytes;
+};
+static size_t rgbd_bwd_layout(int B, int H, int W, int levels, int64_t iterations, void *ws, RgbdBwdWs *out) {
+    Carve c{(char *)ws};
+    RgbdBwdWs t;
+    rgbd_layout(B, H, W, levels, nullptr, &t.f);
+    t.f.T = nullptr;
+    t.f.partials = nullptr;
+    const size_t pyr = sizeof(float2) * (size_t)t.f.off[levels] * B;
+    t.gT = c.take<float>(sizeof(float) * 16 * B);
+    t.adj = c.take<float>(sizeof(float) * RGBD_ADJ_WORDS * (size_t)std::max<int64_t>(iterations, 1) * B);
+    t.partials12 = c.take<float>(sizeof(float) * 12 * (size_t)t.f.prow * B);
+    t.f.tgt = c.take<float2>(pyr);
+    t.f.src = c.take<float2>(pyr);
+    t.adj_pyr_bytes = 2 * pyr;
+    t.gtgt = c.take<float2>(t.adj_pyr_bytes);
+    t.gsrc = t.gtgt ? t.gtgt + (size_t)t.f.off[levels] * B : nullptr;
+    const size_t before = c.off;
+    t.fold = fold_carve(c, (size_t)B * H * W, 2);
+    t.fold_base = t.fold.maxbits;
+    t.fold_bytes = c.off - before;
+    if (out) *out = t;
+    return c.off;
+}
+
 }  // namespace gs
 
 using namespace gs;
@@ -372,25 +712,20 @@ int gs_rgbd_rows(const float *tgt_depth, const float *tgt_rgb, const float *src_
     hipLaunchKernelGGL(rgbd_linearize_k<true>, dim3(w.prow, B), dim3(RGBD_T), 0, st, w.tgt, w.src, H, W, 0, intrinsics, T, wI, wD,
                        depth_diff_max, w.partials, w.prow, valid, rows);
     GS_LAUNCH_CHECK("gs_rgbd_rows/linearize");
-    hipLaunchKernelGGL(rgbd_step_k, dim3(B), dim3(1024), 0, st, w.T, w.partials, w.prow, w.prow, 0.0f, 0, 1, 0, 0, (float *)nullptr,
-                       (float *)nullptr, sums);
+    hipLaunchKernelGGL(rgbd_step_k<false>, dim3(B), dim3(1024), 0, st, w.T, w.partials, w.prow, w.prow, 0.0f, 0, 1, 0, 0, (float *)nullptr,
+                       (float *)nullptr, sums, (float *)nullptr);
     GS_LAUNCH_CHECK("gs_rgbd_rows/sums");
     return 0;
 }
 
-int gs_rgbd_odometry(const float *tgt_depth, const float *tgt_rgb, const float *src_depth, const float *src_rgb, int B, int H, int W,
-                     const float *intrinsics, const float *init, int levels, const int *numiters, float lambda_geo,
-                     float depth_diff_max, float damp, float rgb_scale, float *out_T, float *info, void *ws, size_t ws_bytes,
-                     gs_stream_t stream) {
-    GS_REQUIRE(tgt_depth && tgt_rgb && src_depth && src_rgb && intrinsics && numiters && out_T && info, "gs_rgbd_odometry: null pointer");
-    RGBD_REQUIRE_SHAPE("gs_rgbd_odometry");
-    RGBD_REQUIRE_LAMBDA("gs_rgbd_odometry");
-    RGBD_REQUIRE_PARAMS("gs_rgbd_odometry");
-    GS_REQUIRE(damp >= 0.0f && damp < INFINITY, "gs_rgbd_odometry: damp must be finite and not negative, got %g", (double)damp);
-    for (int l = 0; l < levels; ++l)
-        GS_REQUIRE(numiters[l] >= 0 && numiters[l] <= (1 << 20), "gs_rgbd_odometry: numiters[%d] must be in [0, 2^20], got %d", l, numiters[l]);
+}  // extern "C"
+
+// gs_rgbd_odometry (tape = NULL) and gs_rgbd_odometry_taped: one loop, the same launches
+static int rgbd_run(const float *tgt_depth, const float *tgt_rgb, const float *src_depth, const float *src_rgb, int B, int H, int W,
+                    const float *intrinsics, const float *init, int levels, const int *numiters, float lambda_geo, float depth_diff_max,
+                    float damp, float rgb_scale, float *out_T, float *info, void *ws, size_t ws_bytes, gs_stream_t stream, float *tape) {
     const size_t need = gs_rgbd_odometry_ws_bytes(B, H, W, levels);
-    GS_REQUIRE_WS("gs_rgbd_odometry", ws, ws_bytes, need);
+    GS_REQUIRE_WS(tape ? "gs_rgbd_odometry_taped" : "gs_rgbd_odometry", ws, ws_bytes, need);
     hipStream_t st = (hipStream_t)stream;
     RgbdWs w;
     rgbd_layout(B, H, W, levels, ws, &w);
@@ -402,6 +737,7 @@ int gs_rgbd_odometry(const float *tgt_depth, const float *tgt_rgb, const float *
     rc = rgbd_build_pyramid("gs_rgbd_odometry/pyramid", src_depth, src_rgb, B, levels, w, depth_diff_max, rgb_scale, w.src, st);
     if (rc) return rc;
     const float wI = sqrtf(1.0f - lambda_geo), wD = sqrtf(lambda_geo);
+    float *rec = tape;  // one row per (iteration, batch element), in the order the iterations run
     for (int l = levels - 1; l >= 0; --l) {
         const int nblocks = cdiv((int64_t)w.Hl[l] * w.Wl[l], RGBD_T);
         for (int it = 0; it < numiters[l]; ++it) {
@@ -409,12 +745,209 @@ int gs_rgbd_odometry(const float *tgt_depth, const float *tgt_rgb, const float *
                                w.Hl[l], w.Wl[l], l, intrinsics, w.T, wI, wD, depth_diff_max, w.partials, w.prow, (int32_t *)nullptr,
                                (float *)nullptr);
             GS_LAUNCH_CHECK("gs_rgbd_odometry/linearize");
-            hipLaunchKernelGGL(rgbd_step_k, dim3(B), dim3(1024), 0, st, w.T, w.partials, nblocks, w.prow, damp, l, levels, it, 1, out_T,
-                               info, (float *)nullptr);
+            if (tape) {
+                hipLaunchKernelGGL(rgbd_step_k<true>, dim3(B), dim3(1024), 0, st, w.T, w.partials, nblocks, w.prow, damp, l, levels, it, 1,
+                                   out_T, info, (float *)nullptr, rec);
+                rec += (size_t)RGBD_TAPE_WORDS * B;
+            } else {
+                hipLaunchKernelGGL(rgbd_step_k<false>, dim3(B), dim3(1024), 0, st, w.T, w.partials, nblocks, w.prow, damp, l, levels, it, 1,
+                                   out_T, info, (float *)nullptr, (float *)nullptr);
+            }
             GS_LAUNCH_CHECK("gs_rgbd_odometry/step");
         }
     }
     return 0;
+}
+
+// the reverse pass of the loop: rgbd_backward_run.  `T`: (B, tstride) floats, batch element b's transform at T + tstride b (a tape
+// row or a plain (B,16)); `adj`: (B, RGBD_ADJ_WORDS) adjoints of the 29 sums.
+static int rgbd_pixel_bwd_launch(const char *name, int mode, const RgbdBwdWs &w, int B, int l, const float *K, const float *T, int tstride,
+                                 const float *adj, float wI, float wD, float ddm, int lg, hipStream_t st) {
+    const int nblocks = cdiv((int64_t)w.f.Hl[l] * w.f.Wl[l], RGBD_T);
+    const float2 *tgt = w.f.tgt + B * w.f.off[l], *src = w.f.src + B * w.f.off[l];
+    float2 *gsrc = w.gsrc + B * w.f.off[l];
+    if (mode == RGBD_BWD_MAX)
+        hipLaunchKernelGGL(rgbd_pixel_bwd_k<RGBD_BWD_MAX>, dim3(nblocks, B), dim3(RGBD_T), 0, st, tgt, src, w.f.Hl[l], w.f.Wl[l], l, K, T, tstride,
+                           adj, wI, wD, ddm, w.fold, lg, gsrc, w.partials12, w.f.prow);
+    else
+        hipLaunchKernelGGL(rgbd_pixel_bwd_k<RGBD_BWD_ACC>, dim3(nblocks, B), dim3(RGBD_T), 0, st, tgt, src, w.f.Hl[l], w.f.Wl[l], l, K, T, tstride,
+                           adj, wI, wD, ddm, w.fold, lg, gsrc, w.partials12, w.f.prow);
+    GS_LAUNCH_CHECK(name);
+    return 0;
+}
+static int rgbd_fold_finish_launch(const char *name, const RgbdBwdWs &w, int B, int l, int lg, hipStream_t st) {
+    const int64_t n = (int64_t)B * w.f.Hl[l] * w.f.Wl[l];
+    hipLaunchKernelGGL(rgbd_fold_finish_k, dim3(cdiv(n, 256)), dim3(256), 0, st, w.fold, lg, n, w.gtgt + B * w.f.off[l]);
+    GS_LAUNCH_CHECK(name);
+    return 0;
+}
+// both pyramids (rebuilt: the forward's workspace need not have survived), the adjoint pyramids zeroed
+static int rgbd_bwd_prepare(const char *name, const float *tgt_depth, const float *tgt_rgb, const float *src_depth, const float *src_rgb,
+                            int B, int levels, const RgbdBwdWs &w, float ddm, float rgb_scale, hipStream_t st) {
+    int rc = rgbd_build_pyramid(name, tgt_depth, tgt_rgb, B, levels, w.f, ddm, rgb_scale, w.f.tgt, st);
+    if (rc) return rc;
+    rc = rgbd_build_pyramid(name, src_depth, src_rgb, B, levels, w.f, ddm, rgb_scale, w.f.src, st);
+    if (rc) return rc;
+    GS_HIP(hipMemsetAsync(w.gtgt, 0, w.adj_pyr_bytes, st), name);  // gtgt | gsrc
+    return 0;
+}
+// the adjoint pyramids, coarsest to finest, then level 0 into the images; any of the four may be NULL
+static int rgbd_pyramid_bwd(const char *name, const float *depth, const float2 *pyr, float2 *gpyr, int B, int levels, const RgbdWs &f,
+                            float ddm, float rgb_scale, float *g_depth, float *g_rgb, hipStream_t st) {
+    if (!g_depth && !g_rgb) return 0;
+    for (int l = levels - 1; l >= 1; --l) {
+        hipLaunchKernelGGL(rgbd_down_bwd_k, dim3(cdiv((int64_t)f.Hl[l - 1] * f.Wl[l - 1], 256), B), dim3(256), 0, st, pyr + B * f.off[l - 1],
+                           f.Hl[l - 1], f.Wl[l - 1], f.Hl[l], f.Wl[l], ddm, gpyr + B * f.off[l], gpyr + B * f.off[l - 1]);
+        GS_LAUNCH_CHECK(name);
+    }
+    const int64_t n0 = (int64_t)B * f.Hl[0] * f.Wl[0];
+    hipLaunchKernelGGL(rgbd_level0_bwd_k, dim3(cdiv(n0, 256)), dim3(256), 0, st, depth, gpyr, n0, rgb_scale, g_depth, g_rgb);
+    GS_LAUNCH_CHECK(name);
+    return 0;
+}
+
+extern "C" {
+
+#define RGBD_REQUIRE_ODOMETRY(name)                                                                                               \
+    do {                                                                                                                          \
+        RGBD_REQUIRE_SHAPE(name);                                                                                                 \
+        RGBD_REQUIRE_LAMBDA(name);                                                                                                \
+        RGBD_REQUIRE_PARAMS(name);                                                                                                \
+        GS_REQUIRE(damp >= 0.0f && damp < INFINITY, name ": damp must be finite and not negative, got %g", (double)damp);         \
+        for (int l = 0; l < levels; ++l)                                                                                          \
+            GS_REQUIRE(numiters[l] >= 0 && numiters[l] <= (1 << 20), name ": numiters[%d] must be in [0, 2^20], got %d", l, numiters[l]); \
+    } while (0)
+
+int gs_rgbd_odometry(const float *tgt_depth, const float *tgt_rgb, const float *src_depth, const float *src_rgb, int B, int H, int W,
+                     const float *intrinsics, const float *init, int levels, const int *numiters, float lambda_geo,
+                     float depth_diff_max, float damp, float rgb_scale, float *out_T, float *info, void *ws, size_t ws_bytes,
+                     gs_stream_t stream) {
+    GS_REQUIRE(tgt_depth && tgt_rgb && src_depth && src_rgb && intrinsics && numiters && out_T && info, "gs_rgbd_odometry: null pointer");
+    RGBD_REQUIRE_ODOMETRY("gs_rgbd_odometry");
+    return rgbd_run(tgt_depth, tgt_rgb, src_depth, src_rgb, B, H, W, intrinsics, init, levels, numiters, lambda_geo, depth_diff_max, damp,
+                    rgb_scale, out_T, info, ws, ws_bytes, stream, nullptr);
+}
+
+// (numiters here: the SUM of the levels' counts)
+size_t gs_rgbd_odometry_tape_size(int B, int levels, int numiters) {
+    if (B < 1 || B > 65535 || levels < 1 || levels > RGBD_MAX_LEVELS || numiters < 0 || numiters > levels * (1 << 20)) return 0;
+    return one_piece_bytes(sizeof(float) * RGBD_TAPE_WORDS * (size_t)std::max(numiters, 1) * B);
+}
+
+int gs_rgbd_odometry_taped(const float *tgt_depth, const float *tgt_rgb, const float *src_depth, const float *src_rgb, int B, int H,
+                           int W, const float *intrinsics, const float *init, int levels, const int *numiters, float lambda_geo,
+                           float depth_diff_max, float damp, float rgb_scale, float *out_T, float *info, void *ws, size_t ws_bytes,
+                           gs_stream_t stream, float *tape) {
+    GS_REQUIRE(tgt_depth && tgt_rgb && src_depth && src_rgb && intrinsics && numiters && out_T && info && tape,
+               "gs_rgbd_odometry_taped: null pointer");
+    RGBD_REQUIRE_ODOMETRY("gs_rgbd_odometry_taped");
+    return rgbd_run(tgt_depth, tgt_rgb, src_depth, src_rgb, B, H, W, intrinsics, init, levels, numiters, lambda_geo, depth_diff_max, damp,
+                    rgb_scale, out_T, info, ws, ws_bytes, stream, tape);
+}
+
+size_t gs_rgbd_odometry_bwd_ws_size(int B, int H, int W, int levels, int numiters) {
+    if (!rgbd_shape_ok(B, H, W, levels) || numiters < 0 || numiters > levels * (1 << 20)) return 0;
+    return rgbd_bwd_layout(B, H, W, levels, numiters, nullptr, nullptr);
+}
+
+int gs_rgbd_odometry_bwd(const float *tgt_depth, const float *tgt_rgb, const float *src_depth, const float *src_rgb, int B, int H, int W,
+                         const float *intrinsics, int levels, const int *numiters, float lambda_geo, float depth_diff_max, float damp,
+                         float rgb_scale, const float *tape, const float *grad_T, float *g_tgt_depth, float *g_tgt_rgb, float *g_src_depth,
+                         float *g_src_rgb, float *g_init, void *ws, size_t ws_bytes, gs_stream_t stream) {
+    GS_REQUIRE(tgt_depth && tgt_rgb && src_depth && src_rgb && intrinsics && numiters && tape && grad_T, "gs_rgbd_odometry_bwd: null pointer");
+    RGBD_REQUIRE_ODOMETRY("gs_rgbd_odometry_bwd");
+    int total = 0, base[RGBD_MAX_LEVELS];  // base[l]: iterations that ran before level l's (the coarser levels')
+    for (int l = levels - 1; l >= 0; --l) { base[l] = total; total += numiters[l]; }
+    const size_t need = gs_rgbd_odometry_bwd_ws_size(B, H, W, levels, total);
+    GS_REQUIRE_WS("gs_rgbd_odometry_bwd", ws, ws_bytes, need);
+    hipStream_t st = (hipStream_t)stream;
+    RgbdBwdWs w;
+    rgbd_bwd_layout(B, H, W, levels, total, ws, &w);
+    int rc = rgbd_bwd_prepare("gs_rgbd_odometry_bwd/pyramid", tgt_depth, tgt_rgb, src_depth, src_rgb, B, levels, w, depth_diff_max, rgb_scale, st);
+    if (rc) return rc;
+    hipLaunchKernelGGL(rgbd_gT_k, dim3(B), dim3(BWD_T), 0, st, grad_T, (const float *)nullptr, 0, w.f.prow, w.gT, 16);
+    GS_LAUNCH_CHECK("gs_rgbd_odometry_bwd/begin");
+    const float wI = sqrtf(1.0f - lambda_geo), wD = sqrtf(lambda_geo);
+    int prev_nblocks = 0;  // rows the pixel pass before left for the next step's fold
+    // without a target gradient nothing reads the corner sums: no fold (only its maximum's word, which <MAX> touches, is zeroed)
+    const bool want_tgt = g_tgt_depth || g_tgt_rgb;
+    for (int l = 0; l < levels; ++l) {
+        const int n = numiters[l];
+        if (n == 0) continue;
+        const int nblocks = cdiv((int64_t)w.f.Hl[l] * w.f.Wl[l], RGBD_T);
+        const int lg = fold_lg((int64_t)w.f.Hl[l] * w.f.Wl[l] * n);  // a corner receives at most one term per source pixel and iteration
+        GS_HIP(hipMemsetAsync(w.fold_base, 0, want_tgt ? w.fold_bytes : sizeof(uint32_t), st), "gs_rgbd_odometry_bwd/zero");
+        for (int it = n - 1; it >= 0; --it) {
+            const float *rec = tape + (size_t)(base[l] + it) * B * RGBD_TAPE_WORDS;
+            float *adj = w.adj + (size_t)(base[l] + it) * B * RGBD_ADJ_WORDS;
+            hipLaunchKernelGGL(rgbd_step_bwd_k, dim3(B), dim3(BWD_T), 0, st, w.gT, w.partials12, prev_nblocks, w.f.prow, rec, damp, adj);
+            GS_LAUNCH_CHECK("gs_rgbd_odometry_bwd/step");
+            rc = rgbd_pixel_bwd_launch("gs_rgbd_odometry_bwd/pixels", RGBD_BWD_MAX, w, B, l, intrinsics, rec, RGBD_TAPE_WORDS, adj, wI, wD,
+                                       depth_diff_max, lg, st);
+            if (rc) return rc;
+            prev_nblocks = nblocks;
+        }
+        if (!want_tgt) continue;
+        for (int it = n - 1; it >= 0; --it) {
+            rc = rgbd_pixel_bwd_launch("gs_rgbd_odometry_bwd/corners", RGBD_BWD_ACC, w, B, l, intrinsics,
+                                       tape + (size_t)(base[l] + it) * B * RGBD_TAPE_WORDS, RGBD_TAPE_WORDS,
+                                       w.adj + (size_t)(base[l] + it) * B * RGBD_ADJ_WORDS, wI, wD, depth_diff_max, lg, st);
+            if (rc) return rc;
+        }
+        rc = rgbd_fold_finish_launch("gs_rgbd_odometry_bwd/finish", w, B, l, lg, st);
+        if (rc) return rc;
+    }
+    if (g_init) {
+        hipLaunchKernelGGL(rgbd_gT_k, dim3(B), dim3(BWD_T), 0, st, (const float *)w.gT, (const float *)w.partials12, prev_nblocks, w.f.prow,
+                           g_init, 16);
+        GS_LAUNCH_CHECK("gs_rgbd_odometry_bwd/init");
+    }
+    rc = rgbd_pyramid_bwd("gs_rgbd_odometry_bwd/target", tgt_depth, w.f.tgt, w.gtgt, B, levels, w.f, depth_diff_max, rgb_scale, g_tgt_depth,
+                          g_tgt_rgb, st);
+    if (rc) return rc;
+    return rgbd_pyramid_bwd("gs_rgbd_odometry_bwd/source", src_depth, w.f.src, w.gsrc, B, levels, w.f, depth_diff_max, rgb_scale, g_src_depth,
+                            g_src_rgb, st);
+}
+
+int gs_rgbd_rows_bwd(const float *tgt_depth, const float *tgt_rgb, const float *src_depth, const float *src_rgb, int B, int H, int W,
+                     const float *intrinsics, const float *T, float lambda_geo, float depth_diff_max, float rgb_scale, const float *g_sums,
+                     float *g_tgt_depth, float *g_tgt_rgb, float *g_src_depth, float *g_src_rgb, float *g_T, void *ws, size_t ws_bytes,
+                     gs_stream_t stream) {
+    GS_REQUIRE(tgt_depth && tgt_rgb && src_depth && src_rgb && intrinsics && T && g_sums, "gs_rgbd_rows_bwd: null pointer");
+    const int levels = 1;
+    RGBD_REQUIRE_SHAPE("gs_rgbd_rows_bwd");
+    RGBD_REQUIRE_LAMBDA("gs_rgbd_rows_bwd");
+    RGBD_REQUIRE_PARAMS("gs_rgbd_rows_bwd");
+    const size_t need = gs_rgbd_odometry_bwd_ws_size(B, H, W, levels, 1);
+    GS_REQUIRE_WS("gs_rgbd_rows_bwd", ws, ws_bytes, need);
+    hipStream_t st = (hipStream_t)stream;
+    RgbdBwdWs w;
+    rgbd_bwd_layout(B, H, W, levels, 1, ws, &w);
+    int rc = rgbd_bwd_prepare("gs_rgbd_rows_bwd/pyramid", tgt_depth, tgt_rgb, src_depth, src_rgb, B, levels, w, depth_diff_max, rgb_scale, st);
+    if (rc) return rc;
+    const bool want_tgt = g_tgt_depth || g_tgt_rgb;  // (as in gs_rgbd_odometry_bwd)
+    GS_HIP(hipMemsetAsync(w.fold_base, 0, want_tgt ? w.fold_bytes : sizeof(uint32_t), st), "gs_rgbd_rows_bwd/zero");
+    hipLaunchKernelGGL(rgbd_sums_adj_k, dim3(cdiv((int64_t)B * RGBD_ADJ_WORDS, 256)), dim3(256), 0, st, g_sums, B, w.adj);
+    GS_LAUNCH_CHECK("gs_rgbd_rows_bwd/adjoints");
+    const float wI = sqrtf(1.0f - lambda_geo), wD = sqrtf(lambda_geo);
+    const int lg = fold_lg((int64_t)H * W);
+    rc = rgbd_pixel_bwd_launch("gs_rgbd_rows_bwd/pixels", RGBD_BWD_MAX, w, B, 0, intrinsics, T, 16, w.adj, wI, wD, depth_diff_max, lg, st);
+    if (rc) return rc;
+    if (want_tgt) {
+        rc = rgbd_pixel_bwd_launch("gs_rgbd_rows_bwd/corners", RGBD_BWD_ACC, w, B, 0, intrinsics, T, 16, w.adj, wI, wD, depth_diff_max, lg, st);
+        if (rc) return rc;
+        rc = rgbd_fold_finish_launch("gs_rgbd_rows_bwd/finish", w, B, 0, lg, st);
+        if (rc) return rc;
+    }
+    if (g_T) {
+        hipLaunchKernelGGL(rgbd_gT_k, dim3(B), dim3(BWD_T), 0, st, (const float *)nullptr, (const float *)w.partials12, w.f.prow, w.f.prow, g_T, 12);
+        GS_LAUNCH_CHECK("gs_rgbd_rows_bwd/transform");
+    }
+    rc = rgbd_pyramid_bwd("gs_rgbd_rows_bwd/target", tgt_depth, w.f.tgt, w.gtgt, B, levels, w.f, depth_diff_max, rgb_scale, g_tgt_depth,
+                          g_tgt_rgb, st);
+    if (rc) return rc;
+    return rgbd_pyramid_bwd("gs_rgbd_rows_bwd/source", src_depth, w.f.src, w.gsrc, B, levels, w.f, depth_diff_max, rgb_scale, g_src_depth,
+                            g_src_rgb, st);
 }
 
 }  // extern "C"

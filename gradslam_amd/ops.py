@@ -1767,8 +1767,8 @@ def tsdf_raycast(tsdf, weight, color, origin, voxel_size, K, poses, height: int,
 
 
 # ------------------------------------------------------------------ dense RGB-D odometry (csrc/rgbd.hip)
-def _rgbd_frame(depth, rgb, which, op, B=None, H=None, W=None):
-    """depth (B,H,W) or (B,H,W,1), rgb (B,H,W,3) -> contiguous fp32 (B,H,W), (B,H,W,3)."""
+def _rgbd_frame(depth, rgb, which, op, B=None, H=None, W=None, attached=False):
+    """depth (B,H,W) or (B,H,W,1), rgb (B,H,W,3) -> contiguous fp32 (B,H,W), (B,H,W,3); detached unless `attached`."""
     for name, t in (("depth", depth), ("rgb", rgb)):
         if not torch.is_tensor(t):
             raise TypeError("{}: expected {}_{} to be a tensor; got {}".format(op, which, name, type(t)))
@@ -1781,6 +1781,8 @@ def _rgbd_frame(depth, rgb, which, op, B=None, H=None, W=None):
     if B is not None and tuple(depth.shape) != (B, H, W):
         raise ValueError("{}: both frames should have the same batch size and image size ({} != {}).".format(
             op, tuple(depth.shape), (B, H, W)))
+    if attached:
+        return depth.float().contiguous(), rgb.float().contiguous()
     return _f32c(depth.detach()), _f32c(rgb.detach())
 
 
@@ -1792,11 +1794,13 @@ def _rgbd_K(K, B, op):
     return _f32c(K.detach().reshape(B, 4, 4))
 
 
-def _rgbd_T(T, B, name, op):
+def _rgbd_T(T, B, name, op, attached=False):
     if not torch.is_tensor(T):
         raise TypeError("{}: expected {} to be a tensor; got {}".format(op, name, type(T)))
     if T.numel() != B * 16 or tuple(T.shape[-2:]) != (4, 4):
         raise ValueError("{}: {} should have shape ({}, 4, 4) or ({}, 1, 4, 4). Got {}.".format(op, name, B, B, tuple(T.shape)))
+    if attached:
+        return T.reshape(B, 16).float().contiguous()
     return _f32c(T.detach().reshape(B, 16))
 
 
@@ -1860,18 +1864,89 @@ def rgbd_rows_raw(tgt_depth, tgt_rgb, src_depth, src_rgb, intrinsics, T, lambda_
     return valid, rows, sums
 
 
-def rgbd_odometry(tgt_depth, tgt_rgb, src_depth, src_rgb, intrinsics, init=None, numiters=(10, 5, 3), levels: int = 3,
-                  lambda_geo: float = 0.968, depth_diff_max: float = 0.07, damp: float = 1e-8, rgb_scale: float = 1.0 / 255.0):
-    """Dense RGB-D odometry, coarse to fine (the rule of include/gradslam_hip.h): frames as depth (B,H,W[,1]) and rgb (B,H,W,3) with
-    shared intrinsics -> (T (B,4,4) taking source-camera to target-camera coordinates, info (B,levels,4) = cnt, err, status bits,
-    iterations per level).  `numiters`: iterations per level, finest first (an int: that count at every level).  No gradients;
-    no host synchronisation."""
-    op = "rgbd_odometry"
+def rgbd_rows_bwd_raw(tgt_depth, tgt_rgb, src_depth, src_rgb, intrinsics, T, g_sums, lambda_geo: float = 0.968,
+                      depth_diff_max: float = 0.07, rgb_scale: float = 1.0 / 255.0):
+    """The reverse of rgbd_rows_raw, the decisions held constant: g_sums (B,29), the adjoint of `sums` as rgbd_rows_raw returns them
+    (err's is honoured, cnt's ignored) -> (g_tgt_depth (B,H,W), g_tgt_rgb (B,H,W,3), g_src_depth, g_src_rgb, g_T (B,3,4), rows 0..2
+    of T's).  The seam the tests check."""
+    op = "rgbd_rows_bwd"
     td, tc = _rgbd_frame(tgt_depth, tgt_rgb, "target", op)
     B, H, W = td.shape
     sd, sc = _rgbd_frame(src_depth, src_rgb, "source", op, B, H, W)
+    K, T = _rgbd_K(intrinsics, B, op), _rgbd_T(T, B, "T", op)
+    lam, ddm, scale = _rgbd_params(1, lambda_geo, depth_diff_max, rgb_scale, H, W, op)
+    if not torch.is_tensor(g_sums) or tuple(g_sums.shape) != (B, 29):
+        raise ValueError("{}: g_sums should be a tensor of shape ({}, 29).".format(op, B))
+    g_sums = _f32c(g_sums.detach())
+    require_hip(td, tc, sd, sc, K, T, g_sums, op=op)
+    dev = td.device
+    g_td, g_tc, g_sd, g_sc = (torch.empty_like(t) for t in (td, tc, sd, sc))
+    g_T = torch.empty((B, 3, 4), dtype=torch.float32, device=dev)
+    ws = workspace(ws_bytes("gs_rgbd_odometry_bwd_ws_size", B, H, W, 1, 1), dev, "rgbd")
+    call("gs_rgbd_rows_bwd", ptr(td), ptr(tc), ptr(sd), ptr(sc), B, H, W, ptr(K), ptr(T), lam, ddm, scale, ptr(g_sums), ptr(g_td),
+         ptr(g_tc), ptr(g_sd), ptr(g_sc), ptr(g_T), ptr(ws), ws.numel(), stream())
+    return g_td, g_tc, g_sd, g_sc, g_T
+
+
+class _RgbdOdometryFn(torch.autograd.Function):
+    """rgbd_odometry as one autograd node: the taped forward (the plain call's bits) and gs_rgbd_odometry_bwd.  td, tc, sd, sc, K
+    are contiguous fp32; init (B,16) contiguous fp32 or None."""
+
+    @staticmethod
+    def forward(ctx, td, tc, sd, sc, init, K, numiters, levels, lam, ddm, damp, scale):
+        B, H, W = td.shape
+        dev = td.device
+        out_T = torch.empty((B, 4, 4), dtype=torch.float32, device=dev)
+        info = torch.empty((B, levels, 4), dtype=torch.float32, device=dev)
+        tape = torch.empty(ws_bytes("gs_rgbd_odometry_tape_size", B, levels, sum(numiters)) // 4, dtype=torch.float32, device=dev)
+        ws = workspace(ws_bytes("gs_rgbd_odometry_ws_bytes", B, H, W, levels), dev, "rgbd")
+        counts = (nv.c_i * levels)(*numiters)
+        call("gs_rgbd_odometry_taped", ptr(td), ptr(tc), ptr(sd), ptr(sc), B, H, W, ptr(K), ptr(init), levels, counts, lam, ddm, damp,
+             scale, ptr(out_T), ptr(info), ptr(ws), ws.numel(), stream(), ptr(tape))
+        ctx.save_for_backward(td, tc, sd, sc, K, tape)
+        ctx.params = (numiters, levels, lam, ddm, damp, scale, init is not None)
+        ctx.mark_non_differentiable(info)
+        return out_T, info
+
+    @staticmethod
+    def backward(ctx, grad_T, _grad_info):
+        td, tc, sd, sc, K, tape = ctx.saved_tensors
+        numiters, levels, lam, ddm, damp, scale, has_init = ctx.params
+        B, H, W = td.shape
+        dev = td.device
+        grad_T = _f32c(grad_T)
+        need = list(ctx.needs_input_grad[:5])
+        need[4] = need[4] and has_init
+        grads = [torch.empty_like(t) if n else None for t, n in zip((td, tc, sd, sc), need)]
+        grads.append(torch.empty((B, 16), dtype=torch.float32, device=dev) if need[4] else None)
+        ws = workspace(ws_bytes("gs_rgbd_odometry_bwd_ws_size", B, H, W, levels, sum(numiters)), dev, "rgbd")
+        counts = (nv.c_i * levels)(*numiters)
+        call("gs_rgbd_odometry_bwd", ptr(td), ptr(tc), ptr(sd), ptr(sc), B, H, W, ptr(K), levels, counts, lam, ddm, damp, scale, ptr(tape),
+             ptr(grad_T), *(ptr(g) for g in grads), ptr(ws), ws.numel(), stream())
+        return (*grads, None, None, None, None, None, None, None)
+
+
+def rgbd_odometry(tgt_depth, tgt_rgb, src_depth, src_rgb, intrinsics, init=None, numiters=(10, 5, 3), levels: int = 3,
+                  lambda_geo: float = 0.968, depth_diff_max: float = 0.07, damp: float = 1e-8, rgb_scale: float = 1.0 / 255.0,
+                  differentiable: bool = False):
+    """Dense RGB-D odometry, coarse to fine (the rule of include/gradslam_hip.h): frames as depth (B,H,W[,1]) and rgb (B,H,W,3) with
+    shared intrinsics -> (T (B,4,4) taking source-camera to target-camera coordinates, info (B,levels,4) = cnt, err, status bits,
+    iterations per level).  `numiters`: iterations per level, finest first (an int: that count at every level).  No host
+    synchronisation.  `differentiable=False` (the default): no gradients, the inputs are detached.  `differentiable=True`: when grad
+    mode is on and one of the two depths, the two colours or `init` requires a gradient, T carries the graph -- one autograd
+    node, the taped forward (the same bits) and a reverse pass on the device that holds every decision of the forward constant
+    (validity, cells, the pyramid's selection, which steps were applied); of `init` rows 0..2 are differentiable; the scalar
+    parameters and info are not, nor are the intrinsics (with `differentiable=True` intrinsics that require a gradient are refused)."""
+    op = "rgbd_odometry"
+    attached = bool(differentiable) and torch.is_grad_enabled() and any(
+        torch.is_tensor(t) and t.requires_grad for t in (tgt_depth, tgt_rgb, src_depth, src_rgb, init))
+    if differentiable and torch.is_grad_enabled() and torch.is_tensor(intrinsics) and intrinsics.requires_grad:
+        raise NotImplementedError("{}: gradients with respect to the intrinsics are not implemented; detach them.".format(op))
+    td, tc = _rgbd_frame(tgt_depth, tgt_rgb, "target", op, attached=attached)
+    B, H, W = td.shape
+    sd, sc = _rgbd_frame(src_depth, src_rgb, "source", op, B, H, W, attached=attached)
     K = _rgbd_K(intrinsics, B, op)
-    init = None if init is None else _rgbd_T(init, B, "init", op)
+    init = None if init is None else _rgbd_T(init, B, "init", op, attached=attached)
     lam, ddm, scale = _rgbd_params(levels, lambda_geo, depth_diff_max, rgb_scale, H, W, op)
     damp = _number(damp, "damp", op)
     if not (0.0 <= damp < math.inf):
@@ -1882,6 +1957,8 @@ def rgbd_odometry(tgt_depth, tgt_rgb, src_depth, src_rgb, intrinsics, init=None,
     if len(numiters) != levels or any(not isinstance(n, int) or isinstance(n, bool) or n < 0 for n in numiters):
         raise ValueError("{}: numiters should be {} non-negative integers (finest level first). Got {!r}.".format(op, levels, numiters))
     require_hip(td, tc, sd, sc, K, init, op=op)
+    if attached:
+        return _RgbdOdometryFn.apply(td, tc, sd, sc, init, K, numiters, levels, lam, ddm, damp, scale)
     dev = td.device
     out_T = torch.empty((B, 4, 4), dtype=torch.float32, device=dev)
     info = torch.empty((B, levels, 4), dtype=torch.float32, device=dev)

@@ -41,8 +41,12 @@ class KinectFusion(nn.Module):
         target = volume.raycast(K, pose_{s-1}, H, W, step=step, min_weight=min_weight)     (the coloured image of the model)
         pose_s = compose_transformations(odomprov.provide(target, live frame), pose_{s-1})
 
-    at full resolution (`dsratio` and `dist_thresh` are not used).  It has no reverse pass: under autograd with inputs that
-    require gradients `provide` raises NotImplementedError, whatever `pose_gradients` says.  A camera that sees nothing of the volume, or a frame without valid
+    at full resolution (`dsratio` and `dist_thresh` are not used).  The alignment is differentiated only with
+    `odom_gradients=True`, which builds the provider with `differentiable=True`: gradients then reach the depths and colours of
+    the frames through the alignment too (its decisions held constant, see RGBDOdometryProvider), and together with
+    `pose_gradients=True` the chain pose_{s-1} -> coloured cast -> alignment -> pose_s -> integrate is attached like the ICP
+    branch's.  With `odom_gradients=False` (the default) it is as it was: under autograd with inputs that require gradients
+    `provide` raises NotImplementedError, whatever `pose_gradients` says.  A camera that sees nothing of the volume, or a frame without valid
     pixels, leaves the pose where it was and sets the status bit in `odomprov.last_info` (nothing synchronises the host)."""
 
     def __init__(self, *, dims, voxel_size, origin=(0.0, 0.0, 0.0), trunc=None, max_weight: float = 128.0, color: bool = True,
@@ -50,7 +54,7 @@ class KinectFusion(nn.Module):
                  dist_thresh: Union[float, int, None] = None, lambda_max: Union[float, int] = 2.0, B: Union[float, int] = 1.0,
                  B2: Union[float, int] = 1.0, nu: Union[float, int] = 200.0, step: Optional[float] = None, min_weight: float = 1.0,
                  device: Union[torch.device, str, None] = None, levels: int = 3, lambda_geo: float = 0.968,
-                 pose_gradients: bool = False):
+                 pose_gradients: bool = False, odom_gradients: bool = False):
         super().__init__()
         if odom not in ["gt", "icp", "gradicp", "rgbd"]:
             msg = "odometry method ({}) not supported for KinectFusion. ".format(odom)
@@ -62,13 +66,17 @@ class KinectFusion(nn.Module):
             raise ValueError("KinectFusion: dsratio should be a positive integer. Got {!r}.".format(dsratio))
         if not isinstance(pose_gradients, bool):
             raise TypeError("KinectFusion: pose_gradients should be a bool. Got {!r}.".format(pose_gradients))
+        if not isinstance(odom_gradients, bool):
+            raise TypeError("KinectFusion: odom_gradients should be a bool. Got {!r}.".format(odom_gradients))
+        if odom_gradients and odom != "rgbd":
+            raise ValueError("KinectFusion: odom_gradients belongs to odom='rgbd' (the ICP providers always carry gradients).")
         odomprov = None
         if odom == "icp":
             odomprov = ICPOdometryProvider(numiters, damp, dist_thresh)
         elif odom == "gradicp":
             odomprov = GradICPOdometryProvider(numiters, damp, dist_thresh, lambda_max, B, B2, nu)
         elif odom == "rgbd":
-            odomprov = RGBDOdometryProvider(numiters, levels, lambda_geo, damp=damp)
+            odomprov = RGBDOdometryProvider(numiters, levels, lambda_geo, damp=damp, differentiable=odom_gradients)
         self.odom = odom
         self.odomprov = odomprov
         self.dsratio = dsratio

@@ -987,6 +987,56 @@ int gs_rgbd_rows(const float *tgt_depth, const float *tgt_rgb, const float *src_
 int gs_rgbd_pyramid(const float *depth, const float *rgb, int B, int H, int W, int levels, float depth_diff_max, float rgb_scale,
                     float *out, gs_stream_t stream);
 
+/* The reverse pass of the dense RGB-D odometry.  It differentiates the rule above with every DECISION HELD CONSTANT: the validity
+ * tests (d > 0, q_z > 0, the cell bounds, the four corner depths, |r_D| <= depth_diff_max), the cell (floor x, floor y), the
+ * pyramid's foreground selection (the smallest depth m, which depths are taken, n), the depth clean-up at level 0, and whether a
+ * step was applied (cnt < 6, or a solve / product that was not finite: the step is the identity and its adjoint passes through).
+ * Differentiable: target depth and rgb, source depth and rgb, and rows 0..2 of `init` (the bottom row is the constant (0, 0, 0, 1):
+ * its gradient is zero).  Not differentiable: the intrinsics, lambda_geo, damp, rgb_scale, info.  Only rows 0..2 of grad_T are read.
+ *   tape       gs_rgbd_odometry_taped is gs_rgbd_odometry -- the same loop, the same launches, out_T and info bit for bit -- whose
+ *              step also writes one row of 64 floats per (iteration, batch element), in the order the iterations run:
+ *              T before the step (16) | the 29 sums as reduced (the six of g not negated) | xi (6) | 1 if the step was applied,
+ *              else 0 | unused.  gs_rgbd_odometry_tape_size(B, levels, numiters) = 256 B max(numiters, 1), where numiters is
+ *              the SUM of the levels' counts (in both size queries); 0 for a B, levels or sum the loop refuses.
+ *   step       iterations last to first (level 0 first).  T-bar_{k+1} = the carried adjoint + the 12 sums that iteration k+1's
+ *              pixel pass left (T_{k+1}'s adjoint through its linearisation).  An applied step T_{k+1} = dT T_k, dT = exp(xi),
+ *              xi = (H + damp I)^-1 g:  dT-bar = T-bar_{k+1} T_k^T,  T-bar_k = dT^T T-bar_{k+1} (rows 0..2),  xi-bar from the
+ *              exponential's adjoint, y = (H + damp I)^-1 xi-bar (fp64, the forward's solver),  H-bar = -y xi^T,  g-bar = y.
+ *   pixels     the pixel's forward values again from the taped T_k, by the forward's operations in the forward's order; the
+ *              adjoints of J_I, r_I, J_D, r_D from those of the sums; through rows, residuals and the interpolant F^, F_x, F_y to
+ *              the eight corner values, to the cell coordinates (F_x's derivative in b = F_y's in a = X1 - X0: the interpolant's
+ *              one second derivative inside a cell), to q, to the source pixel (I_s, d) and to T.  fp32.
+ *   sums       T: 12 sums per block of 256 pixels (wave butterflies, offsets 32 .. 1, then the 4 waves in order), the blocks' rows
+ *              g, g + 16, .. in order and the 16 group sums in order.  Source pixel: its own lane adds, iteration after iteration.
+ *              Target corners -- many source pixels land in one cell -- : the exact fold of csrc/gs_fixed128.hpp, one per level
+ *              over all its iterations, rounded once.  No float atomics: the same bits from run to run.
+ *   pyramids   after all levels, coarsest to finest: a fine pixel gathers 0.25 I-bar and, where its depth was taken, D-bar / n
+ *              from its coarse pixel; then level 0: rgb-bar = rgb_scale I-bar (0.299, 0.587, 0.114), depth-bar = D-bar where
+ *              0 < depth < inf.
+ * Three launches per iteration (step reverse; pixels; the corner terms again for the fold) and one finish per level -- two and
+ * none when neither g_tgt_depth nor g_tgt_rgb is asked for: nothing else reads the corner sums; the pyramids
+ * are rebuilt (the forward's workspace need not survive); nothing synchronises the host.  Outputs: g_tgt_depth (B,H,W), g_tgt_rgb
+ * (B,H,W,3), g_src_depth, g_src_rgb, g_init (B,16); any may be NULL.  Workspace, every piece rounded up to 256 bytes, with
+ * P = sum_l H_l W_l and N = max(sum of numiters, 1):  64 B | 128 B N (the sums' adjoints) | 48 B ceil(H W / 256) | 8 B P, twice
+ * (the pyramids) | 16 B P (their adjoints) | the fold of B H W rows x 2 channels: 4 | 4 B H W | 32 B H W. */
+size_t gs_rgbd_odometry_tape_size(int B, int levels, int numiters);
+int gs_rgbd_odometry_taped(const float *tgt_depth, const float *tgt_rgb, const float *src_depth, const float *src_rgb, int B, int H,
+                           int W, const float *intrinsics, const float *init, int levels, const int *numiters, float lambda_geo,
+                           float depth_diff_max, float damp, float rgb_scale, float *out_T, float *info, void *ws, size_t ws_bytes,
+                           gs_stream_t stream, float *tape);
+size_t gs_rgbd_odometry_bwd_ws_size(int B, int H, int W, int levels, int numiters);
+int gs_rgbd_odometry_bwd(const float *tgt_depth, const float *tgt_rgb, const float *src_depth, const float *src_rgb, int B, int H, int W,
+                         const float *intrinsics, int levels, const int *numiters, float lambda_geo, float depth_diff_max, float damp,
+                         float rgb_scale, const float *tape, const float *grad_T, float *g_tgt_depth, float *g_tgt_rgb, float *g_src_depth,
+                         float *g_src_rgb, float *g_init, void *ws, size_t ws_bytes, gs_stream_t stream);
+/* The reverse of gs_rgbd_rows: g_sums (B,29) is the adjoint of `sums` exactly as gs_rgbd_rows returns them (g is MINUS the sum);
+ * err's adjoint is honoured, cnt's is ignored.  The four image gradients and g_T (B,12), rows 0..2 of T's; any may be NULL.  The
+ * workspace of gs_rgbd_odometry_bwd_ws_size(B, H, W, 1, 1). */
+int gs_rgbd_rows_bwd(const float *tgt_depth, const float *tgt_rgb, const float *src_depth, const float *src_rgb, int B, int H, int W,
+                     const float *intrinsics, const float *T, float lambda_geo, float depth_diff_max, float rgb_scale, const float *g_sums,
+                     float *g_tgt_depth, float *g_tgt_rgb, float *g_src_depth, float *g_src_rgb, float *g_T, void *ws, size_t ws_bytes,
+                     gs_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -6,6 +6,9 @@ calls, each timed with a pair of device events.
   pyramids_ms        the same call with zero iterations at every level: the pyramids and the start-up launch
   level0_iter_us     (call with numiters (N0 + 10, ..) - call with (N0, ..)) / 10: one linearise + step pair at level 0
   gradicp_ms         one GradICPOdometryProvider.provide on the same pair at dsratio = 4 (clouds built outside the timing)
+  taped_forward_ms   the call with differentiable=True and inputs that require gradients: the taped loop (and the tape's allocation)
+  forward_backward_ms  that call and .backward() of a sum over T: the reverse pass (gs_rgbd_odometry_bwd) on top
+  backward_launches, backward_ws_bytes  the reverse pass's launches (3 per iteration) and its workspace
 The level-0 linearise launch must move 8 B per source pixel, 8 B per target pixel (every corner once) and 116 B per block of 256
 pixels: `level0_bytes`, quoted against the HBM bandwidth as `level0_hbm_floor_us`.  The sums of the 480 x 640 call are also
 checked against a float64 sum of the device's own rows (what no test does at this size: more than 512 partial rows)."""
@@ -14,6 +17,7 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import gradslam_amd as gs
+from gradslam_amd import _native as nv
 from gradslam_amd import ops
 from gradslam_amd.odometry.icputils import downsample_rgbdimages
 from gradslam_amd.synthetic import make_sequence_cached as make_sequence
@@ -70,6 +74,22 @@ if __name__ == "__main__":
     more = (counts[0] + 10,) + counts[1:]
     full, pyr, longer = event_ms(lambda: run(counts), a.runs, a.warmup), event_ms(lambda: run((0,) * levels), a.runs, a.warmup), \
         event_ms(lambda: run(more), a.runs, a.warmup)
+    # the differentiable call: the taped forward alone, then with the reverse pass
+    leaves = [x.clone().requires_grad_(True) for x in args[:4]]
+    taped_run = lambda: ops.rgbd_odometry(*leaves, K, numiters=counts, levels=levels, differentiable=True)
+    T_taped, info_taped = taped_run()
+    assert torch.equal(T_taped.detach(), T) and torch.equal(info_taped, info)
+
+    def fwd_bwd():
+        for x in leaves:
+            x.grad = None
+        taped_run()[0][:, :3].sum().backward()
+
+    taped, both = event_ms(taped_run, a.runs, a.warmup), event_ms(fwd_bwd, a.runs, a.warmup)
+    assert all(torch.isfinite(x.grad).all() and x.grad.abs().max() > 0 for x in leaves)
+    used = sum(1 for n in counts if n > 0)
+    bwd_launches = 2 * levels + 2 + 1 + 3 * sum(counts) + 2 * used + 2 * levels  # pyramids, zero, begin | loop | fold zero + finish | adjoint pyramids
+    bwd_ws = int(nv.ws_bytes("gs_rgbd_odometry_bwd_ws_size", 1, H, W, levels, sum(counts)))
     # the sums at this size against float64 sums of the device's own rows
     valid, rows, sums = ops.rgbd_rows_raw(*args, T)
     r = rows.double().reshape(-1, 14)
@@ -90,6 +110,7 @@ if __name__ == "__main__":
             "odometry_ms": full, "pyramids_ms": pyr, "level0_iter_us": round(100.0 * (longer[0] - full[0]), 2),
             "launches": 1 + 2 * levels + 2 * sum(counts), "level0_bytes": level0_bytes,
             "level0_hbm_floor_us": round(1e6 * level0_bytes / HBM_BYTES_PER_S, 3), "gradicp_dsratio4_numiters20_ms": gradicp,
+            "taped_forward_ms": taped, "forward_backward_ms": both, "backward_launches": bwd_launches, "backward_ws_bytes": bwd_ws,
             "info": info[0].tolist(), "translation_error_m": float((T[0, :3, 3].double() - true[:3, 3]).norm()),
             "sums_worst_error_over_bound": round(worst, 4), "chain_length": k, "device": torch.cuda.get_device_name(0),
             "date": a.date, "commit": a.commit or commit()}

@@ -1,5 +1,6 @@
 // gs_icp_step.hpp -- the O(1) step (X) of an ICP iteration: loop state, 6x6 solve, SE(3) exponential, LM / gradLM
-// control, and the step as a launch of its own (icp_step_k).  Included by icp.hip.
+// control, the step by one wave (step_wave0).  Device functions and types only, no kernel: any translation unit may include it
+// (icp.hip, whose icp_step_k is the step as a launch of its own; rgbd.hip and gs_se3_bwd.hpp for solve6 and se3_exp_dev).
 //
 // X  the O(1) step of an iteration (reduce the partials, LM / gradLM decision, fp64 6x6 solve, SE(3)
 //    exponential) runs in the prologue of the NEXT association launch: every block recomputes it on its wave 0
@@ -388,38 +389,6 @@ __device__ __forceinline__ void step_wave0(IcpState *S, const float *acc, int mo
     if (out_T && t < 16) out_T[t] = new_T;
     GS_STAMP(13);  // (diagnostic build, wave 0: the books are written -- after 14 on this wave)
     wave_sync();
-}
-
-__global__ __launch_bounds__(1024) void icp_step_k(IcpState *__restrict__ Sg, const float *__restrict__ partials, int nblocks,
-                                                  int mode, GradParams gp, float *__restrict__ trace /* or NULL */,
-                                                  float *__restrict__ out_T, int look_slot,
-                                                  float *__restrict__ rec /* this step's tape record or NULL */, int solve,
-                                                  const float *__restrict__ compose_right, float *__restrict__ compose_out) {
-    __shared__ float acc[NACC];
-    __shared__ double lu_sm[42];
-    __shared__ IcpState st;  // work on an LDS copy: ~200 dependent accesses at LDS, not HBM, latency
-    constexpr int kWords = sizeof(IcpState) / 4;
-#ifdef GS_DIAG_STAMPS
-    if (g_diag && threadIdx.x == 0) g_diag[0] = wall_clock64();
-#endif
-    if (threadIdx.x < kWords) reinterpret_cast<int *>(&st)[threadIdx.x] = reinterpret_cast<const int *>(Sg)[threadIdx.x];
-    reduce_partials(partials, nblocks, acc);  // ends with a barrier: st and acc are visible
-    // (from the global copy: wave 0 is about to change the LDS one)
-    if (rec && threadIdx.x < kWords) reinterpret_cast<int *>(rec)[REC_STATE + threadIdx.x] = reinterpret_cast<const int *>(Sg)[threadIdx.x];
-#ifdef GS_DIAG_STAMPS
-    if (g_diag && threadIdx.x == 0) g_diag[1] = wall_clock64();
-#endif
-    if (threadIdx.x < 64) step_wave0(&st, acc, mode, gp, trace, out_T, look_slot, rec, lu_sm, solve != 0);
-#ifdef GS_DIAG_STAMPS
-    if (g_diag && threadIdx.x == 0) g_diag[2] = wall_clock64();
-#endif
-    __syncthreads();
-    if (threadIdx.x < kWords) {
-        const int v = reinterpret_cast<const int *>(&st)[threadIdx.x];
-        reinterpret_cast<int *>(Sg)[threadIdx.x] = v;
-        if (rec) reinterpret_cast<int *>(rec)[REC_WORDS + REC_STATE + threadIdx.x] = v;  // head of the next record = state after
-    }
-    if (compose_out && threadIdx.x == 0) compose44(st.T, compose_right, compose_out);  // e.g. T . previous pose
 }
 
 }  // namespace gs

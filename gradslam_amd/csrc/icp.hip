@@ -4,11 +4,11 @@
 // One translation unit; the device code lives in role headers, each with its part of the design at its top:
 //   gs_icp_assoc.hpp   K  keys, row algebra, the tile search (chunk boxes, grid windows) up to knn_tile
 //   gs_icp_reduce.hpp  J  block_reduce_store, the rp_* partial-row reduction, expand44
-//   gs_icp_step.hpp    X  IcpState, LoopBufs, solve6*, se3_exp_dev, GradParams, tape records, step_wave0, icp_step_k
+//   gs_icp_step.hpp    X  IcpState, LoopBufs, solve6*, se3_exp_dev, GradParams, tape records, step_wave0
 //   gs_icp_loop.hpp       LoopConst, the camera proof, knn1_loop_k, icp_init_state_k, icp_prepare_k, copy_best_last_k
 //   gs_icp_bwd.hpp        the reverse pass: BwdState ... bwd_finish_k, bwd_ws_layout
 //   gs_icp.hpp            what slam.hip calls here
-// This file: the stand-alone kernels behind gs_knn1* / gs_icp_linearize* / gs_icp_rows / gs_transform_points, launch
+// This file: the stand-alone kernels behind gs_knn1* / gs_icp_linearize* / gs_icp_rows / gs_transform_points, icp_step_k, launch
 // geometry, profiling, the knobs, the workspace and tape layouts, icp_run, icp_backward_run and the C entry points.
 #include <stddef.h>
 #include <stdlib.h>
@@ -347,6 +347,39 @@ static inline GradParams make_grad_params(float lambda_max, float B, float B2, f
                       (float)(1.0 / (double)nu)};
 }
 static inline GradParams lm_grad_params() { return GradParams{0.5f, 1.5f, 1.0f, 1.0f, 0.005f}; }
+
+// X as a launch of its own (a loop's last step): step_wave0 on an LDS copy of the state.  grid 1, 1024 threads
+__global__ __launch_bounds__(1024) void icp_step_k(IcpState *__restrict__ Sg, const float *__restrict__ partials, int nblocks,
+                                                  int mode, GradParams gp, float *__restrict__ trace /* or NULL */,
+                                                  float *__restrict__ out_T, int look_slot,
+                                                  float *__restrict__ rec /* this step's tape record or NULL */, int solve,
+                                                  const float *__restrict__ compose_right, float *__restrict__ compose_out) {
+    __shared__ float acc[NACC];
+    __shared__ double lu_sm[42];
+    __shared__ IcpState st;  // work on an LDS copy: ~200 dependent accesses at LDS, not HBM, latency
+    constexpr int kWords = sizeof(IcpState) / 4;
+#ifdef GS_DIAG_STAMPS
+    if (g_diag && threadIdx.x == 0) g_diag[0] = wall_clock64();
+#endif
+    if (threadIdx.x < kWords) reinterpret_cast<int *>(&st)[threadIdx.x] = reinterpret_cast<const int *>(Sg)[threadIdx.x];
+    reduce_partials(partials, nblocks, acc);  // ends with a barrier: st and acc are visible
+    // (from the global copy: wave 0 is about to change the LDS one)
+    if (rec && threadIdx.x < kWords) reinterpret_cast<int *>(rec)[REC_STATE + threadIdx.x] = reinterpret_cast<const int *>(Sg)[threadIdx.x];
+#ifdef GS_DIAG_STAMPS
+    if (g_diag && threadIdx.x == 0) g_diag[1] = wall_clock64();
+#endif
+    if (threadIdx.x < 64) step_wave0(&st, acc, mode, gp, trace, out_T, look_slot, rec, lu_sm, solve != 0);
+#ifdef GS_DIAG_STAMPS
+    if (g_diag && threadIdx.x == 0) g_diag[2] = wall_clock64();
+#endif
+    __syncthreads();
+    if (threadIdx.x < kWords) {
+        const int v = reinterpret_cast<const int *>(&st)[threadIdx.x];
+        reinterpret_cast<int *>(Sg)[threadIdx.x] = v;
+        if (rec) reinterpret_cast<int *>(rec)[REC_WORDS + REC_STATE + threadIdx.x] = v;  // head of the next record = state after
+    }
+    if (compose_out && threadIdx.x == 0) compose44(st.T, compose_right, compose_out);  // e.g. T . previous pose
+}
 
 static int icp_run(bool grad, const float *src, const int32_t *d_ns, int max_ns, const float *tgt, const float *nrm,
                    const int32_t *d_nt, int max_nt, const float *init_T, int numiters, float damp, float thresh,

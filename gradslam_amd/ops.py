@@ -1843,24 +1843,33 @@ def rgbd_pyramid_raw(depth, rgb, levels: int, depth_diff_max: float = 0.07, rgb_
     return pyr
 
 
-def rgbd_rows_raw(tgt_depth, tgt_rgb, src_depth, src_rgb, intrinsics, T, lambda_geo: float = 0.968, depth_diff_max: float = 0.07,
-                  rgb_scale: float = 1.0 / 255.0):
-    """One level-0 linearisation of the RGB-D alignment at T (B,4,4) (source camera -> target camera) -> (valid (B,H,W) int32,
-    rows (B,H,W,14) = J_I | r_I | J_D | r_D, sums (B,29) = H upper triangle | g | err | cnt).  The seam the tests check."""
-    op = "rgbd_rows"
+def _rgbd_seam_args(op, tgt_depth, tgt_rgb, src_depth, src_rgb, intrinsics, T, lambda_geo, depth_diff_max, rgb_scale, *g_sums):
+    """What rgbd_rows_raw and rgbd_rows_bwd_raw hand their entry points: the checked frames, K, T (and rgbd_rows_bwd_raw's g_sums)
+    on the current HIP device -> (frames, g_sums as given to the device, the argument list up to the scalar parameters)."""
     td, tc = _rgbd_frame(tgt_depth, tgt_rgb, "target", op)
     B, H, W = td.shape
     sd, sc = _rgbd_frame(src_depth, src_rgb, "source", op, B, H, W)
     K, T = _rgbd_K(intrinsics, B, op), _rgbd_T(T, B, "T", op)
     lam, ddm, scale = _rgbd_params(1, lambda_geo, depth_diff_max, rgb_scale, H, W, op)
-    require_hip(td, tc, sd, sc, K, T, op=op)
-    dev = td.device
+    if any(not torch.is_tensor(g) or tuple(g.shape) != (B, 29) for g in g_sums):
+        raise ValueError("{}: g_sums should be a tensor of shape ({}, 29).".format(op, B))
+    g_sums = [_f32c(g.detach()) for g in g_sums]
+    require_hip(td, tc, sd, sc, K, T, *g_sums, op=op)
+    return (td, tc, sd, sc), g_sums, (ptr(td), ptr(tc), ptr(sd), ptr(sc), B, H, W, ptr(K), ptr(T), lam, ddm, scale)
+
+
+def rgbd_rows_raw(tgt_depth, tgt_rgb, src_depth, src_rgb, intrinsics, T, lambda_geo: float = 0.968, depth_diff_max: float = 0.07,
+                  rgb_scale: float = 1.0 / 255.0):
+    """One level-0 linearisation of the RGB-D alignment at T (B,4,4) (source camera -> target camera) -> (valid (B,H,W) int32,
+    rows (B,H,W,14) = J_I | r_I | J_D | r_D, sums (B,29) = H upper triangle | g | err | cnt).  The seam the tests check."""
+    (td, _, _, _), _, args = _rgbd_seam_args("rgbd_rows", tgt_depth, tgt_rgb, src_depth, src_rgb, intrinsics, T, lambda_geo,
+                                             depth_diff_max, rgb_scale)
+    (B, H, W), dev = td.shape, td.device
     valid = torch.empty((B, H, W), dtype=torch.int32, device=dev)
     rows = torch.empty((B, H, W, 14), dtype=torch.float32, device=dev)
     sums = torch.empty((B, 29), dtype=torch.float32, device=dev)
     ws = workspace(ws_bytes("gs_rgbd_odometry_ws_bytes", B, H, W, 1), dev, "rgbd")
-    call("gs_rgbd_rows", ptr(td), ptr(tc), ptr(sd), ptr(sc), B, H, W, ptr(K), ptr(T), lam, ddm, scale, ptr(valid), ptr(rows), ptr(sums),
-         ptr(ws), ws.numel(), stream())
+    call("gs_rgbd_rows", *args, ptr(valid), ptr(rows), ptr(sums), ptr(ws), ws.numel(), stream())
     return valid, rows, sums
 
 
@@ -1869,23 +1878,29 @@ def rgbd_rows_bwd_raw(tgt_depth, tgt_rgb, src_depth, src_rgb, intrinsics, T, g_s
     """The reverse of rgbd_rows_raw, the decisions held constant: g_sums (B,29), the adjoint of `sums` as rgbd_rows_raw returns them
     (err's is honoured, cnt's ignored) -> (g_tgt_depth (B,H,W), g_tgt_rgb (B,H,W,3), g_src_depth, g_src_rgb, g_T (B,3,4), rows 0..2
     of T's).  The seam the tests check."""
-    op = "rgbd_rows_bwd"
-    td, tc = _rgbd_frame(tgt_depth, tgt_rgb, "target", op)
-    B, H, W = td.shape
-    sd, sc = _rgbd_frame(src_depth, src_rgb, "source", op, B, H, W)
-    K, T = _rgbd_K(intrinsics, B, op), _rgbd_T(T, B, "T", op)
-    lam, ddm, scale = _rgbd_params(1, lambda_geo, depth_diff_max, rgb_scale, H, W, op)
-    if not torch.is_tensor(g_sums) or tuple(g_sums.shape) != (B, 29):
-        raise ValueError("{}: g_sums should be a tensor of shape ({}, 29).".format(op, B))
-    g_sums = _f32c(g_sums.detach())
-    require_hip(td, tc, sd, sc, K, T, g_sums, op=op)
-    dev = td.device
-    g_td, g_tc, g_sd, g_sc = (torch.empty_like(t) for t in (td, tc, sd, sc))
-    g_T = torch.empty((B, 3, 4), dtype=torch.float32, device=dev)
+    frames, (g_sums,), args = _rgbd_seam_args("rgbd_rows_bwd", tgt_depth, tgt_rgb, src_depth, src_rgb, intrinsics, T, lambda_geo,
+                                              depth_diff_max, rgb_scale, g_sums)
+    (B, H, W), dev = frames[0].shape, frames[0].device
+    grads = [torch.empty_like(t) for t in frames] + [torch.empty((B, 3, 4), dtype=torch.float32, device=dev)]
     ws = workspace(ws_bytes("gs_rgbd_odometry_bwd_ws_size", B, H, W, 1, 1), dev, "rgbd")
-    call("gs_rgbd_rows_bwd", ptr(td), ptr(tc), ptr(sd), ptr(sc), B, H, W, ptr(K), ptr(T), lam, ddm, scale, ptr(g_sums), ptr(g_td),
-         ptr(g_tc), ptr(g_sd), ptr(g_sc), ptr(g_T), ptr(ws), ws.numel(), stream())
-    return g_td, g_tc, g_sd, g_sc, g_T
+    call("gs_rgbd_rows_bwd", *args, ptr(g_sums), *(ptr(g) for g in grads), ptr(ws), ws.numel(), stream())
+    return tuple(grads)
+
+
+def _rgbd_odometry_call(td, tc, sd, sc, init, K, numiters, levels, lam, ddm, damp, scale, taped):
+    """gs_rgbd_odometry, or with `taped` gs_rgbd_odometry_taped (the same launches, the same bits) -> (T, info, tape or None)."""
+    (B, H, W), dev = td.shape, td.device
+    out_T = torch.empty((B, 4, 4), dtype=torch.float32, device=dev)
+    info = torch.empty((B, levels, 4), dtype=torch.float32, device=dev)
+    ws = workspace(ws_bytes("gs_rgbd_odometry_ws_bytes", B, H, W, levels), dev, "rgbd")
+    counts = (nv.c_i * levels)(*numiters)
+    tape, extra = None, ()
+    if taped:
+        tape = torch.empty(ws_bytes("gs_rgbd_odometry_tape_size", B, levels, sum(numiters)) // 4, dtype=torch.float32, device=dev)
+        extra = (ptr(tape),)
+    call("gs_rgbd_odometry_taped" if taped else "gs_rgbd_odometry", ptr(td), ptr(tc), ptr(sd), ptr(sc), B, H, W, ptr(K), ptr(init), levels,
+         counts, lam, ddm, damp, scale, ptr(out_T), ptr(info), ptr(ws), ws.numel(), stream(), *extra)
+    return out_T, info, tape
 
 
 class _RgbdOdometryFn(torch.autograd.Function):
@@ -1894,15 +1909,7 @@ class _RgbdOdometryFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, td, tc, sd, sc, init, K, numiters, levels, lam, ddm, damp, scale):
-        B, H, W = td.shape
-        dev = td.device
-        out_T = torch.empty((B, 4, 4), dtype=torch.float32, device=dev)
-        info = torch.empty((B, levels, 4), dtype=torch.float32, device=dev)
-        tape = torch.empty(ws_bytes("gs_rgbd_odometry_tape_size", B, levels, sum(numiters)) // 4, dtype=torch.float32, device=dev)
-        ws = workspace(ws_bytes("gs_rgbd_odometry_ws_bytes", B, H, W, levels), dev, "rgbd")
-        counts = (nv.c_i * levels)(*numiters)
-        call("gs_rgbd_odometry_taped", ptr(td), ptr(tc), ptr(sd), ptr(sc), B, H, W, ptr(K), ptr(init), levels, counts, lam, ddm, damp,
-             scale, ptr(out_T), ptr(info), ptr(ws), ws.numel(), stream(), ptr(tape))
+        out_T, info, tape = _rgbd_odometry_call(td, tc, sd, sc, init, K, numiters, levels, lam, ddm, damp, scale, taped=True)
         ctx.save_for_backward(td, tc, sd, sc, K, tape)
         ctx.params = (numiters, levels, lam, ddm, damp, scale, init is not None)
         ctx.mark_non_differentiable(info)
@@ -1912,8 +1919,7 @@ class _RgbdOdometryFn(torch.autograd.Function):
     def backward(ctx, grad_T, _grad_info):
         td, tc, sd, sc, K, tape = ctx.saved_tensors
         numiters, levels, lam, ddm, damp, scale, has_init = ctx.params
-        B, H, W = td.shape
-        dev = td.device
+        (B, H, W), dev = td.shape, td.device
         grad_T = _f32c(grad_T)
         need = list(ctx.needs_input_grad[:5])
         need[4] = need[4] and has_init
@@ -1959,11 +1965,4 @@ def rgbd_odometry(tgt_depth, tgt_rgb, src_depth, src_rgb, intrinsics, init=None,
     require_hip(td, tc, sd, sc, K, init, op=op)
     if attached:
         return _RgbdOdometryFn.apply(td, tc, sd, sc, init, K, numiters, levels, lam, ddm, damp, scale)
-    dev = td.device
-    out_T = torch.empty((B, 4, 4), dtype=torch.float32, device=dev)
-    info = torch.empty((B, levels, 4), dtype=torch.float32, device=dev)
-    ws = workspace(ws_bytes("gs_rgbd_odometry_ws_bytes", B, H, W, levels), dev, "rgbd")
-    counts = (nv.c_i * levels)(*numiters)
-    call("gs_rgbd_odometry", ptr(td), ptr(tc), ptr(sd), ptr(sc), B, H, W, ptr(K), ptr(init), levels, counts, lam, ddm, damp, scale,
-         ptr(out_T), ptr(info), ptr(ws), ws.numel(), stream())
-    return out_T, info
+    return _rgbd_odometry_call(td, tc, sd, sc, init, K, numiters, levels, lam, ddm, damp, scale, taped=False)[:2]

@@ -478,6 +478,13 @@ def icp_device_loop(src, tgt, nrm, init_T, numiters, damp, dist_thresh, grad_par
     return T, best, trace
 
 
+def _grad_lm(grad_params):
+    """grad_params (lambda_max, B, B2, nu) of gradICP, or None for plain ICP -> (grad_lm, lmax, Bp, B2, nu) as the C calls
+    take them (plain ICP ignores the four floats)."""
+    lmax, Bp, B2, nu = grad_params if grad_params is not None else (2.0, 1.0, 1.0, 200.0)
+    return (1 if grad_params is not None else 0), float(lmax), float(Bp), float(B2), float(nu)
+
+
 class _IcpLoopFn(torch.autograd.Function):
     """Differentiable point_to_plane_ICP / gradICP as ONE node: the taped device loop forward, the
     device-side reverse pass over the tape backward (no host sync in either direction)."""
@@ -489,18 +496,17 @@ class _IcpLoopFn(torch.autograd.Function):
         ns, nt = src.shape[0], tgt.shape[0]
         if ns == 0 or nt == 0:
             raise ValueError("ICP needs non-empty source and target clouds (got {} and {} points)".format(ns, nt))
-        grad_lm = 1 if grad_params is not None else 0
-        lmax, Bp, B2, nu = grad_params if grad_params is not None else (2.0, 1.0, 1.0, 200.0)
+        grad_lm, lmax, Bp, B2, nu = _grad_lm(grad_params)
         T = torch.empty((4, 4), dtype=torch.float32, device=dev)
         best = torch.empty(ns, dtype=torch.int64, device=dev)
         tape = torch.empty(ws_bytes("gs_icp_tape_bytes", ns, int(numiters), grad_lm), dtype=torch.uint8, device=dev)
         ws = workspace(ws_bytes("gs_icp_ws_bytes", ns, nt), dev, "icp")
         d_ns, d_nt = dev_int(ns, dev), dev_int(nt, dev)
         call("gs_icp_point_to_plane_taped", ptr(src), ptr(d_ns), ns, ptr(tgt), ptr(nrm), ptr(d_nt), nt, ptr(init_T),
-             int(numiters), float(damp), _thresh(dist_thresh), grad_lm, float(lmax), float(Bp), float(B2), float(nu), None,
+             int(numiters), float(damp), _thresh(dist_thresh), grad_lm, lmax, Bp, B2, nu, None,
              ptr(T), ptr(best), ptr(tape), tape.numel(), ptr(ws), ws.numel(), stream())
         ctx.save_for_backward(src, tgt, nrm, init_T, tape, d_ns, d_nt)
-        ctx.cfg = (int(numiters), _thresh(dist_thresh), grad_lm, float(lmax), float(Bp), float(B2), float(nu))
+        ctx.cfg = (int(numiters), _thresh(dist_thresh), grad_lm, lmax, Bp, B2, nu)
         ctx.mark_non_differentiable(best)
         return T, best
 
@@ -554,68 +560,100 @@ def slam_localize_raw(depth, K, prev_poses, map_points, map_normals, map_counts_
     elif not (out.is_contiguous() and out.dtype == torch.float32 and out.numel() == 16 * B and out.device == dev):
         raise ValueError("slam_localize: `out` must be a contiguous float32 (B,1,4,4) tensor on the inputs' device")
     ws = workspace(ws_bytes("gs_slam_localize_ws_bytes", B, H, W, int(ds), Nmax), dev, "localize")
-    lmax, Bp, B2, nu = grad_params if grad_params is not None else (2.0, 1.0, 1.0, 200.0)
+    grad_lm, lmax, Bp, B2, nu = _grad_lm(grad_params)
     call("gs_slam_localize", ptr(depth), ptr(K), ptr(prev), B, H, W, int(ds), ptr(mp), ptr(mn), ptr(map_counts_i32), Nmax,
-         1 if grad_params is not None else 0, int(numiters), float(damp), _thresh(dist_thresh), float(lmax), float(Bp),
-         float(B2), float(nu), ptr(V), ptr(N), ptr(gV), None, ptr(out), ptr(ws), ws.numel(), stream())
+         grad_lm, int(numiters), float(damp), _thresh(dist_thresh), lmax, Bp, B2, nu, ptr(V), ptr(N), ptr(gV), None, ptr(out),
+         ptr(ws), ws.numel(), stream())
     return out, V, N
 
 
+def slam_localize_taped_raw(gV, depth, K, prev_poses, map_points, map_normals, map_counts_i32, ds, numiters, damp, dist_thresh,
+                            grad_params=None):
+    """slam_localize_raw that also fills the tape of its reverse pass -> (poses (B,1,4,4), tape).  gV (B,1,H,W,3) is the live
+    frame's global vertex map under the previous pose: an input here, so that its adjoint chains into the maps' own."""
+    require_hip(gV, depth, K, prev_poses, map_points, map_normals, map_counts_i32, op="slam_localize")
+    gV, depth, K, prev = _f32c(gV.detach()), _f32c(depth.detach()), _f32c(K.detach()), _f32c(prev_poses.detach())
+    mp, mn = _f32c(map_points.detach()), _f32c(map_normals.detach())
+    B, _, H, W = depth.shape[:4]
+    Nmax = mp.shape[1]
+    dev = depth.device
+    grad_lm, lmax, Bp, B2, nu = _grad_lm(grad_params)
+    out = torch.empty((B, 1, 4, 4), dtype=torch.float32, device=dev)
+    tape = torch.empty(ws_bytes("gs_slam_localize_tape_bytes", B, H, W, int(ds), Nmax, int(numiters), grad_lm),
+                       dtype=torch.uint8, device=dev)
+    ws = workspace(ws_bytes("gs_slam_localize_ws_bytes", B, H, W, int(ds), Nmax), dev, "localize")
+    call("gs_slam_localize_taped", ptr(depth), ptr(gV), ptr(K), ptr(prev), B, H, W, int(ds), ptr(mp), ptr(mn),
+         ptr(map_counts_i32), Nmax, grad_lm, int(numiters), float(damp), _thresh(dist_thresh), lmax, Bp, B2, nu, ptr(out),
+         ptr(tape), tape.numel(), ptr(ws), ws.numel(), stream())
+    return out, tape
+
+
+def slam_localize_backward_raw(prev_poses, map_points, map_normals, nmax, H, W, ds, numiters, dist_thresh, grad_params, tape,
+                               g_poses, g_gV, g_map_points, g_map_normals, g_prev, accumulate):
+    """Reverse pass of slam_localize_taped_raw (same prev_poses and map; `nmax` its row bound, the arrays may hold more rows
+    by now) into the caller's contiguous float32 buffers: g_gV (B,1,H,W,3) and g_prev (B,1,4,4) are written, g_map_points /
+    g_map_normals (None = not wanted) written (accumulate = 0) or added into (1: the running adjoint of a whole map)."""
+    B, dev = prev_poses.shape[0], prev_poses.device
+    ds, numiters = int(ds), int(numiters)
+    grad_lm, lmax, Bp, B2, nu = _grad_lm(grad_params)
+    g_poses = _f32c(g_poses)
+    if deterministic():
+        det, size = "_det", ws_bytes("gs_slam_localize_backward_det_ws_bytes", B, H, W, ds, nmax, numiters, grad_lm)
+    else:
+        det, size = "", ws_bytes("gs_slam_localize_backward_ws_bytes", B, H, W, ds, nmax)
+    ws = workspace(size, dev, "localize_bwd" + det)
+    call("gs_slam_localize_backward" + det, ptr(prev_poses), B, H, W, ds, ptr(map_points), ptr(map_normals), nmax, grad_lm,
+         numiters, _thresh(dist_thresh), lmax, Bp, B2, nu, ptr(tape), tape.numel(), ptr(g_poses), ptr(g_gV), ptr(g_map_points),
+         ptr(g_map_normals), ptr(g_prev), int(accumulate), ptr(ws), ws.numel(), stream())
+
+
 class _LocalizeFn(torch.autograd.Function):
-    """Differentiable ICPSLAM._localize as ONE node (gs_slam_localize_taped / _backward): gradients reach the
-    live frame's global vertex map, the map points / normals that served as ICP targets and the previous
+    """Differentiable ICPSLAM._localize as ONE node (slam_localize_taped_raw / slam_localize_backward_raw): gradients reach
+    the live frame's global vertex map, the map points / normals that served as ICP targets and the previous
     pose; nothing synchronises with the host in either direction."""
 
     @staticmethod
     def forward(ctx, gV, depth, K, prev_poses, mp, mn, counts_i32, ds, numiters, damp, dist_thresh, grad_params):
-        gV, depth, K, prev = _f32c(gV.detach()), _f32c(depth.detach()), _f32c(K.detach()), _f32c(prev_poses.detach())
-        mp, mn = _f32c(mp.detach()), _f32c(mn.detach())
-        B, _, H, W = depth.shape[:4]
-        Nmax = mp.shape[1]
-        dev = depth.device
-        grad_lm = 1 if grad_params is not None else 0
-        lmax, Bp, B2, nu = grad_params if grad_params is not None else (2.0, 1.0, 1.0, 200.0)
-        out = torch.empty((B, 1, 4, 4), dtype=torch.float32, device=dev)
-        tape = torch.empty(ws_bytes("gs_slam_localize_tape_bytes", B, H, W, int(ds), Nmax, int(numiters), grad_lm),
-                           dtype=torch.uint8, device=dev)
-        ws = workspace(ws_bytes("gs_slam_localize_ws_bytes", B, H, W, int(ds), Nmax), dev, "localize")
-        call("gs_slam_localize_taped", ptr(depth), ptr(gV), ptr(K), ptr(prev), B, H, W, int(ds), ptr(mp), ptr(mn),
-             ptr(counts_i32), Nmax, grad_lm, int(numiters), float(damp), _thresh(dist_thresh), float(lmax), float(Bp), float(B2),
-             float(nu), ptr(out), ptr(tape), tape.numel(), ptr(ws), ws.numel(), stream())
+        prev, mp, mn = _f32c(prev_poses.detach()), _f32c(mp.detach()), _f32c(mn.detach())
+        out, tape = slam_localize_taped_raw(gV, depth, K, prev, mp, mn, counts_i32, ds, numiters, damp, dist_thresh, grad_params)
         ctx.save_for_backward(prev, mp, mn, tape)
-        ctx.cfg = (B, H, W, int(ds), Nmax, grad_lm, int(numiters), _thresh(dist_thresh), float(lmax), float(Bp), float(B2), float(nu))
+        ctx.cfg = (depth.shape[2], depth.shape[3], ds, numiters, dist_thresh, grad_params)
         return out
 
     @staticmethod
     def backward(ctx, g_out):
         prev, mp, mn, tape = ctx.saved_tensors
-        B, H, W, ds, Nmax, grad_lm, numiters, thresh, lmax, Bp, B2, nu = ctx.cfg
-        dev = prev.device
-        g_out = _f32c(g_out)
+        H, W = ctx.cfg[:2]
+        B, dev = prev.shape[0], prev.device
         g_gV = torch.empty((B, 1, H, W, 3), dtype=torch.float32, device=dev)
         g_mp = torch.empty_like(mp) if ctx.needs_input_grad[4] else None
         g_mn = torch.empty_like(mn) if ctx.needs_input_grad[5] else None
         g_prev = torch.empty((B, 1, 4, 4), dtype=torch.float32, device=dev)
-        entry, ws = _localize_backward_ws(B, H, W, ds, Nmax, numiters, grad_lm, dev)
-        call(entry, ptr(prev), B, H, W, ds, ptr(mp), ptr(mn), Nmax, grad_lm, numiters, thresh, lmax, Bp, B2,
-             nu, ptr(tape), tape.numel(), ptr(g_out), ptr(g_gV), ptr(g_mp), ptr(g_mn), ptr(g_prev), 0, ptr(ws), ws.numel(), stream())
+        slam_localize_backward_raw(prev, mp, mn, mp.shape[1], *ctx.cfg, tape, g_out, g_gV, g_mp, g_mn, g_prev, 0)
         return g_gV, None, None, g_prev, g_mp, g_mn, None, None, None, None, None, None
-
-
-def _localize_backward_ws(B, H, W, ds, Nmax, numiters, grad_lm, dev):
-    """(entry, workspace) of the localisation reverse pass: the `_det` one under torch.use_deterministic_algorithms."""
-    if deterministic():
-        return "gs_slam_localize_backward_det", workspace(
-            ws_bytes("gs_slam_localize_backward_det_ws_bytes", B, H, W, ds, Nmax, numiters, grad_lm), dev, "localize_bwd_det")
-    return "gs_slam_localize_backward", workspace(ws_bytes("gs_slam_localize_backward_ws_bytes", B, H, W, ds, Nmax), dev, "localize_bwd")
 
 
 def slam_localize_autograd(gV, depth, K, prev_poses, map_points, map_normals, map_counts_i32, ds, numiters, damp, dist_thresh,
                            grad_params=None):
     """Differentiable fused localisation -> poses (B,1,4,4) with grad_fn."""
-    require_hip(gV, depth, K, prev_poses, map_points, map_normals, map_counts_i32, op="slam_localize")
     return _LocalizeFn.apply(gV, depth, K, prev_poses, map_points, map_normals, map_counts_i32, ds, numiters, damp, dist_thresh,
                              grad_params)
+
+
+def _pointfusion_update_args(depth, rgb, K, poses, map_points, map_normals, map_colors, map_ccounts, map_counts_i32, nmax=None):
+    """The checks and the C argument prefix that gs_pointfusion_update, its taped form and its reverse pass share
+    -> (B, H, W, nmax, held, prefix).  nmax: the row bound handed to the kernels (default: the rows the map arrays hold);
+    held: the contiguous K and poses behind the prefix's pointers, for the caller to keep until its call is made."""
+    require_hip(depth, rgb, K, poses, map_points, map_normals, map_colors, map_ccounts, map_counts_i32, op="pointfusion_update")
+    for name, x in (("map_points", map_points), ("map_normals", map_normals), ("map_colors", map_colors),
+                    ("map_ccounts", map_ccounts), ("depth", depth), ("rgb", rgb)):
+        if not (x.is_contiguous() and x.dtype == torch.float32):
+            raise ValueError("pointfusion_update: {} must be contiguous float32 (it is updated / read in place)".format(name))
+    B, H, W = depth.shape[:3]
+    nmax = map_points.shape[1] if nmax is None else int(nmax)
+    held = K, poses = _f32c(K), _f32c(poses)
+    return B, H, W, nmax, held, (ptr(depth), ptr(rgb), ptr(K), ptr(poses), B, H, W, ptr(map_points), ptr(map_normals),
+                                 ptr(map_colors), ptr(map_ccounts), ptr(map_counts_i32), nmax)
 
 
 def pointfusion_update_raw(depth, rgb, K, poses, map_points, map_normals, map_colors, map_ccounts, map_counts_i32, dist_th,
@@ -624,18 +662,34 @@ def pointfusion_update_raw(depth, rgb, K, poses, map_points, map_normals, map_co
     inplace=True).  depth (B,H,W[,1]), rgb (B,H,W,3), K / poses (B,[1,]4,4); map_* (B,Nmax,C) float32 contiguous,
     rows beyond map_counts zero; the caller guarantees counts + H*W <= Nmax.  Everything is updated in place,
     including map_counts_i32 (B,) int32 on the device; `stats` (4+B,) int32 receives the step's counters."""
-    require_hip(depth, rgb, K, poses, map_points, map_normals, map_colors, map_ccounts, map_counts_i32, op="pointfusion_update")
-    for name, x in (("map_points", map_points), ("map_normals", map_normals), ("map_colors", map_colors),
-                    ("map_ccounts", map_ccounts), ("depth", depth), ("rgb", rgb)):
-        if not (x.is_contiguous() and x.dtype == torch.float32):
-            raise ValueError("pointfusion_update: {} must be contiguous float32 (it is updated / read in place)".format(name))
-    B, H, W = depth.shape[:3]
-    Nmax = map_points.shape[1]
-    K, poses = _f32c(K), _f32c(poses)
+    B, H, W, Nmax, held, prefix = _pointfusion_update_args(depth, rgb, K, poses, map_points, map_normals, map_colors, map_ccounts,
+                                                           map_counts_i32)
     ws = workspace(ws_bytes("gs_pointfusion_update_ws_bytes", B, H, W, Nmax), depth.device, "fusion_step")
-    call("gs_pointfusion_update", ptr(depth), ptr(rgb), ptr(K), ptr(poses), B, H, W, ptr(map_points), ptr(map_normals),
-         ptr(map_colors), ptr(map_ccounts), ptr(map_counts_i32), Nmax, float(dist_th), float(dot_th), float(sigma), ptr(stats),
+    call("gs_pointfusion_update", *prefix, float(dist_th), float(dot_th), float(sigma), ptr(stats), ptr(ws), ws.numel(), stream())
+
+
+def pointfusion_update_taped_raw(depth, rgb, K, poses, map_points, map_normals, map_colors, map_ccounts, map_counts_i32, dist_th,
+                                 dot_th, sigma, stats=None):
+    """pointfusion_update_raw that also fills the frame's tape for pointfusion_update_backward_raw -> tape."""
+    B, H, W, Nmax, held, prefix = _pointfusion_update_args(depth, rgb, K, poses, map_points, map_normals, map_colors, map_ccounts,
+                                                           map_counts_i32)
+    tape = torch.empty(ws_bytes("gs_pointfusion_update_tape_bytes", B, H, W), dtype=torch.uint8, device=depth.device)
+    ws = workspace(ws_bytes("gs_pointfusion_update_ws_bytes", B, H, W, Nmax), depth.device, "fusion_step")
+    call("gs_pointfusion_update_taped", *prefix, float(dist_th), float(dot_th), float(sigma), ptr(stats), ptr(tape), tape.numel(),
          ptr(ws), ws.numel(), stream())
+    return tape
+
+
+def pointfusion_update_backward_raw(depth, rgb, K, poses, map_points, map_normals, map_colors, map_ccounts, map_counts_i32, nmax,
+                                    sigma, tape, G_points, G_normals, G_colors, G_ccounts, g_V, g_gV, g_gN, g_rgb):
+    """One frame back over the tape of pointfusion_update_taped_raw (`nmax`: that call's row bound; the arrays may hold more
+    rows by now).  G_* (B,rows,C), the running adjoint of the WHOLE map, is pulled back in place at the matched / appended rows;
+    the map and counts are restored to the previous frame's; g_V, g_gV, g_gN, g_rgb (B,H,W,3) receive the frame's adjoints."""
+    B, H, W, nmax, held, prefix = _pointfusion_update_args(depth, rgb, K, poses, map_points, map_normals, map_colors, map_ccounts,
+                                                           map_counts_i32, nmax)
+    ws = workspace(ws_bytes("gs_pointfusion_update_backward_ws_bytes", B, H, W), depth.device, "fusion_bwd")
+    call("gs_pointfusion_update_backward", *prefix, float(sigma), ptr(tape), tape.numel(), ptr(G_points), ptr(G_normals),
+         ptr(G_colors), ptr(G_ccounts), ptr(g_V), ptr(g_gV), ptr(g_gN), ptr(g_rgb), ptr(ws), ws.numel(), stream())
 
 
 def aggregate_update_raw(depth, rgb, K, poses, map_points, map_normals, map_colors, map_counts_i32, stats=None):
@@ -650,165 +704,6 @@ def aggregate_update_raw(depth, rgb, K, poses, map_points, map_normals, map_colo
     ws = workspace(ws_bytes("gs_aggregate_update_ws_bytes", B, H, W), depth.device, "aggregate_step")
     call("gs_aggregate_update", ptr(depth), ptr(rgb), ptr(K), ptr(poses), B, H, W, ptr(map_points), ptr(map_normals),
          ptr(map_colors), ptr(map_counts_i32), map_points.shape[1], ptr(stats), ptr(ws), ws.numel(), stream())
-
-
-class _PointFusionSeqFn(torch.autograd.Function):
-    """PointFusion over a whole batch of sequences as ONE autograd node.
-
-    forward  = the arena-backed frame loop with the taped forms of its two calls per frame
-               (gs_slam_localize_taped, gs_pointfusion_update_taped): no host synchronisation until the map is
-               handed back, the map updated in place.
-    backward = the frames in reverse on a copy of the final arena: per frame gs_pointfusion_update_backward (pulls the
-               running adjoint of the whole map back through merge + append at the matched / appended rows only and
-               restores the arena to the previous frame's), the adjoint of the frame's vertex / normal maps, then
-               gs_slam_localize_backward (adds the ICP targets' adjoints into the running map adjoint) and the adjoint of
-               the live maps under the previous pose.  What is a constant in the reference's graph is a constant here
-               (correspondence tables, association indices, accept decisions).
-    reference: torch autograd through slam/icpslam.py:125-137 with slam/pointfusion.py:107-112."""
-
-    @staticmethod
-    def forward(ctx, rgb, depth, K, poses, cfg):
-        odom, ds, numiters, damp, dist_thresh, gparams, dist_th, dot_th, sigma, arena_cls = cfg
-        rgb, depth, K = _f32c(rgb.detach()), _f32c(depth.detach()), _f32c(K.detach())
-        poses_c = _f32c(poses.detach()) if poses is not None else None
-        B, L, H, W = depth.shape[:4]
-        dev = depth.device
-        arena = arena_cls(B, H * W, dev, with_features=True)
-        recovered = torch.empty((B, L, 4, 4), dtype=torch.float32, device=dev)
-        stats = torch.zeros((L, 4 + B), dtype=torch.int32, device=dev)
-        grad_lm = 1 if gparams is not None else 0
-        lmax, Bp, B2, nu = gparams if gparams is not None else (2.0, 1.0, 1.0, 200.0)
-        fuse_tape_b = ws_bytes("gs_pointfusion_update_tape_bytes", B, H, W)
-        frames = []
-        prev, bound = None, None
-        for s in range(L):
-            d_s, c_s = depth[:, s].contiguous(), rgb[:, s].contiguous()
-            rec = {}
-            if s == 0 or odom == "gt":
-                pose = (poses_c[:, s:s + 1].contiguous() if poses_c is not None else
-                        torch.eye(4, dtype=torch.float32, device=dev).view(1, 1, 4, 4).repeat(B, 1, 1, 1))
-            else:
-                mp, mn, _, _ = arena.rows(bound)
-                _, _, gV, _ = vertex_normal_maps_raw(d_s.unsqueeze(1), K, prev, want_local=False, want_global=True)
-                pose = torch.empty((B, 1, 4, 4), dtype=torch.float32, device=dev)
-                tape = torch.empty(ws_bytes("gs_slam_localize_tape_bytes", B, H, W, int(ds), bound, int(numiters), grad_lm),
-                                   dtype=torch.uint8, device=dev)
-                ws = workspace(ws_bytes("gs_slam_localize_ws_bytes", B, H, W, int(ds), bound), dev, "localize")
-                call("gs_slam_localize_taped", ptr(d_s), ptr(gV), ptr(K), ptr(prev), B, H, W, int(ds), ptr(mp), ptr(mn),
-                     ptr(arena.counts), bound, grad_lm, int(numiters), float(damp), _thresh(dist_thresh), float(lmax), float(Bp),
-                     float(B2), float(nu), ptr(pose), ptr(tape), tape.numel(), ptr(ws), ws.numel(), stream())
-                rec["loc"] = (tape, bound)
-            bound = arena.reserve_frame()
-            mp, mn, mc, mf = arena.rows(bound)
-            ftape = torch.empty(fuse_tape_b, dtype=torch.uint8, device=dev)
-            ws = workspace(ws_bytes("gs_pointfusion_update_ws_bytes", B, H, W, bound), dev, "fusion_step")
-            call("gs_pointfusion_update_taped", ptr(d_s), ptr(c_s), ptr(K), ptr(pose), B, H, W, ptr(mp), ptr(mn), ptr(mc), ptr(mf),
-                 ptr(arena.counts), bound, float(dist_th), float(dot_th), float(sigma), ptr(stats[s]), ptr(ftape), ftape.numel(),
-                 ptr(ws), ws.numel(), stream())
-            arena.appended()
-            rec["fuse"] = (ftape, bound)
-            frames.append(rec)
-            recovered[:, s] = pose[:, 0]
-            prev = pose
-        n = arena.counts.tolist()  # the one host synchronisation of the sequence
-        ctx.arena, ctx.frames, ctx.n_final = arena, frames, n
-        ctx.cfg = (odom, int(ds), int(numiters), _thresh(dist_thresh), grad_lm, float(lmax), float(Bp), float(B2), float(nu), float(sigma))
-        ctx.has_poses = poses is not None
-        ctx.save_for_backward(rgb, depth, K, recovered)
-        ctx.stats = stats
-        cut = lambda x: x[:, : max(n)].clone()  # zero-padded to the largest map (rows beyond a sequence's count are zero)
-        ctx.mark_non_differentiable(stats)
-        return cut(arena.points), cut(arena.normals), cut(arena.colors), cut(arena.ccounts), recovered.clone(), stats
-
-    @staticmethod
-    def backward(ctx, g_p, g_n, g_c, g_f, g_poses, _g_stats):
-        rgb, depth, K, recovered = ctx.saved_tensors
-        odom, ds, numiters, thresh, grad_lm, lmax, Bp, B2, nu, sigma = ctx.cfg
-        arena, frames, n_final = ctx.arena, ctx.frames, ctx.n_final
-        B, L, H, W = depth.shape[:4]
-        dev = depth.device
-        cap = arena.cap
-        # work on copies: the arena is restored frame by frame, the running adjoint of the map is pulled back in place
-        mp, mn, mc, mf = (x.clone() for x in (arena.points, arena.normals, arena.colors, arena.ccounts))
-        counts = arena.counts.clone()
-
-        def running(g, c):
-            G = torch.zeros((B, cap, c), dtype=torch.float32, device=dev)
-            if g is not None:
-                for b in range(B):  # (rows beyond a sequence's count are padding of the output, not map points)
-                    G[b, :n_final[b]] = g[b, :n_final[b]]
-            return G
-
-        Gp, Gn, Gc, Gf = running(g_p, 3), running(g_n, 3), running(g_c, 3), running(g_f, 1)
-        gpose = g_poses.clone().float() if g_poses is not None else torch.zeros((B, L, 4, 4), dtype=torch.float32, device=dev)
-        g_rgb, g_depth, g_K = torch.zeros_like(rgb), torch.zeros_like(depth), torch.zeros_like(K)
-        g_poses_in = torch.zeros((B, L, 4, 4), dtype=torch.float32, device=dev) if ctx.has_poses else None
-        mk = lambda c: torch.empty((B, H, W, c), dtype=torch.float32, device=dev)
-        g_V, g_gV, g_gN = mk(3), mk(3), mk(3)
-        g_live = torch.empty((B, 1, H, W, 3), dtype=torch.float32, device=dev)
-        g_prev = torch.empty((B, 1, 4, 4), dtype=torch.float32, device=dev)
-        # One sequence (B = 1): the per-frame slices of the adjoints are contiguous, so every kernel writes or ADDS straight
-        # into them -- no per-frame temporaries, zero fills or `+=` launches (a dozen small torch kernels per frame, and
-        # their host cost, in the first version of this loop).  A batch takes contiguous per-frame buffers and copies.
-        one = B == 1
-        if not one:
-            t_rgb, t_depth, t_pose, t_pose2 = mk(3), torch.empty((B, 1, H, W, 1), dtype=torch.float32, device=dev), \
-                torch.empty((B, 1, 4, 4), dtype=torch.float32, device=dev), torch.empty((B, 1, 4, 4), dtype=torch.float32, device=dev)
-        stride = cap
-
-        def restride(n):
-            # A batch's arrays are (B, stride, C) and the kernels take ONE number for row bound and row stride.  The arena
-            # may have grown during the forward pass; the tapes of earlier frames were laid out with the stride of their
-            # time.  Walking back, the map only shrinks: repack the working arrays to the older, smaller stride once per
-            # growth step (rows beyond it did not exist yet; their adjoints have been consumed by their own frames).
-            nonlocal mp, mn, mc, mf, Gp, Gn, Gc, Gf, stride
-            if one or n == stride:
-                return
-            mp, mn, mc, mf, Gp, Gn, Gc, Gf = (x[:, :n].contiguous() for x in (mp, mn, mc, mf, Gp, Gn, Gc, Gf))
-            stride = n
-
-        for s in reversed(range(L)):
-            d_s, c_s = depth[:, s].contiguous(), rgb[:, s].contiguous()
-            pose_s = recovered[:, s:s + 1].contiguous()
-            ftape, bound = frames[s]["fuse"]
-            restride(bound)
-            ws = workspace(ws_bytes("gs_pointfusion_update_backward_ws_bytes", B, H, W), dev, "fusion_bwd")
-            call("gs_pointfusion_update_backward", ptr(d_s), ptr(c_s), ptr(K), ptr(pose_s), B, H, W, ptr(mp), ptr(mn), ptr(mc), ptr(mf),
-                 ptr(counts), bound, sigma, ptr(ftape), ftape.numel(), ptr(Gp), ptr(Gn), ptr(Gc), ptr(Gf), ptr(g_V), ptr(g_gV),
-                 ptr(g_gN), ptr(g_rgb[:, s] if one else t_rgb), ptr(ws), ws.numel(), stream())
-            if one:
-                gd_s, gpose_s = g_depth[:, s], gpose[:, s]
-            else:
-                g_rgb[:, s] = t_rgb
-                gd_s, gpose_s = t_depth.zero_(), t_pose.zero_()
-            vertex_normal_maps_backward_into(d_s.unsqueeze(1), K, pose_s, g_V.unsqueeze(1), None, g_gV.unsqueeze(1), g_gN.unsqueeze(1),
-                                             gd_s, g_K, gpose_s)
-            if not one:
-                gpose[:, s] += t_pose[:, 0]
-            if "loc" in frames[s]:
-                tape, nmax = frames[s]["loc"]
-                restride(nmax)
-                prev = recovered[:, s - 1:s].contiguous()
-                entry, ws = _localize_backward_ws(B, H, W, ds, nmax, numiters, grad_lm, dev)
-                call(entry, ptr(prev), B, H, W, ds, ptr(mp), ptr(mn), nmax, grad_lm, numiters, thresh, lmax, Bp, B2,
-                     nu, ptr(tape), tape.numel(), ptr(gpose[:, s:s + 1].contiguous()), ptr(g_live), ptr(Gp), ptr(Gn), ptr(g_prev), 1,
-                     ptr(ws), ws.numel(), stream())
-                gprev_s = gpose[:, s - 1] if one else t_pose2.zero_()
-                vertex_normal_maps_backward_into(d_s.unsqueeze(1), K, prev, None, None, g_live, None, gd_s, g_K, gprev_s)
-                if not one:
-                    gpose[:, s - 1] += t_pose2[:, 0]
-                gpose[:, s - 1] += g_prev.view(B, 4, 4)
-            elif g_poses_in is not None:
-                g_poses_in[:, s] += gpose[:, s]
-            if not one:
-                g_depth[:, s] += t_depth[:, 0]
-        return g_rgb, g_depth, g_K, g_poses_in, None
-
-
-def pointfusion_sequence_autograd(rgb, depth, K, poses, cfg):
-    """-> (points, normals, colors, ccounts (1, N, C) each, recovered poses (1, L, 4, 4), stats) with grad_fn."""
-    require_hip(rgb, depth, K, poses, op="pointfusion_sequence")
-    return _PointFusionSeqFn.apply(rgb, depth, K, poses, cfg)
 
 
 # ---------------------------------------------------------------------------------------------- C / U / F / A

@@ -6,10 +6,12 @@ from typing import Union
 
 import torch
 
+from .. import ops
 from ..structures.pointclouds import Pointclouds
 from ..structures.rgbdimages import RGBDImages
 from .fusionutils import update_map_fusion
 from .icpslam import ICPSLAM
+from .sequence import _PointFusionSeqFn
 
 __all__ = ["PointFusion"]
 
@@ -46,26 +48,16 @@ class PointFusion(ICPSLAM):
     # arena-backed sequence driver (ICPSLAM._forward_streamed): the PointFusion update and its warnings
     _arena_features = True
 
-    def _arena_update(self, arena, depth_s, rgb_s, K, pose, bound, stats_row):
-        from .. import ops
+    def _update_args(self):
+        return self.dist_th, self.dot_th, self.sigma
 
-        mp, mn, mc, mf = arena.rows(bound)
-        ops.pointfusion_update_raw(depth_s, rgb_s, K, pose, mp, mn, mc, mf, arena.counts, self.dist_th, self.dot_th, self.sigma,
-                                   stats_row)
+    def _arena_update(self, arena, depth_s, rgb_s, K, pose, bound, stats_row):
+        ops.pointfusion_update_raw(depth_s, rgb_s, K, pose, *arena.rows(bound), arena.counts, *self._update_args(), stats_row)
 
     def _can_fuse_sequence(self, frames) -> bool:
-        """forward() with gradients as one node: channels-last float32 sequences on the device, the mapping step not
-        overridden by a subclass."""
-        if not getattr(type(self)._map, "_gs_arena_form", False) or frames.channels_first or self.device.type != "cuda":
-            return False
-        tensors = (frames.rgb_image, frames.depth_image, frames.intrinsics, frames.poses)
-        if frames.poses is None and self.odom == "gt":
-            return False
-        if any(t is not None and (not t.is_cuda or t.dtype != torch.float32) for t in tensors):
-            return False
-        if not (torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in tensors)):
-            return False  # nothing to differentiate: the streamed / step-by-step drivers
-        if not (frames.shape[0] <= 60 and frames.shape[2] >= 2 and frames.shape[3] >= 2):
+        """forward() with gradients as one node: a sequence that fits the arena, has something to differentiate (else the
+        streamed / step-by-step drivers take it) and whose tapes fit the device."""
+        if not self._fits_arena(frames, with_grad=True):
             return False
         # Memory law of the sequence node: it keeps, until backward, one fusion tape (44 B per pixel) and one localisation
         # tape (the ICP loop's clouds and neighbour arrays, ~20 B per ds-grid point and association, + 4 B per target slot)
@@ -94,19 +86,9 @@ class PointFusion(ICPSLAM):
         return L * per_frame + 2 * 40 * map_pts  # + the arena and its copy in backward
 
     def _forward_sequence_node(self, frames: RGBDImages):
-        from .. import ops
-        from .icpslam import _MapArena
-
-        p = self.odomprov
-        gparams = (p.lambda_max, p.B, p.B2, p.nu) if self.odom == "gradicp" else None
-        cfg = (self.odom, self.dsratio, p.numiters if p is not None else 0, p.damp if p is not None else 0.0,
-               p.dist_thresh if p is not None else None, gparams, self.dist_th, self.dot_th, self.sigma, _MapArena)
-        pts, nrm, col, cc, poses, stats = ops.pointfusion_sequence_autograd(frames.rgb_image, frames.depth_image, frames.intrinsics,
-                                                                            frames.poses, cfg)
-        for s, row in enumerate(stats.tolist()):  # the reference's warnings, raised once the sequence is done
-            if row[2]:
-                raise RuntimeError("map arena overflow at frame {} (internal capacity bound violated)".format(s))
-            self._stream_warnings(s, row)
+        pts, nrm, col, cc, poses, stats = _PointFusionSeqFn.apply(frames.rgb_image, frames.depth_image, frames.intrinsics,
+                                                                  frames.poses, self._localize_args(), self._update_args())
+        self._sequence_diagnostics(stats.tolist())
         n = [int(x) for x in stats[:, 4:4 + pts.shape[0]].sum(0).tolist()]  # rows every sequence's map holds (appended, summed)
         pick = lambda x: [x[b, : n[b]] for b in range(x.shape[0])]
         return Pointclouds(points=pick(pts), normals=pick(nrm), colors=pick(col), features=pick(cc)), poses

@@ -1402,7 +1402,7 @@ def test_downsample_pointclouds_accepts_an_unsorted_table(gs, golden):
 @pytest.mark.parametrize("odom", ["gt", "icp", "gradicp"])
 def test_sequence_node_gradients_equal_per_op_nodes(gs, odom):
     """PointFusion.forward with gradients as ONE autograd node per sequence (taped arena update + reverse pass over the
-    frames, ops._PointFusionSeqFn) against the per-frame formulation (one node per localisation, staged differentiable
+    frames, slam.sequence._PointFusionSeqFn) against the per-frame formulation (one node per localisation, staged differentiable
     mapping step): same poses and map bit for bit (same kernels), input gradients to 1e-5 of their maximum (the
     unmatched map points' adjoints pass through exactly here, through (c x) (1 / c) there)."""
     from gradslam_amd.synthetic import make_sequence
@@ -1700,7 +1700,7 @@ def test_dense_regime_step_vs_oracle(gs, odom, k):
 
 
 @pytest.mark.parametrize("odom", ["gt", "gradicp"])
-def test_sequence_node_batch_equals_single_runs(gs, odom):
+def test_sequence_node_batch_equals_single_runs(gs, monkeypatch, odom):
     """The sequence-level autograd node on a BATCH: three sequences of different lengths of map in one
     call against three single-sequence calls -- poses and maps bit for bit (sequences never interact), all four input
     gradients to 1e-5 of their maximum (the scattered target adjoints are float atomics: ~1e-7)."""
@@ -1721,17 +1721,24 @@ def test_sequence_node_batch_equals_single_runs(gs, odom):
         return pcs, poses.detach(), [x.grad if x.grad is not None else torch.zeros_like(x) for x in leaves]
 
     singles = [run(slice(b, b + 1)) for b in range(B)]
-    from gradslam_amd.slam import icpslam as _icpslam
+    from gradslam_amd.slam import sequence as _sequence
 
+    reserve, bounds = _sequence._MapArena.reserve_frame, []
+
+    def watched_reserve(arena):
+        bounds.append(reserve(arena))
+        return bounds[-1]
+
+    monkeypatch.setattr(_sequence._MapArena, "reserve_frame", watched_reserve)
     for grow in (False, True):
         # grow: the host never learns the map counts, so its bound -- and with it the batch's row stride -- outgrows the
         # first capacity in the middle of the sequence: the tapes of the early frames carry the old stride, and the
         # reverse pass has to repack its working arrays when it walks back past the growth step
-        _icpslam._NO_READBACK = grow
-        try:
-            pcs, poses, grads = run(slice(0, B))
-        finally:
-            _icpslam._NO_READBACK = False
+        monkeypatch.setattr(_sequence, "_NO_READBACK", grow)
+        del bounds[:]
+        pcs, poses, grads = run(slice(0, B))
+        if grow:  # (not a race against the read-backs: without them the bounds are 32768, 32768, 65536, 65536)
+            assert len(bounds) == L and len(set(bounds)) == 2, bounds
         assert len(set(pcs.num_points_per_pointcloud.tolist())) == B  # really ragged
         for b in range(B):
             spcs, sposes, sgrads = singles[b]

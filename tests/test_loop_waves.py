@@ -71,8 +71,11 @@ def _with_arg16(fn, typ, body):
         fn.argtypes = old
 
 
-def run_loops(gs, sc, numiters=6, grad_lm=0, hints=True):
-    """One plain and one taped loop through the C ABI on fresh zeroed buffers -> everything they wrote, on the host."""
+def run_loops(gs, sc, numiters=6, grad_lm=0, hints=True, thresh=-1.0, ns_dev=None, rows_fill=0):
+    """One plain and one taped loop through the C ABI on fresh zeroed buffers -> everything they wrote, on the host.
+    thresh: the squared-distance threshold (negative: none).  ns_dev: the device count, at most the capacity src.shape[0]
+    (None: the capacity).  rows_fill: the byte both partial-row regions of the workspaces hold at the start -- they and
+    nothing else (the regions that carry indices must not hold junk)."""
     from gradslam_amd import _native as nv
     from gradslam_amd import ops
 
@@ -86,17 +89,20 @@ def run_loops(gs, sc, numiters=6, grad_lm=0, hints=True):
                   sc["cam_pose"].data_ptr(), sc["cam_K"].data_ptr(), sc["ds"])
     hp = ctypes.byref(h) if h is not None else None
     T0 = torch.eye(4, device=DEV)
-    d_ns, d_nt = ops.dev_int(ns, DEV), ops.dev_int(nt, DEV)
+    assert ns_dev is None or 0 < ns_dev <= ns
+    d_ns, d_nt = ops.dev_int(ns if ns_dev is None else ns_dev, DEV), ops.dev_int(nt, DEV)
     b, t, rows = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
     assert lib.gs_icp_launch_geometry(ns, 1, ctypes.byref(b), ctypes.byref(t), ctypes.byref(rows)) == 0
     al = lambda x: (x + 255) // 256 * 256
     # icp.hip icp_ws_layout: state x 2 | clouds x 2 | neighbour keys x 2 | partial rows x 2 | ...
-    ws_head = 2 * al(348) + 2 * al(ns * 12) + 2 * al(ns * 8) + 2 * al(rows.value * 29 * 4)
+    part0 = 2 * al(348) + 2 * al(ns * 12) + 2 * al(ns * 8)
+    ws_head = part0 + 2 * al(rows.value * 29 * 4)
     out = {"blocks": b.value}
     ws_n = nv.ws_bytes("gs_icp_ws_bytes", ns, nt)
     assert ws_head < ws_n
     # plain loop: pose, trace, last keys, workspace head (state, clouds, keys, partial rows)
     ws = torch.zeros(ws_n, dtype=torch.uint8, device=DEV)
+    ws[part0:ws_head] = rows_fill
     T = torch.zeros(4, 4, device=DEV)
     best = torch.zeros(ns, dtype=torch.int64, device=DEV)
     trace = torch.zeros(numiters, 48, device=DEV)
@@ -105,7 +111,7 @@ def run_loops(gs, sc, numiters=6, grad_lm=0, hints=True):
     old = list(fnp.argtypes)
     fnp.argtypes = old[:hint_pos] + [ctypes.POINTER(Hints)] + old[hint_pos + 1:]
     try:
-        args = [src.data_ptr(), d_ns.data_ptr(), ns, tgt.data_ptr(), nrm.data_ptr(), d_nt.data_ptr(), nt, T0.data_ptr(), numiters, 1e-8, -1.0]
+        args = [src.data_ptr(), d_ns.data_ptr(), ns, tgt.data_ptr(), nrm.data_ptr(), d_nt.data_ptr(), nt, T0.data_ptr(), numiters, 1e-8, thresh]
         if grad_lm:
             args += [2.0, 1.0, 1.0, 200.0]
         args += [hp, T.data_ptr(), best.data_ptr(), trace.data_ptr(), ws.data_ptr(), ws.numel(), nv.stream()]
@@ -117,17 +123,17 @@ def run_loops(gs, sc, numiters=6, grad_lm=0, hints=True):
     out.update(T=T.cpu(), best_last=best.cpu(), trace=trace.cpu(), ws_head=ws[:ws_head].cpu())
     # taped loop: the tape is the loop's working storage (every launch's cloud and keys, every step's record)
     ws = torch.zeros(ws_n, dtype=torch.uint8, device=DEV)
+    ws[part0:ws_head] = rows_fill
     tape = torch.zeros(nv.ws_bytes("gs_icp_tape_bytes", ns, numiters, grad_lm), dtype=torch.uint8, device=DEV)
     T2 = torch.zeros(4, 4, device=DEV)
     best2 = torch.zeros(ns, dtype=torch.int64, device=DEV)
     fn = lib.gs_icp_point_to_plane_taped
     rc = _with_arg16(fn, ctypes.POINTER(Hints), lambda: fn(
-        src.data_ptr(), d_ns.data_ptr(), ns, tgt.data_ptr(), nrm.data_ptr(), d_nt.data_ptr(), nt, T0.data_ptr(), numiters, 1e-8, -1.0,
+        src.data_ptr(), d_ns.data_ptr(), ns, tgt.data_ptr(), nrm.data_ptr(), d_nt.data_ptr(), nt, T0.data_ptr(), numiters, 1e-8, thresh,
         grad_lm, 2.0, 1.0, 1.0, 200.0, hp, T2.data_ptr(), best2.data_ptr(), tape.data_ptr(), tape.numel(), ws.data_ptr(), ws.numel(),
         nv.stream()))
     assert rc == 0, lib.gs_last_error()
     torch.cuda.synchronize()
-    part0 = 2 * al(348) + 2 * al(ns * 12) + 2 * al(ns * 8)
     out.update(T_taped=T2.cpu(), best_last_taped=best2.cpu(), tape=tape.cpu(), partial_rows_taped=ws[part0:ws_head].cpu(),
                state_taped=ws[:2 * al(348)].cpu())
     return out

@@ -405,13 +405,7 @@ __global__ __launch_bounds__(CORR_T) void corr_pass1_k(const float *__restrict__
     __shared__ Cam cam;
     __shared__ int red[2][CORR_T / 64];
     const int b = blockIdx.y;
-    if (threadIdx.x < 32) {  // the camera: 32 words in ONE round of loads (a single lane doing make_cam alone would chain them)
-        const float w = threadIdx.x < 16 ? poses[16 * b + threadIdx.x] : Ks[16 * b + threadIdx.x - 16];
-        __shared__ float raw[32];
-        raw[threadIdx.x] = w;
-        __builtin_amdgcn_wave_barrier();
-        if (threadIdx.x == 0) cam = make_cam(raw, raw + 16);
-    }
+    block_cam(cam, poses, Ks, b);
     const int cnt = min(counts[b], Nmax);
     const int64_t HW = (int64_t)H * W;
     const int64_t base = (int64_t)b * Nmax;

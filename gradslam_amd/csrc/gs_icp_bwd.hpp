@@ -166,7 +166,7 @@ __device__ void small_g2(BwdState *Sb, const float *rec, const float *sums) {
 // Everything the step reads -- the state, its tape record with the head of the next one, the partial rows -- is requested in
 // ONE batch at kernel start and handed over through LDS: the step runs on one lane, and every global word it used to
 // fetch for itself (the record's state, sums, flags: a dozen dependent round trips) is an LDS read now; the rows' loads
-// used to follow each other through a four-deep loop (same order of summation as reduce12: the sums do not change).
+// used to follow each other through a four-deep loop (same order of summation as gs_rowsum.hpp's fold_rows with 16 groups: the sums do not change).
 __device__ __forceinline__ void bwd_fold(BwdState &sb, const BwdState *__restrict__ Sb_in, BwdState *__restrict__ Sb_out, int fold,
                                          const float *__restrict__ rec, const float *__restrict__ partials_in, int nblocks,
                                          GradParams gp, int arg) {
@@ -242,7 +242,7 @@ __global__ __launch_bounds__(BWD_T) void bwd_look_k(const BwdState *__restrict__
         const f3 a = rot_t(R, ld3(gP, i)), b = rot_t(R1, gl);
         st3(gP, i, f3{a.x + b.x, a.y + b.y, a.z + b.z});
     }
-    block_store12(acc, partials);
+    block_row<12, BWD_WAVES>(acc, [&](unsigned n) { return &partials[blockIdx.x * 12 + n]; });
 }
 
 // C, with S2 (gradLM) or S (LM) folded in: gP_i <- (rotate ? R2^T gP_i : gP_i) + adjoint of (H, g, e) at the iteration's
@@ -285,7 +285,7 @@ __global__ __launch_bounds__(BWD_T) void bwd_lin_k(const BwdState *__restrict__ 
         st3(gP, i, g);
         acc_outer(acc, g, ld3(prev, i));
     }
-    block_store12(acc, partials);
+    block_row<12, BWD_WAVES>(acc, [&](unsigned n) { return &partials[blockIdx.x * 12 + n]; });
 }
 
 struct BwdWs {
@@ -340,7 +340,7 @@ __global__ __launch_bounds__(BWD_T) void bwd_finish_k(const float *__restrict__ 
     const int ns = *d_ns;
     for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < ns; i += gridDim.x * blockDim.x) st3(g_src, i, rot_t(R, ld3(gP, i)));
     if (blockIdx.x == 0) {  // (block-uniform)
-        reduce12(partials, nblocks, sums);
+        fold_rows<12, BWD_GROUPS, 16>(partials, nblocks, 12, sums);
         if (threadIdx.x < 16) g_init_T[threadIdx.x] = Sb->gT[threadIdx.x] + (threadIdx.x < 12 ? sums[threadIdx.x] : 0.0f);
     }
 }

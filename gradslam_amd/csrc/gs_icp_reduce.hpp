@@ -1,5 +1,5 @@
-// gs_icp_reduce.hpp -- the fixed-order reduction (J) of the 29 linearisation sums: per block, then over the blocks'
-// partial rows.  Included by icp.hip ahead of its stand-alone kernels, and by gs_icp_step.hpp.
+// gs_icp_reduce.hpp -- the fixed-order reduction (J) of the 29 linearisation sums over the blocks' partial rows (a block's
+// row itself: gs_rowsum.hpp's block_row).  Included by icp.hip ahead of its stand-alone kernels, and by gs_icp_step.hpp.
 //
 // J  gather + 29-term reduction, HBM/L2-bound at 40 algorithmic bytes per source point; wave
 //    butterflies + a fixed-order two-level tree (deterministic, no float atomics).  Fused into the association
@@ -9,24 +9,6 @@
 #include "gs_icp_assoc.hpp"
 
 namespace gs {
-
-// block-level fixed-order reduction of the 29 accumulators -> partials[blockIdx.x]
-__device__ __forceinline__ void block_reduce_store(float *acc, float *__restrict__ partials) {
-    __shared__ float sm[LIN_T / 64][NACC];
-    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-#pragma unroll
-    for (int k = 0; k < NACC; ++k) {
-        const float v = wave_sum(acc[k]);
-        if (lane == 0) sm[wid][k] = v;
-    }
-    __syncthreads();
-    if (threadIdx.x < NACC) {
-        float v = 0.0f;
-#pragma unroll
-        for (int w = 0; w < LIN_T / 64; ++w) v += sm[w][threadIdx.x];
-        partials[blockIdx.x * NACC + threadIdx.x] = v;
-    }
-}
 
 // Fixed-order reduction of the per-block partials by a 1024-thread block into acc_sm[NACC]:
 // thread (g, k) = (t / 32, t % 32) sums rows g, g+32, g+64, ... of accumulator k (coalesced over k),

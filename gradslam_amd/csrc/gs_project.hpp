@@ -28,6 +28,17 @@ __device__ __forceinline__ Cam make_cam(const float *__restrict__ T, const float
     for (int i = 0; i < 16; ++i) c.K[i] = K[i];
     return c;
 }
+// The block's camera of batch element b into LDS: the first 32 threads load pose and intrinsics in ONE round (a single lane
+// doing make_cam alone would chain 32 loads), then thread 0 builds it.  The caller's next block barrier makes `cam` visible.
+__device__ __forceinline__ void block_cam(Cam &cam, const float *__restrict__ poses, const float *__restrict__ Ks, int b) {
+    if (threadIdx.x < 32) {
+        const float w = threadIdx.x < 16 ? poses[16 * b + threadIdx.x] : Ks[16 * b + threadIdx.x - 16];
+        __shared__ float raw[32];
+        raw[threadIdx.x] = w;
+        __builtin_amdgcn_wave_barrier();
+        if (threadIdx.x == 0) cam = make_cam(raw, raw + 16);
+    }
+}
 // Projects map point p of batch element with camera c.  Returns true iff the point is active and
 // fills (h, w).  reference slam/fusionutils.py:250-274, structures/pointclouds.py:501-517,423-425,
 // geometry/projutils.py:221-236.

@@ -2,7 +2,7 @@
 // which launches them (rgbd_bwd_run); the pixel's forward values and the pyramid's rules are gs_rgbd_pixel.hpp's, the forward's own code.
 // Per iteration, last to first:
 // Xb step reverse, one 256-thread block per batch element: the pixel pass before left 12-sum rows -- the adjoint of T_{k+1}
-//    through ITS linearisation -- which are folded (reduce12) into the carried adjoint; then, one lane, fp64 where the forward's
+//    through ITS linearisation -- which are folded (fold_rows) into the carried adjoint; then, one lane, fp64 where the forward's
 //    fp32 value would lose the gradient: dT-bar = T-bar_{k+1} T_k^T, T-bar_k = dT^T T-bar_{k+1}, the exponential's and the
 //    solve's adjoints -> the adjoints of the iteration's 29 sums.  A step that was not applied is the identity.
 // Lb pixel reverse, the forward's geometry: the pixel's forward values again from the taped T_k (rgbd_pixel_fwd, rgbd_chan_row),
@@ -27,7 +27,7 @@ __global__ __launch_bounds__(BWD_T) void rgbd_gT_k(const float *__restrict__ gT_
                                                   int prow, float *__restrict__ out, int stride) {
     __shared__ float sums[12];
     const int b = blockIdx.x;
-    reduce12(partials12 + (int64_t)b * prow * 12, nblocks, sums);
+    fold_rows<12, BWD_GROUPS, 16>(partials12 + (int64_t)b * prow * 12, nblocks, 12, sums);
     if ((int)threadIdx.x < stride)
         out[stride * b + threadIdx.x] = threadIdx.x < 12 ? (gT_in ? gT_in[16 * b + threadIdx.x] : 0.0f) + sums[threadIdx.x] : 0.0f;
 }
@@ -50,7 +50,7 @@ __global__ __launch_bounds__(BWD_T) void rgbd_step_bwd_k(float *__restrict__ gTa
     __shared__ float g[16], xi[6], dT[16], hg[44], gx[6], y[6];
     __shared__ double gdT[12], gxi[6];
     const int b = blockIdx.x;
-    reduce12(partials12 + (int64_t)b * prow * 12, nblocks, sums);
+    fold_rows<12, BWD_GROUPS, 16>(partials12 + (int64_t)b * prow * 12, nblocks, 12, sums);
     if (threadIdx.x != 0) return;
     const float *rec = rec_all + RGBD_TAPE_WORDS * b;
     float *gT = gTall + 16 * b, *A = adj_all + RGBD_ADJ_WORDS * b;
@@ -124,7 +124,7 @@ __global__ __launch_bounds__(RGBD_T) void rgbd_pixel_bwd_k(const float2 *__restr
                                                           int tstride, const float *__restrict__ adj, float wI, float wD, float ddm,
                                                           Fold fold, int lg, float2 *__restrict__ gsrc, float *__restrict__ partials12,
                                                           int prow) {
-    static_assert(RGBD_T == BWD_T, "block_store12 sizes its shared memory for blocks of BWD_T threads");
+    static_assert(RGBD_T == BWD_T, "the 12-wide rows are block_row<12, BWD_WAVES>'s: blocks of BWD_T threads");
     __shared__ float M[36], g[6], e2s;
     const int b = blockIdx.y, npix = Hl * Wl;
     const int p = blockIdx.x * RGBD_T + threadIdx.x;
@@ -195,7 +195,7 @@ __global__ __launch_bounds__(RGBD_T) void rgbd_pixel_bwd_k(const float2 *__restr
         // almost none is issued (thousands of waves, one address).  The maximum is the same whichever are skipped.
         if (mx <= __hip_atomic_load(fold.maxbits, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) mx = 0;
         fold_max_commit(fold.maxbits, mx);
-        block_store12(acc, partials12 + (int64_t)b * prow * 12);
+        block_row<12, BWD_WAVES>(acc, [&](unsigned n) { return &partials12[(int64_t)b * prow * 12 + (blockIdx.x * 12 + n)]; });
     }
 }
 

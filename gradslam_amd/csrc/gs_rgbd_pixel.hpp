@@ -11,7 +11,7 @@
 
 namespace gs {
 
-constexpr int RGBD_T = LIN_T;  // lanes (= source pixels) per linearise block: block_reduce_store's geometry
+constexpr int RGBD_T = LIN_T;  // lanes (= source pixels) per linearise block: linearize_k's geometry (icp.hip)
 
 // An iteration's tape row of batch element b (RGBD_TAPE_WORDS floats at tape + RGBD_TAPE_WORDS b): T before the step (16), the 29
 // sums as reduced (g not yet negated), xi (6), 1 if the step was applied else 0 -- what the reverse pass replays.

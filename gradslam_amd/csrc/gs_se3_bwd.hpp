@@ -1,31 +1,16 @@
-// gs_se3_bwd.hpp -- the O(1) adjoints of a Gauss-Newton step on SE(3) and the fixed-order sums of 12-wide rows: device functions,
-// no kernels, so that every translation unit with a reverse pass (icp.hip through gs_icp_bwd.hpp, rgbd.hip) can include it.
+// gs_se3_bwd.hpp -- the O(1) adjoints of a Gauss-Newton step on SE(3): device functions, no kernels, so that every translation
+// unit with a reverse pass (icp.hip through gs_icp_bwd.hpp, rgbd.hip) can include it.
 //   T' = dT T, dT = exp(xi), xi = (H + damp I)^-1 g:  top3_times_Tt / pull_gT, se3_exp_bwd, solve_bwd (fp64 on one lane)
-//   the adjoint of a transform is a sum of 12 terms per point or pixel:  block_store12 (a block's row), reduce12 (the rows)
+//   the adjoint of a transform is a sum of 12 terms per point or pixel, in gs_rowsum.hpp's order: block_row<12, BWD_WAVES> by
+//   blocks of BWD_T threads, fold_rows<12, BWD_GROUPS, 16> over their rows
 #pragma once
 
 #include "gs_icp_step.hpp"
+#include "gs_rowsum.hpp"
 
 namespace gs {
 
-constexpr int BWD_T = 256;
-
-// 12 running sums of a block -> partials[blockIdx.x][12] (fixed order: wave butterflies, then waves in order)
-__device__ __forceinline__ void block_store12(float *acc, float *__restrict__ partials) {
-    __shared__ float wsum[BWD_T / 64][12];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-    for (int k = 0; k < 12; ++k) {
-        const float v = wave_sum(acc[k]);
-        if (lane == 0) wsum[wave][k] = v;
-    }
-    __syncthreads();
-    if (threadIdx.x < 12) {
-        float v = 0.0f;
-        for (int w = 0; w < BWD_T / 64; ++w) v += wsum[w][threadIdx.x];
-        partials[blockIdx.x * 12 + threadIdx.x] = v;
-    }
-}
+constexpr int BWD_T = 256, BWD_WAVES = BWD_T / kWave, BWD_GROUPS = BWD_T / 16;
 
 // ---- O(1) adjoints, fp64 on one lane
 // adjoint of T = se3_exp(xi) (se3_exp_dev above, both branches) given gT (top 3 rows, row-major 3x4)
@@ -71,26 +56,6 @@ __device__ void se3_exp_bwd(const float *xi, const double *gT, double *gxi) {
     gw[2] += gWh[3] - gWh[1];
     for (int j = 0; j < 3; ++j) gxi[j] = V[j] * gt[0] + V[3 + j] * gt[1] + V[6 + j] * gt[2];  // V^T gt
     gxi[3] = gw[0]; gxi[4] = gw[1]; gxi[5] = gw[2];
-}
-
-// sum of the 12-wide partial rows by a 256-thread block: 16 groups stride over the rows, then 12 threads
-// add the 16 group sums in order (any number of rows)
-__device__ __forceinline__ void reduce12(const float *__restrict__ partials, int nblocks, float *out_sm) {
-    __shared__ float stage[12][17];
-    const int k = threadIdx.x & 15, g = threadIdx.x >> 4;
-    if (k < 12) {
-        float v = 0.0f;
-        for (int b = g; b < nblocks; b += 16) v += partials[b * 12 + k];
-        stage[k][g] = v;
-    }
-    __syncthreads();
-    if (threadIdx.x < 12) {
-        float v = 0.0f;
-#pragma unroll
-        for (int q = 0; q < 16; ++q) v += stage[threadIdx.x][q];
-        out_sm[threadIdx.x] = v;
-    }
-    __syncthreads();
 }
 
 __device__ __forceinline__ void top3_times_Tt(const float *gTn, const float *T, double *out12) {  // (gTn . T^T) rows 0..2

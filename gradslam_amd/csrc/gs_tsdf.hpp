@@ -5,6 +5,7 @@
 
 #include "gs_common.hpp"
 #include "gs_project.hpp"
+#include "gs_rowsum.hpp"
 
 namespace gs {
 
@@ -197,14 +198,13 @@ __device__ __forceinline__ bool tsdf_hit_at(const TsdfVol &g, const float *__res
 
 // ------------------------------------------------------------------ the pose sums of the reverse passes (integration and cast)
 // A camera's pose adjoint is N sums over the threads of many blocks (integration: N = 4 over the voxels, cast: N = 12 over the
-// pixels).  Plain fp32 in ONE fixed order, no atomics, so the same bits from run to run:
-//   1. tsdf_pose_wave: per wave the 64-lane butterfly of wave_sum (offsets 32, 16, .. 1); lane 0 leaves the wave's N sums in LDS.
-//      `on`: this lane holds terms (else its x must be +0).  A wave without any skips the butterfly and leaves +0.
-//   2. tsdf_pose_block (behind a barrier): thread n < N adds the block's 4 waves in ascending order: one row of N per block.
-//   3. tsdf_pose_rows (the finishing launch, 1024 threads per camera): thread (r, n) = (tid / 16, tid % 16) adds rows r, r + 64,
-//      r + 128, .. in ascending order onto +0; then thread n adds the 64 partial sums r = 0 .. 63 in ascending order -> sm[1024 + n].
+// pixels).  Plain fp32 in gs_rowsum.hpp's fixed order, no atomics, so the same bits from run to run:
+//   1. tsdf_pose_wave: the wave's butterflies.  `on`: this lane holds terms (else its x must be +0).  A wave without any skips
+//      the butterfly and leaves +0 (what the butterfly of 64 +0 gives).  tsdf_bwd_k keeps one set of wave sums per frame of a chunk.
+//   2. block_row_sum<N, TSDF_WAVES> behind a barrier: one row of N per block and camera.
+//   3. fold_rows<N, TSDF_POSE_GROUPS, 16> in the finishing launch, TSDF_POSE_T threads per camera.
 constexpr int TSDF_WAVES = TSDF_T / kWave;
-constexpr int TSDF_POSE_T = 1024, TSDF_POSE_LANES = 64;
+constexpr int TSDF_POSE_T = 1024, TSDF_POSE_GROUPS = TSDF_POSE_T / 16;
 template <int N>
 __device__ __forceinline__ void tsdf_pose_wave(const float (&x)[N], bool on, float *__restrict__ red) {  // red: [TSDF_WAVES][N]
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
@@ -214,29 +214,6 @@ __device__ __forceinline__ void tsdf_pose_wave(const float (&x)[N], bool on, flo
         const float s = any ? wave_sum(x[n]) : 0.0f;
         if (lane == 0) red[wave * N + n] = s;
     }
-}
-template <int N>
-__device__ __forceinline__ float tsdf_pose_block(const float *__restrict__ red, int n) {
-    float s = red[n];
-#pragma unroll
-    for (int w = 1; w < TSDF_WAVES; ++w) s = s + red[w * N + n];
-    return s;
-}
-template <int N>
-__device__ __forceinline__ void tsdf_pose_rows(const float *__restrict__ rows, int nrow, float *sm) {  // sm: [1024 + 16]
-    static_assert(N <= 16, "16 sums per row at most");
-    const int r = threadIdx.x >> 4, n = threadIdx.x & 15;
-    float a = 0.0f;
-    if (n < N)
-        for (int row = r; row < nrow; row += TSDF_POSE_LANES) a = a + rows[(int64_t)row * N + n];
-    sm[threadIdx.x] = a;
-    __syncthreads();
-    if ((int)threadIdx.x < N) {
-        float t = sm[threadIdx.x];
-        for (int q = 1; q < TSDF_POSE_LANES; ++q) t = t + sm[q * 16 + threadIdx.x];
-        sm[TSDF_POSE_T + threadIdx.x] = t;
-    }
-    __syncthreads();
 }
 
 }  // namespace gs

@@ -3,7 +3,7 @@
 //
 // One translation unit; the device code lives in role headers, each with its part of the design at its top:
 //   gs_icp_assoc.hpp   K  keys, row algebra, the tile search (chunk boxes, grid windows) up to knn_tile
-//   gs_icp_reduce.hpp  J  block_reduce_store, the rp_* partial-row reduction, expand44
+//   gs_icp_reduce.hpp  J  the rp_* partial-row reduction, expand44 (a block's row: gs_rowsum.hpp)
 //   gs_icp_step.hpp    X  IcpState, LoopBufs, solve6*, se3_exp_dev, GradParams, tape records, step_wave0
 //   gs_icp_loop.hpp       LoopConst, the camera proof, knn1_loop_k, icp_init_state_k, icp_prepare_k, copy_best_last_k
 //   gs_icp_bwd.hpp        the reverse pass: BwdState ... bwd_finish_k, bwd_ws_layout
@@ -18,6 +18,7 @@
 #include "gs_detfold.hpp"
 #include "gs_icp.hpp"
 #include "gs_icp_reduce.hpp"
+#include "gs_rowsum.hpp"
 
 namespace gs {
 
@@ -115,7 +116,7 @@ __global__ __launch_bounds__(LIN_T) void linearize_k(const float *__restrict__ s
         const Row r = make_row(src, tgt, nrm, best, i, ns, thresh);
         if (r.valid) accumulate_row(r, acc);
     }
-    block_reduce_store(acc, partials);
+    block_row<NACC, LIN_T / kWave>(acc, [&](unsigned n) { return &partials[blockIdx.x * NACC + n]; });
 }
 
 __global__ __launch_bounds__(1024) void finalize44_k(const float *__restrict__ partials, int nblocks, float *__restrict__ out44) {

@@ -11,6 +11,7 @@
 #include "gs_drivers.hpp"
 #include "gs_maps.hpp"
 #include "gs_project.hpp"
+#include "gs_rowsum.hpp"
 
 namespace gs {
 
@@ -100,19 +101,8 @@ __global__ __launch_bounds__(256) void vn_bwd_pass1_k(const float *__restrict__ 
         st3(dhb, pix, f3{dv.y * cb.z - dv.z * cb.y, dv.z * cb.x - dv.x * cb.z, dv.x * cb.y - dv.y * cb.x});
         st3(dvb, pix, f3{cb.y * dh.z - cb.z * dh.y, cb.z * dh.x - cb.x * dh.z, cb.x * dh.y - cb.y * dh.x});
     }
-    {   // per-block partial sums; vn_bwd_final_k adds them up (no same-address atomics, fixed order)
-        __shared__ float sm[4][9];
-        const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-#pragma unroll
-        for (int i = 0; i < 9; ++i) {
-            const float v = wave_sum(rbar[i]);
-            if (lane == 0) sm[wid][i] = v;
-        }
-        __syncthreads();
-        if (threadIdx.x < 9)
-            part[((int64_t)bl * gridDim.x + blockIdx.x) * VN_PART + 16 + threadIdx.x] =
-                sm[0][threadIdx.x] + sm[1][threadIdx.x] + sm[2][threadIdx.x] + sm[3][threadIdx.x];
-    }
+    // the block's row; vn_bwd_final_k folds the rows (no same-address atomics, fixed order: gs_rowsum.hpp)
+    block_row<9, 4>(rbar, [&](unsigned n) { return &part[((int64_t)bl * gridDim.x + blockIdx.x) * VN_PART + 16 + n]; });
 }
 
 __global__ __launch_bounds__(256) void vn_bwd_pass2_k(const float *__restrict__ depth, const float *__restrict__ Ks,
@@ -181,17 +171,7 @@ __global__ __launch_bounds__(256) void vn_bwd_pass2_k(const float *__restrict__ 
         const float rbx = m * d * vb.x, rby = m * d * vb.y;
         acc[12] = rbx * (float)w; acc[13] = rbx; acc[14] = rby * (float)h; acc[15] = rby;
     }
-    __shared__ float sm[4][16];
-    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-#pragma unroll
-    for (int i = 0; i < 16; ++i) {
-        const float v = wave_sum(acc[i]);
-        if (lane == 0) sm[wid][i] = v;
-    }
-    __syncthreads();
-    if (threadIdx.x < 16)
-        part[((int64_t)bl * gridDim.x + blockIdx.x) * VN_PART + threadIdx.x] =
-            sm[0][threadIdx.x] + sm[1][threadIdx.x] + sm[2][threadIdx.x] + sm[3][threadIdx.x];
+    block_row<16, 4>(acc, [&](unsigned n) { return &part[((int64_t)bl * gridDim.x + blockIdx.x) * VN_PART + n]; });
 }
 
 // one block per (b,l): adds the per-block partials up and applies them to the pose / intrinsics adjoints.
@@ -200,24 +180,10 @@ template <bool DET>
 __global__ __launch_bounds__(1024) void vn_bwd_final_k(const float *__restrict__ part, int nblocks, int have_pass1,
                                                       const float *__restrict__ Ks, const float *__restrict__ poses, int L,
                                                       float *__restrict__ g_K, float *__restrict__ g_poses) {
-    __shared__ float stage[VN_PART][33];
     __shared__ float tot[VN_PART];
     const int bl = blockIdx.x, b = bl / L;
-    const int k = threadIdx.x & 31, g = threadIdx.x >> 5;  // 32 groups
-    float v = 0.0f;
-    if (k < VN_PART && (k < 16 || have_pass1)) {
-#pragma unroll 4
-        for (int i = g; i < nblocks; i += 32) v += part[((int64_t)bl * nblocks + i) * VN_PART + k];
-    }
-    if (k < VN_PART) stage[k][g] = v;
-    __syncthreads();
-    if (threadIdx.x < VN_PART) {
-        float t = 0.0f;
-#pragma unroll
-        for (int q = 0; q < 32; ++q) t += stage[threadIdx.x][q];
-        tot[threadIdx.x] = t;
-    }
-    __syncthreads();
+    // (columns 16 .. 24 are pass 1's: unwritten workspace when it did not run)
+    fold_rows<VN_PART, 32, 32>(part + (int64_t)bl * nblocks * VN_PART, nblocks, have_pass1 ? VN_PART : 16, tot);
     if (threadIdx.x < 12 && g_poses && poses) {
         const int i = threadIdx.x;
         const int slot = (i < 9) ? 4 * (i / 3) + (i % 3) : 4 * (i - 9) + 3;

@@ -23,10 +23,11 @@
 //    g_poses[b][j][2]       = sum_pix g_depth * (p_j - t_j)          (rotation column 2)
 //    g_poses[b][j][3]       = -R[j][2] * sum_pix g_depth             (translation)
 // The intrinsics adjoint is zero almost everywhere and not produced.  A map row wins at most one pixel, so the scatter
-// is plain stores: no atomics anywhere, and the four pose sums per b go through per-block partials and one fixed-order
-// final reduce (vn_bwd_pass2_k / vn_bwd_final_k's pattern in maps.hip) -- the same bits from run to run.
+// is plain stores: no atomics anywhere, and the four pose sums per b go through per-block rows and one fixed-order fold
+// (gs_rowsum.hpp) -- the same bits from run to run.
 #include "gs_common.hpp"
 #include "gs_project.hpp"
+#include "gs_rowsum.hpp"
 
 namespace gs {
 
@@ -44,13 +45,7 @@ __global__ __launch_bounds__(REND_T) void render_pass_k(const float *__restrict_
                                                         float umax, float vmax, unsigned long long *__restrict__ pix_key) {
     __shared__ Cam cam;
     const int b = blockIdx.y;
-    if (threadIdx.x < 32) {  // 32 words in ONE round of loads (a single lane doing make_cam alone would chain them)
-        const float w = threadIdx.x < 16 ? poses[16 * b + threadIdx.x] : Ks[16 * b + threadIdx.x - 16];
-        __shared__ float raw[32];
-        raw[threadIdx.x] = w;
-        __builtin_amdgcn_wave_barrier();
-        if (threadIdx.x == 0) cam = make_cam(raw, raw + 16);
-    }
+    block_cam(cam, poses, Ks, b);
     const int cnt = min(counts[b], Nmax);
     const int64_t HW = (int64_t)H * W;
     const int64_t base = (int64_t)b * Nmax;
@@ -144,36 +139,15 @@ __global__ __launch_bounds__(REND_T) void render_bwd_pix_k(const int32_t *__rest
     if (!part) return;  // (uniform: no pose adjoint wanted)
     const float m = hit ? gd : 0.0f;
     float acc[REND_PART] = {hit ? m * (p.x - t0) : 0.0f, hit ? m * (p.y - t1) : 0.0f, hit ? m * (p.z - t2) : 0.0f, m};
-    __shared__ float sm[REND_T / 64][REND_PART];
-    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-#pragma unroll
-    for (int i = 0; i < REND_PART; ++i) {
-        const float s = wave_sum(acc[i]);
-        if (lane == 0) sm[wid][i] = s;
-    }
-    __syncthreads();
-    if (threadIdx.x < REND_PART)
-        part[((int64_t)b * gridDim.x + blockIdx.x) * REND_PART + threadIdx.x] =
-            ((sm[0][threadIdx.x] + sm[1][threadIdx.x]) + sm[2][threadIdx.x]) + sm[3][threadIdx.x];
+    block_row<REND_PART, REND_T / kWave>(acc, [&](unsigned n) { return &part[((int64_t)b * gridDim.x + blockIdx.x) * REND_PART + n]; });
 }
 
 // one block per b: the per-block partials added up in a fixed order, all 16 entries of g_poses[b] written
 __global__ __launch_bounds__(REND_T) void render_bwd_final_k(const float *__restrict__ part, int nblocks,
                                                              const float *__restrict__ poses, float *__restrict__ g_poses) {
-    __shared__ float stage[REND_PART][REND_T / REND_PART];
     __shared__ float tot[REND_PART];
     const int b = blockIdx.x;
-    const int k = threadIdx.x & (REND_PART - 1), g = threadIdx.x / REND_PART;  // 64 groups
-    float v = 0.0f;
-    for (int i = g; i < nblocks; i += REND_T / REND_PART) v += part[((int64_t)b * nblocks + i) * REND_PART + k];
-    stage[k][g] = v;
-    __syncthreads();
-    if (threadIdx.x < REND_PART) {
-        float t = 0.0f;
-        for (int q = 0; q < REND_T / REND_PART; ++q) t += stage[threadIdx.x][q];
-        tot[threadIdx.x] = t;
-    }
-    __syncthreads();
+    fold_rows<REND_PART, REND_T / REND_PART, REND_PART>(part + (int64_t)b * nblocks * REND_PART, nblocks, REND_PART, tot);
     if (threadIdx.x < 16) {
         const int i = threadIdx.x >> 2, j = threadIdx.x & 3;
         float out = 0.0f;

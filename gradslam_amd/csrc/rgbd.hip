@@ -56,8 +56,8 @@ __global__ __launch_bounds__(256) void rgbd_down_k(const float2 *__restrict__ in
 }
 
 // ------------------------------------------------------------------ L: linearise
-// The block's 29 sums -> partials[blockIdx.x], in block_reduce_store's geometry and order of magnitude (six pairwise steps in
-// the wave, then the waves in order), but as a TRANSPOSING butterfly: at step s a lane keeps one half of its values and hands
+// The block's 29 sums -> partials[blockIdx.x], in the geometry of linearize_k's block row (icp.hip, gs_rowsum.hpp) and its
+// order of magnitude (six pairwise steps in the wave, then the waves in order), but as a TRANSPOSING butterfly: at step s a lane keeps one half of its values and hands
 // the other half to its partner (the lane 2^s away), so the 32 (29 + 3 zeros) values per lane halve at every step -- 31
 // exchanges per lane instead of 29 x 6 -- and steps 0 .. 3 are DPP moves in the vector pipeline (quad permutes, rotations of
 // the 16-lane row), not LDS permutes: at one source pixel per lane the permutes of 29 plain butterflies were the kernel's whole

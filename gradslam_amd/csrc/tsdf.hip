@@ -223,7 +223,7 @@ __global__ __launch_bounds__(TSDF_T) void tsdf_bwd_k(TsdfVol vol, TsdfFrames fr,
         __syncthreads();
         if ((int)threadIdx.x < 4 * fr.Lc) {
             const int l = threadIdx.x >> 2, n = threadIdx.x & 3;
-            psum[(((int64_t)b * fr.Lc + l) * gridDim.x + blockIdx.x) * 4 + n] = tsdf_pose_block<4>(red + l * TSDF_WAVES * 4, n);
+            psum[(((int64_t)b * fr.Lc + l) * gridDim.x + blockIdx.x) * 4 + n] = block_row_sum<4, TSDF_WAVES>(red + l * TSDF_WAVES * 4, n);
         }
     }
 }
@@ -253,15 +253,15 @@ __global__ __launch_bounds__(TSDF_T) void tsdf_fold_finish_k(Fold fold, int lg, 
 // every other entry 0.
 __global__ __launch_bounds__(TSDF_POSE_T) void tsdf_pose_finish_k(const float *__restrict__ psum, int nrow, const float *__restrict__ poses,
                                                                   int L, int l0, int Lc, float *__restrict__ g_poses) {
-    __shared__ float sm[TSDF_POSE_T + 16];
+    __shared__ float S[4];
     const int b = blockIdx.y, l = blockIdx.x;
-    tsdf_pose_rows<4>(psum + ((int64_t)b * Lc + l) * nrow * 4, nrow, sm);
+    fold_rows<4, TSDF_POSE_GROUPS, 16>(psum + ((int64_t)b * Lc + l) * nrow * 4, nrow, 4, S);
     if (threadIdx.x < 16) {
         const int64_t cam = (int64_t)b * L + l0 + l;
         const int i = threadIdx.x >> 2, j = threadIdx.x & 3;
         float r = 0.0f;
-        if (i < 3 && j == 2) r = -sm[TSDF_POSE_T + 1 + i];
-        if (i < 3 && j == 3) r = poses[cam * 16 + 4 * i + 2] * sm[TSDF_POSE_T];
+        if (i < 3 && j == 2) r = -S[1 + i];
+        if (i < 3 && j == 3) r = poses[cam * 16 + 4 * i + 2] * S[0];
         g_poses[cam * 16 + threadIdx.x] = r;
     }
 }
@@ -619,19 +619,19 @@ __global__ __launch_bounds__(TSDF_T) void tsdf_raycast_bwd_k(TsdfVol vol, TsdfCa
         tsdf_pose_wave<12>(ps, hit, red);
         __syncthreads();
         if (threadIdx.x < 12)
-            psum[((((int64_t)b * cast.L + l) * gridDim.x) + blockIdx.x) * 12 + threadIdx.x] = tsdf_pose_block<12>(red, threadIdx.x);
+            psum[((((int64_t)b * cast.L + l) * gridDim.x) + blockIdx.x) * 12 + threadIdx.x] = block_row_sum<12, TSDF_WAVES>(red, threadIdx.x);
     }
 }
 
 // The pose adjoint of every camera from its blocks' rows.  grid (x: frame, y: batch element), TSDF_POSE_T threads.  Sum 3 i + j
 // is entry [i][j] of the rotation, sum 9 + i entry [i][3]; row 3 is zero.
 __global__ __launch_bounds__(TSDF_POSE_T) void tsdf_cast_pose_finish_k(const float *__restrict__ psum, int nrow, float *__restrict__ g_poses) {
-    __shared__ float sm[TSDF_POSE_T + 16];
+    __shared__ float S[12];
     const int64_t cam = (int64_t)blockIdx.y * gridDim.x + blockIdx.x;
-    tsdf_pose_rows<12>(psum + cam * nrow * 12, nrow, sm);
+    fold_rows<12, TSDF_POSE_GROUPS, 16>(psum + cam * nrow * 12, nrow, 12, S);
     if (threadIdx.x < 16) {
         const int i = threadIdx.x >> 2, j = threadIdx.x & 3;
-        g_poses[cam * 16 + threadIdx.x] = i == 3 ? 0.0f : sm[TSDF_POSE_T + (j == 3 ? 9 + i : 3 * i + j)];
+        g_poses[cam * 16 + threadIdx.x] = i == 3 ? 0.0f : S[j == 3 ? 9 + i : 3 * i + j];
     }
 }
 

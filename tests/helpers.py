@@ -23,6 +23,38 @@ def rel_err(a, b):
     return float((a - b).abs().max() / b.abs().max().clamp_min(1e-30))
 
 
+# ------------------------------------------------------------------ the fixed-order fp32 sums (gs_rowsum.hpp), restated
+def block_rows_f32(terms, waves):
+    """terms (nblocks, waves, 64 lanes, N) float32 -> (nblocks, N): the butterfly (offsets 32 .. 1), then the waves in order
+    starting from wave 0's sum."""
+    x = terms
+    assert x.dtype == np.float32 and x.shape[1:3] == (waves, 64)
+    for half in (32, 16, 8, 4, 2, 1):
+        x = x[:, :, :half] + x[:, :, half:2 * half]
+    x = x[:, :, 0]
+    out = x[:, 0]
+    for w in range(1, waves):
+        out = out + x[:, w]
+    assert out.dtype == np.float32
+    return out
+
+
+def fold_rows_f32(rows, groups):
+    """rows (nrow, N) float32 -> (N,): rows g, g + groups, .. in ascending order onto +0, then the partial sums g = 0, 1, ..
+    in ascending order (onto +0: the first of them is never -0)."""
+    nrow, N = rows.shape
+    pad = -nrow % groups
+    x = np.concatenate([rows, np.zeros((pad, N), np.float32)]).reshape(-1, groups, N)
+    acc = np.zeros((groups, N), np.float32)
+    for it in range(x.shape[0]):
+        acc = acc + x[it]
+    t = acc[0]
+    for g in range(1, groups):
+        t = t + acc[g]
+    assert t.dtype == np.float32
+    return t
+
+
 # ------------------------------------------------------------------ exact sums of fp32 values (the references of the folds)
 def f32_to_int(bits):
     """fp32 bit patterns (finite) -> Python integers in units of 2^-149 (exact)."""

@@ -6,8 +6,8 @@ work, and the Python front refuses CPU tensors and malformed arguments.
 GPU part: the z-buffer against exact statements of its rules.  A frame's own cloud rendered into the frame's camera gives the
 frame back; copies of a cloud at half the distance win every pixel and equal depths go to the smaller row (both exact in
 fp32); a general view is compared bit for bit with a restatement of the key in fp32 (fused steps through oracle.icp_step.fma32);
-rows beyond the count, image borders and empty maps; and the reverse pass against a float64 restatement gathered by the
-kernel's own index image."""
+rows beyond the count, image borders and empty maps; the reverse pass against a float64 restatement gathered by the
+kernel's own index image; and the pose adjoint bit for bit against the stated order of summation (tests/helpers.py)."""
 import ctypes
 
 import numpy as np
@@ -19,6 +19,7 @@ from gradslam_amd import _native as nv
 from gradslam_amd import ops
 from gradslam_amd.structures.utils import pointclouds_from_rgbdimages, rgbdimages_from_pointclouds
 from gradslam_amd.synthetic import make_sequence
+from tests.helpers import block_rows_f32, fold_rows_f32
 
 DEV = "cuda:0"
 U = 2.0 ** -24  # unit roundoff of fp32
@@ -469,6 +470,62 @@ def test_gradients_against_a_float64_restatement(dev, scene3):
             nv.ptr(gd_d), None, None, None, nv.ptr(o_p), None, None, nv.ptr(o_T), nv.ptr(ws), ws.numel(), nv.stream())
     assert torch.equal(o_T.view(1, 4, 4).cpu(), gT) and bool(torch.isfinite(o_p).all())
     assert torch.equal(o_p[0].cpu()[n], (g_depth.reshape(-1)[hit][:, None] * T[:3, 2].float()[None, :]))
+
+
+def _pose_sums_restated(terms, groups):
+    """terms (H * W, 4) float32 of one batch element -> the four pose sums in the reverse pass's order (gs_rowsum.hpp):
+    thread = pixel, 256 consecutive pixels per block, 4 waves; then the fold of the blocks' rows by `groups` groups."""
+    pad = -len(terms) % 256
+    blocks = np.concatenate([terms, np.zeros((pad, 4), np.float32)]).reshape(-1, 4, 64, 4)
+    return fold_rows_f32(block_rows_f32(blocks, 4), groups)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("B,H,W", [(1, 5, 7), (1, 64, 256), (2, 120, 160)])
+def test_pose_adjoint_bits_follow_the_stated_order_of_summation(dev, B, H, W):
+    """gs_render_map_backward's g_poses, bit for bit, against the numpy restatement of the fixed-order sum (tests/helpers.py)
+    on a frame's own cloud: 5 x 7 is one partial block; 64 x 256 exactly 64 blocks, one row per group of the fold; 120 x 160
+    with B = 2 is 75 blocks, so groups 0 .. 10 fold two rows, and the batch stride of the rows.  g_depth spans six decades, so
+    that the order shows: folding by 32 groups instead of 64 gives other bits (asserted before any device work)."""
+    seq = make_sequence(B, 3, H, W)
+    rng = np.random.RandomState(H * W + B)
+    g_depth = (rng.randn(B, H, W) * 10.0 ** rng.uniform(-3, 3, (B, H, W))).astype(np.float32)
+    if (H, W) == (120, 160):
+        valid = (seq[1][:, 2, :, :, 0] > 0).numpy()
+        for b in range(B):
+            m = np.where(valid[b], g_depth[b], np.float32(0.0)).reshape(-1, 1).repeat(4, 1)  # the fourth term, on the frame's valid pixels
+            assert _pose_sums_restated(m, 32)[3].tobytes() != _pose_sums_restated(m, 64)[3].tobytes()
+    fr = _frame(seq, 2, dev)
+    pc = pointclouds_from_rgbdimages(fr)
+    pts, counts = pc.points_padded.contiguous(), pc._counts_i32()
+    pose, K = fr.poses[:, 0].contiguous(), fr.intrinsics[:, 0].contiguous()
+    index = ops.render_map_raw(pts, pc.normals_padded, pc.colors_padded, counts, pose, K, H, W)[0]
+    N = pts.shape[1]
+    o_p, o_T = torch.full((B, N, 3), float("nan"), device=dev), torch.full((B, 16), float("nan"), device=dev)
+    ws = torch.full((nv.ws_bytes("gs_render_map_backward_ws_bytes", B, H, W),), 0xFF, dtype=torch.uint8, device=dev)
+    gd_d = torch.from_numpy(g_depth).to(dev)
+    nv.call("gs_render_map_backward", nv.ptr(pts), nv.ptr(counts), B, N, nv.ptr(pose), H, W, nv.ptr(index), nv.ptr(gd_d), None, None, None,
+            nv.ptr(o_p), None, None, nv.ptr(o_T), nv.ptr(ws), ws.numel(), nv.stream())
+    got = o_T.cpu().numpy().reshape(B, 4, 4)
+    idx, P, T = index.cpu().numpy().reshape(B, -1), pts.cpu().numpy(), pose.cpu().numpy()
+    assert P.dtype == np.float32 and T.dtype == np.float32
+    for b in range(B):
+        hit = idx[b] >= 0
+        assert hit.any() and (idx[b][hit] < int(counts[b])).all()
+        p, zero = P[b][np.where(hit, idx[b], 0)], np.float32(0.0)
+        m = np.where(hit, g_depth[b].reshape(-1), zero)
+        # render_bwd_pix_k's four terms: m * (p_j - t_j) with two roundings (no fused multiply-add), then m; zeros where no row won
+        terms = np.stack([np.where(hit, m * (p[:, j] - T[b, j, 3]), zero) for j in range(3)] + [m], -1)
+        assert terms.dtype == np.float32
+        S = _pose_sums_restated(terms, 64)
+        want = np.zeros((4, 4), np.float32)
+        want[:3, 2] = S[:3]
+        want[:3, 3] = (-T[b, :3, 2]) * S[3]
+        assert (S != 0).all()
+        if H * W > 64 * 256:
+            assert _pose_sums_restated(terms, 32).tobytes() != S.tobytes()
+        print("render pose adjoint %dx%d b=%d: %d of %d pixels hit\n" % (H, W, b, int(hit.sum()), H * W), got[b], "\n", want)
+        assert got[b].tobytes() == want.tobytes()
 
 
 @pytest.mark.gpu

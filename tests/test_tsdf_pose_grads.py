@@ -29,6 +29,7 @@ from gradslam_amd.synthetic import make_intrinsics, make_sequence
 from tests import test_kinectfusion as tk
 from tests import test_tsdf as tt
 from tests import test_tsdf_raycast as tr
+from tests.helpers import block_rows_f32, fold_rows_f32
 from tests.test_tsdf import ref_centres, ref_integrate, small_cpu_scene, torch_integrate
 from tests.test_tsdf_raycast import POSES, STEPS, host_volume, ref_cast, reference, torch_cast
 
@@ -59,34 +60,7 @@ def make_K20():
     return K
 
 
-# ------------------------------------------------------------------ the reduction, as the header states it
-def block_rows_f32(terms):
-    """terms (nblocks, 4 waves, 64 lanes, N) float32 -> (nblocks, N): the butterfly (offsets 32 .. 1), then the waves in order."""
-    x = terms
-    assert x.dtype == F32 and x.shape[1:3] == (4, 64)
-    for half in (32, 16, 8, 4, 2, 1):
-        x = x[:, :, :half] + x[:, :, half:2 * half]
-    x = x[:, :, 0]
-    out = ((x[:, 0] + x[:, 1]) + x[:, 2]) + x[:, 3]
-    assert out.dtype == F32
-    return out
-
-
-def fold_rows_f32(rows):
-    """rows (nrow, N) float32 -> (N,): rows r, r + 64, .. in ascending order onto +0, then the 64 partial sums in order."""
-    nrow, N = rows.shape
-    pad = -nrow % 64
-    x = np.concatenate([rows, np.zeros((pad, N), F32)]).reshape(-1, 64, N)
-    acc = np.zeros((64, N), F32)
-    for it in range(x.shape[0]):
-        acc = acc + x[it]
-    t = acc[0]
-    for r in range(1, 64):
-        t = t + acc[r]
-    assert t.dtype == F32
-    return t
-
-
+# ------------------------------------------------------------------ the reduction, as the header states it (tests/helpers.py)
 def voxel_blocks(terms):
     """(nvox, N) per-voxel terms -> (nblocks, 4, 64, N): thread = voxel, 256 consecutive voxels per block."""
     n, N = terms.shape
@@ -146,7 +120,7 @@ def integrate_pose_f32(rec, cent, P, g_f, trunc):
         g = np.where(upd, g * keep, g)
         terms = np.stack([gd, gd * (c[:, 0] - P[l, 0, 3]), gd * (c[:, 1] - P[l, 1, 3]), gd * (c[:, 2] - P[l, 2, 3])], -1)
         assert terms.dtype == F32 and g.dtype == F32
-        S = fold_rows_f32(block_rows_f32(voxel_blocks(terms)))
+        S = fold_rows_f32(block_rows_f32(voxel_blocks(terms), 4), 64)
         out[l, :3, 2] = -S[1:]
         out[l, :3, 3] = P[l, :3, 2] * S[0]
     return out
@@ -263,7 +237,7 @@ def ref_cast_pose_backward(vol, rec, K, Ho, Wo, stride, g_depth, g_rgb, absolute
 
 def cast_pose_f32(vol, rec, K, Ho, Wo, stride, g_depth, g_rgb):
     t = cast_pose_terms(vol, rec, K, Ho, Wo, stride, g_depth, g_rgb, F32)
-    return sums_to_pose(fold_rows_f32(block_rows_f32(pixel_blocks(t, Ho, Wo))))
+    return sums_to_pose(fold_rows_f32(block_rows_f32(pixel_blocks(t, Ho, Wo), 4), 64))
 
 
 @lru_cache(maxsize=None)

@@ -1040,8 +1040,11 @@ def _voxel_index_args(x, voxel_of, voxel_count, M_max, op):
 
 
 def voxel_reduce_raw(x, counts_i32, voxel_of, n_voxels, voxel_count, M_max, mode=VOXEL_MEAN):
-    """x (B,N,C) -> (B,M_max,C): per voxel the exact sum of its members rounded once to fp32 (mode 0) or that value divided by
-    the member count (mode 1); rows beyond n_voxels are zero.  Same bits whatever the order of the rows."""
+    """x (B,N,C) -> (B,M_max,C): per voxel the sum of its members by the fold of gs_fixed128.hpp, rounded once to fp32 (mode 0),
+    or that value divided by the member count (mode 1); rows beyond n_voxels are zero.  Same bits whatever the order of the
+    rows.  The sum is exact while all terms of the call (every batch element, every channel) lie within 102 - ceil(log2 N)
+    binary places of the call's largest finite |x|; what lies below that is truncated toward zero, term by term.  A NaN or
+    infinite member gives its sum what a float sum gives and does not count towards the largest."""
     x, counts = _voxel_rows(x, counts_i32, "voxel_reduce")
     voxel_of, voxel_count = _voxel_index_args(x, voxel_of, voxel_count, M_max, "voxel_reduce")
     require_hip(n_voxels, op="voxel_reduce")
@@ -1084,7 +1087,8 @@ class _VoxelReduceFn(torch.autograd.Function):
 
 
 def voxel_reduce(x, counts_i32, voxel_of, n_voxels, voxel_count, M_max, mean=True):
-    """Autograd-aware voxel_reduce_raw over the assignment of `voxel_assign`: (B,N,C) -> (B,M_max,C), gradients reach x."""
+    """Autograd-aware voxel_reduce_raw over the assignment of `voxel_assign`: (B,N,C) -> (B,M_max,C), gradients reach x.
+    (Exact under voxel_reduce_raw's condition: all terms of the call within 102 - ceil(log2 N) binary places of its largest.)"""
     return _VoxelReduceFn.apply(x, counts_i32, voxel_of, n_voxels, voxel_count, int(M_max), VOXEL_MEAN if mean else VOXEL_SUM)
 
 
@@ -1122,7 +1126,9 @@ def knn_unpack(keys: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
 
 def knn_backward_raw(src, tgt, src_counts, tgt_counts, keys, g_d2):
     """Adjoint of knn's distances: g_d2 (B,Ns,K) -> (g_src (B,Ns,3), g_tgt (B,Nt,3)), both fully written; the keys are constants.
-    g_src is the fp32 sum in slot order, g_tgt the exact sum rounded once: one path, the same bits from run to run."""
+    g_src is the fp32 sum in slot order, g_tgt the fold of gs_fixed128.hpp rounded once: one path, the same bits from run to
+    run.  The fold is exact while all terms of the call lie within 102 - lg binary places of the call's largest (2^lg: the
+    most terms one sum can have); what lies below that is truncated toward zero, term by term."""
     require_hip(keys, g_d2, op="knn_backward")
     if keys.ndim != 3 or keys.dtype != torch.int64:
         raise ValueError("knn_backward: keys should be (B, Ns, K) int64. Got {} of {}.".format(tuple(keys.shape), keys.dtype))
@@ -1342,7 +1348,9 @@ def _tsdf_integrate_backward(op, with_poses, want_state, want_frames, depth, K, 
 def tsdf_integrate_backward_raw(depth, K, poses, weight, origin, voxel_size, trunc, max_weight, g_tsdf, g_color=None):
     """Adjoint of tsdf_integrate_raw: the adjoints g_tsdf (B,nz,ny,nx) / g_color (B,nz,ny,nx,3 or None) of the new state ->
     (g_tsdf_in, g_color_in, g_depth (B,L,H,W), g_rgb (B,L,H,W,3)); `weight` is the weight BEFORE the integration.  The pixel sums
-    are exact and rounded once: the same bits from run to run (one path, with or without torch.use_deterministic_algorithms)."""
+    are the fold of gs_fixed128.hpp, rounded once: the same bits from run to run (one path, with or without
+    torch.use_deterministic_algorithms); exact while all terms of the call lie within 102 - lg binary places of the call's
+    largest (2^lg: the most terms one sum can have), truncated toward zero below that."""
     return _tsdf_integrate_backward("tsdf_integrate_backward", False, True, True, depth, K, poses, weight, origin, voxel_size, trunc,
                                     max_weight, g_tsdf, g_color)[:4]
 
@@ -1600,8 +1608,10 @@ def _tsdf_raycast_backward(op, with_poses, want_volume, tsdf, weight, color, ori
 def tsdf_raycast_backward_raw(tsdf, weight, color, origin, voxel_size, K, poses, height: int, width: int, stride, step, min_weight,
                               k_end, g_depth=None, g_rgb=None):
     """Adjoint of tsdf_raycast_raw for the tape k_end (a constant): g_depth (B,L,Ho,Wo), g_rgb (B,L,Ho,Wo,3) (None: zero) ->
-    (g_tsdf, g_color or None), written in full.  Every voxel's sum over its pixels is exact and rounded once: the same bits from
-    run to run (one path, with or without torch.use_deterministic_algorithms).  Poses, intrinsics and weights get no gradient."""
+    (g_tsdf, g_color or None), written in full.  Every voxel's sum over its pixels is the fold of gs_fixed128.hpp, rounded once:
+    the same bits from run to run (one path, with or without torch.use_deterministic_algorithms); exact while all terms of the
+    call lie within 102 - lg binary places of the call's largest (2^lg: the most terms one sum can have), truncated toward zero
+    below that.  Poses, intrinsics and weights get no gradient."""
     return _tsdf_raycast_backward("tsdf_raycast_backward", False, True, tsdf, weight, color, origin, voxel_size, K, poses, height, width,
                                   stride, step, min_weight, k_end, g_depth, g_rgb)[:2]
 

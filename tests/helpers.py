@@ -67,15 +67,14 @@ def f32_to_int(bits):
 
 
 def int_to_f32(t, unit=-149):
-    """A Python integer in units of 2^unit (default 2^-149) -> the nearest fp32 (ties to even), rounded once.  (Other units: for
-    results that are normal numbers only.)"""
+    """A Python integer in units of 2^unit (default 2^-149) -> the nearest fp32 (ties to even), rounded once: to 24 bits, or
+    to the subnormal quantum 2^-149 where that is coarser."""
     if t == 0:
         return np.float32(0.0)
     a = abs(t)
     nb = a.bit_length()
-    mant, sh = a, 0
-    if nb > 24:
-        sh = nb - 24
+    mant, sh = a, max(nb - 24, -149 - unit, 0)
+    if sh > 0:
         mant = a >> sh
         rem, half = a & ((1 << sh) - 1), 1 << (sh - 1)
         if rem > half or (rem == half and (mant & 1)):
@@ -95,3 +94,41 @@ def exact_sum_f32(values):
             return np.float32(np.nan)
         return np.float32(np.inf if np.isposinf(bad).any() else -np.inf)
     return int_to_f32(sum(f32_to_int(values.view(np.uint32))))
+
+
+# ------------------------------------------------------------------ the exact fold's rule (gs_fixed128.hpp), restated
+def _finite_max_bits(call_terms):
+    """The float bits of the largest finite |x| of a call's terms (0 for none)."""
+    u = np.asarray(call_terms, dtype=np.float32).ravel().view(np.uint32) & np.uint32(0x7FFFFFFF)
+    u = u[u < 0x7F800000]
+    return int(u.max()) if u.size else 0
+
+
+def fold_rule_int(values, lg, call_terms=None):
+    """The fold's 128-bit sum of finite fp32 `values` as a Python integer, and its scale -> (total, E): total 2^-E is the sum
+    of the terms, each truncated toward zero to a multiple of 2^-E.  E = 252 - eb - lg with eb the biased exponent (at least 1)
+    of the largest finite |x| of `call_terms` (the maximum itself, or all terms of the call; default: `values`)."""
+    values = np.asarray(values, dtype=np.float32).ravel()
+    assert np.isfinite(values).all()
+    eb = max(_finite_max_bits(values if call_terms is None else call_terms) >> 23, 1)
+    E = 252 - eb - int(lg)
+    total = 0
+    for b in values.view(np.uint32).tolist():
+        e, m = (b >> 23) & 0xFF, b & 0x7FFFFF
+        mant = (m | 0x800000) if e else m
+        s = max(e, 1) - 150 + E  # x = mant 2^(s - E)
+        u = mant << s if s >= 0 else mant >> -s
+        total += -u if b >> 31 else u
+    return total, E
+
+
+def fold_rule_f32(values, lg, call_terms=None):
+    """What the exact fold gives for one sum of fp32 `values` with at most 2^lg terms per sum: non-finite members give what
+    exact_sum_f32 gives; otherwise every term is truncated toward zero to a multiple of 2^-E (fold_rule_int: E follows from the
+    largest finite |x| of the whole CALL, `call_terms`), the integers are added exactly and the sum is rounded once to fp32,
+    ties to even.  Equal to exact_sum_f32 while every term of the call lies within 102 - lg binary places of the largest."""
+    values = np.asarray(values, dtype=np.float32).ravel()
+    if not np.isfinite(values).all():
+        return exact_sum_f32(values)
+    total, E = fold_rule_int(values, lg, call_terms)
+    return int_to_f32(total, unit=-E)

@@ -64,4 +64,52 @@ __device__ __forceinline__ void fold_rows(const float *__restrict__ rows, int nr
     __syncthreads();
 }
 
+// ------------------------------------------------------------------ the transposing butterfly (rgbd.hip, sdf.hip)
+// A block's N <= 32 sums when every LANE brings N terms of its own (one pixel per lane): the geometry of steps 1 and 2 and
+// their order of magnitude (six pairwise steps in the wave, then the waves in order), but as a TRANSPOSING butterfly: at step s a lane keeps one half of its values and hands
+// the other half to its partner (the lane 2^s away), so the 32 (N + zeros) values per lane halve at every step -- 31
+// exchanges per lane instead of N x 6 -- and steps 0 .. 3 are DPP moves in the vector pipeline (quad permutes, rotations of
+// the 16-lane row), not LDS permutes: at one source pixel per lane the permutes of 29 plain butterflies were the kernel's whole
+// time (16 us at 480 x 640).  Partners: lane ^ 1, lane ^ 2, the lane 4 further round its row (same low bits, bit 2 flipped),
+// lane ^ 8, lane ^ 16, lane ^ 32.  Value k ends in the lanes whose low five bits are k's bits reversed.  Every addition is
+// keep + received, in a fixed order: the same bits from run to run.
+template <int CTRL>
+__device__ __forceinline__ float rowsum_dpp(float v) {
+    return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xF, 0xF, false));
+}
+template <int N, int CTRL>
+__device__ __forceinline__ void rowsum_fold_dpp(float (&a)[32], bool up) {  // N values -> N / 2; `up` lanes keep the upper half
+#pragma unroll
+    for (int j = 0; j < N / 2; ++j) {
+        const float send = up ? a[j] : a[j + N / 2], keep = up ? a[j + N / 2] : a[j];
+        a[j] = keep + rowsum_dpp<CTRL>(send);
+    }
+}
+// a[0 .. N) the lane's terms, a[N .. 32) zeros -> partials[blockIdx.x * N + n], the block's row; all WAVES waves arrive
+template <int N, int WAVES>
+__device__ __forceinline__ void block_row_transposed(float (&a)[32], float *__restrict__ partials) {
+    static_assert(N <= 32, "one value per lane of half a wave");
+    __shared__ float sm[WAVES][32];
+    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+    rowsum_fold_dpp<32, 0xB1>(a, lane & 1);    // quad_perm [1, 0, 3, 2]
+    rowsum_fold_dpp<16, 0x4E>(a, lane & 2);    // quad_perm [2, 3, 0, 1]
+    rowsum_fold_dpp<8, 0x124>(a, lane & 4);    // row_ror 4
+    rowsum_fold_dpp<4, 0x128>(a, lane & 8);    // row_ror 8
+    {
+        const bool up = lane & 16;
+        const float send = up ? a[0] : a[1], keep = up ? a[1] : a[0];
+        a[0] = keep + __shfl_xor(send, 16, kWave);
+    }
+    a[0] = a[0] + __shfl_xor(a[0], 32, kWave);
+    const int k = ((lane & 1) << 4) | ((lane & 2) << 2) | (lane & 4) | ((lane & 8) >> 2) | ((lane & 16) >> 4);
+    if (lane < 32) sm[wid][k] = a[0];
+    __syncthreads();
+    if (threadIdx.x < N) {
+        float v = 0.0f;
+#pragma unroll
+        for (int w = 0; w < WAVES; ++w) v += sm[w][threadIdx.x];
+        partials[blockIdx.x * N + threadIdx.x] = v;
+    }
+}
+
 }  // namespace gs

@@ -19,6 +19,7 @@
 
 #include "gs_icp_step.hpp"  // solve6, se3_exp_dev; it brings gs_icp_reduce.hpp
 #include "gs_rgbd_pixel.hpp"
+#include "gs_rowsum.hpp"  // block_row_transposed
 
 namespace gs {
 
@@ -56,50 +57,8 @@ __global__ __launch_bounds__(256) void rgbd_down_k(const float2 *__restrict__ in
 }
 
 // ------------------------------------------------------------------ L: linearise
-// The block's 29 sums -> partials[blockIdx.x], in the geometry of linearize_k's block row (icp.hip, gs_rowsum.hpp) and its
-// order of magnitude (six pairwise steps in the wave, then the waves in order), but as a TRANSPOSING butterfly: at step s a lane keeps one half of its values and hands
-// the other half to its partner (the lane 2^s away), so the 32 (29 + 3 zeros) values per lane halve at every step -- 31
-// exchanges per lane instead of 29 x 6 -- and steps 0 .. 3 are DPP moves in the vector pipeline (quad permutes, rotations of
-// the 16-lane row), not LDS permutes: at one source pixel per lane the permutes of 29 plain butterflies were the kernel's whole
-// time (16 us at 480 x 640).  Partners: lane ^ 1, lane ^ 2, the lane 4 further round its row (same low bits, bit 2 flipped),
-// lane ^ 8, lane ^ 16, lane ^ 32.  Value k ends in the lanes whose low five bits are k's bits reversed.  Every addition is
-// keep + received, in a fixed order: the same bits from run to run.
-template <int CTRL>
-__device__ __forceinline__ float rgbd_dpp(float v) {
-    return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xF, 0xF, false));
-}
-template <int N, int CTRL>
-__device__ __forceinline__ void rgbd_fold_dpp(float (&a)[32], bool up) {  // N values -> N / 2; `up` lanes keep the upper half
-#pragma unroll
-    for (int j = 0; j < N / 2; ++j) {
-        const float send = up ? a[j] : a[j + N / 2], keep = up ? a[j + N / 2] : a[j];
-        a[j] = keep + rgbd_dpp<CTRL>(send);
-    }
-}
-__device__ __forceinline__ void rgbd_block_reduce_store(float (&a)[32], float *__restrict__ partials) {
-    __shared__ float sm[RGBD_T / 64][32];
-    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-    rgbd_fold_dpp<32, 0xB1>(a, lane & 1);    // quad_perm [1, 0, 3, 2]
-    rgbd_fold_dpp<16, 0x4E>(a, lane & 2);    // quad_perm [2, 3, 0, 1]
-    rgbd_fold_dpp<8, 0x124>(a, lane & 4);    // row_ror 4
-    rgbd_fold_dpp<4, 0x128>(a, lane & 8);    // row_ror 8
-    {
-        const bool up = lane & 16;
-        const float send = up ? a[0] : a[1], keep = up ? a[1] : a[0];
-        a[0] = keep + __shfl_xor(send, 16, kWave);
-    }
-    a[0] = a[0] + __shfl_xor(a[0], 32, kWave);
-    const int k = ((lane & 1) << 4) | ((lane & 2) << 2) | (lane & 4) | ((lane & 8) >> 2) | ((lane & 16) >> 4);
-    if (lane < 32) sm[wid][k] = a[0];
-    __syncthreads();
-    if (threadIdx.x < NACC) {
-        float v = 0.0f;
-#pragma unroll
-        for (int w = 0; w < RGBD_T / 64; ++w) v += sm[w][threadIdx.x];
-        partials[blockIdx.x * NACC + threadIdx.x] = v;
-    }
-}
-
+// The block's 29 sums -> partials[blockIdx.x]: gs_rowsum.hpp's transposing butterfly (block_row_transposed), in the geometry of
+// linearize_k's block row (icp.hip).
 // grid (blocks of RGBD_T source pixels, B).  tgt / src: this level's (B, Hl, Wl) float2 images; K (B, 4, 4) of level 0;
 // T (B, 16).  partials: row blockIdx.x of batch element b at partials + (b * prow + blockIdx.x) * NACC.
 // ROWS: also write the per-pixel valid flag and the 14 floats J_I | r_I | J_D | r_D (zeros where not valid).
@@ -157,7 +116,7 @@ __global__ __launch_bounds__(RGBD_T) void rgbd_linearize_k(const float2 *__restr
     acc[27] = rI * rI + rD * rD;
     acc[28] = ok ? 1.0f : 0.0f;
     acc[29] = 0.0f; acc[30] = 0.0f; acc[31] = 0.0f;
-    rgbd_block_reduce_store(acc, partials + (int64_t)b * prow * NACC);
+    block_row_transposed<NACC, RGBD_T / 64>(acc, partials + (int64_t)b * prow * NACC);
 }
 
 // ------------------------------------------------------------------ X: step

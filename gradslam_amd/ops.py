@@ -1871,3 +1871,88 @@ def rgbd_odometry(tgt_depth, tgt_rgb, src_depth, src_rgb, intrinsics, init=None,
     if attached:
         return _RgbdOdometryFn.apply(td, tc, sd, sc, init, K, numiters, levels, lam, ddm, damp, scale)
     return _rgbd_odometry_call(td, tc, sd, sc, init, K, numiters, levels, lam, ddm, damp, scale, taped=False)[:2]
+
+
+# ------------------------------------------------------------------ SDF odometry (csrc/sdf.hip)
+def _sdf_args(op, depth, intrinsics, poses, tsdf, weight, origin, voxel_size, trunc, min_weight, stride, levels, **transforms):
+    """The checked inputs of sdf_rows_raw / sdf_odometry (the caller requires the HIP device, after its own checks): depth (B,H,W[,1]), intrinsics, poses and the
+    named transforms (B,4,4) or (B,1,4,4), the volume's tsdf / weight (B,nz,ny,nx) and origin -> (tensors to keep alive, named
+    transforms as (B,16) or None, (B, H, W), the C argument lists up to `stride`)."""
+    for name, t in (("depth", depth), ("intrinsics", intrinsics), ("poses", poses), ("tsdf", tsdf), ("weight", weight)):
+        if not torch.is_tensor(t):
+            raise TypeError("{}: expected {} to be a tensor; got {}".format(op, name, type(t)))
+    if depth.ndim == 4 and depth.shape[-1] == 1:
+        depth = depth[..., 0]
+    if depth.ndim != 3 or 0 in depth.shape:
+        raise ValueError("{}: depth should have shape (B, H, W) or (B, H, W, 1). Got {}.".format(op, tuple(depth.shape)))
+    B, H, W = (int(n) for n in depth.shape)
+    K = _rgbd_K(intrinsics, B, op)
+    poses = _rgbd_T(poses, B, "poses", op)
+    named = {n: (None if t is None else _rgbd_T(t, B, n, op)) for n, t in transforms.items()}
+    if tsdf.ndim != 4 or tsdf.shape[0] != B:
+        raise ValueError("{}: tsdf should have shape ({}, nz, ny, nx), the frames' batch size. Got {}.".format(op, B, tuple(tsdf.shape)))
+    _, dims = _tsdf_volume(tsdf, weight, op)
+    v, tr, mw = _positive(voxel_size, "voxel_size", op), _positive(trunc, "trunc", op), _number(min_weight, "min_weight", op)
+    if not isinstance(stride, int) or isinstance(stride, bool) or stride < 1:
+        raise ValueError("{}: stride should be a positive integer. Got {!r}.".format(op, stride))
+    if not isinstance(levels, int) or isinstance(levels, bool) or levels < 1 or levels > 8:
+        raise ValueError("{}: levels should be an integer in [1, 8]. Got {!r}.".format(op, levels))
+    s = stride << (levels - 1)
+    if -(-H // s) < 4 or -(-W // s) < 4:
+        raise ValueError("{}: the coarsest of {} grids of a {} x {} image at stride {} would be smaller than 4 x 4.".format(
+            op, levels, H, W, stride))
+    depth, tsdf, weight = _f32c(depth.detach()), _f32c(tsdf.detach()), _f32c(weight.detach())
+    origin = tsdf_origin(origin, B, tsdf.device, op)
+    keep = (depth, K, poses, tsdf, weight, origin)
+    return keep, named, (B, H, W), (ptr(depth), B, H, W, ptr(K), ptr(poses)), (ptr(tsdf), ptr(weight), *dims, ptr(origin), v, tr, mw, stride)
+
+
+def sdf_rows_raw(depth, intrinsics, poses, D, tsdf, weight, origin, voxel_size, trunc, min_weight: float = 1.0, stride: int = 1):
+    """One level-0 linearisation of the SDF alignment at the world-frame delta D (B,4,4) -> (valid (B,Hs,Ws) int32, rows
+    (B,Hs,Ws,7) = J | r, sums (B,29) = H upper triangle | g | err | cnt) on the [::stride, ::stride] pixel grid.  The seam the
+    tests check."""
+    op = "sdf_rows"
+    keep, named, (B, H, W), frame, volume = _sdf_args(op, depth, intrinsics, poses, tsdf, weight, origin, voxel_size, trunc, min_weight,
+                                                      stride, 1, D=D)
+    if named["D"] is None:
+        raise TypeError("{}: expected D to be a tensor; got {}".format(op, type(D)))
+    require_hip(*keep, named["D"], op=op)
+    dev, Hs, Ws = keep[0].device, -(-H // stride), -(-W // stride)
+    valid = torch.empty((B, Hs, Ws), dtype=torch.int32, device=dev)
+    rows = torch.empty((B, Hs, Ws, 7), dtype=torch.float32, device=dev)
+    sums = torch.empty((B, 29), dtype=torch.float32, device=dev)
+    ws = workspace(ws_bytes("gs_sdf_odometry_ws_size", B, H, W, stride), dev, "sdf")
+    call("gs_sdf_rows", *frame, ptr(named["D"]), *volume, ptr(valid), ptr(rows), ptr(sums), ptr(ws), ws.numel(), stream())
+    return valid, rows, sums
+
+
+def sdf_odometry(depth, intrinsics, poses, tsdf, weight, origin, voxel_size, trunc, init=None, numiters=(10, 5, 3), levels: int = 3,
+                 stride: int = 1, min_weight: float = 1.0, damp: float = 1e-8):
+    """SDF odometry (the rule of include/gradslam_hip.h): the frame depth (B,H,W[,1]) carrying the camera-to-world poses (B,4,4)
+    is aligned directly against the volume tsdf / weight (B,nz,ny,nx) at `origin` -- no ray cast, no cloud -> (T (B,4,4), the
+    WORLD-frame delta: the new pose is compose_transformations(T, poses), the ICP providers' convention; info (B,levels,4) = cnt,
+    err, status bits, iterations per level).  Level l uses the pixel grid [::stride 2^l, ::stride 2^l]; `numiters`: iterations per
+    level, finest first (an int: that count at every level).  No host synchronisation.  No gradients: under autograd, a depth,
+    poses, init or tsdf that requires one is refused rather than cut silently."""
+    op = "sdf_odometry"
+    if torch.is_grad_enabled() and any(torch.is_tensor(t) and t.requires_grad for t in (depth, poses, init, tsdf)):
+        raise NotImplementedError("{}: gradients are not implemented (the reverse pass is not built); detach the inputs or call "
+                                  "under torch.no_grad().".format(op))
+    keep, named, (B, H, W), frame, volume = _sdf_args(op, depth, intrinsics, poses, tsdf, weight, origin, voxel_size, trunc, min_weight,
+                                                      stride, levels, init=init)
+    damp = _number(damp, "damp", op)
+    if not (0.0 <= damp < math.inf):
+        raise ValueError("{}: damp should be finite and not negative. Got {!r}.".format(op, damp))
+    if isinstance(numiters, int) and not isinstance(numiters, bool):
+        numiters = (numiters,) * levels
+    numiters = tuple(numiters)
+    if len(numiters) != levels or any(not isinstance(n, int) or isinstance(n, bool) or n < 0 for n in numiters):
+        raise ValueError("{}: numiters should be {} non-negative integers (finest level first). Got {!r}.".format(op, levels, numiters))
+    require_hip(*keep, named["init"], op=op)
+    dev = keep[0].device
+    out_T = torch.empty((B, 4, 4), dtype=torch.float32, device=dev)
+    info = torch.empty((B, levels, 4), dtype=torch.float32, device=dev)
+    ws = workspace(ws_bytes("gs_sdf_odometry_ws_size", B, H, W, stride), dev, "sdf")
+    counts = (nv.c_i * levels)(*numiters)
+    call("gs_sdf_odometry", *frame, ptr(named["init"]), *volume, levels, counts, damp, ptr(out_T), ptr(info), ptr(ws), ws.numel(), stream())
+    return out_T, info

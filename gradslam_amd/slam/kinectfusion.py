@@ -11,6 +11,7 @@ from ..odometry.gradicp import GradICPOdometryProvider
 from ..odometry.icp import ICPOdometryProvider
 from ..odometry.icputils import downsample_rgbdimages
 from ..odometry.rgbd import RGBDOdometryProvider
+from ..odometry.sdf import SDFOdometryProvider
 from ..structures.rgbdimages import RGBDImages
 from ..structures.tsdfvolume import TSDFVolume
 
@@ -47,7 +48,16 @@ class KinectFusion(nn.Module):
     `pose_gradients=True` the chain pose_{s-1} -> coloured cast -> alignment -> pose_s -> integrate is attached like the ICP
     branch's.  With `odom_gradients=False` (the default) it is as it was: under autograd with inputs that require gradients
     `provide` raises NotImplementedError, whatever `pose_gradients` says.  A camera that sees nothing of the volume, or a frame without valid
-    pixels, leaves the pose where it was and sets the status bit in `odomprov.last_info` (nothing synchronises the host)."""
+    pixels, leaves the pose where it was and sets the status bit in `odomprov.last_info` (nothing synchronises the host).
+
+    `odom="sdf"` tracks the frame directly against the volume's distance field with SDFOdometryProvider (`numiters`, `levels`,
+    `damp`, `min_weight`; `stride = dsratio`, the ICP branch's pixel subset; colour is not needed):
+
+        pose_s = compose_transformations(odomprov.provide(volume, live frame carrying pose_{s-1}), pose_{s-1})
+
+    There is no ray cast, no cloud and no host read.  A camera that sees nothing of the volume leaves the pose where it was and
+    sets the status bit, as `odom="rgbd"` does.  It has no reverse pass: `odom_gradients=True` is refused, and under autograd
+    inputs that require gradients raise NotImplementedError."""
 
     def __init__(self, *, dims, voxel_size, origin=(0.0, 0.0, 0.0), trunc=None, max_weight: float = 128.0, color: bool = True,
                  odom: str = "gradicp", dsratio: int = 4, numiters: int = 20, damp: float = 1e-8,
@@ -56,9 +66,9 @@ class KinectFusion(nn.Module):
                  device: Union[torch.device, str, None] = None, levels: int = 3, lambda_geo: float = 0.968,
                  pose_gradients: bool = False, odom_gradients: bool = False):
         super().__init__()
-        if odom not in ["gt", "icp", "gradicp", "rgbd"]:
+        if odom not in ["gt", "icp", "gradicp", "rgbd", "sdf"]:
             msg = "odometry method ({}) not supported for KinectFusion. ".format(odom)
-            msg += "Currently supported odometry modules for KinectFusion are: 'gt', 'icp', 'gradicp', 'rgbd'"
+            msg += "Currently supported odometry modules for KinectFusion are: 'gt', 'icp', 'gradicp', 'rgbd', 'sdf'"
             raise ValueError(msg)
         if odom == "rgbd" and not color:
             raise ValueError("KinectFusion: odom='rgbd' tracks against the colours of the volume and needs color=True.")
@@ -69,7 +79,8 @@ class KinectFusion(nn.Module):
         if not isinstance(odom_gradients, bool):
             raise TypeError("KinectFusion: odom_gradients should be a bool. Got {!r}.".format(odom_gradients))
         if odom_gradients and odom != "rgbd":
-            raise ValueError("KinectFusion: odom_gradients belongs to odom='rgbd' (the ICP providers always carry gradients).")
+            raise ValueError("KinectFusion: odom_gradients belongs to odom='rgbd' (the ICP providers always carry gradients; "
+                             "odom='sdf' has no reverse pass).")
         odomprov = None
         if odom == "icp":
             odomprov = ICPOdometryProvider(numiters, damp, dist_thresh)
@@ -77,6 +88,8 @@ class KinectFusion(nn.Module):
             odomprov = GradICPOdometryProvider(numiters, damp, dist_thresh, lambda_max, B, B2, nu)
         elif odom == "rgbd":
             odomprov = RGBDOdometryProvider(numiters, levels, lambda_geo, damp=damp, differentiable=odom_gradients)
+        elif odom == "sdf":
+            odomprov = SDFOdometryProvider(numiters, levels, stride=dsratio, min_weight=min_weight, damp=damp)
         self.odom = odom
         self.odomprov = odomprov
         self.dsratio = dsratio
@@ -148,6 +161,10 @@ class KinectFusion(nn.Module):
         if live_frame.channels_first:
             live_frame = live_frame.to_channels_last()
         H, W = live_frame.shape[2:4]
+        if self.odom == "sdf":  # no cast, no cloud, no host read: the frame under the previous pose against the volume itself
+            source = RGBDImages(live_frame.rgb_image, live_frame.depth_image, live_frame.intrinsics, prev_frame.poses)
+            transform = self.odomprov.provide(volume, source)
+            return compose_transformations(transform.squeeze(1), prev_frame.poses.squeeze(1)).unsqueeze(1)
         if self.odom == "rgbd":
             cast = volume.raycast(live_frame.intrinsics, self._volume_poses(prev_frame.poses), H, W, step=self.step_size,
                                   min_weight=self.min_weight)

@@ -1037,6 +1037,51 @@ int gs_rgbd_rows_bwd(const float *tgt_depth, const float *tgt_rgb, const float *
                      float *g_tgt_depth, float *g_tgt_rgb, float *g_src_depth, float *g_src_rgb, float *g_T, void *ws, size_t ws_bytes,
                      gs_stream_t stream);
 
+/* SDF odometry: a frame tracked directly against a TSDF volume (Bylow, Sturm, Kerl, Kahl, Cremers, RSS 2013), by Gauss-Newton
+ * on the sum over the frame's pixels of phi(D P p)^2, phi the volume's interpolated distance: no ray cast, no association, no
+ * cloud.  depth (B,H,W); intrinsics (B,4,4) (fx = K[0], fy = K[5], cx = K[2], cy = K[6]); poses P (B,16 row-major 4x4, camera
+ * to world): the pose the frame carries; the volume tsdf, weight (B,nz,ny,nx), origin (B,3), voxel_size, trunc as for
+ * gs_tsdf_integrate.  D (B,16) is the loop state, a WORLD-frame delta.  IEEE fp32 in the order written, no contraction.
+ *   levels     level l uses the pixels (h, w) = (i s_l, j s_l) of the image, s_l = stride * 2^l: ceil(H / s_l) x ceil(W / s_l)
+ *              of them, row-major.  There is no pyramid: a level only selects pixels.
+ *   point      pixel (h, w) with depth d, used only if 0 < d < inf:  px = d * (((float)w - cx) / fx),
+ *              py = d * (((float)h - cy) / fy),  pw_i = ((P_i0 px + P_i1 py) + P_i2 d) + P_i3,
+ *              q_i = ((D_i0 pw_x + D_i1 pw_y) + D_i2 pw_z) + D_i3.
+ *   sample     the cell of q by the ray cast's rule (per axis g = (q - o) / v - 0.5f, i = floorf(g), a = g - i; inside iff
+ *              0 <= i and i + 1 <= n - 1; a NaN or an infinity is outside); all 8 corner weights >= min_weight; all 8 corner
+ *              values f_c < 1.0f (no corner is clamped free space); f^ the trilinear interpolant (four lerps along x, two along
+ *              y, one along z, lerp(p, q, s) = p + s (q - p)) and g its gradient in voxel units (differences along the axis,
+ *              lerped over the other two, x before y before z).  A pixel that passes every test is valid.
+ *   row        kappa = trunc / voxel_size, formed once;  r = trunc * f^;  n = kappa * g;
+ *              J = (n_x, n_y, n_z, q_y n_z - q_z n_y, q_z n_x - q_x n_z, q_x n_y - q_y n_x)   (xi = [v; omega], d q / d xi = [I | -q^]).
+ *   sums       per valid pixel the 29 terms  J[m] J[n] (m <= n, row-major: 21) | J[m] r (6) | r r | 1.  Blocks of 256
+ *              consecutive pixels of the level's grid, in the order gs_rgbd_odometry documents: six pairwise steps over a
+ *              wave's 64 lanes, the 4 waves added in order; then, per batch element, thread (g, k) of a 1024-thread block adds
+ *              rows g, g + 32, ... of sum k in order, and the 32 group sums are added in order.  No float atomics: the same
+ *              bits from run to run.  H = the 21, g = MINUS the 6.
+ *   step       gs_rgbd_odometry's: cnt < 6: status bit 1, D stays.  Else xi = (H + damp I)^-1 g (damping added in fp32, the
+ *              system solved in fp64), D <- exp(xi) D; xi or the product not finite: status bit 2, D stays.
+ *   loop       from level `levels` - 1 down to 0, numiters[l] iterations at level l (a host array, finest first), from `init`
+ *              (B,16; NULL: the identity).  out_T = D: the new pose is D . P (the ICP providers' convention).  info
+ *              (B, levels, 4) floats as gs_rgbd_odometry's: cnt and err of the level's last linearisation, the status bits of
+ *              the level's iterations or-ed, the iterations run at the level (zeros for a level with none).
+ * Two launches per iteration (linearise, one pixel per lane; step) and one to start; nothing synchronises the host, the loop
+ * state lives in the workspace.  Refused before any device work: NULL pointers, B outside [1, 65535], H W > 2^24,
+ * B H W > 2^30, stride < 1, levels outside [1, 8] or a coarsest grid smaller than 4 x 4, dims not positive or nx ny nz > 2^29,
+ * voxel_size or trunc not finite and positive, min_weight not a number, damp negative or not finite, a count outside
+ * [0, 2^20].  Workspace, every piece rounded up to 256 bytes, with Hs = ceil(H / stride), Ws = ceil(W / stride):
+ *   64 B (D) | 116 B ceil(Hs Ws / 256) (partial rows). */
+size_t gs_sdf_odometry_ws_size(int B, int H, int W, int stride);
+int gs_sdf_odometry(const float *depth, int B, int H, int W, const float *intrinsics, const float *poses, const float *init,
+                    const float *tsdf, const float *weight, int nx, int ny, int nz, const float *origin, float voxel_size, float trunc,
+                    float min_weight, int stride, int levels, const int *numiters, float damp, float *out_T, float *info, void *ws,
+                    size_t ws_bytes, gs_stream_t stream);
+/* One level-0 linearisation at the given D (B,16): valid (B,Hs,Ws) int32, rows (B,Hs,Ws,7) = J | r (zeros where not valid),
+ * sums (B,29) = H upper triangle | g | err | cnt.  The workspace of gs_sdf_odometry_ws_size(B, H, W, stride). */
+int gs_sdf_rows(const float *depth, int B, int H, int W, const float *intrinsics, const float *poses, const float *D, const float *tsdf,
+                const float *weight, int nx, int ny, int nz, const float *origin, float voxel_size, float trunc, float min_weight,
+                int stride, int32_t *valid, float *rows, float *sums, void *ws, size_t ws_bytes, gs_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

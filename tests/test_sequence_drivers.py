@@ -6,7 +6,7 @@ they were before the frame loop was stated once (two copies of the loop, the tap
 import pytest
 import torch
 
-from tests.test_workspace_exact import Watch, deterministic
+from tests.workspace_check import Watch, deterministic
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"

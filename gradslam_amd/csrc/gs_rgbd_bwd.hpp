@@ -1,5 +1,6 @@
 // gs_rgbd_bwd.hpp -- the kernels of the dense RGB-D odometry's reverse pass (the rule: include/gradslam_hip.h).  Included by rgbd.hip,
 // which launches them (rgbd_bwd_run); the pixel's forward values and the pyramid's rules are gs_rgbd_pixel.hpp's, the forward's own code.
+// The tape row's layout (GN_TAPE_*) is gs_gn_step.hpp's, which rgbd.hip includes before this header.
 // Per iteration, last to first:
 // Xb step reverse, one 256-thread block per batch element: the pixel pass before left 12-sum rows -- the adjoint of T_{k+1}
 //    through ITS linearisation -- which are folded (fold_rows) into the carried adjoint; then, one lane, fp64 where the forward's
@@ -52,18 +53,18 @@ __global__ __launch_bounds__(BWD_T) void rgbd_step_bwd_k(float *__restrict__ gTa
     const int b = blockIdx.x;
     fold_rows<12, BWD_GROUPS, 16>(partials12 + (int64_t)b * prow * 12, nblocks, 12, sums);
     if (threadIdx.x != 0) return;
-    const float *rec = rec_all + RGBD_TAPE_WORDS * b;
+    const float *rec = rec_all + GN_TAPE_WORDS * b;
     float *gT = gTall + 16 * b, *A = adj_all + RGBD_ADJ_WORDS * b;
     for (int k = 0; k < 16; ++k) g[k] = k < 12 ? gT[k] + sums[k] : 0.0f;
     for (int k = 0; k < RGBD_ADJ_WORDS; ++k) A[k] = 0.0f;
-    if (rec[RGBD_TAPE_APPLIED] != 0.0f) {
-        for (int k = 0; k < 6; ++k) xi[k] = rec[RGBD_TAPE_XI + k];
+    if (rec[GN_TAPE_APPLIED] != 0.0f) {
+        for (int k = 0; k < 6; ++k) xi[k] = rec[GN_TAPE_XI + k];
         se3_exp_dev(xi, dT);  // the forward's dT, bit for bit
         top3_times_Tt(g, rec, gdT);
         pull_gT(g, dT);
         se3_exp_bwd(xi, gdT, gxi);
         // xi = M^-1 g', M = H + damp I symmetric, g' = MINUS the six sums:  y = M^-1 xi-bar;  H-bar = -y xi^T, g'-bar = y
-        expand44(rec + RGBD_TAPE_SUMS, hg);
+        expand44(rec + GN_TAPE_SUMS, hg);
         for (int k = 0; k < 6; ++k) gx[k] = (float)gxi[k];
         solve6(hg, gx, damp, y, lu_sm);
         int q = 0;

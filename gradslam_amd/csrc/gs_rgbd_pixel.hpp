@@ -4,7 +4,7 @@
 //                 residual).  Both passes run THIS code -- the rule of include/gradslam_hip.h, every fp32 operation in its order --
 //                 so the reverse pass differentiates exactly the pixels the forward pass used.
 //   the pyramid   rgbd_depth_kept (level 0), rgbd_down_select (the 2 x 2 reduction's depth selection).
-//   the tape      the layout of an iteration's tape row, written by rgbd_step_k<true>, read by rgbd_step_bwd_k.
+// (The layout of an iteration's tape row, written by rgbd_step_k<true> and read by rgbd_step_bwd_k, is the step's: gs_gn_step.hpp.)
 #pragma once
 
 #include "gs_icp_reduce.hpp"
@@ -12,10 +12,6 @@
 namespace gs {
 
 constexpr int RGBD_T = LIN_T;  // lanes (= source pixels) per linearise block: linearize_k's geometry (icp.hip)
-
-// An iteration's tape row of batch element b (RGBD_TAPE_WORDS floats at tape + RGBD_TAPE_WORDS b): T before the step (16), the 29
-// sums as reduced (g not yet negated), xi (6), 1 if the step was applied else 0 -- what the reverse pass replays.
-constexpr int RGBD_TAPE_WORDS = 64, RGBD_TAPE_SUMS = 16, RGBD_TAPE_XI = 45, RGBD_TAPE_APPLIED = 51;
 
 struct RgbdCam { float fx, fy, cx, cy; };
 // intrinsics (4 x 4 row-major) at pyramid level `level`: fx, fy halve; cx' = (cx + 0.5) / 2 - 0.5 (pixel centres at integers)

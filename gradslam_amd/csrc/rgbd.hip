@@ -2,7 +2,8 @@
 // (gs_rgbd_odometry, gs_rgbd_rows, gs_rgbd_pyramid) and its reverse pass (gs_rgbd_odometry_taped, gs_rgbd_odometry_bwd,
 // gs_rgbd_rows_bwd).  The rule -- every fp32 operation in order -- is stated in include/gradslam_hip.h above the entry points;
 // the code follows it line by line (the library is built without contraction).  One translation unit, the device code by role:
-//   gs_rgbd_pixel.hpp  what forward and reverse kernels must agree on bit for bit, once: the pixel, the pyramid's rules, the tape row
+//   gs_rgbd_pixel.hpp  what forward and reverse kernels must agree on bit for bit, once: the pixel, the pyramid's rules
+//   gs_gn_step.hpp     what this loop shares with the SDF odometry's (sdf.hip): constants, the tape row's layout, the start-up, host checks
 //   gs_rgbd_bwd.hpp    Xb, Lb, Pb: the kernels of the reverse pass
 //   this file          P, L, X: the forward kernels; every launch, the workspaces and the C entry points
 // P  pyramid: level 0 is (intensity, depth or 0) per pixel as ONE float2, so that a bilinear corner is one 8-byte load; every
@@ -17,16 +18,11 @@
 #include <algorithm>
 #include <type_traits>
 
-#include "gs_icp_step.hpp"  // solve6, se3_exp_dev; it brings gs_icp_reduce.hpp
+#include "gs_gn_step.hpp"  // constants, the tape row, the start-up, the shared host checks; it brings gs_icp_step.hpp (solve6, se3_exp_dev)
 #include "gs_rgbd_pixel.hpp"
 #include "gs_rowsum.hpp"  // block_row_transposed
 
 namespace gs {
-
-constexpr int RGBD_MAX_LEVELS = 8;
-constexpr int RGBD_MIN_SIDE = 4;     // the coarsest level is at least 4 x 4
-constexpr int RGBD_STATUS_FEW = 1;   // fewer than 6 valid pixels
-constexpr int RGBD_STATUS_SOLVE = 2; // the solve (or the composed transform) was not finite
 
 // ------------------------------------------------------------------ P: pyramid
 __global__ __launch_bounds__(256) void rgbd_level0_k(const float *__restrict__ depth, const float *__restrict__ rgb, int64_t n,
@@ -123,7 +119,7 @@ __global__ __launch_bounds__(RGBD_T) void rgbd_linearize_k(const float2 *__restr
 // grid B, 1024 threads.  Reduces batch element b's `nblocks` partial rows; `sums` (B, 29: H upper | g = -sum | err | cnt)
 // is written when given; with `apply`, lane 0 solves and composes T[b] <- exp(xi) T[b], and writes out_T[b] and the level's
 // info row (cnt, err, status bits of the level so far, iterations run at the level).
-// TAPE: also the iteration's tape row of batch element b (gs_rgbd_pixel.hpp: RGBD_TAPE_*).
+// TAPE: also the iteration's tape row of batch element b (gs_gn_step.hpp: GN_TAPE_*).
 template <bool TAPE>
 __global__ __launch_bounds__(1024) void rgbd_step_k(float *__restrict__ Tall, const float *__restrict__ partials, int nblocks, int prow,
                                                    float damp, int level, int levels, int it, int apply, float *__restrict__ out_T,
@@ -141,15 +137,15 @@ __global__ __launch_bounds__(1024) void rgbd_step_k(float *__restrict__ Tall, co
     float *row = info + ((int64_t)b * levels + level) * 4;
     int status = it == 0 ? 0 : (int)row[2];
     const float cnt = acc[28];
-    float *rec = TAPE ? tape + RGBD_TAPE_WORDS * b : nullptr;
+    float *rec = TAPE ? tape + GN_TAPE_WORDS * b : nullptr;
     if constexpr (TAPE) {
         for (int k = 0; k < 16; ++k) rec[k] = T[k];
-        for (int k = 0; k < NACC; ++k) rec[RGBD_TAPE_SUMS + k] = acc[k];
-        for (int k = 0; k < 6; ++k) rec[RGBD_TAPE_XI + k] = 0.0f;
-        rec[RGBD_TAPE_APPLIED] = 0.0f;
+        for (int k = 0; k < NACC; ++k) rec[GN_TAPE_SUMS + k] = acc[k];
+        for (int k = 0; k < 6; ++k) rec[GN_TAPE_XI + k] = 0.0f;
+        rec[GN_TAPE_APPLIED] = 0.0f;
     }
     if (cnt < 6.0f) {
-        status |= RGBD_STATUS_FEW;
+        status |= GN_STATUS_FEW;
     } else {
         float hg[44], xi[6], dT[16], Tn[16];
         expand44(acc, hg);
@@ -164,12 +160,12 @@ __global__ __launch_bounds__(1024) void rgbd_step_k(float *__restrict__ Tall, co
         }
         if (fin) {
             if constexpr (TAPE) {
-                for (int k = 0; k < 6; ++k) rec[RGBD_TAPE_XI + k] = xi[k];
-                rec[RGBD_TAPE_APPLIED] = 1.0f;
+                for (int k = 0; k < 6; ++k) rec[GN_TAPE_XI + k] = xi[k];
+                rec[GN_TAPE_APPLIED] = 1.0f;
             }
             for (int k = 0; k < 16; ++k) T[k] = Tn[k];
         } else {
-            status |= RGBD_STATUS_SOLVE;
+            status |= GN_STATUS_SOLVE;
         }
     }
     row[0] = cnt;
@@ -179,16 +175,9 @@ __global__ __launch_bounds__(1024) void rgbd_step_k(float *__restrict__ Tall, co
     for (int k = 0; k < 16; ++k) out_T[16 * b + k] = T[k];
 }
 
-// T[b] = out_T[b] = init[b] or the identity; info = 0.  One thread per word.
 __global__ __launch_bounds__(256) void rgbd_init_k(const float *__restrict__ init, int B, int n_info, float *__restrict__ Tall,
                                                   float *__restrict__ out_T, float *__restrict__ info) {
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i < 16 * B) {
-        const float v = init ? init[i] : (((i & 15) % 5 == 0) ? 1.0f : 0.0f);
-        Tall[i] = v;
-        out_T[i] = v;
-    }
-    if (i < n_info) info[i] = 0.0f;
+    gn_init(init, B, n_info, Tall, out_T, info);
 }
 
 }  // namespace gs
@@ -203,8 +192,8 @@ struct RgbdWs {
     float *partials;  // B x prow x NACC
     float2 *tgt, *src;  // level-major pyramids: level l at + B * off[l] pixels
     int prow;
-    int Hl[RGBD_MAX_LEVELS], Wl[RGBD_MAX_LEVELS];
-    int64_t off[RGBD_MAX_LEVELS + 1];  // pixels per batch element in the levels before l
+    int Hl[GN_MAX_LEVELS], Wl[GN_MAX_LEVELS];
+    int64_t off[GN_MAX_LEVELS + 1];  // pixels per batch element in the levels before l
 };
 static size_t rgbd_layout(int B, int H, int W, int levels, void *ws, RgbdWs *w) {
     Carve c{(char *)ws};
@@ -226,21 +215,17 @@ static size_t rgbd_layout(int B, int H, int W, int levels, void *ws, RgbdWs *w) 
 // The bounds on (B, H, W, levels), once: 0 if the entry points take the shape, else the number of the first bound it breaks, in
 // the order RGBD_REQUIRE_SHAPE words them.  A size query returns 0 for a shape that breaks one.
 static int rgbd_shape_fault(int B, int H, int W, int levels) {
-    if (!(B >= 1 && B <= 65535)) return 1;
-    if (!(H >= 1 && W >= 1 && (int64_t)H * W <= (1 << 24))) return 2;
-    if (!((int64_t)B * H * W <= (1 << 30))) return 3;
-    if (!(levels >= 1 && levels <= RGBD_MAX_LEVELS)) return 4;
-    if (!((H >> (levels - 1)) >= RGBD_MIN_SIDE && (W >> (levels - 1)) >= RGBD_MIN_SIDE)) return 5;
+    if (const int fault = gn_image_fault(B, H, W)) return fault;
+    if (!(levels >= 1 && levels <= GN_MAX_LEVELS)) return 4;
+    if (!((H >> (levels - 1)) >= GN_MIN_SIDE && (W >> (levels - 1)) >= GN_MIN_SIDE)) return 5;
     return 0;
 }
 static bool rgbd_shape_ok(int B, int H, int W, int levels) { return rgbd_shape_fault(B, H, W, levels) == 0; }
 #define RGBD_REQUIRE_SHAPE(name)                                                                                                  \
     do {                                                                                                                          \
         const int fault__ = rgbd_shape_fault(B, H, W, levels);                                                                    \
-        GS_REQUIRE(fault__ != 1, name ": B must be in [1, 65535], got %d", B);                                                    \
-        GS_REQUIRE(fault__ != 2, name ": H x W must be positive and at most 2^24 pixels, got %d x %d", H, W);                     \
-        GS_REQUIRE(fault__ != 3, name ": B H W must be at most 2^30, got %d x %d x %d", B, H, W);                                 \
-        GS_REQUIRE(fault__ != 4, name ": levels must be in [1, %d], got %d", RGBD_MAX_LEVELS, levels);                            \
+        GN_REQUIRE_IMAGE(name, fault__);                                                                                          \
+        GS_REQUIRE(fault__ != 4, name ": levels must be in [1, %d], got %d", GN_MAX_LEVELS, levels);                              \
         GS_REQUIRE(fault__ != 5, name ": the coarsest of %d levels of a %d x %d image would be smaller than 4 x 4", levels, H, W); \
     } while (0)
 #define RGBD_REQUIRE_PARAMS(name)                                                                                                 \
@@ -379,7 +364,7 @@ static int rgbd_run(const float *tgt_depth, const float *tgt_rgb, const float *s
             hipLaunchKernelGGL(step, dim3(B), dim3(1024), 0, st, w.T, w.partials, nblocks, w.prow, damp, l, levels, it, 1, out_T, info,
                                (float *)nullptr, rec);
             GS_LAUNCH_CHECK("gs_rgbd_odometry/step");
-            if (tape) rec += (size_t)RGBD_TAPE_WORDS * B;
+            if (tape) rec += (size_t)GN_TAPE_WORDS * B;
         }
     }
     return 0;
@@ -411,7 +396,7 @@ static int rgbd_bwd_run(const RgbdBwdNames &nm, const float *tgt_depth, const fl
                         float rgb_scale, const float *tape, const float *grad_T, const float *T, const float *g_sums, float *g_tgt_depth,
                         float *g_tgt_rgb, float *g_src_depth, float *g_src_rgb, float *g_T, void *ws, size_t ws_bytes, hipStream_t st) {
     const bool seam = !tape;
-    int total = 0, base[RGBD_MAX_LEVELS];  // base[l]: iterations that ran before level l's (the coarser levels')
+    int total = 0, base[GN_MAX_LEVELS];  // base[l]: iterations that ran before level l's (the coarser levels')
     for (int l = levels - 1; l >= 0; --l) { base[l] = total; total += numiters[l]; }
     const size_t need = gs_rgbd_odometry_bwd_ws_size(B, H, W, levels, total);
     GS_REQUIRE_WS(nm.op, ws, ws_bytes, need);
@@ -442,12 +427,12 @@ static int rgbd_bwd_run(const RgbdBwdNames &nm, const float *tgt_depth, const fl
         }
         const int nblocks = cdiv((int64_t)w.f.Hl[l] * w.f.Wl[l], RGBD_T);
         // iteration `it`'s transform (the seam's T, or the head of its tape row) and the adjoints of its sums
-        const auto T_of = [&](int it) { return seam ? T : tape + (size_t)(base[l] + it) * B * RGBD_TAPE_WORDS; };
+        const auto T_of = [&](int it) { return seam ? T : tape + (size_t)(base[l] + it) * B * GN_TAPE_WORDS; };
         const auto adj_of = [&](int it) { return w.adj + (size_t)(base[l] + it) * B * RGBD_ADJ_WORDS; };
         const auto pixels = [&](decltype(&rgbd_pixel_bwd_k<RGBD_BWD_MAX>) kernel, const char *name, int it) {
             hipLaunchKernelGGL(kernel, dim3(nblocks, B), dim3(RGBD_T), 0, st, (const float2 *)(w.f.tgt + B * w.f.off[l]),
                                (const float2 *)(w.f.src + B * w.f.off[l]), w.f.Hl[l], w.f.Wl[l], l, intrinsics, T_of(it),
-                               seam ? 16 : RGBD_TAPE_WORDS, (const float *)adj_of(it), wI, wD, ddm, w.fold, lg, w.gsrc + B * w.f.off[l],
+                               seam ? 16 : GN_TAPE_WORDS, (const float *)adj_of(it), wI, wD, ddm, w.fold, lg, w.gsrc + B * w.f.off[l],
                                w.partials12, w.f.prow);
             GS_LAUNCH_CHECK(name);
             return 0;
@@ -485,9 +470,7 @@ extern "C" {
         RGBD_REQUIRE_SHAPE(name);                                                                                                 \
         RGBD_REQUIRE_LAMBDA(name);                                                                                                \
         RGBD_REQUIRE_PARAMS(name);                                                                                                \
-        GS_REQUIRE(damp >= 0.0f && damp < INFINITY, name ": damp must be finite and not negative, got %g", (double)damp);         \
-        for (int l = 0; l < levels; ++l)                                                                                          \
-            GS_REQUIRE(numiters[l] >= 0 && numiters[l] <= (1 << 20), name ": numiters[%d] must be in [0, 2^20], got %d", l, numiters[l]); \
+        GN_REQUIRE_LOOP(name);                                                                                                    \
     } while (0)
 
 int gs_rgbd_odometry(const float *tgt_depth, const float *tgt_rgb, const float *src_depth, const float *src_rgb, int B, int H, int W,
@@ -502,8 +485,8 @@ int gs_rgbd_odometry(const float *tgt_depth, const float *tgt_rgb, const float *
 
 // (numiters here: the SUM of the levels' counts)
 size_t gs_rgbd_odometry_tape_size(int B, int levels, int numiters) {
-    if (B < 1 || B > 65535 || levels < 1 || levels > RGBD_MAX_LEVELS || numiters < 0 || numiters > levels * (1 << 20)) return 0;
-    return one_piece_bytes(sizeof(float) * RGBD_TAPE_WORDS * (size_t)std::max(numiters, 1) * B);
+    if (B < 1 || B > 65535 || levels < 1 || levels > GN_MAX_LEVELS || numiters < 0 || numiters > levels * (1 << 20)) return 0;
+    return one_piece_bytes(sizeof(float) * GN_TAPE_WORDS * (size_t)std::max(numiters, 1) * B);
 }
 
 int gs_rgbd_odometry_taped(const float *tgt_depth, const float *tgt_rgb, const float *src_depth, const float *src_rgb, int B, int H,

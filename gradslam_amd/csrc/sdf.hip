@@ -13,16 +13,12 @@
 #include <stddef.h>
 #include <algorithm>
 
-#include "gs_icp_step.hpp"  // solve6, se3_exp_dev; it brings gs_icp_reduce.hpp (reduce_partials, expand44, NACC)
+#include "gs_gn_step.hpp"  // constants, the start-up, the shared host checks; it brings gs_icp_step.hpp (solve6, se3_exp_dev, reduce_partials)
 #include "gs_sdf_pixel.hpp"
 
 namespace gs {
 
-constexpr int SDF_T = LIN_T;         // lanes (= pixels) per linearise block
-constexpr int SDF_MAX_LEVELS = 8;
-constexpr int SDF_MIN_SIDE = 4;      // the coarsest grid is at least 4 x 4
-constexpr int SDF_STATUS_FEW = 1;    // fewer than 6 valid pixels
-constexpr int SDF_STATUS_SOLVE = 2;  // the solve (or the composed transform) was not finite
+constexpr int SDF_T = LIN_T;  // lanes (= pixels) per linearise block
 
 // what a level's grid is: pixels (i s, j s) of the H x W image, Hs x Ws of them
 struct SdfGrid { int H, W, s, Hs, Ws; };
@@ -106,7 +102,7 @@ __global__ __launch_bounds__(1024) void sdf_step_k(float *__restrict__ Dall, con
     int status = it == 0 ? 0 : (int)row[2];
     const float cnt = acc[28];
     if (cnt < 6.0f) {
-        status |= SDF_STATUS_FEW;
+        status |= GN_STATUS_FEW;
     } else {
         float hg[44], xi[6], dT[16], Dn[16];
         expand44(acc, hg);
@@ -122,7 +118,7 @@ __global__ __launch_bounds__(1024) void sdf_step_k(float *__restrict__ Dall, con
         if (fin) {
             for (int k = 0; k < 16; ++k) D[k] = Dn[k];
         } else {
-            status |= SDF_STATUS_SOLVE;
+            status |= GN_STATUS_SOLVE;
         }
     }
     row[0] = cnt;
@@ -132,16 +128,9 @@ __global__ __launch_bounds__(1024) void sdf_step_k(float *__restrict__ Dall, con
     for (int k = 0; k < 16; ++k) out_T[16 * b + k] = D[k];
 }
 
-// D[b] = out_T[b] = init[b] or the identity; info = 0.  One thread per word.
 __global__ __launch_bounds__(256) void sdf_init_k(const float *__restrict__ init, int B, int n_info, float *__restrict__ Dall,
                                                  float *__restrict__ out_T, float *__restrict__ info) {
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i < 16 * B) {
-        const float v = init ? init[i] : (((i & 15) % 5 == 0) ? 1.0f : 0.0f);
-        Dall[i] = v;
-        out_T[i] = v;
-    }
-    if (i < n_info) info[i] = 0.0f;
+    gn_init(init, B, n_info, Dall, out_T, info);
 }
 
 // ------------------------------------------------------------------ host
@@ -167,24 +156,20 @@ static size_t sdf_layout(int B, int H, int W, int stride, void *ws, SdfWs *w) {
 // The bounds on (B, H, W, stride, levels), once: 0 if the entry points take the shape, else the number of the first bound it
 // breaks, in the order SDF_REQUIRE_SHAPE words them.  A size query returns 0 for a shape that breaks one.
 static int sdf_shape_fault(int B, int H, int W, int stride, int levels) {
-    if (!(B >= 1 && B <= 65535)) return 1;
-    if (!(H >= 1 && W >= 1 && (int64_t)H * W <= (1 << 24))) return 2;
-    if (!((int64_t)B * H * W <= (1 << 30))) return 3;
+    if (const int fault = gn_image_fault(B, H, W)) return fault;
     if (!(stride >= 1)) return 4;
-    if (!(levels >= 1 && levels <= SDF_MAX_LEVELS)) return 5;
+    if (!(levels >= 1 && levels <= GN_MAX_LEVELS)) return 5;
     const int64_t s = (int64_t)stride << (levels - 1);  // (stride < 2^31, levels <= 8: no overflow)
-    if (!((H + s - 1) / s >= SDF_MIN_SIDE && (W + s - 1) / s >= SDF_MIN_SIDE)) return 6;
+    if (!((H + s - 1) / s >= GN_MIN_SIDE && (W + s - 1) / s >= GN_MIN_SIDE)) return 6;
     return 0;
 }
 static bool sdf_pos(float x) { return x > 0.0f && x < INFINITY; }
 #define SDF_REQUIRE_SHAPE(name)                                                                                                    \
     do {                                                                                                                           \
         const int fault__ = sdf_shape_fault(B, H, W, stride, levels);                                                              \
-        GS_REQUIRE(fault__ != 1, name ": B must be in [1, 65535], got %d", B);                                                     \
-        GS_REQUIRE(fault__ != 2, name ": H x W must be positive and at most 2^24 pixels, got %d x %d", H, W);                      \
-        GS_REQUIRE(fault__ != 3, name ": B H W must be at most 2^30, got %d x %d x %d", B, H, W);                                  \
+        GN_REQUIRE_IMAGE(name, fault__);                                                                                           \
         GS_REQUIRE(fault__ != 4, name ": stride must be at least 1, got %d", stride);                                              \
-        GS_REQUIRE(fault__ != 5, name ": levels must be in [1, %d], got %d", SDF_MAX_LEVELS, levels);                              \
+        GS_REQUIRE(fault__ != 5, name ": levels must be in [1, %d], got %d", GN_MAX_LEVELS, levels);                               \
         GS_REQUIRE(fault__ != 6, name ": the coarsest of %d grids of a %d x %d image at stride %d would be smaller than 4 x 4",    \
                    levels, H, W, stride);                                                                                          \
     } while (0)
@@ -246,9 +231,7 @@ int gs_sdf_odometry(const float *depth, int B, int H, int W, const float *intrin
     GS_REQUIRE(depth && intrinsics && poses && tsdf && weight && origin && numiters && out_T && info, "gs_sdf_odometry: null pointer");
     SDF_REQUIRE_SHAPE("gs_sdf_odometry");
     SDF_REQUIRE_VOLUME("gs_sdf_odometry");
-    GS_REQUIRE(damp >= 0.0f && damp < INFINITY, "gs_sdf_odometry: damp must be finite and not negative, got %g", (double)damp);
-    for (int l = 0; l < levels; ++l)
-        GS_REQUIRE(numiters[l] >= 0 && numiters[l] <= (1 << 20), "gs_sdf_odometry: numiters[%d] must be in [0, 2^20], got %d", l, numiters[l]);
+    GN_REQUIRE_LOOP("gs_sdf_odometry");
     const size_t need = gs_sdf_odometry_ws_size(B, H, W, stride);
     GS_REQUIRE_WS("gs_sdf_odometry", ws, ws_bytes, need);
     hipStream_t st = (hipStream_t)stream;

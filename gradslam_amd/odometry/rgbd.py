@@ -7,7 +7,7 @@ import torch
 
 from .. import ops
 from ..structures.rgbdimages import RGBDImages
-from .base import OdometryProvider
+from .base import OdometryProvider, check_init, check_levels_numiters
 
 __all__ = ["RGBDOdometryProvider"]
 
@@ -28,14 +28,7 @@ class RGBDOdometryProvider(OdometryProvider):
 
     def __init__(self, numiters: Union[int, Sequence[int]] = (10, 5, 3), levels: int = 3, lambda_geo: float = 0.968,
                  depth_diff_max: float = 0.07, damp: float = 1e-8, rgb_scale: float = 1.0 / 255.0, differentiable: bool = False):
-        if not isinstance(levels, int) or isinstance(levels, bool) or levels < 1:
-            raise ValueError("RGBDOdometryProvider: levels should be a positive integer. Got {!r}.".format(levels))
-        if isinstance(numiters, int) and not isinstance(numiters, bool):
-            numiters = (numiters,) * levels
-        numiters = tuple(numiters)
-        if len(numiters) != levels or any(not isinstance(n, int) or isinstance(n, bool) or n < 0 for n in numiters):
-            raise ValueError("RGBDOdometryProvider: numiters should be an integer or {} non-negative integers (finest level first). "
-                             "Got {!r}.".format(levels, numiters))
+        numiters = check_levels_numiters("RGBDOdometryProvider", numiters, levels)
         self.numiters = numiters
         self.levels = levels
         self.lambda_geo = lambda_geo
@@ -64,8 +57,7 @@ class RGBDOdometryProvider(OdometryProvider):
             raise ValueError("Image size of target_frames and source_frames should be equal ({0} != {1})".format(
                 tuple(target_frames.shape[2:]), tuple(source_frames.shape[2:])))
         B = len(target_frames)
-        if init is not None and (init.numel() != 16 * B or tuple(init.shape[-2:]) != (4, 4)):
-            raise ValueError("Expected init to have shape ({0}, 1, 4, 4). Got {1}.".format(B, tuple(init.shape)))
+        check_init(init, B)
         tensors = [target_frames.rgb_image, target_frames.depth_image, target_frames.intrinsics, source_frames.rgb_image,
                    source_frames.depth_image, source_frames.intrinsics, init]
         if not self.differentiable and torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in tensors):

@@ -8,7 +8,7 @@ import torch
 from .. import ops
 from ..structures.rgbdimages import RGBDImages
 from ..structures.tsdfvolume import TSDFVolume
-from .base import OdometryProvider
+from .base import OdometryProvider, check_init, check_levels_numiters
 
 __all__ = ["SDFOdometryProvider"]
 
@@ -25,14 +25,7 @@ class SDFOdometryProvider(OdometryProvider):
 
     def __init__(self, numiters: Union[int, Sequence[int]] = (10, 5, 3), levels: int = 3, stride: int = 1, min_weight: float = 1.0,
                  damp: float = 1e-8):
-        if not isinstance(levels, int) or isinstance(levels, bool) or levels < 1:
-            raise ValueError("SDFOdometryProvider: levels should be a positive integer. Got {!r}.".format(levels))
-        if isinstance(numiters, int) and not isinstance(numiters, bool):
-            numiters = (numiters,) * levels
-        numiters = tuple(numiters)
-        if len(numiters) != levels or any(not isinstance(n, int) or isinstance(n, bool) or n < 0 for n in numiters):
-            raise ValueError("SDFOdometryProvider: numiters should be an integer or {} non-negative integers (finest level first). "
-                             "Got {!r}.".format(levels, numiters))
+        numiters = check_levels_numiters("SDFOdometryProvider", numiters, levels)
         if not isinstance(stride, int) or isinstance(stride, bool) or stride < 1:
             raise ValueError("SDFOdometryProvider: stride should be a positive integer. Got {!r}.".format(stride))
         self.numiters = numiters
@@ -57,8 +50,7 @@ class SDFOdometryProvider(OdometryProvider):
         if not source_frames.has_poses:
             raise ValueError("source_frames must have poses (the pose the frame is tracked from).")
         B = len(volume)
-        if init is not None and (init.numel() != 16 * B or tuple(init.shape[-2:]) != (4, 4)):
-            raise ValueError("Expected init to have shape ({0}, 1, 4, 4). Got {1}.".format(B, tuple(init.shape)))
+        check_init(init, B)
         tensors = [source_frames.depth_image, source_frames.poses, init, volume.tsdf]
         if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in tensors):
             raise NotImplementedError("SDFOdometryProvider: gradients are not implemented; detach the frames, the poses, init and "

@@ -1709,9 +1709,34 @@ def _rgbd_T(T, B, name, op, attached=False):
     return _f32c(T.detach().reshape(B, 16))
 
 
-def _rgbd_params(levels, lambda_geo, depth_diff_max, rgb_scale, H, W, op):
+def _gn_levels(levels, op):
+    """The level count of the two image-aligned odometries (rgbd_*, sdf_*): an integer in [1, 8]."""
     if not isinstance(levels, int) or isinstance(levels, bool) or levels < 1 or levels > 8:
         raise ValueError("{}: levels should be an integer in [1, 8]. Got {!r}.".format(op, levels))
+
+
+def _gn_loop(numiters, levels, damp, op):
+    """The loop's parameters, checked -> (numiters as `levels` counts, finest first (an int: that count at every level), damp)."""
+    damp = _number(damp, "damp", op)
+    if not (0.0 <= damp < math.inf):
+        raise ValueError("{}: damp should be finite and not negative. Got {!r}.".format(op, damp))
+    if isinstance(numiters, int) and not isinstance(numiters, bool):
+        numiters = (numiters,) * levels
+    numiters = tuple(numiters)
+    if len(numiters) != levels or any(not isinstance(n, int) or isinstance(n, bool) or n < 0 for n in numiters):
+        raise ValueError("{}: numiters should be {} non-negative integers (finest level first). Got {!r}.".format(op, levels, numiters))
+    return numiters, damp
+
+
+def _gn_outputs(B, numiters, dev):
+    """What a loop's C call fills and takes: (out_T (B,4,4), info (B,levels,4), the levels' counts as a C int array)."""
+    out_T = torch.empty((B, 4, 4), dtype=torch.float32, device=dev)
+    info = torch.empty((B, len(numiters), 4), dtype=torch.float32, device=dev)
+    return out_T, info, (nv.c_i * len(numiters))(*numiters)
+
+
+def _rgbd_params(levels, lambda_geo, depth_diff_max, rgb_scale, H, W, op):
+    _gn_levels(levels, op)
     if (H >> (levels - 1)) < 4 or (W >> (levels - 1)) < 4:
         raise ValueError("{}: the coarsest of {} levels of a {} x {} image would be smaller than 4 x 4.".format(op, levels, H, W))
     lam, ddm, scale = (_number(x, n, op) for x, n in ((lambda_geo, "lambda_geo"), (depth_diff_max, "depth_diff_max"),
@@ -1795,10 +1820,8 @@ def rgbd_rows_bwd_raw(tgt_depth, tgt_rgb, src_depth, src_rgb, intrinsics, T, g_s
 def _rgbd_odometry_call(td, tc, sd, sc, init, K, numiters, levels, lam, ddm, damp, scale, taped):
     """gs_rgbd_odometry, or with `taped` gs_rgbd_odometry_taped (the same launches, the same bits) -> (T, info, tape or None)."""
     (B, H, W), dev = td.shape, td.device
-    out_T = torch.empty((B, 4, 4), dtype=torch.float32, device=dev)
-    info = torch.empty((B, levels, 4), dtype=torch.float32, device=dev)
+    out_T, info, counts = _gn_outputs(B, numiters, dev)
     ws = workspace(ws_bytes("gs_rgbd_odometry_ws_bytes", B, H, W, levels), dev, "rgbd")
-    counts = (nv.c_i * levels)(*numiters)
     tape, extra = None, ()
     if taped:
         tape = torch.empty(ws_bytes("gs_rgbd_odometry_tape_size", B, levels, sum(numiters)) // 4, dtype=torch.float32, device=dev)
@@ -1859,14 +1882,7 @@ def rgbd_odometry(tgt_depth, tgt_rgb, src_depth, src_rgb, intrinsics, init=None,
     K = _rgbd_K(intrinsics, B, op)
     init = None if init is None else _rgbd_T(init, B, "init", op, attached=attached)
     lam, ddm, scale = _rgbd_params(levels, lambda_geo, depth_diff_max, rgb_scale, H, W, op)
-    damp = _number(damp, "damp", op)
-    if not (0.0 <= damp < math.inf):
-        raise ValueError("{}: damp should be finite and not negative. Got {!r}.".format(op, damp))
-    if isinstance(numiters, int) and not isinstance(numiters, bool):
-        numiters = (numiters,) * levels
-    numiters = tuple(numiters)
-    if len(numiters) != levels or any(not isinstance(n, int) or isinstance(n, bool) or n < 0 for n in numiters):
-        raise ValueError("{}: numiters should be {} non-negative integers (finest level first). Got {!r}.".format(op, levels, numiters))
+    numiters, damp = _gn_loop(numiters, levels, damp, op)
     require_hip(td, tc, sd, sc, K, init, op=op)
     if attached:
         return _RgbdOdometryFn.apply(td, tc, sd, sc, init, K, numiters, levels, lam, ddm, damp, scale)
@@ -1895,8 +1911,7 @@ def _sdf_args(op, depth, intrinsics, poses, tsdf, weight, origin, voxel_size, tr
     v, tr, mw = _positive(voxel_size, "voxel_size", op), _positive(trunc, "trunc", op), _number(min_weight, "min_weight", op)
     if not isinstance(stride, int) or isinstance(stride, bool) or stride < 1:
         raise ValueError("{}: stride should be a positive integer. Got {!r}.".format(op, stride))
-    if not isinstance(levels, int) or isinstance(levels, bool) or levels < 1 or levels > 8:
-        raise ValueError("{}: levels should be an integer in [1, 8]. Got {!r}.".format(op, levels))
+    _gn_levels(levels, op)
     s = stride << (levels - 1)
     if -(-H // s) < 4 or -(-W // s) < 4:
         raise ValueError("{}: the coarsest of {} grids of a {} x {} image at stride {} would be smaller than 4 x 4.".format(
@@ -1940,19 +1955,10 @@ def sdf_odometry(depth, intrinsics, poses, tsdf, weight, origin, voxel_size, tru
                                   "under torch.no_grad().".format(op))
     keep, named, (B, H, W), frame, volume = _sdf_args(op, depth, intrinsics, poses, tsdf, weight, origin, voxel_size, trunc, min_weight,
                                                       stride, levels, init=init)
-    damp = _number(damp, "damp", op)
-    if not (0.0 <= damp < math.inf):
-        raise ValueError("{}: damp should be finite and not negative. Got {!r}.".format(op, damp))
-    if isinstance(numiters, int) and not isinstance(numiters, bool):
-        numiters = (numiters,) * levels
-    numiters = tuple(numiters)
-    if len(numiters) != levels or any(not isinstance(n, int) or isinstance(n, bool) or n < 0 for n in numiters):
-        raise ValueError("{}: numiters should be {} non-negative integers (finest level first). Got {!r}.".format(op, levels, numiters))
+    numiters, damp = _gn_loop(numiters, levels, damp, op)
     require_hip(*keep, named["init"], op=op)
     dev = keep[0].device
-    out_T = torch.empty((B, 4, 4), dtype=torch.float32, device=dev)
-    info = torch.empty((B, levels, 4), dtype=torch.float32, device=dev)
+    out_T, info, counts = _gn_outputs(B, numiters, dev)
     ws = workspace(ws_bytes("gs_sdf_odometry_ws_size", B, H, W, stride), dev, "sdf")
-    counts = (nv.c_i * levels)(*numiters)
     call("gs_sdf_odometry", *frame, ptr(named["init"]), *volume, levels, counts, damp, ptr(out_T), ptr(info), ptr(ws), ws.numel(), stream())
     return out_T, info

@@ -1,14 +1,17 @@
 #!/usr/bin/env python3
-"""Records tests/golden/rgbd_bits.npz: what the cases of tests/test_rgbd_bits.py (CASES: the pyramid, the seam and the whole call
-with its reverse pass, on the scenes of tests/test_rgbd_odometry.py) leave behind, packed as that file's `pack` packs them --
-small arrays whole, large ones as SHA-256 and shape.  Run it on an MI355X with the library whose bits are to be pinned; every
-case is run twice and must repeat itself.
+"""Records tests/golden/rgbd_bits.npz or tests/golden/sdf_bits.npz: what the cases of tests/test_rgbd_bits.py (CASES: the pyramid,
+the seam and the whole call with its reverse pass, on the scenes of tests/test_rgbd_odometry.py) or of tests/test_sdf_bits.py
+(CASES: the seam and the whole call, on the scenes of tests/test_sdf_odometry.py) leave behind, packed as test_rgbd_bits' `pack`
+packs them -- small arrays whole, large ones as SHA-256 and shape.  Run it on an MI355X with the library whose bits are to be
+pinned; every case is run twice and must repeat itself.
 
-    python3 tools/gen_golden_rgbd_bits.py [LIBRARY] [OUT.npz]
+    python3 tools/gen_golden_rgbd_bits.py [--module rgbd|sdf] [LIBRARY] [OUT.npz]
 
-LIBRARY is the libgradslam_hip.so to record (default: the in-tree build).  The file in the repository was recorded with the
-library built from the commit before the pixel's arithmetic moved into gs_rgbd_pixel.hpp (d13c0fa).
+LIBRARY is the libgradslam_hip.so to record (default: the in-tree build).  rgbd_bits.npz in the repository was recorded with the
+library built from the commit before the pixel's arithmetic moved into gs_rgbd_pixel.hpp (d13c0fa); sdf_bits.npz with the library
+built from the commit before the loops' shared parts moved into gs_gn_step.hpp (9ff1be4).
 """
+import importlib
 import os
 import sys
 
@@ -18,16 +21,22 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from gradslam_amd import _native  # noqa: E402
 
-if len(sys.argv) > 1:
-    _native.LIB_PATH = os.path.abspath(sys.argv[1])  # before the first call loads it
-from tests import test_rgbd_bits as S  # noqa: E402
+args = sys.argv[1:]
+module = "rgbd"
+if args and args[0] == "--module":
+    module, args = args[1], args[2:]
+assert module in ("rgbd", "sdf"), module
+if len(args) > 0:
+    _native.LIB_PATH = os.path.abspath(args[0])  # before the first call loads it
+from tests.test_rgbd_bits import pack, same_bits  # noqa: E402
 
-out_path = sys.argv[2] if len(sys.argv) > 2 else os.path.join(ROOT, "tests", "golden", "rgbd_bits.npz")
+S = importlib.import_module("tests.test_{}_bits".format(module))
+out_path = args[1] if len(args) > 1 else os.path.join(ROOT, "tests", "golden", module + "_bits.npz")
 out = {}
 for case, run in S.CASES.items():
-    r, again = S.pack(case, run()), S.pack(case, run())
+    r, again = pack(case, run()), pack(case, run())
     assert sorted(r) == sorted(again), case
-    assert all(S.same_bits(r[k], again[k]) for k in r), [k for k in r if not S.same_bits(r[k], again[k])]
+    assert all(same_bits(r[k], again[k]) for k in r), [k for k in r if not same_bits(r[k], again[k])]
     out.update(r)
     print(case, sorted(k[len(case) + 1:] for k in r))
 np.savez_compressed(out_path, **out)

@@ -1,6 +1,7 @@
 // gs_gn_step.hpp -- what the Gauss-Newton loops of the two image-aligned odometries (rgbd.hip, sdf.hip) share, stated once:
-// the level and status constants, the layout of the tape row (written by rgbd_step_k<true>, read by rgbd_step_bwd_k in
-// gs_rgbd_bwd.hpp, which rgbd.hip includes after this header), gn_init (the start-up kernels' body) and the host checks on the
+// the level and status constants, the layout of the tape row (written by rgbd_step_k<true> and sdf_step_k<true>, read by
+// rgbd_step_bwd_k in gs_rgbd_bwd.hpp and sdf_step_bwd_k in gs_sdf_bwd.hpp, which rgbd.hip and sdf.hip include after this
+// header), gn_init (the start-up kernels' body) and the host checks on the
 // image and the loop's parameters; no kernels.  The step kernels and the lane's 29 terms stay in their units: as inlined
 // functions of this header they compiled to other instructions than in place ("SDF odometry").
 #pragma once

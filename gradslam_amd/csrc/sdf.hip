@@ -3,7 +3,8 @@
 // rule -- every fp32 operation in order -- is stated in include/gradslam_hip.h above the entry points; the code follows it line
 // by line (the library is built without contraction).
 //   gs_sdf_pixel.hpp  the pixel, once: back-projection, the gates in their order, the row
-//   this file         L, X: the kernels; every launch, the workspace and the C entry points
+//   gs_sdf_bwd.hpp    Xb, Lb: the kernels of the reverse pass (gs_sdf_odometry_taped, gs_sdf_odometry_bwd, gs_sdf_rows_bwd)
+//   this file         L, X: the forward kernels; every launch, the workspace, the tape, the room and the C entry points
 // L  linearise: one pixel of the level's grid per lane: depth, two transforms, the cell, 16 gathers in one batch, the row, the
 //    lane's 29 terms; gs_rowsum.hpp's transposing butterfly leaves one partial row per block.
 // X  step: one 1024-thread block per batch element: reduce_partials (fixed order), then one lane solves (gs::solve6, fp64) and
@@ -85,9 +86,11 @@ __global__ __launch_bounds__(SDF_T) void sdf_linearize_k(const float *__restrict
 // grid B, 1024 threads.  Reduces batch element b's `nblocks` partial rows; `sums` (B, 29: H upper | g = -sum | err | cnt) is
 // written when given; with `apply`, lane 0 solves and composes D[b] <- exp(xi) D[b], and writes out_T[b] and the level's info
 // row (cnt, err, status bits of the level so far, iterations run at the level).
+// TAPE: also the iteration's tape row of batch element b (gs_gn_step.hpp: GN_TAPE_*).
+template <bool TAPE>
 __global__ __launch_bounds__(1024) void sdf_step_k(float *__restrict__ Dall, const float *__restrict__ partials, int nblocks, int prow,
                                                   float damp, int level, int levels, int it, int apply, float *__restrict__ out_T,
-                                                  float *__restrict__ info, float *__restrict__ sums) {
+                                                  float *__restrict__ info, float *__restrict__ sums, float *__restrict__ tape) {
     __shared__ float acc[NACC];
     __shared__ double lu_sm[42];
     const int b = blockIdx.x;
@@ -101,6 +104,13 @@ __global__ __launch_bounds__(1024) void sdf_step_k(float *__restrict__ Dall, con
     float *row = info + ((int64_t)b * levels + level) * 4;
     int status = it == 0 ? 0 : (int)row[2];
     const float cnt = acc[28];
+    float *rec = TAPE ? tape + GN_TAPE_WORDS * b : nullptr;
+    if constexpr (TAPE) {
+        for (int k = 0; k < 16; ++k) rec[k] = D[k];
+        for (int k = 0; k < NACC; ++k) rec[GN_TAPE_SUMS + k] = acc[k];
+        for (int k = 0; k < 6; ++k) rec[GN_TAPE_XI + k] = 0.0f;
+        rec[GN_TAPE_APPLIED] = 0.0f;
+    }
     if (cnt < 6.0f) {
         status |= GN_STATUS_FEW;
     } else {
@@ -116,6 +126,10 @@ __global__ __launch_bounds__(1024) void sdf_step_k(float *__restrict__ Dall, con
             for (int k = 0; k < 12; ++k) fin = fin && fabsf(Dn[k]) < INFINITY;
         }
         if (fin) {
+            if constexpr (TAPE) {
+                for (int k = 0; k < 6; ++k) rec[GN_TAPE_XI + k] = xi[k];
+                rec[GN_TAPE_APPLIED] = 1.0f;
+            }
             for (int k = 0; k < 16; ++k) D[k] = Dn[k];
         } else {
             status |= GN_STATUS_SOLVE;
@@ -133,6 +147,12 @@ __global__ __launch_bounds__(256) void sdf_init_k(const float *__restrict__ init
     gn_init(init, B, n_info, Dall, out_T, info);
 }
 
+}  // namespace gs
+
+#include "gs_sdf_bwd.hpp"  // Xb, Lb: the kernels of the reverse pass, after the forward ones
+
+namespace gs {
+
 // ------------------------------------------------------------------ host
 static SdfGrid sdf_grid(int H, int W, int stride, int level) {
     const int s = stride << level;
@@ -143,14 +163,64 @@ struct SdfWs {
     float *partials;  // B x prow x NACC
     int prow;         // partial rows of level 0, the largest grid
 };
-static size_t sdf_layout(int B, int H, int W, int stride, void *ws, SdfWs *w) {
-    Carve c{(char *)ws};
+// the loop's state, which opens the workspace and the tape alike
+static SdfWs sdf_carve_loop(Carve &c, int B, int H, int W, int stride) {
     SdfWs t;
     const SdfGrid g = sdf_grid(H, W, stride, 0);
     t.prow = cdiv((int64_t)g.Hs * g.Ws, SDF_T);
     t.D = c.take<float>(sizeof(float) * 16 * B);
     t.partials = c.take<float>(sizeof(float) * NACC * (size_t)t.prow * B);
+    return t;
+}
+static size_t sdf_layout(int B, int H, int W, int stride, void *ws, SdfWs *w) {
+    Carve c{(char *)ws};
+    const SdfWs t = sdf_carve_loop(c, B, H, W, stride);
     if (w) *w = t;
+    return c.off;
+}
+// the taped forward's buffer: the loop's state, then one tape row per (iteration, batch element) in the order the iterations run
+struct SdfTape {
+    SdfWs f;
+    float *rows;  // max(iterations, 1) x B x GN_TAPE_WORDS
+};
+static size_t sdf_tape_layout(int B, int H, int W, int stride, int64_t iterations, void *tape, SdfTape *out) {
+    Carve c{(char *)tape};
+    SdfTape t;
+    t.f = sdf_carve_loop(c, B, H, W, stride);
+    t.rows = c.take<float>(sizeof(float) * GN_TAPE_WORDS * (size_t)std::max<int64_t>(iterations, 1) * B);
+    if (out) *out = t;
+    return c.off;
+}
+// the reverse pass's working memory; without a volume adjoint there is no fold (fold.maxbits is NULL)
+struct SdfRoom {
+    float *gD, *gP;        // B x 16 each: the carried adjoint of D, the running adjoint of the poses
+    float *adj;            // max(iterations, 1) x B x SDF_ADJ_WORDS, in the order the iterations ran
+    float *partD, *partP;  // B x prow x 12 each
+    int prow;
+    Fold fold;             // B nx ny nz rows x 1 channel
+    void *fold_base;
+    size_t fold_bytes;
+};
+static size_t sdf_room_layout(int B, int H, int W, int stride, int64_t iterations, int64_t nvox, bool want_tsdf, void *room, SdfRoom *out) {
+    Carve c{(char *)room};
+    SdfRoom t;
+    const SdfGrid g = sdf_grid(H, W, stride, 0);
+    t.prow = cdiv((int64_t)g.Hs * g.Ws, SDF_T);
+    t.gD = c.take<float>(sizeof(float) * 16 * B);
+    t.gP = c.take<float>(sizeof(float) * 16 * B);
+    t.adj = c.take<float>(sizeof(float) * SDF_ADJ_WORDS * (size_t)std::max<int64_t>(iterations, 1) * B);
+    t.partD = c.take<float>(sizeof(float) * 12 * (size_t)t.prow * B);
+    t.partP = c.take<float>(sizeof(float) * 12 * (size_t)t.prow * B);
+    t.fold = Fold{nullptr, nullptr, nullptr, 1};
+    t.fold_base = nullptr;
+    t.fold_bytes = 0;
+    if (want_tsdf) {
+        const size_t before = c.off;
+        t.fold = fold_carve(c, (size_t)B * nvox, 1);
+        t.fold_base = t.fold.maxbits;
+        t.fold_bytes = c.off - before;
+    }
+    if (out) *out = t;
     return c.off;
 }
 // The bounds on (B, H, W, stride, levels), once: 0 if the entry points take the shape, else the number of the first bound it
@@ -218,10 +288,133 @@ int gs_sdf_rows(const float *depth, int B, int H, int W, const float *intrinsics
     const SdfVolume vo{tsdf, weight, origin, nx, ny, nz, voxel_size, trunc, trunc / voxel_size, min_weight};
     sdf_launch_linearize(true, depth, B, sdf_grid(H, W, stride, 0), intrinsics, poses, D, vo, w, valid, rows, st);
     GS_LAUNCH_CHECK("gs_sdf_rows/linearize");
-    hipLaunchKernelGGL(sdf_step_k, dim3(B), dim3(1024), 0, st, w.D, w.partials, w.prow, w.prow, 0.0f, 0, 1, 0, 0, (float *)nullptr,
-                       (float *)nullptr, sums);
+    hipLaunchKernelGGL(sdf_step_k<false>, dim3(B), dim3(1024), 0, st, w.D, w.partials, w.prow, w.prow, 0.0f, 0, 1, 0, 0, (float *)nullptr,
+                       (float *)nullptr, sums, (float *)nullptr);
     GS_LAUNCH_CHECK("gs_sdf_rows/sums");
     return 0;
+}
+
+}  // extern "C"
+
+// gs_sdf_odometry (rec = NULL) and gs_sdf_odometry_taped: one loop, the same launches
+static int sdf_run(const float *depth, int B, int H, int W, const float *intrinsics, const float *poses, const float *init,
+                   const SdfVolume &vo, int stride, int levels, const int *numiters, float damp, float *out_T, float *info, const SdfWs &w,
+                   float *rec, hipStream_t st) {
+    const int n_info = B * levels * 4;
+    hipLaunchKernelGGL(sdf_init_k, dim3(cdiv(std::max(16 * B, n_info), 256)), dim3(256), 0, st, init, B, n_info, w.D, out_T, info);
+    GS_LAUNCH_CHECK("gs_sdf_odometry/init");
+    const auto step = rec ? sdf_step_k<true> : sdf_step_k<false>;
+    for (int l = levels - 1; l >= 0; --l) {
+        const SdfGrid g = sdf_grid(H, W, stride, l);
+        const int nblocks = cdiv((int64_t)g.Hs * g.Ws, SDF_T);
+        for (int it = 0; it < numiters[l]; ++it) {
+            sdf_launch_linearize(false, depth, B, g, intrinsics, poses, w.D, vo, w, nullptr, nullptr, st);
+            GS_LAUNCH_CHECK("gs_sdf_odometry/linearize");
+            hipLaunchKernelGGL(step, dim3(B), dim3(1024), 0, st, w.D, w.partials, nblocks, w.prow, damp, l, levels, it, 1, out_T, info,
+                               (float *)nullptr, rec);
+            GS_LAUNCH_CHECK("gs_sdf_odometry/step");
+            if (rec) rec += (size_t)GN_TAPE_WORDS * B;  // one row per (iteration, batch element), in the order the iterations run
+        }
+    }
+    return 0;
+}
+
+#define SDF_REQUIRE_ROOM(name, ptr, have, need) GS_REQUIRE_BYTES_("room", GS_ERR_WORKSPACE_TOO_SMALL, name, ptr, have, need)
+static bool sdf_total_ok(int levels, int64_t numiters_total) { return numiters_total >= 0 && numiters_total <= (int64_t)levels * (1 << 20); }
+static bool sdf_dims_ok(int nx, int ny, int nz) { return nx >= 1 && ny >= 1 && nz >= 1 && (int64_t)nx * ny * nz <= TSDF_NMAX; }
+
+// The reverse pass, for both of its entry points (`nm`: the entry point's launch names).  The loop (gs_sdf_odometry_bwd): the
+// levels finest first, each level's iterations last to first -- Xb, then Lb<MAX> at the tape row's D -- then, if the volume's
+// gradient is wanted, Lb<ACC> over the same iterations at the kept adjoint rows and one finish.  The seam (gs_sdf_rows_bwd,
+// `rows` NULL) is that with one level, one iteration, the caller's `D` (B,16) and the adjoints of `g_sums` for the tape row and
+// Xb, and 12-wide g_poses and g_D for the loop's 16-wide g_poses and g_init.
+struct SdfBwdNames { const char *op, *zero, *begin, *step, *pixels, *corners, *finish, *last; };
+#define SDF_BWD_NAMES(op, begin) SdfBwdNames { op, op "/zero", op begin, op "/step", op "/pixels", op "/corners", op "/finish", op "/last" }
+static int sdf_bwd_run(const SdfBwdNames &nm, const float *depth, int B, int H, int W, const float *intrinsics, const float *poses,
+                       const SdfVolume &vo, int stride, int levels, const int *numiters, float damp, const float *rows, const float *grad_T,
+                       const float *D, const float *g_sums, float *g_depth, float *g_poses, float *g_D, float *g_tsdf, void *room,
+                       size_t room_cap, hipStream_t st) {
+    const bool seam = !rows, want_tsdf = g_tsdf != nullptr;
+    int total = 0, base[GN_MAX_LEVELS];  // base[l]: iterations that ran before level l's (the coarser levels')
+    int64_t terms = 0;                   // a pixel gives a voxel at most one term per iteration
+    for (int l = levels - 1; l >= 0; --l) {
+        const SdfGrid g = sdf_grid(H, W, stride, l);
+        base[l] = total;
+        total += numiters[l];
+        terms += (int64_t)numiters[l] * g.Hs * g.Ws;
+    }
+    const int64_t nvox = (int64_t)vo.nx * vo.ny * vo.nz;
+    const size_t need = sdf_room_layout(B, H, W, stride, total, nvox, want_tsdf, nullptr, nullptr);
+    SDF_REQUIRE_ROOM(nm.op, room, room_cap, need);
+    SdfRoom w;
+    sdf_room_layout(B, H, W, stride, total, nvox, want_tsdf, room, &w);
+    if (g_depth) GS_HIP(hipMemsetAsync(g_depth, 0, sizeof(float) * (size_t)B * H * W, st), nm.zero);
+    if (want_tsdf) GS_HIP(hipMemsetAsync(w.fold_base, 0, w.fold_bytes, st), nm.zero);
+    if (seam) {
+        hipLaunchKernelGGL(sdf_sums_adj_k, dim3(cdiv((int64_t)B * SDF_ADJ_WORDS, 256)), dim3(256), 0, st, g_sums, B, w.adj);
+    } else {
+        hipLaunchKernelGGL(sdf_bwd_begin_k, dim3(cdiv(16 * B, 256)), dim3(256), 0, st, grad_T, B, w.gD, w.gP);
+    }
+    GS_LAUNCH_CHECK(nm.begin);
+    const int lg = fold_lg(std::max<int64_t>(terms, 1));
+    float *partP = g_poses ? w.partP : nullptr;
+    int prev_nblocks = 0;  // rows the pixel pass before left for the next step's fold
+    // iteration `it` of level l: its delta (the seam's D, or the head of its tape row) and the adjoints of its sums
+    const auto D_of = [&](int l, int it) { return seam ? D : rows + (size_t)(base[l] + it) * B * GN_TAPE_WORDS; };
+    const auto adj_of = [&](int l, int it) { return w.adj + (size_t)(base[l] + it) * B * SDF_ADJ_WORDS; };
+    const auto pixels = [&](decltype(&sdf_pixel_bwd_k<SDF_BWD_MAX>) kernel, const char *name, int l, int it) {
+        const SdfGrid g = sdf_grid(H, W, stride, l);
+        hipLaunchKernelGGL(kernel, dim3(cdiv((int64_t)g.Hs * g.Ws, SDF_T), B), dim3(SDF_T), 0, st, depth, g, intrinsics, poses, D_of(l, it),
+                           seam ? 16 : GN_TAPE_WORDS, vo, (const float *)adj_of(l, it), w.fold, lg, g_depth, w.partD, partP, w.prow);
+        GS_LAUNCH_CHECK(name);
+        return 0;
+    };
+    int rc;
+    for (int l = 0; l < levels; ++l) {
+        const SdfGrid g = sdf_grid(H, W, stride, l);
+        const int nblocks = cdiv((int64_t)g.Hs * g.Ws, SDF_T);
+        for (int it = numiters[l] - 1; it >= 0; --it) {
+            if (!seam) {
+                hipLaunchKernelGGL(sdf_step_bwd_k, dim3(B), dim3(BWD_T), 0, st, w.gD, w.gP, (const float *)w.partD, (const float *)partP,
+                                   prev_nblocks, w.prow, D_of(l, it), damp, adj_of(l, it));
+                GS_LAUNCH_CHECK(nm.step);
+            }
+            if ((rc = pixels(sdf_pixel_bwd_k<SDF_BWD_MAX>, nm.pixels, l, it))) return rc;
+            prev_nblocks = nblocks;
+        }
+    }
+    if (want_tsdf) {
+        for (int l = 0; l < levels; ++l)
+            for (int it = numiters[l] - 1; it >= 0; --it)
+                if ((rc = pixels(sdf_pixel_bwd_k<SDF_BWD_ACC>, nm.corners, l, it))) return rc;
+        const int64_t n = (int64_t)B * nvox;
+        hipLaunchKernelGGL(sdf_fold_finish_k, dim3(cdiv(n, 256)), dim3(256), 0, st, w.fold, lg, n, g_tsdf);
+        GS_LAUNCH_CHECK(nm.finish);
+    }
+    // the carried adjoints (the seam has none) + what the last pixel pass left: g_init and g_poses (B,16), or the seam's (B,12)
+    if (g_D) {
+        hipLaunchKernelGGL(sdf_fold12_k, dim3(B), dim3(BWD_T), 0, st, seam ? (const float *)nullptr : (const float *)w.gD,
+                           (const float *)w.partD, prev_nblocks, w.prow, g_D, seam ? 12 : 16);
+        GS_LAUNCH_CHECK(nm.last);
+    }
+    if (g_poses) {
+        hipLaunchKernelGGL(sdf_fold12_k, dim3(B), dim3(BWD_T), 0, st, seam ? (const float *)nullptr : (const float *)w.gP,
+                           (const float *)w.partP, prev_nblocks, w.prow, g_poses, seam ? 12 : 16);
+        GS_LAUNCH_CHECK(nm.last);
+    }
+    return 0;
+}
+
+extern "C" {
+
+size_t gs_sdf_odometry_tape_bytes_for(int B, int H, int W, int stride, int levels, int numiters_total) {
+    if (sdf_shape_fault(B, H, W, stride, levels) != 0 || !sdf_total_ok(levels, numiters_total)) return 0;
+    return sdf_tape_layout(B, H, W, stride, numiters_total, nullptr, nullptr);
+}
+
+size_t gs_sdf_odometry_bwd_room(int B, int H, int W, int stride, int levels, int numiters_total, int nx, int ny, int nz, int want_tsdf) {
+    if (sdf_shape_fault(B, H, W, stride, levels) != 0 || !sdf_total_ok(levels, numiters_total) || !sdf_dims_ok(nx, ny, nz)) return 0;
+    return sdf_room_layout(B, H, W, stride, numiters_total, (int64_t)nx * ny * nz, want_tsdf != 0, nullptr, nullptr);
 }
 
 int gs_sdf_odometry(const float *depth, int B, int H, int W, const float *intrinsics, const float *poses, const float *init,
@@ -238,21 +431,63 @@ int gs_sdf_odometry(const float *depth, int B, int H, int W, const float *intrin
     SdfWs w;
     sdf_layout(B, H, W, stride, ws, &w);
     const SdfVolume vo{tsdf, weight, origin, nx, ny, nz, voxel_size, trunc, trunc / voxel_size, min_weight};
-    const int n_info = B * levels * 4;
-    hipLaunchKernelGGL(sdf_init_k, dim3(cdiv(std::max(16 * B, n_info), 256)), dim3(256), 0, st, init, B, n_info, w.D, out_T, info);
-    GS_LAUNCH_CHECK("gs_sdf_odometry/init");
-    for (int l = levels - 1; l >= 0; --l) {
-        const SdfGrid g = sdf_grid(H, W, stride, l);
-        const int nblocks = cdiv((int64_t)g.Hs * g.Ws, SDF_T);
-        for (int it = 0; it < numiters[l]; ++it) {
-            sdf_launch_linearize(false, depth, B, g, intrinsics, poses, w.D, vo, w, nullptr, nullptr, st);
-            GS_LAUNCH_CHECK("gs_sdf_odometry/linearize");
-            hipLaunchKernelGGL(sdf_step_k, dim3(B), dim3(1024), 0, st, w.D, w.partials, nblocks, w.prow, damp, l, levels, it, 1, out_T, info,
-                               (float *)nullptr);
-            GS_LAUNCH_CHECK("gs_sdf_odometry/step");
-        }
-    }
-    return 0;
+    return sdf_run(depth, B, H, W, intrinsics, poses, init, vo, stride, levels, numiters, damp, out_T, info, w, nullptr, st);
+}
+
+static int sdf_total(int levels, const int *numiters) {
+    int total = 0;
+    for (int l = 0; l < levels; ++l) total += numiters[l];
+    return total;
+}
+
+int gs_sdf_odometry_taped(const float *depth, int B, int H, int W, const float *intrinsics, const float *poses, const float *init,
+                          const float *tsdf, const float *weight, int nx, int ny, int nz, const float *origin, float voxel_size,
+                          float trunc, float min_weight, int stride, int levels, const int *numiters, float damp, float *out_T,
+                          float *info, void *tape, size_t tape_cap, gs_stream_t stream) {
+    GS_REQUIRE(depth && intrinsics && poses && tsdf && weight && origin && numiters && out_T && info, "gs_sdf_odometry_taped: null pointer");
+    SDF_REQUIRE_SHAPE("gs_sdf_odometry_taped");
+    SDF_REQUIRE_VOLUME("gs_sdf_odometry_taped");
+    GN_REQUIRE_LOOP("gs_sdf_odometry_taped");
+    const int total = sdf_total(levels, numiters);
+    const size_t need = sdf_tape_layout(B, H, W, stride, total, nullptr, nullptr);
+    GS_REQUIRE_TAPE("gs_sdf_odometry_taped", tape, tape_cap, need, GS_ERR_WORKSPACE_TOO_SMALL);
+    SdfTape t;
+    sdf_tape_layout(B, H, W, stride, total, tape, &t);
+    const SdfVolume vo{tsdf, weight, origin, nx, ny, nz, voxel_size, trunc, trunc / voxel_size, min_weight};
+    return sdf_run(depth, B, H, W, intrinsics, poses, init, vo, stride, levels, numiters, damp, out_T, info, t.f, t.rows, (hipStream_t)stream);
+}
+
+int gs_sdf_odometry_bwd(const float *depth, int B, int H, int W, const float *intrinsics, const float *poses, const float *tsdf,
+                        const float *weight, int nx, int ny, int nz, const float *origin, float voxel_size, float trunc,
+                        float min_weight, int stride, int levels, const int *numiters, float damp, const void *tape, size_t tape_cap,
+                        const float *grad_T, float *g_depth, float *g_poses, float *g_init, float *g_tsdf, void *room, size_t room_cap,
+                        gs_stream_t stream) {
+    GS_REQUIRE(depth && intrinsics && poses && tsdf && weight && origin && numiters && grad_T, "gs_sdf_odometry_bwd: null pointer");
+    SDF_REQUIRE_SHAPE("gs_sdf_odometry_bwd");
+    SDF_REQUIRE_VOLUME("gs_sdf_odometry_bwd");
+    GN_REQUIRE_LOOP("gs_sdf_odometry_bwd");
+    const int total = sdf_total(levels, numiters);
+    const size_t need = sdf_tape_layout(B, H, W, stride, total, nullptr, nullptr);
+    GS_REQUIRE_TAPE("gs_sdf_odometry_bwd", tape, tape_cap, need, GS_ERR_WORKSPACE_TOO_SMALL);
+    SdfTape t;
+    sdf_tape_layout(B, H, W, stride, total, const_cast<void *>(tape), &t);
+    const SdfVolume vo{tsdf, weight, origin, nx, ny, nz, voxel_size, trunc, trunc / voxel_size, min_weight};
+    return sdf_bwd_run(SDF_BWD_NAMES("gs_sdf_odometry_bwd", "/begin"), depth, B, H, W, intrinsics, poses, vo, stride, levels, numiters, damp,
+                       t.rows, grad_T, nullptr, nullptr, g_depth, g_poses, g_init, g_tsdf, room, room_cap, (hipStream_t)stream);
+}
+
+int gs_sdf_rows_bwd(const float *depth, int B, int H, int W, const float *intrinsics, const float *poses, const float *D,
+                    const float *tsdf, const float *weight, int nx, int ny, int nz, const float *origin, float voxel_size, float trunc,
+                    float min_weight, int stride, const float *g_sums, float *g_depth, float *g_poses, float *g_D, float *g_tsdf,
+                    void *room, size_t room_cap, gs_stream_t stream) {
+    GS_REQUIRE(depth && intrinsics && poses && D && tsdf && weight && origin && g_sums, "gs_sdf_rows_bwd: null pointer");
+    const int levels = 1;
+    SDF_REQUIRE_SHAPE("gs_sdf_rows_bwd");
+    SDF_REQUIRE_VOLUME("gs_sdf_rows_bwd");
+    const int one = 1;  // one level, one iteration
+    const SdfVolume vo{tsdf, weight, origin, nx, ny, nz, voxel_size, trunc, trunc / voxel_size, min_weight};
+    return sdf_bwd_run(SDF_BWD_NAMES("gs_sdf_rows_bwd", "/adjoints"), depth, B, H, W, intrinsics, poses, vo, stride, levels, &one, 0.0f,
+                       nullptr, nullptr, D, g_sums, g_depth, g_poses, g_D, g_tsdf, room, room_cap, (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -20,12 +20,17 @@ class SDFOdometryProvider(OdometryProvider):
     count at every level); level l uses the pixel grid [::stride 2^l, ::stride 2^l] (there is no pyramid); a pixel counts where
     all 8 voxels around its point have weight >= `min_weight` and none of them is clamped free space.
 
-    Gradients are not implemented: under autograd a depth, poses, `init` or a volume tsdf that requires one is refused rather than
-    cut silently (the stance of RGBDOdometryProvider(differentiable=False)).  `last_info` is not differentiable."""
+    `differentiable=False` (the default): no gradients; under autograd a depth, poses, `init` or a volume tsdf that requires one is
+    refused rather than cut silently (the stance of RGBDOdometryProvider(differentiable=False)).  `differentiable=True`: the
+    transform carries the graph (ops.sdf_odometry: one autograd node, the decisions of the forward pass held constant) and
+    gradients reach the depth, rows 0..2 of the poses and of `init`, and the volume's tsdf; never the intrinsics, which are refused
+    when they require a gradient.  `last_info` is not differentiable."""
 
     def __init__(self, numiters: Union[int, Sequence[int]] = (10, 5, 3), levels: int = 3, stride: int = 1, min_weight: float = 1.0,
-                 damp: float = 1e-8):
+                 damp: float = 1e-8, differentiable: bool = False):
         numiters = check_levels_numiters("SDFOdometryProvider", numiters, levels)
+        if not isinstance(differentiable, bool):
+            raise TypeError("SDFOdometryProvider: differentiable should be a bool. Got {!r}.".format(differentiable))
         if not isinstance(stride, int) or isinstance(stride, bool) or stride < 1:
             raise ValueError("SDFOdometryProvider: stride should be a positive integer. Got {!r}.".format(stride))
         self.numiters = numiters
@@ -33,6 +38,7 @@ class SDFOdometryProvider(OdometryProvider):
         self.stride = stride
         self.min_weight = min_weight
         self.damp = damp
+        self.differentiable = differentiable
         self.last_info = None  # (B, levels, 4) on the device, unsynchronised: cnt, err, status bits, iterations per level
 
     def provide(self, volume: TSDFVolume, source_frames: RGBDImages, init: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -52,12 +58,12 @@ class SDFOdometryProvider(OdometryProvider):
         B = len(volume)
         check_init(init, B)
         tensors = [source_frames.depth_image, source_frames.poses, init, volume.tsdf]
-        if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in tensors):
+        if not self.differentiable and torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in tensors):
             raise NotImplementedError("SDFOdometryProvider: gradients are not implemented; detach the frames, the poses, init and "
                                       "the volume, or call under torch.no_grad().")
         src = source_frames.to_channels_last() if source_frames.channels_first else source_frames
         T, info = ops.sdf_odometry(src.depth_image[:, 0], src.intrinsics, src.poses[:, 0], volume.tsdf, volume.weight, volume.origin,
                                    volume.voxel_size, volume.trunc, init, self.numiters, self.levels, self.stride, self.min_weight,
-                                   self.damp)
+                                   self.damp, differentiable=self.differentiable)
         self.last_info = info
         return T.unsqueeze(1)

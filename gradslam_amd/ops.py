@@ -1890,10 +1890,12 @@ def rgbd_odometry(tgt_depth, tgt_rgb, src_depth, src_rgb, intrinsics, init=None,
 
 
 # ------------------------------------------------------------------ SDF odometry (csrc/sdf.hip)
-def _sdf_args(op, depth, intrinsics, poses, tsdf, weight, origin, voxel_size, trunc, min_weight, stride, levels, **transforms):
+def _sdf_args(op, depth, intrinsics, poses, tsdf, weight, origin, voxel_size, trunc, min_weight, stride, levels, attached=False,
+              **transforms):
     """The checked inputs of sdf_rows_raw / sdf_odometry (the caller requires the HIP device, after its own checks): depth (B,H,W[,1]), intrinsics, poses and the
     named transforms (B,4,4) or (B,1,4,4), the volume's tsdf / weight (B,nz,ny,nx) and origin -> (tensors to keep alive, named
-    transforms as (B,16) or None, (B, H, W), the C argument lists up to `stride`)."""
+    transforms as (B,16) or None, (B, H, W), the C argument lists up to `stride`).  `attached`: depth, poses, the named
+    transforms and tsdf keep their graphs (contiguous fp32 all the same), for the autograd node."""
     for name, t in (("depth", depth), ("intrinsics", intrinsics), ("poses", poses), ("tsdf", tsdf), ("weight", weight)):
         if not torch.is_tensor(t):
             raise TypeError("{}: expected {} to be a tensor; got {}".format(op, name, type(t)))
@@ -1903,8 +1905,8 @@ def _sdf_args(op, depth, intrinsics, poses, tsdf, weight, origin, voxel_size, tr
         raise ValueError("{}: depth should have shape (B, H, W) or (B, H, W, 1). Got {}.".format(op, tuple(depth.shape)))
     B, H, W = (int(n) for n in depth.shape)
     K = _rgbd_K(intrinsics, B, op)
-    poses = _rgbd_T(poses, B, "poses", op)
-    named = {n: (None if t is None else _rgbd_T(t, B, n, op)) for n, t in transforms.items()}
+    poses = _rgbd_T(poses, B, "poses", op, attached=attached)
+    named = {n: (None if t is None else _rgbd_T(t, B, n, op, attached=attached)) for n, t in transforms.items()}
     if tsdf.ndim != 4 or tsdf.shape[0] != B:
         raise ValueError("{}: tsdf should have shape ({}, nz, ny, nx), the frames' batch size. Got {}.".format(op, B, tuple(tsdf.shape)))
     _, dims = _tsdf_volume(tsdf, weight, op)
@@ -1916,7 +1918,10 @@ def _sdf_args(op, depth, intrinsics, poses, tsdf, weight, origin, voxel_size, tr
     if -(-H // s) < 4 or -(-W // s) < 4:
         raise ValueError("{}: the coarsest of {} grids of a {} x {} image at stride {} would be smaller than 4 x 4.".format(
             op, levels, H, W, stride))
-    depth, tsdf, weight = _f32c(depth.detach()), _f32c(tsdf.detach()), _f32c(weight.detach())
+    if attached:
+        depth, tsdf, weight = depth.float().contiguous(), tsdf.float().contiguous(), _f32c(weight.detach())
+    else:
+        depth, tsdf, weight = _f32c(depth.detach()), _f32c(tsdf.detach()), _f32c(weight.detach())
     origin = tsdf_origin(origin, B, tsdf.device, op)
     keep = (depth, K, poses, tsdf, weight, origin)
     return keep, named, (B, H, W), (ptr(depth), B, H, W, ptr(K), ptr(poses)), (ptr(tsdf), ptr(weight), *dims, ptr(origin), v, tr, mw, stride)
@@ -1941,22 +1946,94 @@ def sdf_rows_raw(depth, intrinsics, poses, D, tsdf, weight, origin, voxel_size, 
     return valid, rows, sums
 
 
+def sdf_rows_bwd_raw(depth, intrinsics, poses, D, g_sums, tsdf, weight, origin, voxel_size, trunc, min_weight: float = 1.0,
+                     stride: int = 1, want_tsdf: bool = True):
+    """The reverse of sdf_rows_raw, the decisions held constant: g_sums (B,29), the adjoint of `sums` as sdf_rows_raw returns them
+    (err's is honoured, cnt's ignored) -> (g_depth (B,H,W), g_poses (B,3,4), g_D (B,3,4): rows 0..2 of the poses' and of D's,
+    g_tsdf (B,nz,ny,nx), or None with `want_tsdf=False`: no fold, no fold memory).  The seam the tests check."""
+    op = "sdf_rows_bwd"
+    keep, named, (B, H, W), frame, volume = _sdf_args(op, depth, intrinsics, poses, tsdf, weight, origin, voxel_size, trunc, min_weight,
+                                                      stride, 1, D=D)
+    if named["D"] is None:
+        raise TypeError("{}: expected D to be a tensor; got {}".format(op, type(D)))
+    if not torch.is_tensor(g_sums) or tuple(g_sums.shape) != (B, 29):
+        raise ValueError("{}: g_sums should be a tensor of shape ({}, 29).".format(op, B))
+    g_sums = _f32c(g_sums.detach())
+    require_hip(*keep, named["D"], g_sums, op=op)
+    dev, dims = keep[0].device, volume[2:5]
+    g_depth = torch.empty((B, H, W), dtype=torch.float32, device=dev)
+    g_poses, g_D = (torch.empty((B, 3, 4), dtype=torch.float32, device=dev) for _ in range(2))
+    g_tsdf = torch.empty_like(keep[3]) if want_tsdf else None
+    room = torch.empty(ws_bytes("gs_sdf_odometry_bwd_room", B, H, W, stride, 1, 1, *dims, int(bool(want_tsdf))), dtype=torch.uint8, device=dev)
+    call("gs_sdf_rows_bwd", *frame, ptr(named["D"]), *volume, ptr(g_sums), ptr(g_depth), ptr(g_poses), ptr(g_D), ptr(g_tsdf), ptr(room),
+         room.numel(), stream())
+    return g_depth, g_poses, g_D, g_tsdf
+
+
+class _SdfOdometryFn(torch.autograd.Function):
+    """sdf_odometry as one autograd node: the taped forward (the plain call's bits) and gs_sdf_odometry_bwd.  depth (B,H,W), poses
+    (B,16), tsdf, weight, K, origin are contiguous fp32; init (B,16) contiguous fp32 or None.  The tape is allocated here and kept
+    until the reverse pass; the reverse pass's room -- 20 bytes per voxel when tsdf takes a gradient -- only while it runs."""
+
+    @staticmethod
+    def forward(ctx, depth, poses, init, tsdf, weight, K, origin, dims, v, tr, mw, stride, levels, numiters, damp):
+        (B, H, W), dev = depth.shape, depth.device
+        out_T, info, counts = _gn_outputs(B, numiters, dev)
+        tape = torch.empty(ws_bytes("gs_sdf_odometry_tape_bytes_for", B, H, W, stride, levels, sum(numiters)), dtype=torch.uint8, device=dev)
+        call("gs_sdf_odometry_taped", ptr(depth), B, H, W, ptr(K), ptr(poses), ptr(init), ptr(tsdf), ptr(weight), *dims, ptr(origin), v, tr,
+             mw, stride, levels, counts, damp, ptr(out_T), ptr(info), ptr(tape), tape.numel(), stream())
+        ctx.save_for_backward(depth, poses, tsdf, weight, K, origin, tape)
+        ctx.params = (dims, v, tr, mw, stride, levels, numiters, damp, init is not None)
+        ctx.mark_non_differentiable(info)
+        return out_T, info
+
+    @staticmethod
+    def backward(ctx, grad_T, _grad_info):
+        depth, poses, tsdf, weight, K, origin, tape = ctx.saved_tensors
+        dims, v, tr, mw, stride, levels, numiters, damp, has_init = ctx.params
+        (B, H, W), dev = depth.shape, depth.device
+        grad_T = _f32c(grad_T)
+        need = list(ctx.needs_input_grad[:4])
+        need[2] = need[2] and has_init
+        g_depth = torch.empty_like(depth) if need[0] else None
+        g_poses, g_init = (torch.empty((B, 16), dtype=torch.float32, device=dev) if n else None for n in need[1:3])
+        g_tsdf = torch.empty_like(tsdf) if need[3] else None
+        room = torch.empty(ws_bytes("gs_sdf_odometry_bwd_room", B, H, W, stride, levels, sum(numiters), *dims, int(need[3])),
+                           dtype=torch.uint8, device=dev)
+        counts = (nv.c_i * levels)(*numiters)
+        call("gs_sdf_odometry_bwd", ptr(depth), B, H, W, ptr(K), ptr(poses), ptr(tsdf), ptr(weight), *dims, ptr(origin), v, tr, mw, stride,
+             levels, counts, damp, ptr(tape), tape.numel(), ptr(grad_T), ptr(g_depth), ptr(g_poses), ptr(g_init), ptr(g_tsdf), ptr(room),
+             room.numel(), stream())
+        return (g_depth, g_poses, g_init, g_tsdf) + (None,) * 11
+
+
 def sdf_odometry(depth, intrinsics, poses, tsdf, weight, origin, voxel_size, trunc, init=None, numiters=(10, 5, 3), levels: int = 3,
-                 stride: int = 1, min_weight: float = 1.0, damp: float = 1e-8):
+                 stride: int = 1, min_weight: float = 1.0, damp: float = 1e-8, differentiable: bool = False):
     """SDF odometry (the rule of include/gradslam_hip.h): the frame depth (B,H,W[,1]) carrying the camera-to-world poses (B,4,4)
     is aligned directly against the volume tsdf / weight (B,nz,ny,nx) at `origin` -- no ray cast, no cloud -> (T (B,4,4), the
     WORLD-frame delta: the new pose is compose_transformations(T, poses), the ICP providers' convention; info (B,levels,4) = cnt,
     err, status bits, iterations per level).  Level l uses the pixel grid [::stride 2^l, ::stride 2^l]; `numiters`: iterations per
-    level, finest first (an int: that count at every level).  No host synchronisation.  No gradients: under autograd, a depth,
-    poses, init or tsdf that requires one is refused rather than cut silently."""
+    level, finest first (an int: that count at every level).  No host synchronisation.  `differentiable=False` (the default): no
+    gradients: under autograd, a depth, poses, init or tsdf that requires one is refused rather than cut silently.
+    `differentiable=True`: when grad mode is on and one of them requires a gradient, T carries the graph -- one autograd node, the
+    taped forward (the same bits) and a reverse pass on the device that holds every decision of the forward constant (the gates,
+    the cells, which steps were applied); of poses and `init` rows 0..2 are differentiable; weight, origin, the scalar parameters
+    and info are not, nor are the intrinsics (with `differentiable=True` intrinsics that require a gradient are refused)."""
     op = "sdf_odometry"
-    if torch.is_grad_enabled() and any(torch.is_tensor(t) and t.requires_grad for t in (depth, poses, init, tsdf)):
+    wants = torch.is_grad_enabled() and any(torch.is_tensor(t) and t.requires_grad for t in (depth, poses, init, tsdf))
+    if wants and not differentiable:
         raise NotImplementedError("{}: gradients are not implemented (the reverse pass is not built); detach the inputs or call "
                                   "under torch.no_grad().".format(op))
+    if differentiable and torch.is_grad_enabled() and torch.is_tensor(intrinsics) and intrinsics.requires_grad:
+        raise NotImplementedError("{}: gradients with respect to the intrinsics are not implemented; detach them.".format(op))
     keep, named, (B, H, W), frame, volume = _sdf_args(op, depth, intrinsics, poses, tsdf, weight, origin, voxel_size, trunc, min_weight,
-                                                      stride, levels, init=init)
+                                                      stride, levels, attached=wants, init=init)
     numiters, damp = _gn_loop(numiters, levels, damp, op)
     require_hip(*keep, named["init"], op=op)
+    if wants:
+        depth, K, poses, tsdf, weight, origin = keep
+        return _SdfOdometryFn.apply(depth, poses, named["init"], tsdf, weight, K, origin, tuple(volume[2:5]), *volume[6:10], levels,
+                                    numiters, damp)
     dev = keep[0].device
     out_T, info, counts = _gn_outputs(B, numiters, dev)
     ws = workspace(ws_bytes("gs_sdf_odometry_ws_size", B, H, W, stride), dev, "sdf")

@@ -56,8 +56,12 @@ class KinectFusion(nn.Module):
         pose_s = compose_transformations(odomprov.provide(volume, live frame carrying pose_{s-1}), pose_{s-1})
 
     There is no ray cast, no cloud and no host read.  A camera that sees nothing of the volume leaves the pose where it was and
-    sets the status bit, as `odom="rgbd"` does.  It has no reverse pass: `odom_gradients=True` is refused, and under autograd
-    inputs that require gradients raise NotImplementedError."""
+    sets the status bit, as `odom="rgbd"` does.  `odom="sdf"` carries no gradients: `odom_gradients=True` is refused, and under
+    autograd inputs that require gradients raise NotImplementedError.  `odom="gradsdf"` (named as "icp" / "gradicp" are) is the
+    same tracker built with `differentiable=True`: the same poses bit for bit, and the transform carries the graph -- gradients
+    reach the live frame's depth, the previous pose and the volume's tsdf (so the depths of the frames fused before) through
+    where the frame was put; the volume and the previous poses are handed over as they are.  `odom_gradients` does not apply to
+    it and is refused."""
 
     def __init__(self, *, dims, voxel_size, origin=(0.0, 0.0, 0.0), trunc=None, max_weight: float = 128.0, color: bool = True,
                  odom: str = "gradicp", dsratio: int = 4, numiters: int = 20, damp: float = 1e-8,
@@ -66,9 +70,9 @@ class KinectFusion(nn.Module):
                  device: Union[torch.device, str, None] = None, levels: int = 3, lambda_geo: float = 0.968,
                  pose_gradients: bool = False, odom_gradients: bool = False):
         super().__init__()
-        if odom not in ["gt", "icp", "gradicp", "rgbd", "sdf"]:
+        if odom not in ["gt", "icp", "gradicp", "rgbd", "gradsdf", "sdf"]:
             msg = "odometry method ({}) not supported for KinectFusion. ".format(odom)
-            msg += "Currently supported odometry modules for KinectFusion are: 'gt', 'icp', 'gradicp', 'rgbd', 'sdf'"
+            msg += "Currently supported odometry modules for KinectFusion are: 'gt', 'icp', 'gradicp', 'rgbd', 'gradsdf', 'sdf'"
             raise ValueError(msg)
         if odom == "rgbd" and not color:
             raise ValueError("KinectFusion: odom='rgbd' tracks against the colours of the volume and needs color=True.")
@@ -79,8 +83,8 @@ class KinectFusion(nn.Module):
         if not isinstance(odom_gradients, bool):
             raise TypeError("KinectFusion: odom_gradients should be a bool. Got {!r}.".format(odom_gradients))
         if odom_gradients and odom != "rgbd":
-            raise ValueError("KinectFusion: odom_gradients belongs to odom='rgbd' (the ICP providers always carry gradients; "
-                             "odom='sdf' has no reverse pass).")
+            raise ValueError("KinectFusion: odom_gradients belongs to odom='rgbd' (the ICP providers and odom='gradsdf' always "
+                             "carry gradients; odom='sdf' never does).")
         odomprov = None
         if odom == "icp":
             odomprov = ICPOdometryProvider(numiters, damp, dist_thresh)
@@ -88,8 +92,9 @@ class KinectFusion(nn.Module):
             odomprov = GradICPOdometryProvider(numiters, damp, dist_thresh, lambda_max, B, B2, nu)
         elif odom == "rgbd":
             odomprov = RGBDOdometryProvider(numiters, levels, lambda_geo, damp=damp, differentiable=odom_gradients)
-        elif odom == "sdf":
-            odomprov = SDFOdometryProvider(numiters, levels, stride=dsratio, min_weight=min_weight, damp=damp)
+        elif odom in ("sdf", "gradsdf"):
+            odomprov = SDFOdometryProvider(numiters, levels, stride=dsratio, min_weight=min_weight, damp=damp,
+                                           differentiable=odom == "gradsdf")
         self.odom = odom
         self.odomprov = odomprov
         self.dsratio = dsratio
@@ -161,7 +166,7 @@ class KinectFusion(nn.Module):
         if live_frame.channels_first:
             live_frame = live_frame.to_channels_last()
         H, W = live_frame.shape[2:4]
-        if self.odom == "sdf":  # no cast, no cloud, no host read: the frame under the previous pose against the volume itself
+        if self.odom in ("sdf", "gradsdf"):  # no cast, no cloud, no host read: the frame under the previous pose against the volume itself
             source = RGBDImages(live_frame.rgb_image, live_frame.depth_image, live_frame.intrinsics, prev_frame.poses)
             transform = self.odomprov.provide(volume, source)
             return compose_transformations(transform.squeeze(1), prev_frame.poses.squeeze(1)).unsqueeze(1)

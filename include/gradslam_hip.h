@@ -1082,6 +1082,69 @@ int gs_sdf_rows(const float *depth, int B, int H, int W, const float *intrinsics
                 const float *weight, int nx, int ny, int nz, const float *origin, float voxel_size, float trunc, float min_weight,
                 int stride, int32_t *valid, float *rows, float *sums, void *ws, size_t ws_bytes, gs_stream_t stream);
 
+/* The reverse pass of the SDF odometry.  It differentiates the rule above with every DECISION HELD CONSTANT: the depth gate, the
+ * cell a point falls in (floorf per axis and the bounds), the weight gate and the free-space gate, cnt < 6, and whether a step was
+ * applied (a step that was not is the identity and its adjoint passes through).  Differentiable: depth, rows 0..2 of poses and
+ * of `init` (the bottom rows are the constant (0, 0, 0, 1): their gradients are zero) and the volume's tsdf.  Not differentiable:
+ * weight, origin, the intrinsics, the scalar parameters, info.  Only rows 0..2 of grad_T are read.  fp32 in the order written.
+ *   tape       gs_sdf_odometry_taped is gs_sdf_odometry -- the same loop, the same launches, out_T and info bit for bit -- whose
+ *              step also writes gs_rgbd_odometry_taped's row of 64 floats per (iteration, batch element), in the order the
+ *              iterations run: D before the step (16) | the 29 sums as reduced | xi (6) | 1 if the step was applied, else 0.
+ *   step       gs_rgbd_odometry_bwd's, iterations last to first (level 0 first): D-bar_{k+1} = the carried adjoint + the 12 sums
+ *              that iteration k+1's pixel pass left; dD-bar = D-bar_{k+1} D_k^T, D-bar_k = dD^T D-bar_{k+1}, xi-bar from the
+ *              exponential's adjoint, y = (H + damp I)^-1 xi-bar (fp64), H-bar = -y xi^T, g-bar = y.  The same launch adds the
+ *              12 sums of the poses' adjoint that iteration k+1's pixel pass left onto the running g_poses.
+ *   pixels     the pixel's forward values again at the taped D_k, by the forward's operations in the forward's order.  With M the
+ *              symmetric 6 x 6 of H-bar with its diagonal doubled, gv the adjoints of the six sums J r and e2 = 2 err-bar:
+ *                Jb = M J + gv r   (Jb_u = gv_u r, then + M_uk J_k for k = 0..5);   rb = e2 r, then + gv_u J_u for u = 0..5;
+ *                n = J[0..2], m = Jb[3..5]:  nb = Jb[0..2] + m x q,  qb = n x m;   gb = kappa nb,  fhb = trunc rb;
+ *                corner c (x + 2 y + 4 z) receives  ((fhb W_c + gb_x dW_c/da_x) + gb_y dW_c/da_y) + gb_z dW_c/da_z  with
+ *                W_c = (w_x w_y) w_z, w = a at the far end of an axis and 1 - a at the near end, dW_c/da_x = (+-w_y) w_z,
+ *                dW_c/da_y = (+-w_x) w_z, dW_c/da_z = +-(w_x w_y);
+ *                ab = fhb g + Hess gb, Hess with a zero diagonal and H_xy = lerp((f3 - f2) - (f1 - f0), (f7 - f6) - (f5 - f4), a_z),
+ *                H_xz = lerp((f5 - f4) - (f1 - f0), (f7 - f6) - (f3 - f2), a_y), H_yz = lerp((f6 - f4) - (f2 - f0), (f7 - f5) - (f3 - f1), a_x),
+ *                ab_x = (fhb g_x + H_xy gb_y) + H_xz gb_z, and so on;   qb += ab / v;
+ *                D-bar += qb (x) (pw, 1);   pwb_j = (D_0j qb_x + D_1j qb_y) + D_2j qb_z;   P-bar += pwb (x) (px, py, d, 1);
+ *                pxb = (P_00 pwb_x + P_10 pwb_y) + P_20 pwb_z, pyb likewise with column 1,
+ *                db = (((P_02 pwb_x + P_12 pwb_y) + P_22 pwb_z) + pxb ux) + pyb vy,  ux = ((float)w - cx) / fx, vy = ((float)h - cy) / fy.
+ *   sums       D and P: 12 sums each per block of 256 pixels (wave butterflies, offsets 32 .. 1, then the 4 waves in order), the
+ *              blocks' rows g, g + 16, .. in order and the 16 group sums in order.  depth: the pixel's own lane adds into
+ *              g_depth (zeroed once), iteration after iteration, level after level.  tsdf -- many pixels land in one cell -- :
+ *              ONE exact fold of csrc/gs_fixed128.hpp over B nx ny nz rows for the whole loop, at most
+ *              2^ceil(log2(sum_l numiters[l] Hs_l Ws_l)) terms per voxel, rounded once.  No float atomics: the same bits from
+ *              run to run.
+ * Two launches per iteration (step reverse; pixels) and, when g_tsdf is asked for, the pixels of every iteration once more for
+ * the fold and one finish; nothing synchronises the host.  Outputs: g_depth (B,H,W), g_poses (B,16), g_init (B,16), g_tsdf
+ * (B,nz,ny,nx), each written in full; any may be NULL, and its work is skipped.
+ * Memory.  These entry points own two buffers with different lifetimes, so they take them by name with a capacity (`tape`,
+ * `tape_cap`; `room`, `room_cap`) instead of one (ws, ws_bytes): the tape is written by the forward pass and kept until the
+ * reverse pass; the room -- 20 bytes per voxel when g_tsdf is wanted -- exists only during the reverse pass.  Both are checked
+ * before any device work (code -2, "tape too small" / "room too small"); a query returns 0 for a shape the entry points refuse.
+ * numiters_total is the SUM of the levels' counts, N = max(numiters_total, 1), R = ceil(Hs Ws / 256) with Hs = ceil(H / stride);
+ * every piece rounded up to 256 bytes:
+ *   tape   64 B (D) | 116 B R (partial rows) | 256 B N (the tape rows)
+ *   room   64 B (D-bar) | 64 B (P-bar) | 128 B N (the sums' adjoints) | 48 B R (D's rows) | 48 B R (P's rows) | with want_tsdf the
+ *          fold of B nx ny nz rows x 1 channel: 4 | 4 B nx ny nz | 16 B nx ny nz. */
+size_t gs_sdf_odometry_tape_bytes_for(int B, int H, int W, int stride, int levels, int numiters_total);
+size_t gs_sdf_odometry_bwd_room(int B, int H, int W, int stride, int levels, int numiters_total, int nx, int ny, int nz, int want_tsdf);
+int gs_sdf_odometry_taped(const float *depth, int B, int H, int W, const float *intrinsics, const float *poses, const float *init,
+                          const float *tsdf, const float *weight, int nx, int ny, int nz, const float *origin, float voxel_size,
+                          float trunc, float min_weight, int stride, int levels, const int *numiters, float damp, float *out_T,
+                          float *info, void *tape, size_t tape_cap, gs_stream_t stream);
+int gs_sdf_odometry_bwd(const float *depth, int B, int H, int W, const float *intrinsics, const float *poses, const float *tsdf,
+                        const float *weight, int nx, int ny, int nz, const float *origin, float voxel_size, float trunc,
+                        float min_weight, int stride, int levels, const int *numiters, float damp, const void *tape, size_t tape_cap,
+                        const float *grad_T, float *g_depth, float *g_poses, float *g_init, float *g_tsdf, void *room, size_t room_cap,
+                        gs_stream_t stream);
+/* The reverse of gs_sdf_rows: g_sums (B,29) is the adjoint of `sums` exactly as gs_sdf_rows returns them (g is MINUS the sum);
+ * err's adjoint is honoured, cnt's is ignored.  g_depth (B,H,W), g_poses (B,12) and g_D (B,12): rows 0..2 of P's and D's, g_tsdf
+ * (B,nz,ny,nx); any may be NULL.  One level, one iteration, the same kernels.  The room of
+ * gs_sdf_odometry_bwd_room(B, H, W, stride, 1, 1, nx, ny, nz, g_tsdf != NULL). */
+int gs_sdf_rows_bwd(const float *depth, int B, int H, int W, const float *intrinsics, const float *poses, const float *D,
+                    const float *tsdf, const float *weight, int nx, int ny, int nz, const float *origin, float voxel_size, float trunc,
+                    float min_weight, int stride, const float *g_sums, float *g_depth, float *g_poses, float *g_D, float *g_tsdf,
+                    void *room, size_t room_cap, gs_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

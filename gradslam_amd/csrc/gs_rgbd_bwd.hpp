@@ -1,11 +1,10 @@
-// gs_rgbd_bwd.hpp -- the kernels of the dense RGB-D odometry's reverse pass (the rule: include/gradslam_hip.h).  Included by rgbd.hip,
-// which launches them (rgbd_bwd_run); the pixel's forward values and the pyramid's rules are gs_rgbd_pixel.hpp's, the forward's own code.
-// The tape row's layout (GN_TAPE_*) is gs_gn_step.hpp's, which rgbd.hip includes before this header.
+// gs_rgbd_bwd.hpp -- the dense RGB-D odometry's own kernels of its reverse pass (the rule: include/gradslam_hip.h).  Included by
+// rgbd.hip, which launches them (rgbd_bwd_run); the pixel's forward values and the pyramid's rules are gs_rgbd_pixel.hpp's, the
+// forward's own code.  The step reverse, the fold of the 12-wide rows, the seam's adjoint row and the layouts of the tape row
+// (GN_TAPE_*) and of the adjoint row (GN_ADJ_*) are gs_gn_step.hpp's, shared with sdf.hip; rgbd.hip includes it before this header.
 // Per iteration, last to first:
-// Xb step reverse, one 256-thread block per batch element: the pixel pass before left 12-sum rows -- the adjoint of T_{k+1}
-//    through ITS linearisation -- which are folded (fold_rows) into the carried adjoint; then, one lane, fp64 where the forward's
-//    fp32 value would lose the gradient: dT-bar = T-bar_{k+1} T_k^T, T-bar_k = dT^T T-bar_{k+1}, the exponential's and the
-//    solve's adjoints -> the adjoints of the iteration's 29 sums.  A step that was not applied is the identity.
+// Xb step reverse (gn_step_bwd_k<false>): folds the 12-sum rows the pixel pass before left into the carried adjoint of T and
+//    leaves the adjoints of the iteration's 28 sums.
 // Lb pixel reverse, the forward's geometry: the pixel's forward values again from the taped T_k (rgbd_pixel_fwd, rgbd_chan_row),
 //    the adjoints of its two rows and residuals from those of the sums, pulled back to q, the eight corner values, the source
 //    pixel and T.  <MAX> does all of it but the corner sums, of which it takes the largest magnitude; <ACC> only adds the corner
@@ -14,67 +13,12 @@
 #pragma once
 
 #include "gs_fixed128.hpp"
+#include "gs_gn_step.hpp"
 #include "gs_rgbd_pixel.hpp"
-#include "gs_se3_bwd.hpp"
 
 namespace gs {
 
-constexpr int RGBD_ADJ_WORDS = 32;  // adjoints of the 28 sums AS REDUCED (the six of g: of the sum, not of minus it; cnt has none)
-constexpr int RGBD_ADJ_LIVE = 28;   // 1: the pixel pass applies them; 0: a step that was not applied -- nothing, not even 0 x inf
 enum { RGBD_BWD_MAX = 0, RGBD_BWD_ACC = 1 };
-
-// out[b] (stride floats, 12 or 16: the bottom row is zero) = gT_in[b] rows 0..2 (NULL: zero) + the sum of b's 12-wide rows
-__global__ __launch_bounds__(BWD_T) void rgbd_gT_k(const float *__restrict__ gT_in, const float *__restrict__ partials12, int nblocks,
-                                                  int prow, float *__restrict__ out, int stride) {
-    __shared__ float sums[12];
-    const int b = blockIdx.x;
-    fold_rows<12, BWD_GROUPS, 16>(partials12 + (int64_t)b * prow * 12, nblocks, 12, sums);
-    if ((int)threadIdx.x < stride)
-        out[stride * b + threadIdx.x] = threadIdx.x < 12 ? (gT_in ? gT_in[16 * b + threadIdx.x] : 0.0f) + sums[threadIdx.x] : 0.0f;
-}
-
-// gs_rgbd_rows_bwd: the adjoints of the sums as gs_rgbd_rows returns them (g = MINUS the sum) -> of the sums as reduced; the
-// adjoint of cnt is ignored
-__global__ __launch_bounds__(256) void rgbd_sums_adj_k(const float *__restrict__ g_sums, int B, float *__restrict__ adj) {
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i >= B * RGBD_ADJ_WORDS) return;
-    const int b = i / RGBD_ADJ_WORDS, k = i - b * RGBD_ADJ_WORDS;
-    const float g = k < 28 ? g_sums[NACC * b + k] : 0.0f;
-    adj[i] = k == RGBD_ADJ_LIVE ? 1.0f : ((k >= 21 && k < 27) ? -g : g);
-}
-
-// grid B.  gT (B,16): the carried adjoint of T (rows 0..2), updated in place; rec: this iteration's tape rows; adj: its (B, 32)
-__global__ __launch_bounds__(BWD_T) void rgbd_step_bwd_k(float *__restrict__ gTall, const float *__restrict__ partials12, int nblocks,
-                                                        int prow, const float *__restrict__ rec_all, float damp, float *__restrict__ adj_all) {
-    __shared__ float sums[12];
-    __shared__ double lu_sm[42];
-    __shared__ float g[16], xi[6], dT[16], hg[44], gx[6], y[6];
-    __shared__ double gdT[12], gxi[6];
-    const int b = blockIdx.x;
-    fold_rows<12, BWD_GROUPS, 16>(partials12 + (int64_t)b * prow * 12, nblocks, 12, sums);
-    if (threadIdx.x != 0) return;
-    const float *rec = rec_all + GN_TAPE_WORDS * b;
-    float *gT = gTall + 16 * b, *A = adj_all + RGBD_ADJ_WORDS * b;
-    for (int k = 0; k < 16; ++k) g[k] = k < 12 ? gT[k] + sums[k] : 0.0f;
-    for (int k = 0; k < RGBD_ADJ_WORDS; ++k) A[k] = 0.0f;
-    if (rec[GN_TAPE_APPLIED] != 0.0f) {
-        for (int k = 0; k < 6; ++k) xi[k] = rec[GN_TAPE_XI + k];
-        se3_exp_dev(xi, dT);  // the forward's dT, bit for bit
-        top3_times_Tt(g, rec, gdT);
-        pull_gT(g, dT);
-        se3_exp_bwd(xi, gdT, gxi);
-        // xi = M^-1 g', M = H + damp I symmetric, g' = MINUS the six sums:  y = M^-1 xi-bar;  H-bar = -y xi^T, g'-bar = y
-        expand44(rec + GN_TAPE_SUMS, hg);
-        for (int k = 0; k < 6; ++k) gx[k] = (float)gxi[k];
-        solve6(hg, gx, damp, y, lu_sm);
-        int q = 0;
-        for (int u = 0; u < 6; ++u)
-            for (int v = u; v < 6; ++v) A[q++] = u == v ? -(y[u] * xi[u]) : -(y[u] * xi[v] + y[v] * xi[u]);
-        for (int u = 0; u < 6; ++u) A[21 + u] = -y[u];
-        A[RGBD_ADJ_LIVE] = 1.0f;
-    }
-    for (int k = 0; k < 12; ++k) gT[k] = g[k];
-}
 
 // One channel F (I or D) of a valid pixel: its row J (6) and residual r again (rgbd_chan_row), their adjoints from those of the
 // sums (M: the symmetric 6 x 6 that J-bar = M J + g r needs, g: the adjoints of the six sums J r, e2 = twice err's), pulled back
@@ -129,7 +73,7 @@ __global__ __launch_bounds__(RGBD_T) void rgbd_pixel_bwd_k(const float2 *__restr
     __shared__ float M[36], g[6], e2s;
     const int b = blockIdx.y, npix = Hl * Wl;
     const int p = blockIdx.x * RGBD_T + threadIdx.x;
-    const float *__restrict__ A = adj + RGBD_ADJ_WORDS * b;
+    const float *__restrict__ A = adj + GN_ADJ_WORDS * b;
     if (threadIdx.x < 36) {
         int u = threadIdx.x / 6, v = threadIdx.x % 6;
         const bool diag = u == v;
@@ -147,7 +91,7 @@ __global__ __launch_bounds__(RGBD_T) void rgbd_pixel_bwd_k(const float2 *__restr
     const float2 *__restrict__ timg = tgt + (int64_t)b * npix;
     RgbdPix P;
     bool ok = false;
-    if (p < npix && A[RGBD_ADJ_LIVE] != 0.0f) {
+    if (p < npix && A[GN_ADJ_LIVE] != 0.0f) {
         const int v = p / Wl, u = p - v * Wl;
         ok = rgbd_pixel_fwd(timg, src[(int64_t)b * npix + p], u, v, Hl, Wl, cam, T, ddm, P);
     }

@@ -4,7 +4,7 @@
 //                 residual).  Both passes run THIS code -- the rule of include/gradslam_hip.h, every fp32 operation in its order --
 //                 so the reverse pass differentiates exactly the pixels the forward pass used.
 //   the pyramid   rgbd_depth_kept (level 0), rgbd_down_select (the 2 x 2 reduction's depth selection).
-// (The layout of an iteration's tape row, written by rgbd_step_k<true> and read by rgbd_step_bwd_k, is the step's: gs_gn_step.hpp.)
+// (The layout of an iteration's tape row, written by gn_step_k<true> and read by gn_step_bwd_k, is the step's: gs_gn_step.hpp.)
 #pragma once
 
 #include "gs_icp_reduce.hpp"

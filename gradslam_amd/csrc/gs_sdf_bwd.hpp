@@ -1,12 +1,11 @@
-// gs_sdf_bwd.hpp -- the kernels of the SDF odometry's reverse pass (the rule: include/gradslam_hip.h).  Included by sdf.hip after its
-// forward kernels (SDF_T, SdfGrid, SdfVolume are sdf.hip's), which launches them (sdf_bwd_run); the pixel's forward values are
-// gs_sdf_pixel.hpp's, the forward's own code; the tape row's layout (GN_TAPE_*) is gs_gn_step.hpp's.
+// gs_sdf_bwd.hpp -- the SDF odometry's own kernels of its reverse pass (the rule: include/gradslam_hip.h).  Included by sdf.hip after
+// its forward kernel (SDF_T, SdfGrid, SdfVolume are sdf.hip's), which launches them (sdf_bwd_run); the pixel's forward values are
+// gs_sdf_pixel.hpp's, the forward's own code.  The step reverse, the fold of the 12-wide rows, the seam's adjoint row and the
+// layouts of the tape row (GN_TAPE_*) and of the adjoint row (GN_ADJ_*) are gs_gn_step.hpp's, shared with rgbd.hip.
 // Per iteration, last to first:
-// Xb step reverse, one 256-thread block per batch element: rgbd_step_bwd_k's body (gs_rgbd_bwd.hpp) on D -- the pixel pass before
-//    left 12-sum rows, the adjoint of D_{k+1} through ITS linearisation, which are folded (fold_rows) into the carried adjoint;
-//    then, one lane: dD-bar = D-bar_{k+1} D_k^T, D-bar_k = dD^T D-bar_{k+1}, the exponential's and the solve's adjoints -> the
-//    adjoints of the iteration's 28 sums -- and the same fold of the pixel pass's 12-sum rows of the POSES' adjoint onto the
-//    running g_poses.  The body is stated a second time here, not shared: rgbd.hip's ISA is left as it is.
+// Xb step reverse (gn_step_bwd_k<true>): folds the 12-sum rows the pixel pass before left into the carried adjoint of D and
+//    leaves the adjoints of the iteration's 28 sums; it also folds the pixel pass's 12-sum rows of the POSES' adjoint onto the
+//    running g_poses.
 // Lb pixel reverse, the forward's geometry: the pixel's forward values again at the taped D_k (sdf_pixel_fwd: the same 16 gathers in
 //    one batch), the adjoints of its row and residual from those of the sums, pulled back to the eight corner values, to q, to D,
 //    to the pose and to the depth.  <MAX> does all of it but the corner sums, of which it takes the largest magnitude; <ACC> only
@@ -14,13 +13,11 @@
 #pragma once
 
 #include "gs_fixed128.hpp"
+#include "gs_gn_step.hpp"
 #include "gs_sdf_pixel.hpp"
-#include "gs_se3_bwd.hpp"
 
 namespace gs {
 
-constexpr int SDF_ADJ_WORDS = 32;  // adjoints of the 28 sums AS REDUCED (the six of g: of the sum, not of minus it; cnt has none)
-constexpr int SDF_ADJ_LIVE = 28;   // 1: the pixel pass applies them; 0: a step that was not applied -- nothing, not even 0 x inf
 enum { SDF_BWD_MAX = 0, SDF_BWD_ACC = 1 };
 
 // the loop's start: gD[b] = rows 0..2 of grad_T[b] (the bottom row zero), gP[b] = 0.  One thread per word of (B, 16).
@@ -30,66 +27,6 @@ __global__ __launch_bounds__(256) void sdf_bwd_begin_k(const float *__restrict__
     if (i >= 16 * B) return;
     gD[i] = (i & 15) < 12 ? grad_T[i] : 0.0f;
     gP[i] = 0.0f;
-}
-
-// gs_sdf_rows_bwd: the adjoints of the sums as gs_sdf_rows returns them (g = MINUS the sum) -> of the sums as reduced; the
-// adjoint of cnt is ignored
-__global__ __launch_bounds__(256) void sdf_sums_adj_k(const float *__restrict__ g_sums, int B, float *__restrict__ adj) {
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i >= B * SDF_ADJ_WORDS) return;
-    const int b = i / SDF_ADJ_WORDS, k = i - b * SDF_ADJ_WORDS;
-    const float g = k < 28 ? g_sums[NACC * b + k] : 0.0f;
-    adj[i] = k == SDF_ADJ_LIVE ? 1.0f : ((k >= 21 && k < 27) ? -g : g);
-}
-
-// out[b] (stride floats, 12 or 16: the bottom row is zero) = g_in[b] rows 0..2 (NULL: zero) + the sum of b's 12-wide rows
-__global__ __launch_bounds__(BWD_T) void sdf_fold12_k(const float *__restrict__ g_in, const float *__restrict__ partials12, int nblocks,
-                                                     int prow, float *__restrict__ out, int stride) {
-    __shared__ float sums[12];
-    const int b = blockIdx.x;
-    fold_rows<12, BWD_GROUPS, 16>(partials12 + (int64_t)b * prow * 12, nblocks, 12, sums);
-    if ((int)threadIdx.x < stride)
-        out[stride * b + threadIdx.x] = threadIdx.x < 12 ? (g_in ? g_in[16 * b + threadIdx.x] : 0.0f) + sums[threadIdx.x] : 0.0f;
-}
-
-// grid B.  gD (B,16): the carried adjoint of D (rows 0..2), updated in place; gP (B,16): the running adjoint of the poses, which
-// takes the rows of partP (NULL: the poses' adjoint is not wanted); rec: this iteration's tape rows; adj: its (B, 32)
-__global__ __launch_bounds__(BWD_T) void sdf_step_bwd_k(float *__restrict__ gDall, float *__restrict__ gPall,
-                                                       const float *__restrict__ partD, const float *__restrict__ partP, int nblocks,
-                                                       int prow, const float *__restrict__ rec_all, float damp,
-                                                       float *__restrict__ adj_all) {
-    __shared__ float sums[12], psums[12];
-    __shared__ double lu_sm[42];
-    __shared__ float g[16], xi[6], dT[16], hg[44], gx[6], y[6];
-    __shared__ double gdT[12], gxi[6];
-    const int b = blockIdx.x;
-    fold_rows<12, BWD_GROUPS, 16>(partD + (int64_t)b * prow * 12, nblocks, 12, sums);
-    if (partP) {
-        fold_rows<12, BWD_GROUPS, 16>(partP + (int64_t)b * prow * 12, nblocks, 12, psums);
-        if (threadIdx.x < 12) gPall[16 * b + threadIdx.x] = gPall[16 * b + threadIdx.x] + psums[threadIdx.x];
-    }
-    if (threadIdx.x != 0) return;
-    const float *rec = rec_all + GN_TAPE_WORDS * b;
-    float *gT = gDall + 16 * b, *A = adj_all + SDF_ADJ_WORDS * b;
-    for (int k = 0; k < 16; ++k) g[k] = k < 12 ? gT[k] + sums[k] : 0.0f;
-    for (int k = 0; k < SDF_ADJ_WORDS; ++k) A[k] = 0.0f;
-    if (rec[GN_TAPE_APPLIED] != 0.0f) {
-        for (int k = 0; k < 6; ++k) xi[k] = rec[GN_TAPE_XI + k];
-        se3_exp_dev(xi, dT);  // the forward's dD, bit for bit
-        top3_times_Tt(g, rec, gdT);
-        pull_gT(g, dT);
-        se3_exp_bwd(xi, gdT, gxi);
-        // xi = M^-1 g', M = H + damp I symmetric, g' = MINUS the six sums:  y = M^-1 xi-bar;  H-bar = -y xi^T, g'-bar = y
-        expand44(rec + GN_TAPE_SUMS, hg);
-        for (int k = 0; k < 6; ++k) gx[k] = (float)gxi[k];
-        solve6(hg, gx, damp, y, lu_sm);
-        int q = 0;
-        for (int u = 0; u < 6; ++u)
-            for (int v = u; v < 6; ++v) A[q++] = u == v ? -(y[u] * xi[u]) : -(y[u] * xi[v] + y[v] * xi[u]);
-        for (int u = 0; u < 6; ++u) A[21 + u] = -y[u];
-        A[SDF_ADJ_LIVE] = 1.0f;
-    }
-    for (int k = 0; k < 12; ++k) gT[k] = g[k];
 }
 
 // grid (blocks of SDF_T pixels of the level's grid, B), sdf_linearize_k's.  D: batch element b's delta at Dall + dstride b; adj
@@ -107,7 +44,7 @@ __global__ __launch_bounds__(SDF_T) void sdf_pixel_bwd_k(const float *__restrict
     __shared__ float M[36], gv[6], e2s;
     const int b = blockIdx.y, npix = gr.Hs * gr.Ws;
     const int p = blockIdx.x * SDF_T + threadIdx.x;
-    const float *__restrict__ A = adj + SDF_ADJ_WORDS * b;
+    const float *__restrict__ A = adj + GN_ADJ_WORDS * b;
     if (threadIdx.x < 36) {
         int u = threadIdx.x / 6, v = threadIdx.x % 6;
         const bool diag = u == v;
@@ -128,7 +65,7 @@ __global__ __launch_bounds__(SDF_T) void sdf_pixel_bwd_k(const float *__restrict
 
     float d = 0.0f;  // (a lane past the grid's last pixel, or a step that was not applied: depth 0, not valid)
     int h = 0, w = 0;
-    if (p < npix && A[SDF_ADJ_LIVE] != 0.0f) {
+    if (p < npix && A[GN_ADJ_LIVE] != 0.0f) {
         const int i = p / gr.Ws, j = p - i * gr.Ws;
         h = i * gr.s;
         w = j * gr.s;

@@ -3,22 +3,23 @@
 // gs_rgbd_rows_bwd).  The rule -- every fp32 operation in order -- is stated in include/gradslam_hip.h above the entry points;
 // the code follows it line by line (the library is built without contraction).  One translation unit, the device code by role:
 //   gs_rgbd_pixel.hpp  what forward and reverse kernels must agree on bit for bit, once: the pixel, the pyramid's rules
-//   gs_gn_step.hpp     what this loop shares with the SDF odometry's (sdf.hip): constants, the tape row's layout, the start-up, host checks
-//   gs_rgbd_bwd.hpp    Xb, Lb, Pb: the kernels of the reverse pass
-//   this file          P, L, X: the forward kernels; every launch, the workspaces and the C entry points
+//   gs_gn_step.hpp     what this loop shares with the SDF odometry's (sdf.hip): constants, the tape and adjoint rows' layout, the
+//                      start-up, X the step, Xb its reverse and the fold of the 12-wide rows as whole kernels, host rules and checks
+//   gs_rgbd_bwd.hpp    Lb, Pb: the reverse pass's own kernels
+//   this file          P, L: the forward's own kernels; the drivers, the workspaces and the C entry points
 // P  pyramid: level 0 is (intensity, depth or 0) per pixel as ONE float2, so that a bilinear corner is one 8-byte load; every
 //    further level is a 2 x 2 reduction of the level before.  One launch per frame and level.
 // L  linearise: one source pixel per lane: warp, four corner loads, the two Jacobian rows and residuals, the lane's 29 terms;
 //    a transposing wave butterfly, then the waves in order, leave one partial row per block (gs_icp_reduce.hpp's geometry).
-// X  step: a launch of its own, one 1024-thread block per batch element: reduce_partials (fixed order), then one lane solves
-//    (gs::solve6, fp64) and composes T <- exp(xi) T.  Two launches per iteration, no float atomics, nothing synchronises the
-//    host; the loop state (T per batch element) lives in the workspace.
+// X  step (gn_step_k): a launch of its own, one 1024-thread block per batch element: reduce_partials (fixed order), then one lane
+//    solves (gs::solve6, fp64) and composes T <- exp(xi) T.  Two launches per iteration, no float atomics, nothing synchronises
+//    the host; the loop state (T per batch element) lives in the workspace.
 #include <math.h>
 #include <stddef.h>
 #include <algorithm>
 #include <type_traits>
 
-#include "gs_gn_step.hpp"  // constants, the tape row, the start-up, the shared host checks; it brings gs_icp_step.hpp (solve6, se3_exp_dev)
+#include "gs_gn_step.hpp"  // the loop's shared constants, kernels and host rules
 #include "gs_rgbd_pixel.hpp"
 #include "gs_rowsum.hpp"  // block_row_transposed
 
@@ -115,74 +116,9 @@ __global__ __launch_bounds__(RGBD_T) void rgbd_linearize_k(const float2 *__restr
     block_row_transposed<NACC, RGBD_T / 64>(acc, partials + (int64_t)b * prow * NACC);
 }
 
-// ------------------------------------------------------------------ X: step
-// grid B, 1024 threads.  Reduces batch element b's `nblocks` partial rows; `sums` (B, 29: H upper | g = -sum | err | cnt)
-// is written when given; with `apply`, lane 0 solves and composes T[b] <- exp(xi) T[b], and writes out_T[b] and the level's
-// info row (cnt, err, status bits of the level so far, iterations run at the level).
-// TAPE: also the iteration's tape row of batch element b (gs_gn_step.hpp: GN_TAPE_*).
-template <bool TAPE>
-__global__ __launch_bounds__(1024) void rgbd_step_k(float *__restrict__ Tall, const float *__restrict__ partials, int nblocks, int prow,
-                                                   float damp, int level, int levels, int it, int apply, float *__restrict__ out_T,
-                                                   float *__restrict__ info, float *__restrict__ sums, float *__restrict__ tape) {
-    __shared__ float acc[NACC];
-    __shared__ double lu_sm[42];
-    const int b = blockIdx.x;
-    reduce_partials(partials + (int64_t)b * prow * NACC, nblocks, acc);
-    if (threadIdx.x != 0) return;
-    if (sums) {
-        for (int k = 0; k < NACC; ++k) sums[NACC * b + k] = (k >= 21 && k < 27) ? -acc[k] : acc[k];
-    }
-    if (!apply) return;
-    float *T = Tall + 16 * b;
-    float *row = info + ((int64_t)b * levels + level) * 4;
-    int status = it == 0 ? 0 : (int)row[2];
-    const float cnt = acc[28];
-    float *rec = TAPE ? tape + GN_TAPE_WORDS * b : nullptr;
-    if constexpr (TAPE) {
-        for (int k = 0; k < 16; ++k) rec[k] = T[k];
-        for (int k = 0; k < NACC; ++k) rec[GN_TAPE_SUMS + k] = acc[k];
-        for (int k = 0; k < 6; ++k) rec[GN_TAPE_XI + k] = 0.0f;
-        rec[GN_TAPE_APPLIED] = 0.0f;
-    }
-    if (cnt < 6.0f) {
-        status |= GN_STATUS_FEW;
-    } else {
-        float hg[44], xi[6], dT[16], Tn[16];
-        expand44(acc, hg);
-        for (int k = 0; k < 6; ++k) hg[36 + k] = -hg[36 + k];
-        solve6(hg, hg + 36, damp, xi, lu_sm);
-        bool fin = true;
-        for (int k = 0; k < 6; ++k) fin = fin && fabsf(xi[k]) < INFINITY;
-        if (fin) {
-            se3_exp_dev(xi, dT);
-            compose44(dT, T, Tn);
-            for (int k = 0; k < 12; ++k) fin = fin && fabsf(Tn[k]) < INFINITY;
-        }
-        if (fin) {
-            if constexpr (TAPE) {
-                for (int k = 0; k < 6; ++k) rec[GN_TAPE_XI + k] = xi[k];
-                rec[GN_TAPE_APPLIED] = 1.0f;
-            }
-            for (int k = 0; k < 16; ++k) T[k] = Tn[k];
-        } else {
-            status |= GN_STATUS_SOLVE;
-        }
-    }
-    row[0] = cnt;
-    row[1] = acc[27];
-    row[2] = (float)status;
-    row[3] = (float)(it + 1);
-    for (int k = 0; k < 16; ++k) out_T[16 * b + k] = T[k];
-}
-
-__global__ __launch_bounds__(256) void rgbd_init_k(const float *__restrict__ init, int B, int n_info, float *__restrict__ Tall,
-                                                  float *__restrict__ out_T, float *__restrict__ info) {
-    gn_init(init, B, n_info, Tall, out_T, info);
-}
-
 }  // namespace gs
 
-#include "gs_rgbd_bwd.hpp"  // Xb, Lb, Pb: the kernels of the reverse pass, after the forward ones
+#include "gs_rgbd_bwd.hpp"  // Lb, Pb: the reverse pass's own kernels, after the forward ones
 
 namespace gs {
 
@@ -254,7 +190,7 @@ static int rgbd_build_pyramid(const char *name, const float *depth, const float 
 struct RgbdBwdWs {
     RgbdWs f;
     float *gT;          // B x 16: the carried adjoint of T
-    float *adj;         // max(iterations, 1) x B x RGBD_ADJ_WORDS, in the order the iterations ran
+    float *adj;         // max(iterations, 1) x B x GN_ADJ_WORDS, in the order the iterations ran
     float *partials12;  // B x prow x 12
     float2 *gtgt, *gsrc;  // the pyramids' adjoints, the forward's layout, one piece (adj_pyr_bytes)
     size_t adj_pyr_bytes;
@@ -270,7 +206,7 @@ static size_t rgbd_bwd_layout(int B, int H, int W, int levels, int64_t iteration
     t.f.partials = nullptr;
     const size_t pyr = sizeof(float2) * (size_t)t.f.off[levels] * B;
     t.gT = c.take<float>(sizeof(float) * 16 * B);
-    t.adj = c.take<float>(sizeof(float) * RGBD_ADJ_WORDS * (size_t)std::max<int64_t>(iterations, 1) * B);
+    t.adj = c.take<float>(sizeof(float) * GN_ADJ_WORDS * (size_t)std::max<int64_t>(iterations, 1) * B);
     t.partials12 = c.take<float>(sizeof(float) * 12 * (size_t)t.f.prow * B);
     t.f.tgt = c.take<float2>(pyr);
     t.f.src = c.take<float2>(pyr);
@@ -327,8 +263,7 @@ int gs_rgbd_rows(const float *tgt_depth, const float *tgt_rgb, const float *src_
     hipLaunchKernelGGL(rgbd_linearize_k<true>, dim3(w.prow, B), dim3(RGBD_T), 0, st, w.tgt, w.src, H, W, 0, intrinsics, T, wI, wD,
                        depth_diff_max, w.partials, w.prow, valid, rows);
     GS_LAUNCH_CHECK("gs_rgbd_rows/linearize");
-    hipLaunchKernelGGL(rgbd_step_k<false>, dim3(B), dim3(1024), 0, st, w.T, w.partials, w.prow, w.prow, 0.0f, 0, 1, 0, 0, (float *)nullptr,
-                       (float *)nullptr, sums, (float *)nullptr);
+    gn_launch_step(B, w.T, w.partials, w.prow, w.prow, 0.0f, 0, 1, 0, 0, nullptr, nullptr, sums, nullptr, st);
     GS_LAUNCH_CHECK("gs_rgbd_rows/sums");
     return 0;
 }
@@ -344,15 +279,13 @@ static int rgbd_run(const float *tgt_depth, const float *tgt_rgb, const float *s
     hipStream_t st = (hipStream_t)stream;
     RgbdWs w;
     rgbd_layout(B, H, W, levels, ws, &w);
-    const int n_info = B * levels * 4;
-    hipLaunchKernelGGL(rgbd_init_k, dim3(cdiv(std::max(16 * B, n_info), 256)), dim3(256), 0, st, init, B, n_info, w.T, out_T, info);
+    gn_launch_init(init, B, levels, w.T, out_T, info, st);
     GS_LAUNCH_CHECK("gs_rgbd_odometry/init");
     int rc = rgbd_build_pyramid("gs_rgbd_odometry/pyramid", tgt_depth, tgt_rgb, B, levels, w, depth_diff_max, rgb_scale, w.tgt, st);
     if (rc) return rc;
     rc = rgbd_build_pyramid("gs_rgbd_odometry/pyramid", src_depth, src_rgb, B, levels, w, depth_diff_max, rgb_scale, w.src, st);
     if (rc) return rc;
     const float wI = sqrtf(1.0f - lambda_geo), wD = sqrtf(lambda_geo);
-    const auto step = tape ? rgbd_step_k<true> : rgbd_step_k<false>;
     float *rec = tape;  // one row per (iteration, batch element), in the order the iterations run
     for (int l = levels - 1; l >= 0; --l) {
         const int nblocks = cdiv((int64_t)w.Hl[l] * w.Wl[l], RGBD_T);
@@ -361,8 +294,7 @@ static int rgbd_run(const float *tgt_depth, const float *tgt_rgb, const float *s
                                w.Hl[l], w.Wl[l], l, intrinsics, w.T, wI, wD, depth_diff_max, w.partials, w.prow, (int32_t *)nullptr,
                                (float *)nullptr);
             GS_LAUNCH_CHECK("gs_rgbd_odometry/linearize");
-            hipLaunchKernelGGL(step, dim3(B), dim3(1024), 0, st, w.T, w.partials, nblocks, w.prow, damp, l, levels, it, 1, out_T, info,
-                               (float *)nullptr, rec);
+            gn_launch_step(B, w.T, w.partials, nblocks, w.prow, damp, l, levels, it, 1, out_T, info, nullptr, rec, st);
             GS_LAUNCH_CHECK("gs_rgbd_odometry/step");
             if (tape) rec += (size_t)GN_TAPE_WORDS * B;
         }
@@ -396,12 +328,11 @@ static int rgbd_bwd_run(const RgbdBwdNames &nm, const float *tgt_depth, const fl
                         float rgb_scale, const float *tape, const float *grad_T, const float *T, const float *g_sums, float *g_tgt_depth,
                         float *g_tgt_rgb, float *g_src_depth, float *g_src_rgb, float *g_T, void *ws, size_t ws_bytes, hipStream_t st) {
     const bool seam = !tape;
-    int total = 0, base[GN_MAX_LEVELS];  // base[l]: iterations that ran before level l's (the coarser levels')
-    for (int l = levels - 1; l >= 0; --l) { base[l] = total; total += numiters[l]; }
-    const size_t need = gs_rgbd_odometry_bwd_ws_size(B, H, W, levels, total);
+    const GnSchedule sch = gn_schedule(levels, numiters);
+    const size_t need = gs_rgbd_odometry_bwd_ws_size(B, H, W, levels, sch.total);
     GS_REQUIRE_WS(nm.op, ws, ws_bytes, need);
     RgbdBwdWs w;
-    rgbd_bwd_layout(B, H, W, levels, total, ws, &w);
+    rgbd_bwd_layout(B, H, W, levels, sch.total, ws, &w);
     // both pyramids again (the forward's workspace need not have survived), the adjoint pyramids zeroed
     int rc = rgbd_build_pyramid(nm.pyramid, tgt_depth, tgt_rgb, B, levels, w.f, ddm, rgb_scale, w.f.tgt, st);
     if (rc) return rc;
@@ -409,7 +340,7 @@ static int rgbd_bwd_run(const RgbdBwdNames &nm, const float *tgt_depth, const fl
     if (rc) return rc;
     GS_HIP(hipMemsetAsync(w.gtgt, 0, w.adj_pyr_bytes, st), nm.pyramid);  // gtgt | gsrc
     if (!seam) {
-        hipLaunchKernelGGL(rgbd_gT_k, dim3(B), dim3(BWD_T), 0, st, grad_T, (const float *)nullptr, 0, w.f.prow, w.gT, 16);
+        hipLaunchKernelGGL(gn_fold12_k, dim3(B), dim3(BWD_T), 0, st, grad_T, (const float *)nullptr, 0, w.f.prow, w.gT, 16);
         GS_LAUNCH_CHECK(nm.begin);
     }
     const float wI = sqrtf(1.0f - lambda_geo), wD = sqrtf(lambda_geo);
@@ -422,13 +353,13 @@ static int rgbd_bwd_run(const RgbdBwdNames &nm, const float *tgt_depth, const fl
         const int lg = fold_lg((int64_t)w.f.Hl[l] * w.f.Wl[l] * n);  // a corner receives at most one term per source pixel and iteration
         GS_HIP(hipMemsetAsync(w.fold_base, 0, want_tgt ? w.fold_bytes : sizeof(uint32_t), st), nm.zero);
         if (seam) {
-            hipLaunchKernelGGL(rgbd_sums_adj_k, dim3(cdiv((int64_t)B * RGBD_ADJ_WORDS, 256)), dim3(256), 0, st, g_sums, B, w.adj);
+            hipLaunchKernelGGL(gn_sums_adj_k, dim3(cdiv((int64_t)B * GN_ADJ_WORDS, 256)), dim3(256), 0, st, g_sums, B, w.adj);
             GS_LAUNCH_CHECK(nm.begin);
         }
         const int nblocks = cdiv((int64_t)w.f.Hl[l] * w.f.Wl[l], RGBD_T);
         // iteration `it`'s transform (the seam's T, or the head of its tape row) and the adjoints of its sums
-        const auto T_of = [&](int it) { return seam ? T : tape + (size_t)(base[l] + it) * B * GN_TAPE_WORDS; };
-        const auto adj_of = [&](int it) { return w.adj + (size_t)(base[l] + it) * B * RGBD_ADJ_WORDS; };
+        const auto T_of = [&](int it) { return seam ? T : tape + (size_t)(sch.base[l] + it) * B * GN_TAPE_WORDS; };
+        const auto adj_of = [&](int it) { return w.adj + (size_t)(sch.base[l] + it) * B * GN_ADJ_WORDS; };
         const auto pixels = [&](decltype(&rgbd_pixel_bwd_k<RGBD_BWD_MAX>) kernel, const char *name, int it) {
             hipLaunchKernelGGL(kernel, dim3(nblocks, B), dim3(RGBD_T), 0, st, (const float2 *)(w.f.tgt + B * w.f.off[l]),
                                (const float2 *)(w.f.src + B * w.f.off[l]), w.f.Hl[l], w.f.Wl[l], l, intrinsics, T_of(it),
@@ -439,8 +370,8 @@ static int rgbd_bwd_run(const RgbdBwdNames &nm, const float *tgt_depth, const fl
         };
         for (int it = n - 1; it >= 0; --it) {
             if (!seam) {
-                hipLaunchKernelGGL(rgbd_step_bwd_k, dim3(B), dim3(BWD_T), 0, st, w.gT, w.partials12, prev_nblocks, w.f.prow, T_of(it), damp,
-                                   adj_of(it));
+                hipLaunchKernelGGL(gn_step_bwd_k<false>, dim3(B), dim3(BWD_T), 0, st, w.gT, (const float *)w.partials12, prev_nblocks, w.f.prow,
+                                   T_of(it), damp, adj_of(it), (float *)nullptr, (const float *)nullptr);
                 GS_LAUNCH_CHECK(nm.step);
             }
             if ((rc = pixels(rgbd_pixel_bwd_k<RGBD_BWD_MAX>, nm.pixels, it))) return rc;
@@ -454,7 +385,7 @@ static int rgbd_bwd_run(const RgbdBwdNames &nm, const float *tgt_depth, const fl
         GS_LAUNCH_CHECK(nm.finish);
     }
     if (g_T) {  // the carried adjoint (the seam has none) + what the last pixel pass left: g_init (B,16), or the seam's g_T (B,12)
-        hipLaunchKernelGGL(rgbd_gT_k, dim3(B), dim3(BWD_T), 0, st, seam ? (const float *)nullptr : (const float *)w.gT,
+        hipLaunchKernelGGL(gn_fold12_k, dim3(B), dim3(BWD_T), 0, st, seam ? (const float *)nullptr : (const float *)w.gT,
                            (const float *)w.partials12, prev_nblocks, w.f.prow, g_T, seam ? 12 : 16);
         GS_LAUNCH_CHECK(nm.last);
     }
@@ -485,7 +416,7 @@ int gs_rgbd_odometry(const float *tgt_depth, const float *tgt_rgb, const float *
 
 // (numiters here: the SUM of the levels' counts)
 size_t gs_rgbd_odometry_tape_size(int B, int levels, int numiters) {
-    if (B < 1 || B > 65535 || levels < 1 || levels > GN_MAX_LEVELS || numiters < 0 || numiters > levels * (1 << 20)) return 0;
+    if (B < 1 || B > 65535 || levels < 1 || levels > GN_MAX_LEVELS || !gn_total_ok(levels, numiters)) return 0;
     return one_piece_bytes(sizeof(float) * GN_TAPE_WORDS * (size_t)std::max(numiters, 1) * B);
 }
 
@@ -501,7 +432,7 @@ int gs_rgbd_odometry_taped(const float *tgt_depth, const float *tgt_rgb, const f
 }
 
 size_t gs_rgbd_odometry_bwd_ws_size(int B, int H, int W, int levels, int numiters) {
-    if (!rgbd_shape_ok(B, H, W, levels) || numiters < 0 || numiters > levels * (1 << 20)) return 0;
+    if (!rgbd_shape_ok(B, H, W, levels) || !gn_total_ok(levels, numiters)) return 0;
     return rgbd_bwd_layout(B, H, W, levels, numiters, nullptr, nullptr);
 }
 

@@ -3,18 +3,20 @@
 // rule -- every fp32 operation in order -- is stated in include/gradslam_hip.h above the entry points; the code follows it line
 // by line (the library is built without contraction).
 //   gs_sdf_pixel.hpp  the pixel, once: back-projection, the gates in their order, the row
-//   gs_sdf_bwd.hpp    Xb, Lb: the kernels of the reverse pass (gs_sdf_odometry_taped, gs_sdf_odometry_bwd, gs_sdf_rows_bwd)
-//   this file         L, X: the forward kernels; every launch, the workspace, the tape, the room and the C entry points
+//   gs_gn_step.hpp    what this loop shares with the RGB-D odometry's (rgbd.hip): constants, the tape and adjoint rows' layout, the
+//                     start-up, X the step, Xb its reverse and the fold of the 12-wide rows as whole kernels, host rules and checks
+//   gs_sdf_bwd.hpp    Lb: the reverse pass's own kernels (gs_sdf_odometry_taped, gs_sdf_odometry_bwd, gs_sdf_rows_bwd)
+//   this file         L: the forward's own kernel; the drivers, the workspace, the tape, the room and the C entry points
 // L  linearise: one pixel of the level's grid per lane: depth, two transforms, the cell, 16 gathers in one batch, the row, the
 //    lane's 29 terms; gs_rowsum.hpp's transposing butterfly leaves one partial row per block.
-// X  step: one 1024-thread block per batch element: reduce_partials (fixed order), then one lane solves (gs::solve6, fp64) and
-//    composes D <- exp(xi) D.  Two launches per iteration plus one to start, no float atomics, nothing synchronises the host; the
+// X  step (gn_step_k): one 1024-thread block per batch element: reduce_partials (fixed order), then one lane solves (gs::solve6,
+//    fp64) and composes D <- exp(xi) D.  Two launches per iteration plus one to start, no float atomics, nothing synchronises the host; the
 //    loop state (D per batch element) lives in the workspace.
 #include <math.h>
 #include <stddef.h>
 #include <algorithm>
 
-#include "gs_gn_step.hpp"  // constants, the start-up, the shared host checks; it brings gs_icp_step.hpp (solve6, se3_exp_dev, reduce_partials)
+#include "gs_gn_step.hpp"  // the loop's shared constants, kernels and host rules
 #include "gs_sdf_pixel.hpp"
 
 namespace gs {
@@ -82,74 +84,9 @@ __global__ __launch_bounds__(SDF_T) void sdf_linearize_k(const float *__restrict
     block_row_transposed<NACC, SDF_T / 64>(acc, partials + (int64_t)b * prow * NACC);
 }
 
-// ------------------------------------------------------------------ X: step
-// grid B, 1024 threads.  Reduces batch element b's `nblocks` partial rows; `sums` (B, 29: H upper | g = -sum | err | cnt) is
-// written when given; with `apply`, lane 0 solves and composes D[b] <- exp(xi) D[b], and writes out_T[b] and the level's info
-// row (cnt, err, status bits of the level so far, iterations run at the level).
-// TAPE: also the iteration's tape row of batch element b (gs_gn_step.hpp: GN_TAPE_*).
-template <bool TAPE>
-__global__ __launch_bounds__(1024) void sdf_step_k(float *__restrict__ Dall, const float *__restrict__ partials, int nblocks, int prow,
-                                                  float damp, int level, int levels, int it, int apply, float *__restrict__ out_T,
-                                                  float *__restrict__ info, float *__restrict__ sums, float *__restrict__ tape) {
-    __shared__ float acc[NACC];
-    __shared__ double lu_sm[42];
-    const int b = blockIdx.x;
-    reduce_partials(partials + (int64_t)b * prow * NACC, nblocks, acc);
-    if (threadIdx.x != 0) return;
-    if (sums) {
-        for (int k = 0; k < NACC; ++k) sums[NACC * b + k] = (k >= 21 && k < 27) ? -acc[k] : acc[k];
-    }
-    if (!apply) return;
-    float *D = Dall + 16 * b;
-    float *row = info + ((int64_t)b * levels + level) * 4;
-    int status = it == 0 ? 0 : (int)row[2];
-    const float cnt = acc[28];
-    float *rec = TAPE ? tape + GN_TAPE_WORDS * b : nullptr;
-    if constexpr (TAPE) {
-        for (int k = 0; k < 16; ++k) rec[k] = D[k];
-        for (int k = 0; k < NACC; ++k) rec[GN_TAPE_SUMS + k] = acc[k];
-        for (int k = 0; k < 6; ++k) rec[GN_TAPE_XI + k] = 0.0f;
-        rec[GN_TAPE_APPLIED] = 0.0f;
-    }
-    if (cnt < 6.0f) {
-        status |= GN_STATUS_FEW;
-    } else {
-        float hg[44], xi[6], dT[16], Dn[16];
-        expand44(acc, hg);
-        for (int k = 0; k < 6; ++k) hg[36 + k] = -hg[36 + k];
-        solve6(hg, hg + 36, damp, xi, lu_sm);
-        bool fin = true;
-        for (int k = 0; k < 6; ++k) fin = fin && fabsf(xi[k]) < INFINITY;
-        if (fin) {
-            se3_exp_dev(xi, dT);
-            compose44(dT, D, Dn);
-            for (int k = 0; k < 12; ++k) fin = fin && fabsf(Dn[k]) < INFINITY;
-        }
-        if (fin) {
-            if constexpr (TAPE) {
-                for (int k = 0; k < 6; ++k) rec[GN_TAPE_XI + k] = xi[k];
-                rec[GN_TAPE_APPLIED] = 1.0f;
-            }
-            for (int k = 0; k < 16; ++k) D[k] = Dn[k];
-        } else {
-            status |= GN_STATUS_SOLVE;
-        }
-    }
-    row[0] = cnt;
-    row[1] = acc[27];
-    row[2] = (float)status;
-    row[3] = (float)(it + 1);
-    for (int k = 0; k < 16; ++k) out_T[16 * b + k] = D[k];
-}
-
-__global__ __launch_bounds__(256) void sdf_init_k(const float *__restrict__ init, int B, int n_info, float *__restrict__ Dall,
-                                                 float *__restrict__ out_T, float *__restrict__ info) {
-    gn_init(init, B, n_info, Dall, out_T, info);
-}
-
 }  // namespace gs
 
-#include "gs_sdf_bwd.hpp"  // Xb, Lb: the kernels of the reverse pass, after the forward ones
+#include "gs_sdf_bwd.hpp"  // Lb: the reverse pass's own kernels, after the forward one
 
 namespace gs {
 
@@ -194,7 +131,7 @@ static size_t sdf_tape_layout(int B, int H, int W, int stride, int64_t iteration
 // the reverse pass's working memory; without a volume adjoint there is no fold (fold.maxbits is NULL)
 struct SdfRoom {
     float *gD, *gP;        // B x 16 each: the carried adjoint of D, the running adjoint of the poses
-    float *adj;            // max(iterations, 1) x B x SDF_ADJ_WORDS, in the order the iterations ran
+    float *adj;            // max(iterations, 1) x B x GN_ADJ_WORDS, in the order the iterations ran
     float *partD, *partP;  // B x prow x 12 each
     int prow;
     Fold fold;             // B nx ny nz rows x 1 channel
@@ -208,7 +145,7 @@ static size_t sdf_room_layout(int B, int H, int W, int stride, int64_t iteration
     t.prow = cdiv((int64_t)g.Hs * g.Ws, SDF_T);
     t.gD = c.take<float>(sizeof(float) * 16 * B);
     t.gP = c.take<float>(sizeof(float) * 16 * B);
-    t.adj = c.take<float>(sizeof(float) * SDF_ADJ_WORDS * (size_t)std::max<int64_t>(iterations, 1) * B);
+    t.adj = c.take<float>(sizeof(float) * GN_ADJ_WORDS * (size_t)std::max<int64_t>(iterations, 1) * B);
     t.partD = c.take<float>(sizeof(float) * 12 * (size_t)t.prow * B);
     t.partP = c.take<float>(sizeof(float) * 12 * (size_t)t.prow * B);
     t.fold = Fold{nullptr, nullptr, nullptr, 1};
@@ -288,8 +225,7 @@ int gs_sdf_rows(const float *depth, int B, int H, int W, const float *intrinsics
     const SdfVolume vo{tsdf, weight, origin, nx, ny, nz, voxel_size, trunc, trunc / voxel_size, min_weight};
     sdf_launch_linearize(true, depth, B, sdf_grid(H, W, stride, 0), intrinsics, poses, D, vo, w, valid, rows, st);
     GS_LAUNCH_CHECK("gs_sdf_rows/linearize");
-    hipLaunchKernelGGL(sdf_step_k<false>, dim3(B), dim3(1024), 0, st, w.D, w.partials, w.prow, w.prow, 0.0f, 0, 1, 0, 0, (float *)nullptr,
-                       (float *)nullptr, sums, (float *)nullptr);
+    gn_launch_step(B, w.D, w.partials, w.prow, w.prow, 0.0f, 0, 1, 0, 0, nullptr, nullptr, sums, nullptr, st);
     GS_LAUNCH_CHECK("gs_sdf_rows/sums");
     return 0;
 }
@@ -300,18 +236,15 @@ int gs_sdf_rows(const float *depth, int B, int H, int W, const float *intrinsics
 static int sdf_run(const float *depth, int B, int H, int W, const float *intrinsics, const float *poses, const float *init,
                    const SdfVolume &vo, int stride, int levels, const int *numiters, float damp, float *out_T, float *info, const SdfWs &w,
                    float *rec, hipStream_t st) {
-    const int n_info = B * levels * 4;
-    hipLaunchKernelGGL(sdf_init_k, dim3(cdiv(std::max(16 * B, n_info), 256)), dim3(256), 0, st, init, B, n_info, w.D, out_T, info);
+    gn_launch_init(init, B, levels, w.D, out_T, info, st);
     GS_LAUNCH_CHECK("gs_sdf_odometry/init");
-    const auto step = rec ? sdf_step_k<true> : sdf_step_k<false>;
     for (int l = levels - 1; l >= 0; --l) {
         const SdfGrid g = sdf_grid(H, W, stride, l);
         const int nblocks = cdiv((int64_t)g.Hs * g.Ws, SDF_T);
         for (int it = 0; it < numiters[l]; ++it) {
             sdf_launch_linearize(false, depth, B, g, intrinsics, poses, w.D, vo, w, nullptr, nullptr, st);
             GS_LAUNCH_CHECK("gs_sdf_odometry/linearize");
-            hipLaunchKernelGGL(step, dim3(B), dim3(1024), 0, st, w.D, w.partials, nblocks, w.prow, damp, l, levels, it, 1, out_T, info,
-                               (float *)nullptr, rec);
+            gn_launch_step(B, w.D, w.partials, nblocks, w.prow, damp, l, levels, it, 1, out_T, info, nullptr, rec, st);
             GS_LAUNCH_CHECK("gs_sdf_odometry/step");
             if (rec) rec += (size_t)GN_TAPE_WORDS * B;  // one row per (iteration, batch element), in the order the iterations run
         }
@@ -320,7 +253,6 @@ static int sdf_run(const float *depth, int B, int H, int W, const float *intrins
 }
 
 #define SDF_REQUIRE_ROOM(name, ptr, have, need) GS_REQUIRE_BYTES_("room", GS_ERR_WORKSPACE_TOO_SMALL, name, ptr, have, need)
-static bool sdf_total_ok(int levels, int64_t numiters_total) { return numiters_total >= 0 && numiters_total <= (int64_t)levels * (1 << 20); }
 static bool sdf_dims_ok(int nx, int ny, int nz) { return nx >= 1 && ny >= 1 && nz >= 1 && (int64_t)nx * ny * nz <= TSDF_NMAX; }
 
 // The reverse pass, for both of its entry points (`nm`: the entry point's launch names).  The loop (gs_sdf_odometry_bwd): the
@@ -335,23 +267,21 @@ static int sdf_bwd_run(const SdfBwdNames &nm, const float *depth, int B, int H, 
                        const float *D, const float *g_sums, float *g_depth, float *g_poses, float *g_D, float *g_tsdf, void *room,
                        size_t room_cap, hipStream_t st) {
     const bool seam = !rows, want_tsdf = g_tsdf != nullptr;
-    int total = 0, base[GN_MAX_LEVELS];  // base[l]: iterations that ran before level l's (the coarser levels')
-    int64_t terms = 0;                   // a pixel gives a voxel at most one term per iteration
-    for (int l = levels - 1; l >= 0; --l) {
+    const GnSchedule sch = gn_schedule(levels, numiters);
+    int64_t terms = 0;  // a pixel gives a voxel at most one term per iteration
+    for (int l = 0; l < levels; ++l) {
         const SdfGrid g = sdf_grid(H, W, stride, l);
-        base[l] = total;
-        total += numiters[l];
         terms += (int64_t)numiters[l] * g.Hs * g.Ws;
     }
     const int64_t nvox = (int64_t)vo.nx * vo.ny * vo.nz;
-    const size_t need = sdf_room_layout(B, H, W, stride, total, nvox, want_tsdf, nullptr, nullptr);
+    const size_t need = sdf_room_layout(B, H, W, stride, sch.total, nvox, want_tsdf, nullptr, nullptr);
     SDF_REQUIRE_ROOM(nm.op, room, room_cap, need);
     SdfRoom w;
-    sdf_room_layout(B, H, W, stride, total, nvox, want_tsdf, room, &w);
+    sdf_room_layout(B, H, W, stride, sch.total, nvox, want_tsdf, room, &w);
     if (g_depth) GS_HIP(hipMemsetAsync(g_depth, 0, sizeof(float) * (size_t)B * H * W, st), nm.zero);
     if (want_tsdf) GS_HIP(hipMemsetAsync(w.fold_base, 0, w.fold_bytes, st), nm.zero);
     if (seam) {
-        hipLaunchKernelGGL(sdf_sums_adj_k, dim3(cdiv((int64_t)B * SDF_ADJ_WORDS, 256)), dim3(256), 0, st, g_sums, B, w.adj);
+        hipLaunchKernelGGL(gn_sums_adj_k, dim3(cdiv((int64_t)B * GN_ADJ_WORDS, 256)), dim3(256), 0, st, g_sums, B, w.adj);
     } else {
         hipLaunchKernelGGL(sdf_bwd_begin_k, dim3(cdiv(16 * B, 256)), dim3(256), 0, st, grad_T, B, w.gD, w.gP);
     }
@@ -360,8 +290,8 @@ static int sdf_bwd_run(const SdfBwdNames &nm, const float *depth, int B, int H, 
     float *partP = g_poses ? w.partP : nullptr;
     int prev_nblocks = 0;  // rows the pixel pass before left for the next step's fold
     // iteration `it` of level l: its delta (the seam's D, or the head of its tape row) and the adjoints of its sums
-    const auto D_of = [&](int l, int it) { return seam ? D : rows + (size_t)(base[l] + it) * B * GN_TAPE_WORDS; };
-    const auto adj_of = [&](int l, int it) { return w.adj + (size_t)(base[l] + it) * B * SDF_ADJ_WORDS; };
+    const auto D_of = [&](int l, int it) { return seam ? D : rows + (size_t)(sch.base[l] + it) * B * GN_TAPE_WORDS; };
+    const auto adj_of = [&](int l, int it) { return w.adj + (size_t)(sch.base[l] + it) * B * GN_ADJ_WORDS; };
     const auto pixels = [&](decltype(&sdf_pixel_bwd_k<SDF_BWD_MAX>) kernel, const char *name, int l, int it) {
         const SdfGrid g = sdf_grid(H, W, stride, l);
         hipLaunchKernelGGL(kernel, dim3(cdiv((int64_t)g.Hs * g.Ws, SDF_T), B), dim3(SDF_T), 0, st, depth, g, intrinsics, poses, D_of(l, it),
@@ -375,8 +305,8 @@ static int sdf_bwd_run(const SdfBwdNames &nm, const float *depth, int B, int H, 
         const int nblocks = cdiv((int64_t)g.Hs * g.Ws, SDF_T);
         for (int it = numiters[l] - 1; it >= 0; --it) {
             if (!seam) {
-                hipLaunchKernelGGL(sdf_step_bwd_k, dim3(B), dim3(BWD_T), 0, st, w.gD, w.gP, (const float *)w.partD, (const float *)partP,
-                                   prev_nblocks, w.prow, D_of(l, it), damp, adj_of(l, it));
+                hipLaunchKernelGGL(gn_step_bwd_k<true>, dim3(B), dim3(BWD_T), 0, st, w.gD, (const float *)w.partD, prev_nblocks, w.prow,
+                                   D_of(l, it), damp, adj_of(l, it), w.gP, (const float *)partP);
                 GS_LAUNCH_CHECK(nm.step);
             }
             if ((rc = pixels(sdf_pixel_bwd_k<SDF_BWD_MAX>, nm.pixels, l, it))) return rc;
@@ -393,12 +323,12 @@ static int sdf_bwd_run(const SdfBwdNames &nm, const float *depth, int B, int H, 
     }
     // the carried adjoints (the seam has none) + what the last pixel pass left: g_init and g_poses (B,16), or the seam's (B,12)
     if (g_D) {
-        hipLaunchKernelGGL(sdf_fold12_k, dim3(B), dim3(BWD_T), 0, st, seam ? (const float *)nullptr : (const float *)w.gD,
+        hipLaunchKernelGGL(gn_fold12_k, dim3(B), dim3(BWD_T), 0, st, seam ? (const float *)nullptr : (const float *)w.gD,
                            (const float *)w.partD, prev_nblocks, w.prow, g_D, seam ? 12 : 16);
         GS_LAUNCH_CHECK(nm.last);
     }
     if (g_poses) {
-        hipLaunchKernelGGL(sdf_fold12_k, dim3(B), dim3(BWD_T), 0, st, seam ? (const float *)nullptr : (const float *)w.gP,
+        hipLaunchKernelGGL(gn_fold12_k, dim3(B), dim3(BWD_T), 0, st, seam ? (const float *)nullptr : (const float *)w.gP,
                            (const float *)w.partP, prev_nblocks, w.prow, g_poses, seam ? 12 : 16);
         GS_LAUNCH_CHECK(nm.last);
     }
@@ -408,12 +338,12 @@ static int sdf_bwd_run(const SdfBwdNames &nm, const float *depth, int B, int H, 
 extern "C" {
 
 size_t gs_sdf_odometry_tape_bytes_for(int B, int H, int W, int stride, int levels, int numiters_total) {
-    if (sdf_shape_fault(B, H, W, stride, levels) != 0 || !sdf_total_ok(levels, numiters_total)) return 0;
+    if (sdf_shape_fault(B, H, W, stride, levels) != 0 || !gn_total_ok(levels, numiters_total)) return 0;
     return sdf_tape_layout(B, H, W, stride, numiters_total, nullptr, nullptr);
 }
 
 size_t gs_sdf_odometry_bwd_room(int B, int H, int W, int stride, int levels, int numiters_total, int nx, int ny, int nz, int want_tsdf) {
-    if (sdf_shape_fault(B, H, W, stride, levels) != 0 || !sdf_total_ok(levels, numiters_total) || !sdf_dims_ok(nx, ny, nz)) return 0;
+    if (sdf_shape_fault(B, H, W, stride, levels) != 0 || !gn_total_ok(levels, numiters_total) || !sdf_dims_ok(nx, ny, nz)) return 0;
     return sdf_room_layout(B, H, W, stride, numiters_total, (int64_t)nx * ny * nz, want_tsdf != 0, nullptr, nullptr);
 }
 
@@ -434,12 +364,6 @@ int gs_sdf_odometry(const float *depth, int B, int H, int W, const float *intrin
     return sdf_run(depth, B, H, W, intrinsics, poses, init, vo, stride, levels, numiters, damp, out_T, info, w, nullptr, st);
 }
 
-static int sdf_total(int levels, const int *numiters) {
-    int total = 0;
-    for (int l = 0; l < levels; ++l) total += numiters[l];
-    return total;
-}
-
 int gs_sdf_odometry_taped(const float *depth, int B, int H, int W, const float *intrinsics, const float *poses, const float *init,
                           const float *tsdf, const float *weight, int nx, int ny, int nz, const float *origin, float voxel_size,
                           float trunc, float min_weight, int stride, int levels, const int *numiters, float damp, float *out_T,
@@ -448,7 +372,7 @@ int gs_sdf_odometry_taped(const float *depth, int B, int H, int W, const float *
     SDF_REQUIRE_SHAPE("gs_sdf_odometry_taped");
     SDF_REQUIRE_VOLUME("gs_sdf_odometry_taped");
     GN_REQUIRE_LOOP("gs_sdf_odometry_taped");
-    const int total = sdf_total(levels, numiters);
+    const int total = gn_schedule(levels, numiters).total;
     const size_t need = sdf_tape_layout(B, H, W, stride, total, nullptr, nullptr);
     GS_REQUIRE_TAPE("gs_sdf_odometry_taped", tape, tape_cap, need, GS_ERR_WORKSPACE_TOO_SMALL);
     SdfTape t;
@@ -466,7 +390,7 @@ int gs_sdf_odometry_bwd(const float *depth, int B, int H, int W, const float *in
     SDF_REQUIRE_SHAPE("gs_sdf_odometry_bwd");
     SDF_REQUIRE_VOLUME("gs_sdf_odometry_bwd");
     GN_REQUIRE_LOOP("gs_sdf_odometry_bwd");
-    const int total = sdf_total(levels, numiters);
+    const int total = gn_schedule(levels, numiters).total;
     const size_t need = sdf_tape_layout(B, H, W, stride, total, nullptr, nullptr);
     GS_REQUIRE_TAPE("gs_sdf_odometry_bwd", tape, tape_cap, need, GS_ERR_WORKSPACE_TOO_SMALL);
     SdfTape t;

@@ -1,8 +1,8 @@
 """The SDF odometry (csrc/sdf.hip) against recorded results, bit for bit.
 
-The SDF loop shares its constants, start-up and host checks with the RGB-D loop (gs_gn_step.hpp), and its step is the RGB-D
-step's text a second time; how that code is arranged is free as long as every value it produces stays what it was: same
-operands, same fp32 operations in the same order.  tests/golden/sdf_bits.npz holds what a build left behind on the MI355X for
+The SDF loop shares its constants, its start-up and step kernels and its host checks with the RGB-D loop (gs_gn_step.hpp); how
+that code is arranged is free as long as every value it produces stays what it was: same operands, same fp32 operations in the
+same order.  tests/golden/sdf_bits.npz holds what a build left behind on the MI355X for
 the scenes of tests/test_sdf_odometry.py (the file holds no inputs, only results; tools/gen_golden_rgbd_bits.py records it with
 the library it is given):
 

@@ -493,10 +493,13 @@ def test_seam_gradients_match_float64_autograd(name, which):
         assert np.array_equal(g.view(np.uint32), g2.view(np.uint32))  # bit for bit from run to run
 
 
-def whole_device(name, counts=None, deterministic=False, only_depth=False):
-    """-> (T, info, [g_depth, g_poses, g_init, g_tsdf]) of sum(W * T[:, :3]) on the device, init = the identity."""
+def whole_device(name, counts=None, deterministic=False, only_depth=False, zero_depth=None):
+    """-> (T, info, [g_depth, g_poses, g_init, g_tsdf]) of sum(W * T[:, :3]) on the device, init = the identity; `zero_depth`:
+    a batch element whose depth is all zero (no valid pixel: none of its steps is applied)."""
     _, _, stride, levels, numiters = size_of(name)
     t = fw.dev_scene(name)
+    if zero_depth is not None:
+        t["depth"][zero_depth] = 0.0  # (dev_scene's tensors are this call's own)
     depth, P, init, tsdf = (x.clone().requires_grad_(True) for x in (t["depth"], t["P"], torch.eye(4, device=DEV).repeat(2, 1, 1), t["tsdf"]))
     if only_depth:
         P, init, tsdf = P.detach(), init.detach(), tsdf.detach()
